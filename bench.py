@@ -11,9 +11,19 @@ contiguous slice of the global ray-index stream of that step, so results do not 
 bins them into the 180x90 detector histogram on its GPU, and the histograms are summed with
 ONE all-reduce over RCCL (torch.distributed backend "nccl").  Weak scaling: per-GPU work is
 fixed -- 5e7 rays per GPU per step for EVERY N, so the N = 1 point of a scaling curve is the
-single-GPU bench.  At N = 8 two more timed loops run BASELINE configs[4] (1e9 rays per step over
-the node: "configs4") and configs[3] (integratingSphereDetectorSweep.C's 362 disc positions share
-1e7 rays per GPU and step, ray-sharded: "configs3"); extra keys only.  Prints one JSON line on rank 0.
+single-GPU bench.  Prints one JSON line on rank 0.
+
+A plain run sets up, warms up, times the `--steps` steps and prints the line.  Everything else it can
+measure runs only with `--full`, after the headline loop, as extra keys of the same line: at N = 1 the
+other BASELINE configurations as timed legs and the CPU baseline (the oracle on this host's cores); at
+N = 8 two more timed loops, BASELINE configs[4] (1e9 rays per step over the node: "configs4") and
+configs[3] (integratingSphereDetectorSweep.C's 362 disc positions share 1e7 rays per GPU and step,
+ray-sharded: "configs3").
+
+`--dump-outputs DIR` writes what the timed path computed in its last step (rank 0):
+DIR/fluxmap.npy, the all-reduced 180x90 histogram as float64, and DIR/census.npy, rank 0's census of
+that step (launched, exited, counted_below_z, absorbed, suspended, bin_increments, wall_hits) as float64.
+The inputs depend only on the arguments (seed, rays, steps, warmup, number of GPUs).
 """
 import argparse
 import json
@@ -51,15 +61,22 @@ def parse():
     ap.add_argument("--rays", type=int, default=0,
                     help="rays per GPU per step; default 5e7 (BASELINE configs[1]) for every --gpus")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED0001)
-    ap.add_argument("--cpu-rays", type=int, default=-1, help="oracle sample size for cpu_baseline (0: skip, -1: auto)")
+    ap.add_argument("--cpu-rays", type=int, default=-1, help="oracle sample size for cpu_baseline with --full (0: skip, -1: auto)")
     ap.add_argument("--trace-mode", choices=["explicit", "chord"], default="explicit",
                     help="explicit: cosine direction + ray-sphere intersection per bounce (default, the reference-shaped "
                          "algorithm); chord: ISX_TRACE_CHORD, next wall point sampled directly (same distribution)")
     ap.add_argument("--reduce", choices=["auto", "device", "host"], default="auto",
                     help="where the histogram lives for the all-reduce")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra timed legs of the N = 1 line (configs0 / configs2 / configs3 / perpos_8p1e8 / size_sweep / surfaces)")
-    return ap.parse_args()
+                    help="with --full: skip the extra timed legs of the N = 1 line (configs0 / configs2 / configs3 / perpos_8p1e8 / size_sweep / surfaces)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline loop also run the extra legs, the CPU baseline (N = 1) and configs4 / configs3 (N = 8)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's histogram and census to DIR/fluxmap.npy and DIR/census.npy (float64)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def default_rays_per_gpu(world):
@@ -459,9 +476,19 @@ def main():
     per_rank = {"kernel_ms": over_ranks(kernel_ms), "trace_ms": over_ranks([k[1] for k in kind_ms]),
                 "bin_ms": over_ranks([k[2] for k in kind_ms]), "allreduce_ms": over_ranks(rec["allreduce_ms"])}
     total_hits = int(hist_dev.sum().item())
-    # BASELINE configs[4] (1e9 rays per step over the 8 GPUs of a node) as a second timed loop at N = 8; extra keys only
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives for its last step: the (all-reduced) histogram and this rank's census
+        # (hist_dev is reused by the configs4 loop below, so it is read here)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "fluxmap.npy"),
+                hist_dev.cpu().numpy().astype(np.float64).reshape(cfg.n_theta, cfg.n_phi))
+        st_last = census[-1][1]
+        np.save(os.path.join(a.dump_outputs, "census.npy"),
+                np.array([st_last.launched, st_last.exited, st_last.counted_below_z, st_last.absorbed, st_last.suspended,
+                          st_last.bin_increments, st_last.wall_hits], dtype=np.float64))
+    # BASELINE configs[4] (1e9 rays per step over the 8 GPUs of a node) as a second timed loop at N = 8 (--full); extra keys only
     configs4 = None
-    if world == 8 and a.rays <= 0:
+    if a.full and world == 8 and a.rays <= 0:
         n4 = 125_000_000
         dt4, rec4 = timed_loop(n4, a.warmup + a.steps, 1, a.steps)
         configs4 = {"workload": "BASELINE configs[4]: 1e9 rays per step over 8 GPUs (1.25e8 per GPU), same map", "rays_per_gpu_per_step": n4,
@@ -469,10 +496,10 @@ def main():
                     "kernel_ms_min_max_over_ranks": over_ranks(rec4["kernel_ms"]),
                     "allreduce_ms_min_max_over_ranks": over_ranks(rec4["allreduce_ms"])}
     # BASELINE configs[3] (integratingSphereDetectorSweep.C:31-105, ray-sharded): the 181 x 2 disc positions of the macro share the
-    # rays -- every rank traces its slice of the step's rays against ALL discs, ONE all-reduce of the 362 counts.  At N = 8
-    # (ISX_BENCH_CONFIGS3=1: at any N, rehearsal); extra keys only.
+    # rays -- every rank traces its slice of the step's rays against ALL discs, ONE all-reduce of the 362 counts.  At N = 8 with
+    # --full (ISX_BENCH_CONFIGS3=1 with --full: at any N, rehearsal); extra keys only.
     configs3 = None
-    if (world == 8 and a.rays <= 0) or os.environ.get("ISX_BENCH_CONFIGS3") == "1":
+    if a.full and ((world == 8 and a.rays <= 0) or os.environ.get("ISX_BENCH_CONFIGS3") == "1"):
         import math
         discs = []
         for th in np.arange(-45.0, 45.0 + 1e-9, 0.5):   # rootMacros::detectorDiskPlacement (integratingSphereDetectorSweep.C:145-172)
@@ -518,9 +545,9 @@ def main():
                     "rays_per_gpu_per_step": n3, "n_discs": int(len(discs)), "value": n3 * world * a.steps / dt3 / 1e6, "unit": "Mrays/s",
                     "ms_per_step": dt3 / a.steps * 1e3, "kernel_ms_min_max_over_ranks": over_ranks(k3),
                     "allreduce_ms_min_max_over_ranks": over_ranks(ar3), "disc_hits_last_step": int(disc_dev.sum().item())}
-    # the other BASELINE configurations as timed legs of the N = 1 line (extra keys only; the headline loop above ran first)
+    # the other BASELINE configurations as timed legs of the N = 1 line with --full (extra keys only; the headline loop above ran first)
     legs = None
-    if world == 1 and a.rays <= 0 and not a.no_extras:
+    if a.full and world == 1 and a.rays <= 0 and not a.no_extras:
         try:
             legs = extra_legs(isx, np, a.seed, cus, load_pmc()[0])
         except Exception as e:   # an extra leg must never cost the headline line: report it and go on
@@ -633,7 +660,7 @@ def main():
                                  "wall_hits": st.wall_hits, "bin_increments": st.bin_increments},
             "hist_sum_last_step": total_hits,
         }
-        if world == 1 and a.cpu_rays != 0:
+        if a.full and world == 1 and a.cpu_rays != 0:
             out["cpu_baseline"] = cpu_baseline(a.seed, a.cpu_rays)
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())

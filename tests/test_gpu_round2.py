@@ -417,7 +417,7 @@ def test_bench_two_ranks_share_the_gpu_over_gloo(isx):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(steps),
-                        "--warmup", str(warmup), "--rays", str(rays), "--cpu-rays", "0"], env=env, capture_output=True, text=True,
+                        "--warmup", str(warmup), "--rays", str(rays), "--cpu-rays", "0", "--full"], env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -443,7 +443,7 @@ def test_bench_two_ranks_share_the_gpu_over_gloo(isx):
         lo, hi = pr[key]
         assert 0 < lo <= hi, (key, pr)
     assert pr["kernel_ms"][1] < out["ms_per_step"] and out["configs4"] is None
-    # the configs[3] leg (the driver's N = 8 launch runs it by default; here ISX_BENCH_CONFIGS3=1 rehearses it with two ranks):
+    # the configs[3] leg (the driver's N = 8 launch runs it with --full; here ISX_BENCH_CONFIGS3=1 rehearses it with two ranks):
     # 362 disc positions share the rays of a step, ray-sharded, ONE all-reduce of the counts -- the last step's summed counts
     # must be those of its two slices swept in this process
     c3 = out["configs3"]
