@@ -83,7 +83,7 @@ struct State {
   int trace_block = 512, trace_blocks_per_cu = 0;
   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is made once per kernel and size, not once per launch
   std::map<const void*, size_t> attr_lds;
-  // ... and so is the occupancy query (resident_per_cu): (kernel, workgroup size, LDS bytes) -> workgroups per CU
+  // ... and so is the occupancy query (blocks_per_cu): (kernel, workgroup size, LDS bytes) -> workgroups per CU
   std::map<std::tuple<const void*, int, size_t>, int> occ;
   // small calls are bound by host round trips: results and census go through ONE pinned staging buffer
   // (asynchronous copies, one synchronisation per call), and a blocking call that finds nothing enqueued before it skips the
@@ -104,14 +104,12 @@ struct DevBuf {
   DevBuf& operator=(const DevBuf&) = delete;
 };
 
-#define HIPCHK(expr)                                 \
-  do {                                               \
-    hipError_t e_ = (expr);                          \
-    if (e_ != hipSuccess) {                          \
-      S.last_hip = (int)e_;                          \
-      return ISX_ERR_HIP;                            \
-    }                                                \
-  } while (0)
+// a HIP status as an isx status (the HIP one is kept for isx_last_hip_error); HIPCHK returns it on failure
+int hip_rc(hipError_t e) {
+  if (e != hipSuccess) S.last_hip = (int)e;
+  return e == hipSuccess ? ISX_OK : ISX_ERR_HIP;
+}
+#define HIPCHK(expr) do { if (hip_rc(expr)) return ISX_ERR_HIP; } while (0)
 
 // ABI v3: the caller's struct must be the library's (isx.h: struct_size)
 bool config_abi_ok(const isx_config* c) { return c->struct_size == (uint32_t)sizeof(isx_config); }
@@ -253,16 +251,6 @@ int ensure_tables(const isx_config* c) {
   return ISX_OK;
 }
 
-int get_event(hipEvent_t* ev) {
-  if (S.ev_used == S.ev_pool.size()) {
-    hipEvent_t e;
-    HIPCHK(hipEventCreate(&e));
-    S.ev_pool.push_back(e);
-  }
-  *ev = S.ev_pool[S.ev_used++];
-  return ISX_OK;
-}
-
 // Launch shape of a SMALL launch (round 5; measured in profiles/r05_small_call_sweep.json).  A launch cannot end before its longest
 // ray has -- about ln(n) / 0.0175 bounces, one after the other (620 for 5e4 rays) -- so a small launch is bound by latency, not by
 // throughput: few rays per tracer lane (the bulk of the work is then short next to the longest ray) and few waves per SIMD (a
@@ -275,19 +263,14 @@ Shape small_shape(uint64_t n, int block_default) {
   sh.rays_per_lane = S.rays_per_lane > 0 ? (uint64_t)S.rays_per_lane : (n < 150000ull ? 1ull : n < 300000ull ? 2ull : 4ull);
   return sh;
 }
-// workgroups of a launch of n rays: `tracer_waves` waves per workgroup trace (all of them unless the workgroup has an assist wave)
-int pick_grid(uint64_t n, int block = kBlock, int blocks_per_cu = 0, int tracer_waves = 0, uint64_t rays_per_lane = 4) {
-  if (S.grid_blocks > 0) return S.grid_blocks;
-  const int full = S.cu_count * (blocks_per_cu > 0 ? blocks_per_cu : S.blocks_per_cu);
-  const uint64_t lanes = (uint64_t)(tracer_waves > 0 ? tracer_waves : block / 64) * 64ull * (rays_per_lane ? rays_per_lane : 1ull);
-  const uint64_t want = (n + lanes - 1) / lanes;
-  if (want < 1) return 1;
-  return want < (uint64_t)full ? (int)want : full;
-}
 
-// workgroups of `fn` (workgroup size `block`, `lds` bytes of dynamic LDS) that are resident on one CU at a time
+// workgroups per CU of a launch's grid (Plan::per_cu): an option's value if > 0, 0 for blocks_per_cu, kResident for what is
+// resident -- workgroups of `fn` (workgroup size `block`, `lds` bytes of dynamic LDS) on one CU at a time (queried once, cached)
+constexpr int kResident = -1;
+int resident_unless(int option) { return option > 0 ? option : kResident; }
 template <class F>
-int resident_per_cu(F fn, int block, size_t lds) {
+int blocks_per_cu(F fn, int block, size_t lds, int per_cu) {
+  if (per_cu != kResident) return per_cu;
   const auto key = std::make_tuple((const void*)fn, block, lds);
   const auto it = S.occ.find(key);
   if (it != S.occ.end()) return it->second;
@@ -305,10 +288,10 @@ uint32_t pick_sub(uint64_t n) {
                  //  64 / 128 / 192 / 256 / 384 / 512 / 1024: 11.26 / 11.18 / 11.19 / 11.20 / 11.23 / 11.33 / 11.40 ms)
 }
 
-// the next block of queue counters, zeroed on the stream ahead of the launch that uses it
-int next_ctr(uint32_t** ctr) {
+// the next block of queue counters, zeroed on `stream` ahead of the launch that uses it
+int next_ctr(hipStream_t stream, uint32_t** ctr) {
   uint32_t* c = S.d_ctr + (S.ctr_next++ % State::kCtrRing) * Q_WORDS;
-  HIPCHK(hipMemsetAsync(c, 0, Q_WORDS * sizeof(uint32_t), S.stream));
+  HIPCHK(hipMemsetAsync(c, 0, Q_WORDS * sizeof(uint32_t), stream));
   *ctr = c;
   S.pending = true;   // (every launch takes a block: from here on the stream holds work whose census has not been collected)
   return ISX_OK;
@@ -333,34 +316,36 @@ int stage_result(const void* dev, size_t bytes) {
   const int rc = ensure_pin(bytes);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(S.h_pin + 64, dev, bytes, hipMemcpyDeviceToHost, S.stream));
+  S.pending = true;
   return ISX_OK;
 }
 void fetch_result(void* host, size_t bytes) { std::memcpy(host, S.h_pin + 64, bytes); }
+// D2H of a call's result straight into the caller's memory: complete once collect_stats() has synchronised
+int copy_out(void* host, const void* dev, size_t bytes) {
+  HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, S.stream));
+  S.pending = true;
+  return ISX_OK;
+}
 
 // one launch addresses its rays by 31-bit offsets from its first ray: larger jobs are cut into launches of this many rays
 constexpr uint64_t kLaunchMax = 1ull << 30;
 
-int ensure_pipeline(size_t rays, size_t waves, int buf = 0, size_t slot_doubles = 6);
 // the disc list of the current isx_disc_sweep call as isx_bin_discs_kernel wants it (upload_discs_clustered below)
 struct DiscClusters { size_t n = 0, off_ordered = 0, off_clusters = 0, off_perm = 0; int n_clusters = 0; } g_disc_clusters;
 
-// enqueue one persistent kernel accumulating into d_hist (device) and S.d_stats
 struct PerPos { uint64_t map_first = 0, rays_per_group = 0; int fold = 1; const double* d_table = nullptr; double width = 0; };
 struct LogSink { double* rec = nullptr; unsigned long long* count = nullptr; uint64_t cap = 0; };
 
-int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t first, unsigned long long* d_hist,
-            int nbins_override, const double* d_discs, double disc_r, double disc_h, const PerPos* pp = nullptr,
-            const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr) {
-  Geom g;
-  int rc = prepare_geom(c, &g);
-  if (rc) return rc;
-  if (n > ISX_MAX_RAYS_PER_CALL) return ISX_ERR_TOO_LARGE;
-  if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;   // first + n (the exclusive end of the index range) must be representable
-  DetGrid d;
+// LDS of a workgroup's histogram: 4 B per bin, 16-byte aligned
+size_t hist_lds(int nbins) { return ((size_t)nbins * 4 + 15) & ~(size_t)15; }
+
+// The DetGrid of a call's sink, checked, and the dynamic LDS of its fused kernel (histogram + tables, census, Geom, DetGrid).
+int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d_discs, double disc_r, double disc_h,
+              const PerPos* pp, const LogSink* lg, DetGrid& d, size_t& lds) {
   std::memset(&d, 0, sizeof(d));
   d.portz = c->exit_port_z;
   d.hit_line_mode = c->hit_line_mode;
-  size_t lds = 0;
+  int rc;
   if (sink == SINK_FLUX) {
     rc = check_grid(c);
     if (rc) return rc;
@@ -371,7 +356,7 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
     d.rho_d = c->det_diameter / 2;
     d.R = c->det_distance;
     d.table = S.d_table; d.rowtab = S.d_rowtab; d.coltab = S.d_coltab;
-    lds = (((size_t)d.nbins * 4 + 15) & ~(size_t)15) + (size_t)(4 * d.n_theta) * 8 + (size_t)(2 * d.n_phi) * sizeof(ColX) + 64 + sizeof(Geom) + sizeof(DetGrid);
+    lds = hist_lds(d.nbins) + (size_t)(4 * d.n_theta) * 8 + (size_t)(2 * d.n_phi) * sizeof(ColX) + 64 + sizeof(Geom) + sizeof(DetGrid);
   } else if (sink == SINK_PERPOS) {
     if (!pp || pp->rays_per_group < 1 || (pp->fold != 1 && pp->fold != 2)) return ISX_ERR_BAD_ARG;
     if (pp->d_table) {  // caller-supplied detector list (traceRays with one Detector)
@@ -390,13 +375,13 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
       d.half_w2 = (c->det_diameter / 2) * (c->det_diameter / 2);
     }
     d.map_first = pp->map_first; d.rays_per_group = pp->rays_per_group; d.fold = pp->fold;
-    lds = (((size_t)d.nbins * 4 + 15) & ~(size_t)15) + 64 + sizeof(Geom) + sizeof(DetGrid);
+    lds = hist_lds(d.nbins) + 64 + sizeof(Geom) + sizeof(DetGrid);
   } else if (sink == SINK_DISCPOS) {
     if (!pp || pp->rays_per_group < 1 || nbins_override < 1 || nbins_override > 36000) return ISX_ERR_BAD_ARG;
     d.nbins = nbins_override;
     d.discs = d_discs; d.disc_r = disc_r; d.disc_h = disc_h;
     d.map_first = pp->map_first; d.rays_per_group = pp->rays_per_group; d.fold = 1;
-    lds = (((size_t)d.nbins * 4 + 15) & ~(size_t)15) + 64 + sizeof(Geom) + sizeof(DetGrid);
+    lds = hist_lds(d.nbins) + 64 + sizeof(Geom) + sizeof(DetGrid);
   } else if (sink == SINK_LOG) {
     if (!lg || !lg->rec || !lg->count) return ISX_ERR_BAD_ARG;
     d.nbins = 1;
@@ -406,7 +391,7 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
     if (nbins_override < 1 || nbins_override > 36000) return ISX_ERR_BAD_ARG;
     d.nbins = nbins_override;
     d.discs = d_discs; d.disc_r = disc_r; d.disc_h = disc_h;
-    lds = (((size_t)d.nbins * 4 + 15) & ~(size_t)15) + 64 + sizeof(Geom) + sizeof(DetGrid);
+    lds = hist_lds(d.nbins) + 64 + sizeof(Geom) + sizeof(DetGrid);
   }
   // the per-block histogram (+ tables) must fit the workgroup's LDS: a grid too fine for that is a configuration error
   if (lds > S.lds_limit) return ISX_ERR_BAD_CONFIG;
@@ -416,275 +401,336 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
     const size_t stage = 16 + (size_t)kBlock * 24;
     if (lds + stage <= S.lds_limit) { lds += stage; d.rec_stage = 1; }
   }
-  if (n == 0) return ISX_OK;
+  return ISX_OK;
+}
+
+// ---- The launch plan of a call: the route, its kernel(s) and their workgroup shapes.
+//  ROUTE_FLUX_PIPE  flux maps: per chunk a trace kernel (exit lines -> HBM workspace) and a binning kernel
+//  ROUTE_DISC_PIPE  the shared-ray disc sweep the same way: assist-wave trace kernel (exit segments) -> isx_bin_discs_kernel
+//  ROUTE_ASSIST     the per-position sinks: one assist-wave kernel, whose assist wave does the exact test per exiting ray
+//  ROUTE_FUSED      one kernel that traces and bins: everything the routes above do not serve
+enum Route { ROUTE_FUSED, ROUTE_ASSIST, ROUTE_FLUX_PIPE, ROUTE_DISC_PIPE };
+typedef void (*KernelFn)(const Geom, const DetGrid, const Work);
+typedef void (*BinFn)(const DetGrid, const Work);
+struct Plan {
+  Route route = ROUTE_FUSED;
+  KernelFn fn = nullptr;        // the kernel (a pipeline's trace kernel)
+  int block = kBlock;           // its workgroup size
+  size_t lds = 0;               // its dynamic LDS
+  int tracers = 0;              // its tracer waves per workgroup
+  uint64_t rays_per_lane = 4;   // rays per tracer lane the grid is sized for
+  int per_cu = 0;               // workgroups per CU (blocks_per_cu)
+  BinFn bin = nullptr;          // pipelines: the binning kernel, its workgroup size, workgroups per CU and dynamic LDS
+  int bblock = 0, bin_per_cu = kResident;
+  size_t lds_bin = 0;
+  bool assist = true;           // the trace kernel has an assist wave (one writing wave per workgroup)
+  bool compat_lines = false;    // isx_compat_lines_kernel runs between the two (ISX_HITLINE_ORIGIN_COMPAT)
+  bool binning = true;          // false: bin_mode 2, a diagnostic: trace only
+  bool overlap = false;         // chunks alternate over two streams (S.overlap)
+  size_t slot_doubles = 6;      // doubles per exit record in the workspace
+};
+
+// workgroups of a launch of n rays: enough for p.rays_per_lane rays per tracer lane, no more than `per_cu` per CU
+int pick_grid(const Plan& p, uint64_t n, int per_cu) {
+  if (S.grid_blocks > 0) return S.grid_blocks;
+  const int full = S.cu_count * (per_cu > 0 ? per_cu : S.blocks_per_cu);
+  const uint64_t lanes = (uint64_t)p.tracers * 64ull * p.rays_per_lane;
+  const uint64_t want = (n + lanes - 1) / lanes;
+  if (want < 1) return 1;
+  return want < (uint64_t)full ? (int)want : full;
+}
+// workgroups of a binning launch: a wave per work unit -- the quarter regions of `cnt` exit lines (sixteenths for pad 2) plus
+// the open region each of `writers` writing waves of the trace kernel leaves behind -- no more than `per_cu` per CU
+int bin_grid(const Plan& p, uint64_t cnt, uint32_t pad, uint64_t writers, int per_cu) {
+  if (S.grid_blocks > 0) return S.grid_blocks;
+  const uint64_t waves = (uint64_t)(p.bblock / 64);
+  const uint64_t want = (cnt / (kRegion >> (2u + pad)) + writers + waves - 1) / waves;
+  const int full = S.cu_count * per_cu;
+  return want < (uint64_t)full ? (int)want : full;
+}
+
+// the shape of a trace kernel with or without an assist wave: workgroup, tracer waves, grid, LDS (census, Geom, DetGrid, and
+// with an assist wave the queues and rings)
+void trace_shape(Plan& p, Shape sh, bool assist, int per_cu) {
+  p.block = sh.block; p.rays_per_lane = sh.rays_per_lane;
+  p.tracers = sh.block / 64 - (assist ? 1 : 0);
+  p.per_cu = per_cu;
+  p.lds = 16 + 64 + sizeof(Geom) + sizeof(DetGrid) + (assist ? 16 + sizeof(AssistQueues) + (size_t)(kResumeCap + kPendCap) * 64 : 0);
+  p.assist = assist;
+}
+
+Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bool discs_in_aux, uint64_t n) {
+  enum { LAMBERT, LOBE, ROUGH } const border =
+      c->surface_model == ISX_SURFACE_LOBE ? LOBE : c->lambertian ? LAMBERT : ROUGH;   // (ISX_SURFACE_ROBAST: Lambertian or rough-specular)
+  const bool pencil = c->source_model == ISX_SOURCE_PENCIL;   // (else ISX_SOURCE_BRDF)
+  const bool chord = c->trace_mode == ISX_TRACE_CHORD;
+  const bool compat = c->hit_line_mode != ISX_HITLINE_LAST_SEGMENT;
+  const bool sp = S.surface_pipeline != 0;
+  // the lean kernels serve the headline border and hit line; every sink has one for the pencil source and the explicit trace
+  const bool lean = border == LAMBERT && !compat;
+  const bool lean_explicit = lean && pencil && !chord;
+  // assist-wave workgroups: the lobe / rough-specular kernels hold 87-93 VGPRs -- four waves per SIMD -- and hand over as often as
+  // the lean one at a third of its pace: 512 threads, 7 tracer waves per assist wave and two workgroups per CU, unless assist_block
+  // was set (measured 47.1 against 48.3 ms and 33.4 against 34.0 ms for 5e7 rays, profiles/r05_surface_shapes.json)
+  const int ablock = (border != LAMBERT && !S.assist_block_set) ? 512 : S.assist_block;
+  Plan p;
+
+  // The flux pipeline's trace kernels without an assist wave serve the lean cases (pencil source, either trace mode; BRDF source,
+  // explicit trace).  Those with one serve, unless surface_pipeline = 0, the origin-compat hit line as well (the assist wave writes
+  // the line the binning kernel is to see) and, with the pencil source, the two other borders -- the chord identity is a property
+  // of the Lambertian border, so trace_mode says nothing there.
+  const bool flux_served = border == LAMBERT ? (!compat || (sp && S.assist)) && (pencil || !chord) : sp && S.assist && pencil;
+  if (sink == SINK_FLUX && flux_served && S.pipeline && S.bin_mode != 0) {
+    p.route = ROUTE_FLUX_PIPE;
+    const bool assist = S.assist != 0;
+    if (border == LOBE) p.fn = isx_trace_assist_lobe_kernel;
+    else if (border == ROUGH) p.fn = isx_trace_assist_rough_kernel;
+    else if (!pencil) p.fn = assist ? isx_trace_assist_brdf_kernel : isx_trace_rec_brdf_kernel;
+    else if (chord) p.fn = assist ? isx_trace_assist_chord_kernel : isx_trace_rec_chord_kernel;
+    else p.fn = assist ? isx_trace_assist_kernel : isx_trace_rec_kernel;
+    trace_shape(p, assist ? small_shape(std::min(n, S.pipe_chunk), ablock) : Shape{S.trace_block, 4}, assist,
+                resident_unless(S.trace_blocks_per_cu));
+    // The binning kernel keeps the histogram and the detector tables in LDS.  With slot queues (1024-thread workgroups: 61 KB of
+    // queues next to the histogram) if the grid fits their 32-bit slot records and the LDS, and then with COLUMN slots (default
+    // for every source since round 4: grazing lines are column slots as well -- prep_band; bin_cols = 0 keeps the row slots of
+    // isx_bin_slots_kernel); else the one without.
+    const size_t tables = hist_lds(d.nbins) + (size_t)(4 * d.n_theta) * 8 + (size_t)(2 * d.n_phi) * sizeof(ColX) + sizeof(DetGrid) + 16;
+    const size_t slots_lds = tables + (size_t)(2 * d.n_phi) * sizeof(ColP) + (size_t)(kBlock / 64) * kSlotWaveWords * 4;
+    const size_t cols_lds = tables + (size_t)(d.n_theta + 4) * sizeof(RowX) + (size_t)(kBlock / 64) * kColWaveWords * 4;
+    const bool slots = S.bin_slots && S.bin_mode == 1 && d.n_theta <= 256 && d.n_phi <= 255 && slots_lds <= S.lds_limit;
+    const bool cols = slots && S.bin_cols && cols_lds <= S.lds_limit;
+    p.bin = cols ? isx_bin_cols_kernel : slots ? isx_bin_slots_kernel : isx_bin_lines_kernel;
+    p.bblock = slots ? kBlock : S.bin_block;
+    p.lds_bin = cols ? cols_lds : slots ? slots_lds : tables + (size_t)(p.bblock / 64) * 128 * 4;
+    p.bin_per_cu = resident_unless(S.bin_blocks_per_cu);
+    p.compat_lines = compat && S.bin_mode != 2;
+    p.binning = S.bin_mode != 2;
+    p.overlap = S.overlap > 1 && S.bin_mode == 1 && n >= (uint64_t)S.overlap * 65536;
+    if (p.lds_bin <= S.lds_limit) return p;
+    p = Plan();   // (a binning kernel whose LDS does not fit: the fused kernel below)
+  }
+
+  // The disc pipeline's binning kernel keeps the histogram, the cluster table, the discs (up to kDiscsInLds) and per-wave lists in
+  // LDS; above ~16 000 discs on gfx950 they do not fit, and the fused SINK_DISC kernel, which needs the histogram only, takes the sweep.
+  const size_t disc_lds = hist_lds(d.nbins) + (size_t)g_disc_clusters.n_clusters * 16 +
+                          (d.nbins <= kDiscsInLds ? (size_t)d.nbins * 48 + (size_t)((d.nbins + 1) & ~1) * 4 : 0) +
+                          (size_t)(kDiscBinBlock / 64) * (64 * 7 + kPairCap / 2) * sizeof(double);
+  if (sink == SINK_DISC && lean_explicit && S.pipeline && S.assist && S.disc_pipeline && g_disc_clusters.n == (size_t)d.nbins &&
+      discs_in_aux && disc_lds <= S.lds_limit) {
+    p.route = ROUTE_DISC_PIPE;
+    p.fn = isx_trace_assist_disc_kernel;
+    trace_shape(p, small_shape(std::min(n, S.pipe_chunk), ablock), true, kResident);
+    p.bin = isx_bin_discs_kernel; p.bblock = kDiscBinBlock; p.lds_bin = disc_lds;
+    p.slot_doubles = 8;   // (exit segments)
+    return p;
+  }
+
+  // (round 5: the lobe / rough-specular borders as well -- SINK_PERPOS only, last-segment hit line: the assist wave's exact test
+  //  takes the line as it is)
+  const bool pp_surface = sink == SINK_PERPOS && sp && pencil && border != LAMBERT && !compat;
+  if ((sink == SINK_PERPOS || sink == SINK_DISCPOS) && (lean_explicit || pp_surface) && S.pipeline && S.assist) {
+    p.route = ROUTE_ASSIST;
+    p.fn = sink == SINK_DISCPOS ? isx_trace_assist_discpos_kernel : border == LOBE ? isx_trace_assist_perpos_lobe_kernel :
+           border == ROUGH ? isx_trace_assist_perpos_rough_kernel : isx_trace_assist_perpos_kernel;
+    trace_shape(p, small_shape(std::min(n, kLaunchMax), ablock), true, resident_unless(S.trace_blocks_per_cu));
+    return p;
+  }
+
+  // the fused kernel: the lean build where there is one, the full-featured one for everything else
+  switch (sink) {
+    case SINK_FLUX: p.fn = lean && pencil ? (chord ? isx_trace_bin_chord_kernel : isx_trace_bin_kernel) :
+                           lean && !chord ? isx_trace_bin_brdf_kernel : isx_trace_bin_full_kernel; break;
+    case SINK_DZ: p.fn = lean_explicit ? isx_trace_dz_lean_kernel : isx_trace_dz_kernel; break;
+    case SINK_DISC: p.fn = lean_explicit ? isx_trace_disc_lean_kernel : isx_trace_disc_kernel; break;
+    case SINK_PERPOS: p.fn = lean_explicit ? isx_trace_perpos_lean_kernel : isx_trace_perpos_kernel; break;
+    case SINK_DISCPOS: p.fn = lean_explicit ? isx_trace_discpos_lean_kernel : isx_trace_discpos_kernel; break;
+    default: p.fn = lean_explicit ? isx_trace_log_lean_kernel : isx_trace_log_kernel; break;
+  }
+  // Workgroup shape.  The kernels that keep the 64.8 KB LDS histogram run one 1024-thread workgroup per CU (4 waves per SIMD,
+  // 128 VGPRs).  The lean trace-only kernels need 75-90 VGPRs and almost no LDS: as 512-thread workgroups (trace_block) they reach
+  // 5-6 waves per SIMD (measured: 18.8 -> 17.5 ms for 5e7 rays, 299 -> 282 ms for the 8.1e8-ray per-position map), and their grid is
+  // what is resident.
+  const bool trace_only = lean_explicit && (sink == SINK_PERPOS || sink == SINK_DISCPOS || sink == SINK_DZ || sink == SINK_LOG);
+  p.block = trace_only ? S.trace_block : kBlock;
+  p.tracers = p.block / 64;
+  p.lds = lds;
+  p.per_cu = trace_only ? resident_unless(S.trace_blocks_per_cu) : 0;
+  return p;
+}
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize): once per kernel and size, not once per launch
+int set_lds(const void* fn, size_t bytes) {
+  size_t& set = S.attr_lds[fn];
+  if (set != bytes) {
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    set = bytes;
+  }
+  return ISX_OK;
+}
+
+// the Work of one launch: rays [wk.first + off, + cnt), a block of queue counters zeroed on `stream`
+int launch_work(const Work& wk, uint64_t off, uint64_t cnt, uint32_t pad, hipStream_t stream, Work* w) {
+  *w = wk;
+  w->first = wk.first + off; w->n = cnt; w->sub = pick_sub(cnt); w->pad = pad;
+  return next_ctr(stream, &w->ctr);
+}
+
+// Events: mark() records a pooled event on `stream` (*at: its index in S.ev_pool); span() records one on S.stream that ends the
+// kernel of `kind` begun at mark *from (kind 0: a whole call, 1: a pipeline's trace kernel, 2: its binning kernel) and moves *from
+// on to it, so that consecutive kernels chain.
+int mark(hipStream_t stream, size_t* at) {
+  if (S.ev_used == S.ev_pool.size()) {
+    hipEvent_t e;
+    HIPCHK(hipEventCreate(&e));
+    S.ev_pool.push_back(e);
+  }
+  *at = S.ev_used++;
+  return hip_rc(hipEventRecord(S.ev_pool[*at], stream));
+}
+int span(int kind, size_t* from) {
+  const size_t a = *from;
+  const int rc = mark(S.stream, from);
+  if (rc == ISX_OK) S.spans.push_back({a, *from, kind});
+  return rc;
+}
+
+// ROUTE_FUSED and ROUTE_ASSIST: launches of at most kLaunchMax rays, one span
+int run_single(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
+  int rc = set_lds((const void*)p.fn, p.lds); if (rc) return rc;
+  const int per_cu = blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
+  size_t t;
+  rc = mark(S.stream, &t); if (rc) return rc;
+  for (uint64_t off = 0; off < wk.n; off += kLaunchMax) {
+    Work w;
+    rc = launch_work(wk, off, std::min(wk.n - off, kLaunchMax), 0, S.stream, &w); if (rc) return rc;
+    hipLaunchKernelGGL(p.fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w);
+    HIPCHK(hipGetLastError());
+  }
+  return span(0, &t);
+}
+
+// workspace of the two-kernel pipeline for a chunk of `rays` rays traced by `waves` waves: every region but a wave's last is
+// closed with more than kRegion - 64 lines in it, and a launch cannot have more lines than rays (isx_kernels.hpp: kRegion)
+int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles) {
+  const size_t regions = (rays / (kRegion - 63) + waves + 1) * slot_doubles / 6 + 1;   // (capacity is counted in 6-double slots)
+  if (regions > S.cap_regions[buf]) {
+    HIPCHK(hipStreamSynchronize(S.stream));
+    if (S.stream2) HIPCHK(hipStreamSynchronize(S.stream2));
+    if (S.d_rec[buf]) HIPCHK(hipFree(S.d_rec[buf]));
+    if (S.d_rec_counts[buf]) HIPCHK(hipFree(S.d_rec_counts[buf]));
+    S.d_rec[buf] = nullptr; S.d_rec_counts[buf] = nullptr; S.cap_regions[buf] = 0;
+    HIPCHK(hipMalloc(&S.d_rec[buf], regions * kRegion * 6 * sizeof(double)));
+    HIPCHK(hipMalloc(&S.d_rec_counts[buf], regions * sizeof(uint32_t)));
+    S.cap_regions[buf] = regions;
+  }
+  return ISX_OK;
+}
+
+// ROUTE_FLUX_PIPE and ROUTE_DISC_PIPE: a trace launch and a binning launch per chunk of at most pipe_chunk rays
+int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
+  int rc = set_lds((const void*)p.fn, p.lds);
+  if (rc == ISX_OK) rc = set_lds((const void*)p.bin, p.lds_bin);
+  if (rc) return rc;
+  const int tres = blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
+  const int bres = blocks_per_cu(p.bin, p.bblock, p.lds_bin, p.bin_per_cu);
+  // what the two kernels see: a flux map's trace kernel keeps no histogram; the disc sweep's kernels walk the discs in cluster order
+  DetGrid dt = d, db = d;
+  if (p.route == ROUTE_FLUX_PIPE) {
+    dt.nbins = 1; dt.n_theta = 0; dt.n_phi = 0;
+  } else {
+    db.discs = S.d_aux + g_disc_clusters.off_ordered;
+    db.clusters = reinterpret_cast<const float*>(S.d_aux + g_disc_clusters.off_clusters);
+    db.disc_perm = reinterpret_cast<const int*>(S.d_aux + g_disc_clusters.off_perm);
+    db.n_clusters = g_disc_clusters.n_clusters;
+    dt = db;
+  }
+  // one trace launch on `st` and the binning of its `cnt` rays from `off` on `sb`, through workspace `buf`.  t: one stream, each
+  // kernel a span of its own from mark *t on; nullptr: an event hands the exit records over from st to sb
+  auto launch_pair = [&](uint64_t off, uint64_t cnt, int buf, hipStream_t st, hipStream_t sb, size_t* t) -> int {
+    if (cnt > kLaunchMax) return ISX_ERR_TOO_LARGE;   // (cannot happen: pipeline_chunk <= 2^26)
+    // (work units of the binning kernel: quarter regions of 256 exit lines; sixteenths -- 64 lines, one batch -- for a small
+    //  launch, whose few thousand lines then spread over as many waves as there are batches)
+    Work w;
+    int r = launch_work(wk, off, cnt, cnt < 1000000ull ? 2u : 0u, st, &w); if (r) return r;
+    dt.rec_lines = db.rec_lines = S.d_rec[buf];
+    dt.rec_counts = db.rec_counts = S.d_rec_counts[buf];
+    const int tgrid = pick_grid(p, cnt, tres);
+    hipLaunchKernelGGL(p.fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w);
+    HIPCHK(hipGetLastError());
+    size_t traced;
+    if (t) r = span(1, t);
+    else if ((r = mark(st, &traced)) == ISX_OK) r = hip_rc(hipStreamWaitEvent(sb, S.ev_pool[traced], 0));
+    if (r) return r;
+    if (p.compat_lines) {   // ISX_HITLINE_ORIGIN_COMPAT: the lines the binning kernel is to see (isx_compat_lines_kernel)
+      hipLaunchKernelGGL(isx_compat_lines_kernel, dim3(S.cu_count * 8), dim3(256), 0, sb, S.d_rec[buf], S.d_rec_counts[buf], w.ctr);
+      HIPCHK(hipGetLastError());
+    }
+    if (p.binning) {
+      // (every writing wave of the trace kernel leaves an open region: one per workgroup with an assist wave)
+      const uint64_t writers = p.assist ? (uint64_t)tgrid : (uint64_t)tgrid * (uint64_t)(p.block / 64);
+      hipLaunchKernelGGL(p.bin, dim3(bin_grid(p, cnt, w.pad, writers, bres)), dim3(p.bblock), p.lds_bin, sb, db, w);
+      HIPCHK(hipGetLastError());
+      if (t && (r = span(2, t))) return r;
+    }
+    return ISX_OK;
+  };
+  const uint64_t n = wk.n;
+  if (p.overlap) {
+    // ---- overlapped: chunk k is binned on the second stream while chunk k+1 is traced on the first (overlap_trace_streams = 2:
+    // odd chunks on a third); chunk k+3 reuses the workspace of chunk k.  (Timing: one wall-clock span around everything; the
+    // kernels' own times overlap.)
+    if (!S.stream2) HIPCHK(hipStreamCreateWithFlags(&S.stream2, hipStreamNonBlocking));
+    if (!S.stream3) HIPCHK(hipStreamCreateWithFlags(&S.stream3, hipStreamNonBlocking));
+    const uint64_t per = ((n + (uint64_t)S.overlap - 1) / (uint64_t)S.overlap + 63) & ~63ull;
+    const uint64_t chunk = std::min(per, S.pipe_chunk);
+    const size_t waves = (size_t)pick_grid(p, chunk, tres) * (p.block / 64);
+    for (int b = 0; b < State::kRecBufs && rc == ISX_OK; ++b) rc = ensure_pipeline((size_t)chunk, waves, b, p.slot_doubles);
+    size_t t0, t1;
+    if (rc == ISX_OK) rc = mark(S.stream, &t0);
+    if (rc) return rc;
+    HIPCHK(hipStreamWaitEvent(S.stream3, S.ev_pool[t0], 0));   // (what the caller enqueued before this call comes first)
+    size_t binned[State::kRecBufs];                            // [k mod kRecBufs]: chunk k is binned, its workspace free
+    int k = 0;
+    for (uint64_t off = 0; off < n; off += chunk, ++k) {
+      const int buf = k % State::kRecBufs;
+      const hipStream_t st = (S.overlap_trace_streams == 2 && (k & 1)) ? S.stream3 : S.stream;
+      if (k >= State::kRecBufs) HIPCHK(hipStreamWaitEvent(st, S.ev_pool[binned[buf]], 0));
+      rc = launch_pair(off, std::min(n - off, chunk), buf, st, S.stream2, nullptr);
+      if (rc == ISX_OK) rc = mark(S.stream2, &binned[buf]);
+      if (rc) return rc;
+    }
+    HIPCHK(hipStreamWaitEvent(S.stream, S.ev_pool[binned[(k - 1) % State::kRecBufs]], 0));   // the caller's stream sees the finished histogram
+    rc = mark(S.stream, &t1); if (rc) return rc;
+    S.spans.push_back({t0, t1, 0});
+    return ISX_OK;
+  }
+  const uint64_t chunk = std::min(n, S.pipe_chunk);
+  rc = ensure_pipeline((size_t)chunk, (size_t)pick_grid(p, chunk, tres) * (p.block / 64), 0, p.slot_doubles); if (rc) return rc;
+  size_t t;
+  rc = mark(S.stream, &t);
+  for (uint64_t off = 0; off < n && rc == ISX_OK; off += chunk)
+    rc = launch_pair(off, std::min(n - off, chunk), 0, S.stream, S.stream, &t);
+  return rc;
+}
+
+// enqueue one call's launches, accumulating into d_hist (device) and S.d_stats (or d_stats)
+int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t first, unsigned long long* d_hist,
+            int nbins_override, const double* d_discs, double disc_r, double disc_h, const PerPos* pp = nullptr,
+            const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr) {
+  Geom g;
+  int rc = prepare_geom(c, &g);
+  if (rc) return rc;
+  if (n > ISX_MAX_RAYS_PER_CALL) return ISX_ERR_TOO_LARGE;
+  if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;   // first + n (the exclusive end of the index range) must be representable
+  DetGrid d;
+  size_t lds = 0;
+  rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, d, lds);
+  if (rc || n == 0) return rc;
   Work wk;
   wk.seed = seed; wk.first = first; wk.n = n; wk.hist = d_hist; wk.stats = d_stats ? d_stats : S.d_stats;
   wk.ctr = nullptr; wk.sub = 0; wk.pad = 0;
-  // the lean kernel serves the headline configuration; anything else takes the full-featured variant
-  const bool lambert = c->lambertian && c->surface_model == ISX_SURFACE_ROBAST;
-  const bool compat = c->hit_line_mode != ISX_HITLINE_LAST_SEGMENT;
-  const bool lean_surface = lambert && !compat;
-  const bool lean = lean_surface && c->source_model == ISX_SOURCE_PENCIL;
-  const bool chord = lean && c->trace_mode == ISX_TRACE_CHORD;
-  const bool brdf = lean_surface && c->source_model == ISX_SOURCE_BRDF && c->trace_mode != ISX_TRACE_CHORD;
-  // what the assist-wave pipeline serves beyond that (round 5; `surface_pipeline` = 0: round 1's fused kernel as before): the
-  // origin-compat hit line (the assist wave writes the line the binning kernel is to see) and the two other border models with
-  // the pencil source -- the chord identity is a property of the Lambertian border, so trace_mode says nothing there
-  const bool sp = S.surface_pipeline != 0;
-  const bool p_lean = lambert && c->source_model == ISX_SOURCE_PENCIL && (!compat || sp);
-  const bool p_chord = p_lean && c->trace_mode == ISX_TRACE_CHORD;
-  const bool p_brdf = lambert && c->source_model == ISX_SOURCE_BRDF && c->trace_mode != ISX_TRACE_CHORD && (!compat || sp);
-  const bool p_lobe = sp && c->surface_model == ISX_SURFACE_LOBE && c->source_model == ISX_SOURCE_PENCIL;
-  const bool p_rough = sp && c->surface_model == ISX_SURFACE_ROBAST && !c->lambertian && c->source_model == ISX_SOURCE_PENCIL;
-  // kernel variant: lean builds serve the headline surface/source configuration, the full builds everything else
-  typedef void (*KernelFn)(const Geom, const DetGrid, const Work);
-  const bool lean_explicit = lean && !chord;
-  KernelFn fn;
-  switch (sink) {
-    case SINK_FLUX: fn = chord ? isx_trace_bin_chord_kernel : lean ? isx_trace_bin_kernel : brdf ? isx_trace_bin_brdf_kernel : isx_trace_bin_full_kernel; break;
-    case SINK_DZ: fn = lean_explicit ? isx_trace_dz_lean_kernel : isx_trace_dz_kernel; break;
-    case SINK_DISC: fn = lean_explicit ? isx_trace_disc_lean_kernel : isx_trace_disc_kernel; break;
-    case SINK_PERPOS: fn = lean_explicit ? isx_trace_perpos_lean_kernel : isx_trace_perpos_kernel; break;
-    case SINK_DISCPOS: fn = lean_explicit ? isx_trace_discpos_lean_kernel : isx_trace_discpos_kernel; break;
-    default: fn = lean_explicit ? isx_trace_log_lean_kernel : isx_trace_log_kernel; break;
-  }
-  // Workgroup shape.  The kernels that keep the 64.8 KB LDS histogram run one 1024-thread workgroup per CU (4 waves per SIMD,
-  // 128 VGPRs).  The lean trace-only kernels need 75-90 VGPRs and almost no LDS: as 512-thread workgroups they reach 5-6 waves
-  // per SIMD (measured: 18.8 -> 17.5 ms for 5e7 rays, 299 -> 282 ms for the 8.1e8-ray per-position map).
-  const bool small = lean_explicit && (sink == SINK_PERPOS || sink == SINK_DISCPOS || sink == SINK_DZ || sink == SINK_LOG);
-  const int block = small ? S.trace_block : kBlock;
-  auto span = [&](int kind, hipEvent_t* first_ev) -> int {   // [previous event, new event) is one kernel of `kind`
-    hipEvent_t e;
-    if (first_ev) { int r = get_event(first_ev); if (r) return r; HIPCHK(hipEventRecord(*first_ev, S.stream)); return ISX_OK; }
-    int r = get_event(&e); if (r) return r;
-    HIPCHK(hipEventRecord(e, S.stream));
-    S.spans.push_back({S.ev_used - 2, S.ev_used - 1, kind});
-    return ISX_OK;
-  };
-  hipEvent_t e0;
-  // ---- two-kernel pipeline (lean flux maps: headline, chord mode, BRDF source): trace kernel -> exit lines in HBM -> binning kernel, chunk by chunk
-  const bool pipe_assist = (p_lean || p_brdf || p_lobe || p_rough) && S.assist != 0;   // (the kernels without an assist wave know the lean cases only)
-  if (sink == SINK_FLUX && (lean || brdf || pipe_assist) && S.pipeline && S.bin_mode != 0) {
-    // trace kernel: with an assist wave per workgroup (ISX_ASSIST_BLOCK threads; isx_kernels.hpp: assist_body) or without
-    const bool assist = S.assist != 0;
-    const KernelFn rec_fn = assist ? (p_lobe ? isx_trace_assist_lobe_kernel : p_rough ? isx_trace_assist_rough_kernel :
-                                      p_chord ? isx_trace_assist_chord_kernel : p_brdf ? isx_trace_assist_brdf_kernel : isx_trace_assist_kernel)
-                                   : (chord ? isx_trace_rec_chord_kernel : brdf ? isx_trace_rec_brdf_kernel : isx_trace_rec_kernel);
-    const size_t lds_trace = 16 + 64 + sizeof(Geom) + sizeof(DetGrid) +
-                             (assist ? 16 + sizeof(AssistQueues) + (size_t)(kResumeCap + kPendCap) * 64 : 0);
-    const size_t lds_tables = (((size_t)d.nbins * 4 + 15) & ~(size_t)15) + (size_t)(4 * d.n_theta) * 8 + (size_t)(2 * d.n_phi) * sizeof(ColX) +
-                              sizeof(DetGrid) + 16;
-    // the binning kernel with slot queues (1024-thread workgroups: 61 KB of queues next to the histogram) if the grid fits its
-    // 32-bit slot records and the LDS; else the one without
-    const bool slots = S.bin_slots && S.bin_mode == 1 && d.n_theta <= 256 && d.n_phi <= 255 &&
-                       lds_tables + (size_t)(2 * d.n_phi) * sizeof(ColP) + (size_t)(kBlock / 64) * kSlotWaveWords * 4 <= S.lds_limit;
-    // ... and with COLUMN slots (default for every source since round 4: grazing lines are column slots as well -- prep_band;
-    // bin_cols = 0 keeps the row slots of isx_bin_slots_kernel)
-    const bool cols = slots && S.bin_cols &&
-                      lds_tables + (size_t)(d.n_theta + 4) * sizeof(RowX) + (size_t)(kBlock / 64) * kColWaveWords * 4 <= S.lds_limit;
-    typedef void (*BinFn)(const DetGrid, const Work);
-    const BinFn bin_fn = cols ? isx_bin_cols_kernel : slots ? isx_bin_slots_kernel : isx_bin_lines_kernel;
-    const uint64_t chunk0 = n < S.pipe_chunk ? n : S.pipe_chunk;
-    // (the lobe / rough-specular kernels hold 87-93 VGPRs -- four waves per SIMD -- and hand over as often as the lean one at a third
-    //  of its pace: 512-thread workgroups, 7 tracer waves per assist wave and two workgroups per CU, measured 47.1 against 48.3 ms
-    //  and 33.4 against 34.0 ms for 5e7 rays, profiles/r05_surface_shapes.json)
-    const int ablock = (!S.assist_block_set && (p_lobe || p_rough)) ? 512 : S.assist_block;
-    const Shape shp = assist ? small_shape(chunk0, ablock) : Shape{S.trace_block, 4};
-    const int pblock = shp.block, bblock = slots ? kBlock : S.bin_block;
-    const int ptracers = assist ? pblock / 64 - 1 : pblock / 64;
-    const size_t lds_bin = lds_tables + (cols ? (size_t)(d.n_theta + 4) * sizeof(RowX) + (size_t)(bblock / 64) * kColWaveWords * 4
-                                         : slots ? (size_t)(2 * d.n_phi) * sizeof(ColP) + (size_t)(bblock / 64) * kSlotWaveWords * 4 : (size_t)(bblock / 64) * 128 * 4);
-    if (lds_bin <= S.lds_limit) {
-      const uint64_t chunk = n < S.pipe_chunk ? n : S.pipe_chunk;
-      if (S.attr_lds[(const void*)rec_fn] != lds_trace) {   // (once per kernel and size, not once per launch)
-        HIPCHK(hipFuncSetAttribute((const void*)rec_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_trace));
-        S.attr_lds[(const void*)rec_fn] = lds_trace;
-      }
-      if (S.attr_lds[(const void*)bin_fn] != lds_bin) {
-        HIPCHK(hipFuncSetAttribute((const void*)bin_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bin));
-        S.attr_lds[(const void*)bin_fn] = lds_bin;
-      }
-      // grids: what is resident, fewer for a small chunk (>= 16 rays per lane; a region of exit lines per binning wave)
-      const int tres = S.trace_blocks_per_cu > 0 ? S.trace_blocks_per_cu : resident_per_cu(rec_fn, pblock, lds_trace);
-      const int bres = S.bin_blocks_per_cu > 0 ? S.bin_blocks_per_cu : resident_per_cu(bin_fn, bblock, lds_bin);
-      // one trace launch + one binning launch of `cnt` rays from `off`, through workspace `buf`, on streams st / sb
-      auto launch_pair = [&](uint64_t off, uint64_t cnt, int buf, hipStream_t st, hipStream_t sb, hipEvent_t traced) -> int {
-        if (cnt > kLaunchMax) return ISX_ERR_TOO_LARGE;   // (cannot happen: pipeline_chunk <= 2^26)
-        Work w2 = wk;
-        w2.first = first + off; w2.n = cnt; w2.sub = pick_sub(cnt);
-        // (work units of the binning kernel: quarter regions of 256 exit lines; sixteenths -- 64 lines, one batch -- for a small
-        //  launch, whose few thousand lines then spread over as many waves as there are batches)
-        w2.pad = cnt < 1000000ull ? 2u : 0u;
-        int r = next_ctr(&w2.ctr); if (r) return r;
-        DetGrid dt = d;              // the trace kernel keeps no histogram
-        dt.nbins = 1; dt.n_theta = 0; dt.n_phi = 0;
-        dt.rec_lines = S.d_rec[buf]; dt.rec_counts = S.d_rec_counts[buf];
-        const int tgrid = pick_grid(cnt, pblock, tres, ptracers, shp.rays_per_lane);
-        hipLaunchKernelGGL(rec_fn, dim3(tgrid), dim3(pblock), lds_trace, st, g, dt, w2);
-        HIPCHK(hipGetLastError());
-        if (traced) { HIPCHK(hipEventRecord(traced, st)); HIPCHK(hipStreamWaitEvent(sb, traced, 0)); }
-        else { r = span(1, nullptr); if (r) return r; }
-        if (compat && S.bin_mode != 2) {   // ISX_HITLINE_ORIGIN_COMPAT: the lines the binning kernel is to see (isx_compat_lines_kernel)
-          hipLaunchKernelGGL(isx_compat_lines_kernel, dim3(S.cu_count * 8), dim3(256), 0, sb, S.d_rec[buf], S.d_rec_counts[buf], w2.ctr);
-          HIPCHK(hipGetLastError());
-        }
-        if (S.bin_mode != 2) {       // bin_mode 2: diagnostic, trace only
-          DetGrid db = d;
-          db.rec_lines = S.d_rec[buf]; db.rec_counts = S.d_rec_counts[buf];
-          // work units of the binning kernel = quarter regions: at most cnt / 256 full ones + the open region every writing wave of
-          // the trace kernel leaves behind (one per workgroup with an assist wave) -- a wave per unit, a workgroup per bblock / 64 units
-          const uint64_t writers = assist ? (uint64_t)tgrid : (uint64_t)tgrid * (uint64_t)(pblock / 64);
-          const uint64_t units = cnt / (kRegion >> (2u + w2.pad)) + writers;
-          const uint64_t bwant = (units + (uint64_t)(bblock / 64) - 1) / (uint64_t)(bblock / 64);
-          const int bfull = S.cu_count * bres;
-          const int gb = S.grid_blocks > 0 ? S.grid_blocks : (bwant < (uint64_t)bfull ? (int)bwant : bfull);
-          hipLaunchKernelGGL(bin_fn, dim3(gb), dim3(bblock), lds_bin, sb, db, w2);
-          HIPCHK(hipGetLastError());
-          if (!traced) { r = span(2, nullptr); if (r) return r; }
-        }
-        return ISX_OK;
-      };
-      const int cgrid = pick_grid(chunk, pblock, tres, ptracers, shp.rays_per_lane);
-      if (S.overlap > 1 && S.bin_mode == 1 && n >= (uint64_t)S.overlap * 65536) {
-        // ---- overlapped: chunk k is binned on the second stream while chunk k+1 is traced on the first; chunk k+3 reuses the
-        // workspace of chunk k.  (Timing: one wall-clock span around everything; the kernels' own times overlap.)
-        if (!S.stream2) HIPCHK(hipStreamCreateWithFlags(&S.stream2, hipStreamNonBlocking));
-        if (!S.stream3) HIPCHK(hipStreamCreateWithFlags(&S.stream3, hipStreamNonBlocking));
-        const uint64_t per = ((n + (uint64_t)S.overlap - 1) / (uint64_t)S.overlap + 63) & ~63ull;
-        const uint64_t oc = per < S.pipe_chunk ? per : S.pipe_chunk;
-        const int ogrid = pick_grid(oc, pblock, tres, ptracers, shp.rays_per_lane);
-        for (int b = 0; b < State::kRecBufs; ++b) { rc = ensure_pipeline((size_t)oc, (size_t)ogrid * (pblock / 64), b); if (rc) return rc; }
-        rc = span(0, &e0); if (rc) return rc;
-        std::vector<hipEvent_t> binned;
-        HIPCHK(hipStreamWaitEvent(S.stream3, e0, 0));             // (what the caller enqueued before this call comes first)
-        int k = 0;
-        for (uint64_t off = 0; off < n; off += oc, ++k) {
-          hipEvent_t traced, done;
-          rc = get_event(&traced); if (rc) return rc;
-          rc = get_event(&done); if (rc) return rc;
-          const hipStream_t st = (S.overlap_trace_streams == 2 && (k & 1)) ? S.stream3 : S.stream;
-          if (k >= State::kRecBufs) HIPCHK(hipStreamWaitEvent(st, binned[k - State::kRecBufs], 0));
-          {   // the queue counters are zeroed on the stream that launches the trace kernel
-            const hipStream_t keep = S.stream;
-            S.stream = st;
-            rc = launch_pair(off, n - off < oc ? n - off : oc, k % State::kRecBufs, st, S.stream2, traced);
-            S.stream = keep;
-            if (rc) return rc;
-          }
-          HIPCHK(hipEventRecord(done, S.stream2));
-          binned.push_back(done);
-        }
-        HIPCHK(hipStreamWaitEvent(S.stream, binned.back(), 0));   // the caller's stream sees the finished histogram
-        hipEvent_t e1;
-        rc = get_event(&e1); if (rc) return rc;
-        HIPCHK(hipEventRecord(e1, S.stream));
-        size_t ia = 0, ib = 0;
-        for (size_t i = 0; i < S.ev_used; ++i) { if (S.ev_pool[i] == e0) ia = i; if (S.ev_pool[i] == e1) ib = i; }
-        S.spans.push_back({ia, ib, 0});
-        return ISX_OK;
-      }
-      rc = ensure_pipeline((size_t)chunk, (size_t)cgrid * (pblock / 64));
-      if (rc) return rc;
-      rc = span(0, &e0); if (rc) return rc;
-      for (uint64_t off = 0; off < n; off += chunk) {
-        rc = launch_pair(off, n - off < chunk ? n - off : chunk, 0, S.stream, S.stream, nullptr); if (rc) return rc;
-      }
-      return ISX_OK;
-    }
-  }
-  // ---- the shared-ray disc sweep as a pipeline as well: assist-wave trace kernel -> exit segments in HBM (8 doubles each) ->
-  // disc-binning kernel (lane = segment, the discs one after the other)
-  // (a disc list whose histogram + cluster table + per-wave lists exceed the workgroup's LDS -- above ~16 000 discs on gfx950 --
-  //  takes the fused SINK_DISC kernel below, which needs the histogram only)
-  const size_t lds_disc_bin = (((size_t)d.nbins * 4 + 15) & ~(size_t)15) + (size_t)g_disc_clusters.n_clusters * 16 +
-                              (d.nbins <= kDiscsInLds ? (size_t)d.nbins * 48 + (size_t)((d.nbins + 1) & ~1) * 4 : 0) +
-                              (size_t)(kDiscBinBlock / 64) * (64 * 7 + kPairCap / 2) * sizeof(double);
-  if (sink == SINK_DISC && lean_explicit && S.pipeline && S.assist && S.disc_pipeline && g_disc_clusters.n == (size_t)d.nbins &&
-      d_discs == S.d_aux && lds_disc_bin <= S.lds_limit) {
-    const Shape shp = small_shape(n < S.pipe_chunk ? n : S.pipe_chunk, S.assist_block);
-    const int pblock = shp.block, bblock = kDiscBinBlock;
-    const size_t lds_trace = 16 + 64 + sizeof(Geom) + sizeof(DetGrid) + 16 + sizeof(AssistQueues) + (size_t)(kResumeCap + kPendCap) * 64;
-    const size_t lds_bin = lds_disc_bin;
-    const KernelFn rec_fn = isx_trace_assist_disc_kernel;
-    if (S.attr_lds[(const void*)rec_fn] != lds_trace) {
-      HIPCHK(hipFuncSetAttribute((const void*)rec_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_trace));
-      S.attr_lds[(const void*)rec_fn] = lds_trace;
-    }
-    if (S.attr_lds[(const void*)isx_bin_discs_kernel] != lds_bin) {
-      HIPCHK(hipFuncSetAttribute((const void*)isx_bin_discs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bin));
-      S.attr_lds[(const void*)isx_bin_discs_kernel] = lds_bin;
-    }
-    const int tres = resident_per_cu(rec_fn, pblock, lds_trace), bres = resident_per_cu(isx_bin_discs_kernel, bblock, lds_bin);
-    const uint64_t chunk = n < S.pipe_chunk ? n : S.pipe_chunk;
-    rc = ensure_pipeline((size_t)chunk, (size_t)pick_grid(chunk, pblock, tres, pblock / 64 - 1, shp.rays_per_lane) * (pblock / 64), 0, 8);
-    if (rc) return rc;
-    rc = span(0, &e0); if (rc) return rc;
-    for (uint64_t off = 0; off < n; off += chunk) {
-      const uint64_t cnt = n - off < chunk ? n - off : chunk;
-      if (cnt > kLaunchMax) return ISX_ERR_TOO_LARGE;     // (cannot happen: pipeline_chunk <= 2^26)
-      Work w2 = wk;
-      w2.first = first + off; w2.n = cnt; w2.sub = pick_sub(cnt);
-      w2.pad = cnt < 1000000ull ? 2u : 0u;   // (64-segment work units for a small launch, as for the flux maps)
-      rc = next_ctr(&w2.ctr); if (rc) return rc;
-      DetGrid dt = d;
-      dt.rec_lines = S.d_rec[0]; dt.rec_counts = S.d_rec_counts[0];
-      dt.discs = S.d_aux + g_disc_clusters.off_ordered;              // (the binning kernel walks the discs in cluster order)
-      dt.clusters = reinterpret_cast<const float*>(S.d_aux + g_disc_clusters.off_clusters);
-      dt.disc_perm = reinterpret_cast<const int*>(S.d_aux + g_disc_clusters.off_perm);
-      dt.n_clusters = g_disc_clusters.n_clusters;
-      const int tgrid = pick_grid(cnt, pblock, tres, pblock / 64 - 1, shp.rays_per_lane);
-      hipLaunchKernelGGL(rec_fn, dim3(tgrid), dim3(pblock), lds_trace, S.stream, g, dt, w2);
-      HIPCHK(hipGetLastError());
-      rc = span(1, nullptr); if (rc) return rc;
-      const uint64_t bwant = (cnt / (kRegion >> (2u + w2.pad)) + (uint64_t)tgrid + (uint64_t)(bblock / 64) - 1) / (uint64_t)(bblock / 64);   // (work units per workgroup, as above)
-      const int bfull = S.cu_count * bres;
-      const int gb = S.grid_blocks > 0 ? S.grid_blocks : (bwant < (uint64_t)bfull ? (int)bwant : bfull);
-      hipLaunchKernelGGL(isx_bin_discs_kernel, dim3(gb), dim3(bblock), lds_bin, S.stream, dt, w2);
-      HIPCHK(hipGetLastError());
-      rc = span(2, nullptr); if (rc) return rc;
-    }
-    return ISX_OK;
-  }
-  // ---- the per-position sinks (one launch for all positions: the reference's 12 524 s map, the macro's own disc loop) with an
-  // assist wave per workgroup as well: the one exact test per exiting ray is per-lane work the assist wave does on the spot
-  // (round 5: the lobe / rough-specular borders as well -- SINK_PERPOS only, last-segment hit line: the assist wave's exact test takes
-  //  the line as it is)
-  const bool pp_surface = sink == SINK_PERPOS && (p_lobe || p_rough) && !compat;
-  if ((sink == SINK_PERPOS || sink == SINK_DISCPOS) && (lean_explicit || pp_surface) && S.pipeline && S.assist) {
-    const KernelFn afn = sink == SINK_DISCPOS ? isx_trace_assist_discpos_kernel :
-                         (pp_surface ? (p_lobe ? isx_trace_assist_perpos_lobe_kernel : isx_trace_assist_perpos_rough_kernel) : isx_trace_assist_perpos_kernel);
-    const Shape shp = small_shape(n < kLaunchMax ? n : kLaunchMax, (!S.assist_block_set && pp_surface) ? 512 : S.assist_block);
-    const int pblock = shp.block;
-    const size_t lds_trace = 16 + 64 + sizeof(Geom) + sizeof(DetGrid) + 16 + sizeof(AssistQueues) + (size_t)(kResumeCap + kPendCap) * 64;
-    if (S.attr_lds[(const void*)afn] != lds_trace) {
-      HIPCHK(hipFuncSetAttribute((const void*)afn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_trace));
-      S.attr_lds[(const void*)afn] = lds_trace;
-    }
-    const int tres = S.trace_blocks_per_cu > 0 ? S.trace_blocks_per_cu : resident_per_cu(afn, pblock, lds_trace);
-    rc = span(0, &e0); if (rc) return rc;
-    for (uint64_t off = 0; off < n; off += kLaunchMax) {
-      Work w2 = wk;
-      w2.first = first + off; w2.n = n - off < kLaunchMax ? n - off : kLaunchMax; w2.sub = pick_sub(w2.n);
-      rc = next_ctr(&w2.ctr); if (rc) return rc;
-      hipLaunchKernelGGL(afn, dim3(pick_grid(w2.n, pblock, tres, pblock / 64 - 1, shp.rays_per_lane)), dim3(pblock), lds_trace, S.stream, g, d, w2);
-      HIPCHK(hipGetLastError());
-    }
-    return span(0, nullptr);
-  }
-  if (S.attr_lds[(const void*)fn] != lds) {
-    HIPCHK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    S.attr_lds[(const void*)fn] = lds;
-  }
-  const int bpc = small ? (S.trace_blocks_per_cu > 0 ? S.trace_blocks_per_cu : resident_per_cu(fn, block, lds)) : 0;
-  rc = span(0, &e0); if (rc) return rc;
-  for (uint64_t off = 0; off < n; off += kLaunchMax) {
-    Work w2 = wk;
-    w2.first = first + off; w2.n = n - off < kLaunchMax ? n - off : kLaunchMax; w2.sub = pick_sub(w2.n);
-    rc = next_ctr(&w2.ctr); if (rc) return rc;
-    hipLaunchKernelGGL(fn, dim3(pick_grid(w2.n, block, bpc)), dim3(block), lds, S.stream, g, d, w2);
-    HIPCHK(hipGetLastError());
-  }
-  return span(0, nullptr);
+  const Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n);
+  return p.route == ROUTE_FLUX_PIPE || p.route == ROUTE_DISC_PIPE ? run_pipeline(p, g, d, wk) : run_single(p, g, d, wk);
 }
 
 // device copy of a caller's detector / disc list in the pooled buffer (no hipMalloc/hipFree per call)
@@ -699,11 +745,12 @@ int upload_aux(const double* host, size_t n_doubles) {
   }
   if (n_doubles * sizeof(double) <= 4096 && ensure_pin(1u << 17) == ISX_OK) {
     // a short list (traceRays' one detector): through the far end of the pinned staging buffer -- the copy engine reads it when the
-    // stream gets there, the caller's `host` is free at once, and nothing waits (every blocking call ends with a synchronisation,
-    // so the next call cannot overwrite it too early)
+    // stream gets there, the caller's `host` is free at once, and nothing waits (S.pending: the call ends through collect_stats, or
+    // else the next call's opening one synchronises before anything writes the slot again)
     unsigned char* slot = S.h_pin + S.cap_pin - 4096;
     std::memcpy(slot, host, n_doubles * sizeof(double));
     HIPCHK(hipMemcpyAsync(S.d_aux, slot, n_doubles * sizeof(double), hipMemcpyHostToDevice, S.stream));
+    S.pending = true;
     return ISX_OK;
   }
   HIPCHK(hipMemcpyAsync(S.d_aux, host, n_doubles * sizeof(double), hipMemcpyHostToDevice, S.stream));
@@ -768,23 +815,6 @@ int upload_discs_clustered(const double* ca, size_t n, double radius, double hal
   return ISX_OK;
 }
 
-// workspace of the two-kernel pipeline for a chunk of `rays` rays traced by `waves` waves: every region but a wave's last is
-// closed with more than kRegion - 64 lines in it, and a launch cannot have more lines than rays (isx_kernels.hpp: kRegion)
-int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles) {
-  const size_t regions = (rays / (kRegion - 63) + waves + 1) * slot_doubles / 6 + 1;   // (capacity is counted in 6-double slots)
-  if (regions > S.cap_regions[buf]) {
-    HIPCHK(hipStreamSynchronize(S.stream));
-    if (S.stream2) HIPCHK(hipStreamSynchronize(S.stream2));
-    if (S.d_rec[buf]) HIPCHK(hipFree(S.d_rec[buf]));
-    if (S.d_rec_counts[buf]) HIPCHK(hipFree(S.d_rec_counts[buf]));
-    S.d_rec[buf] = nullptr; S.d_rec_counts[buf] = nullptr; S.cap_regions[buf] = 0;
-    HIPCHK(hipMalloc(&S.d_rec[buf], regions * kRegion * 6 * sizeof(double)));
-    HIPCHK(hipMalloc(&S.d_rec_counts[buf], regions * sizeof(uint32_t)));
-    S.cap_regions[buf] = regions;
-  }
-  return ISX_OK;
-}
-
 int ensure_hist(size_t nb) {
   if (nb > S.cap_hist) {
     HIPCHK(hipStreamSynchronize(S.stream));
@@ -826,6 +856,17 @@ int collect_stats(isx_stats* out) {
   }
   return ISX_OK;
 }
+
+// The lifecycle of every blocking call.  call_open(): room for its histogram (`bins` words), after collecting the census of
+// anything enqueued earlier so that it does not leak into this call.  Once call_open() has succeeded the call ends through
+// call_close(), on success and on failure alike: the census, with the call's one synchronisation, which also completes its
+// uploads, launches and result copies -- nothing of a failed call is left in flight.  The first error is the call's.
+int call_open(size_t bins) {
+  const int rc = ensure_hist(bins);
+  return rc ? rc : collect_stats(nullptr);
+}
+int zero_hist(size_t bins) { return hip_rc(hipMemsetAsync(S.d_hist, 0, bins * sizeof(unsigned long long), S.stream)); }
+int call_close(int rc, isx_stats* stats) { const int rc2 = collect_stats(stats); return rc ? rc : rc2; }
 
 }  // namespace
 
@@ -1008,19 +1049,14 @@ int isx_fluxmap(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t 
   if (!cfg || !hits) return ISX_ERR_BAD_ARG;
   int rc = check_grid(cfg);
   if (rc) return rc;
-  const size_t nb = (size_t)cfg->n_theta * cfg->n_phi;
-  rc = ensure_hist(nb);
+  const size_t nb = (size_t)cfg->n_theta * cfg->n_phi, bytes = nb * sizeof(unsigned long long);
+  rc = call_open(nb);
   if (rc) return rc;
-  // census of anything enqueued earlier must not leak into this call
-  rc = collect_stats(nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemsetAsync(S.d_hist, 0, nb * sizeof(unsigned long long), S.stream));
-  rc = enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, S.d_hist, 0, nullptr, 0, 0);
-  if (rc) return rc;
-  rc = stage_result(S.d_hist, nb * sizeof(unsigned long long));
-  if (rc) return rc;
-  rc = collect_stats(stats);
-  if (rc == ISX_OK) fetch_result(hits, nb * sizeof(unsigned long long));
+  rc = zero_hist(nb);
+  if (rc == ISX_OK) rc = enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, S.d_hist, 0, nullptr, 0, 0);
+  if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK) fetch_result(hits, bytes);
   return rc;
 }
 
@@ -1085,21 +1121,14 @@ int isx_disc_sweep(const isx_config* cfg, const double* centers_axes, int32_t n_
   if (!cfg || !centers_axes || !hits || n_disc < 1) return ISX_ERR_BAD_ARG;
   if (cfg->source_model != ISX_SOURCE_PENCIL) return ISX_ERR_BAD_CONFIG;
   if (!(radius > 0) || !(half_thick > 0)) return ISX_ERR_BAD_ARG;
-  int rc = ensure_hist((size_t)n_disc);
-  if (rc) return rc;
-  rc = collect_stats(nullptr);
+  int rc = call_open((size_t)n_disc);
   if (rc) return rc;
   g_disc_clusters = DiscClusters();
   rc = S.disc_pipeline ? upload_discs_clustered(centers_axes, (size_t)n_disc, radius, half_thick) : upload_aux(centers_axes, (size_t)n_disc * 6);
-  if (rc) return rc;
-  HIPCHK(hipMemsetAsync(S.d_hist, 0, (size_t)n_disc * sizeof(unsigned long long), S.stream));
-  rc = enqueue(SINK_DISC, cfg, n_rays, seed, first_ray, S.d_hist, n_disc, S.d_aux, radius, half_thick);
-  if (rc == ISX_OK) {
-    const hipError_t e = hipMemcpyAsync(hits, S.d_hist, (size_t)n_disc * sizeof(unsigned long long), hipMemcpyDeviceToHost, S.stream);
-    if (e != hipSuccess) { S.last_hip = (int)e; rc = ISX_ERR_HIP; }
-  }
-  const int rc2 = collect_stats(stats);
-  return rc ? rc : rc2;
+  if (rc == ISX_OK) rc = zero_hist((size_t)n_disc);
+  if (rc == ISX_OK) rc = enqueue(SINK_DISC, cfg, n_rays, seed, first_ray, S.d_hist, n_disc, S.d_aux, radius, half_thick);
+  if (rc == ISX_OK) rc = copy_out(hits, S.d_hist, (size_t)n_disc * sizeof(unsigned long long));
+  return call_close(rc, stats);
 }
 
 int isx_disc_sweep_per_position(const isx_config* cfg, const double* centers_axes, int32_t n_disc, double radius,
@@ -1110,23 +1139,16 @@ int isx_disc_sweep_per_position(const isx_config* cfg, const double* centers_axe
   if (cfg->source_model != ISX_SOURCE_PENCIL) return ISX_ERR_BAD_CONFIG;
   if (!(radius > 0) || !(half_thick > 0)) return ISX_ERR_BAD_ARG;
   if ((uint64_t)n_disc > ISX_MAX_RAYS_PER_CALL / rays_per_position) return ISX_ERR_TOO_LARGE;
-  int rc = ensure_hist((size_t)n_disc);
-  if (rc) return rc;
-  rc = collect_stats(nullptr);
+  int rc = call_open((size_t)n_disc);
   if (rc) return rc;
   rc = upload_aux(centers_axes, (size_t)n_disc * 6);
-  if (rc) return rc;
-  HIPCHK(hipMemsetAsync(S.d_hist, 0, (size_t)n_disc * sizeof(unsigned long long), S.stream));
-  PerPos pp;
-  pp.map_first = first_ray; pp.rays_per_group = rays_per_position; pp.fold = 1;
-  rc = enqueue(SINK_DISCPOS, cfg, (uint64_t)n_disc * rays_per_position, seed, first_ray, S.d_hist, n_disc, S.d_aux, radius,
-               half_thick, &pp);
-  if (rc == ISX_OK) {
-    const hipError_t e = hipMemcpyAsync(hits, S.d_hist, (size_t)n_disc * sizeof(unsigned long long), hipMemcpyDeviceToHost, S.stream);
-    if (e != hipSuccess) { S.last_hip = (int)e; rc = ISX_ERR_HIP; }
-  }
-  const int rc2 = collect_stats(stats);
-  return rc ? rc : rc2;
+  if (rc == ISX_OK) rc = zero_hist((size_t)n_disc);
+  const PerPos pp{first_ray, rays_per_position, 1};
+  if (rc == ISX_OK)
+    rc = enqueue(SINK_DISCPOS, cfg, (uint64_t)n_disc * rays_per_position, seed, first_ray, S.d_hist, n_disc, S.d_aux, radius,
+                 half_thick, &pp);
+  if (rc == ISX_OK) rc = copy_out(hits, S.d_hist, (size_t)n_disc * sizeof(unsigned long long));
+  return call_close(rc, stats);
 }
 
 int isx_fluxmap_per_position(const isx_config* cfg, uint64_t rays_per_position, int32_t fold, uint64_t first_group,
@@ -1140,40 +1162,33 @@ int isx_fluxmap_per_position(const isx_config* cfg, uint64_t rays_per_position, 
   const uint64_t groups_total = nb / (uint64_t)fold;
   if (first_group > groups_total || n_groups > groups_total - first_group) return ISX_ERR_BAD_ARG;
   if (n_groups > ISX_MAX_RAYS_PER_CALL / rays_per_position) return ISX_ERR_TOO_LARGE;
-  rc = ensure_hist(nb);
+  rc = call_open(nb);
   if (rc) return rc;
-  rc = collect_stats(nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemsetAsync(S.d_hist, 0, nb * sizeof(unsigned long long), S.stream));
-  PerPos pp;
-  pp.map_first = first_ray; pp.rays_per_group = rays_per_position; pp.fold = fold;
-  rc = enqueue(SINK_PERPOS, cfg, n_groups * rays_per_position, seed, first_ray + first_group * rays_per_position,
-               S.d_hist, 0, nullptr, 0, 0, &pp);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(hits, S.d_hist, nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, S.stream));
-  return collect_stats(stats);
+  const PerPos pp{first_ray, rays_per_position, fold};
+  rc = zero_hist(nb);
+  if (rc == ISX_OK)
+    rc = enqueue(SINK_PERPOS, cfg, n_groups * rays_per_position, seed, first_ray + first_group * rays_per_position,
+                 S.d_hist, 0, nullptr, 0, 0, &pp);
+  if (rc == ISX_OK) rc = copy_out(hits, S.d_hist, nb * sizeof(unsigned long long));
+  return call_close(rc, stats);
 }
 
 int isx_trace_rays_detector(const isx_config* cfg, const double* detector, double width, uint64_t n_rays, uint64_t seed,
                             uint64_t first_ray, uint64_t* hit_count, isx_stats* stats) {
   if (!S.init) return ISX_ERR_NOT_INIT;
   if (!cfg || !detector || !hit_count || !(width > 0)) return ISX_ERR_BAD_ARG;
-  int rc = ensure_hist(1);
-  if (rc) return rc;
-  rc = collect_stats(nullptr);
+  int rc = call_open(1);
   if (rc) return rc;
   rc = upload_aux(detector, 6);
-  if (rc) return rc;
-  HIPCHK(hipMemsetAsync(S.d_hist, 0, sizeof(unsigned long long), S.stream));
-  PerPos pp;
-  pp.map_first = first_ray; pp.rays_per_group = n_rays > 0 ? n_rays : 1; pp.fold = 1; pp.d_table = S.d_aux; pp.width = width;
-  rc = enqueue(SINK_PERPOS, cfg, n_rays, seed, first_ray, S.d_hist, 1, nullptr, 0, 0, &pp);
+  if (rc == ISX_OK) rc = zero_hist(1);
+  const PerPos pp{first_ray, n_rays > 0 ? n_rays : 1, 1, S.d_aux, width};   // (S.d_aux: after the upload, which may move it)
+  if (rc == ISX_OK) rc = enqueue(SINK_PERPOS, cfg, n_rays, seed, first_ray, S.d_hist, 1, nullptr, 0, 0, &pp);
   unsigned long long h = 0;
   if (rc == ISX_OK) rc = stage_result(S.d_hist, sizeof(h));
-  const int rc2 = collect_stats(stats);
-  if (rc == ISX_OK && rc2 == ISX_OK) fetch_result(&h, sizeof(h));
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK) fetch_result(&h, sizeof(h));
   *hit_count = h;
-  return rc ? rc : rc2;
+  return rc;
 }
 
 int isx_exit_directions(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t first_ray, uint64_t capacity,
@@ -1183,46 +1198,36 @@ int isx_exit_directions(const isx_config* cfg, uint64_t n_rays, uint64_t seed, u
   // no more records than rays, and the 32-byte records of one call must stay addressable (ISX_MAX_LOG_RECORDS)
   if (capacity > n_rays && n_rays > 0) capacity = n_rays;
   if (capacity > ISX_MAX_LOG_RECORDS) return ISX_ERR_TOO_LARGE;
-  int rc = ensure_hist(1);
+  int rc = call_open(1);
   if (rc) return rc;
-  rc = collect_stats(nullptr);
-  if (rc) return rc;
-  double* d_rec = nullptr;
-  unsigned long long* d_cnt = nullptr;
-  HIPCHK(hipMalloc(&d_rec, capacity * 32));
-  hipError_t e = hipMalloc(&d_cnt, 8);
-  if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, 8, S.stream);
-  if (e == hipSuccess) e = hipMemsetAsync(S.d_hist, 0, 8, S.stream);
-  if (e != hipSuccess) { (void)hipFree(d_rec); if (d_cnt) (void)hipFree(d_cnt); S.last_hip = (int)e; return ISX_ERR_HIP; }
-  LogSink lg;
-  lg.rec = d_rec; lg.count = d_cnt; lg.cap = capacity;
-  rc = enqueue(SINK_LOG, cfg, n_rays, seed, first_ray, S.d_hist, 0, nullptr, 0, 0, nullptr, &lg);
+  DevBuf<double> d_rec;               // 4 doubles per record: ray index (bits), direction
+  DevBuf<unsigned long long> d_cnt;
+  rc = hip_rc(d_rec.alloc(capacity * 4));
+  if (rc == ISX_OK) rc = hip_rc(d_cnt.alloc(1));
+  if (rc == ISX_OK) rc = hip_rc(hipMemsetAsync(d_cnt.p, 0, 8, S.stream));
+  if (rc == ISX_OK) rc = zero_hist(1);
+  const LogSink lg{d_rec.p, d_cnt.p, capacity};
+  if (rc == ISX_OK) rc = enqueue(SINK_LOG, cfg, n_rays, seed, first_ray, S.d_hist, 0, nullptr, 0, 0, nullptr, &lg);
   unsigned long long total = 0;
-  std::vector<double> rec;
+  if (rc == ISX_OK) rc = hip_rc(hipStreamSynchronize(S.stream));
+  if (rc == ISX_OK) rc = hip_rc(hipMemcpy(&total, d_cnt.p, 8, hipMemcpyDeviceToHost));
+  const uint64_t kept = total < capacity ? total : capacity;
+  std::vector<double> rec(rc == ISX_OK ? kept * 4 : 0);
+  if (rc == ISX_OK && kept) rc = hip_rc(hipMemcpy(rec.data(), d_rec.p, kept * 32, hipMemcpyDeviceToHost));
   if (rc == ISX_OK) {
-    e = hipStreamSynchronize(S.stream);
-    if (e == hipSuccess) e = hipMemcpy(&total, d_cnt, 8, hipMemcpyDeviceToHost);
-    const uint64_t kept = total < capacity ? total : capacity;
-    rec.resize(kept * 4);
-    if (e == hipSuccess && kept) e = hipMemcpy(rec.data(), d_rec, kept * 32, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { S.last_hip = (int)e; rc = ISX_ERR_HIP; }
-    else {
-      // slots are handed out in completion order: sort by ray index so the log is reproducible
-      std::vector<size_t> order(kept);
-      for (size_t k = 0; k < kept; ++k) order[k] = k;
-      auto id_of = [&](size_t k) { uint64_t v; std::memcpy(&v, &rec[4 * k], 8); return v; };
-      std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return id_of(a) < id_of(b); });
-      for (size_t k = 0; k < kept; ++k) {
-        const size_t o = order[k];
-        ray_ids[k] = id_of(o);
-        directions[3 * k] = rec[4 * (size_t)o + 1]; directions[3 * k + 1] = rec[4 * (size_t)o + 2]; directions[3 * k + 2] = rec[4 * (size_t)o + 3];
-      }
+    // slots are handed out in completion order: sort by ray index so the log is reproducible
+    std::vector<size_t> order(kept);
+    for (size_t k = 0; k < kept; ++k) order[k] = k;
+    auto id_of = [&](size_t k) { uint64_t v; std::memcpy(&v, &rec[4 * k], 8); return v; };
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return id_of(a) < id_of(b); });
+    for (size_t k = 0; k < kept; ++k) {
+      const size_t o = order[k];
+      ray_ids[k] = id_of(o);
+      directions[3 * k] = rec[4 * (size_t)o + 1]; directions[3 * k + 1] = rec[4 * (size_t)o + 2]; directions[3 * k + 2] = rec[4 * (size_t)o + 3];
     }
   }
   *count = total;
-  const int rc2 = collect_stats(stats);
-  (void)hipFree(d_rec); (void)hipFree(d_cnt);
-  return rc ? rc : rc2;
+  return call_close(rc, stats);
 }
 
 int isx_fluxmap_series(const isx_config* cfgs, int32_t n_cfg, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
@@ -1234,30 +1239,23 @@ int isx_fluxmap_series(const isx_config* cfgs, int32_t n_cfg, uint64_t n_rays, u
   for (int k = 1; k < n_cfg; ++k)
     if (!same_grid(cfgs[0], cfgs[k]) || cfgs[k].det_diameter != cfgs[0].det_diameter) return ISX_ERR_BAD_CONFIG;
   const size_t nb = (size_t)cfgs[0].n_theta * cfgs[0].n_phi;
-  rc = ensure_hist(nb * (size_t)n_cfg);
+  rc = call_open(nb * (size_t)n_cfg);
   if (rc) return rc;
-  rc = collect_stats(nullptr);
-  if (rc) return rc;
-  unsigned long long* d_st = nullptr;
-  HIPCHK(hipMalloc(&d_st, (size_t)n_cfg * 8 * sizeof(unsigned long long)));
-  hipError_t e = hipMemsetAsync(d_st, 0, (size_t)n_cfg * 64, S.stream);
-  if (e == hipSuccess) e = hipMemsetAsync(S.d_hist, 0, nb * (size_t)n_cfg * sizeof(unsigned long long), S.stream);
-  if (e != hipSuccess) { (void)hipFree(d_st); S.last_hip = (int)e; return ISX_ERR_HIP; }
+  DevBuf<unsigned long long> d_st;   // the census of each configuration
+  rc = hip_rc(d_st.alloc((size_t)n_cfg * 8));
+  if (rc == ISX_OK) rc = hip_rc(hipMemsetAsync(d_st.p, 0, (size_t)n_cfg * 64, S.stream));
+  if (rc == ISX_OK) rc = zero_hist(nb * (size_t)n_cfg);
   // every configuration is enqueued back to back (no host round trip in between); configuration k
   // uses the ray indices [first_ray + k*n_rays, +n_rays) so the maps are statistically independent
   for (int k = 0; k < n_cfg && rc == ISX_OK; ++k)
     rc = enqueue(SINK_FLUX, &cfgs[k], n_rays, seed, first_ray + (uint64_t)k * n_rays, S.d_hist + (size_t)k * nb, 0, nullptr,
-                 0, 0, nullptr, nullptr, d_st + (size_t)k * 8);
+                 0, 0, nullptr, nullptr, d_st.p + (size_t)k * 8);
   std::vector<unsigned long long> hst((size_t)n_cfg * 8);
-  if (rc == ISX_OK) {
-    e = hipMemcpyAsync(hits, S.d_hist, nb * (size_t)n_cfg * sizeof(unsigned long long), hipMemcpyDeviceToHost, S.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hst.data(), d_st, hst.size() * 8, hipMemcpyDeviceToHost, S.stream);
-    if (e != hipSuccess) { S.last_hip = (int)e; rc = ISX_ERR_HIP; }
-  }
+  if (rc == ISX_OK) rc = copy_out(hits, S.d_hist, nb * (size_t)n_cfg * sizeof(unsigned long long));
+  if (rc == ISX_OK) rc = copy_out(hst.data(), d_st.p, hst.size() * 8);
   isx_stats tot;
-  const int rc2 = collect_stats(&tot);   // syncs; tot.t_kernel_ms = all launches
-  (void)hipFree(d_st);
-  if (rc == ISX_OK && rc2 == ISX_OK && stats) {
+  rc = call_close(rc, &tot);   // tot.t_kernel_ms = all launches
+  if (rc == ISX_OK && stats) {
     for (int k = 0; k < n_cfg; ++k) {
       const unsigned long long* h = &hst[(size_t)k * 8];
       stats[k].launched = h[0]; stats[k].exited = h[1]; stats[k].counted_below_z = h[2]; stats[k].absorbed = h[3];
@@ -1265,22 +1263,19 @@ int isx_fluxmap_series(const isx_config* cfgs, int32_t n_cfg, uint64_t n_rays, u
       stats[k].t_kernel_ms = tot.t_kernel_ms;  // total of the series (launches are not timed separately)
     }
   }
-  return rc ? rc : rc2;
+  return rc;
 }
 
 int isx_exit_dz_hist(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t first_ray, int32_t nbins,
                      uint64_t* hist, isx_stats* stats) {
   if (!S.init) return ISX_ERR_NOT_INIT;
   if (!cfg || !hist || nbins < 1) return ISX_ERR_BAD_ARG;
-  int rc = ensure_hist((size_t)nbins);
+  int rc = call_open((size_t)nbins);
   if (rc) return rc;
-  rc = collect_stats(nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemsetAsync(S.d_hist, 0, (size_t)nbins * sizeof(unsigned long long), S.stream));
-  rc = enqueue(SINK_DZ, cfg, n_rays, seed, first_ray, S.d_hist, nbins, nullptr, 0, 0);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(hist, S.d_hist, (size_t)nbins * sizeof(unsigned long long), hipMemcpyDeviceToHost, S.stream));
-  return collect_stats(stats);
+  rc = zero_hist((size_t)nbins);
+  if (rc == ISX_OK) rc = enqueue(SINK_DZ, cfg, n_rays, seed, first_ray, S.d_hist, nbins, nullptr, 0, 0);
+  if (rc == ISX_OK) rc = copy_out(hist, S.d_hist, (size_t)nbins * sizeof(unsigned long long));
+  return call_close(rc, stats);
 }
 
 #ifdef ISX_DIAG
