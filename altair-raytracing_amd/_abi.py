@@ -32,6 +32,7 @@ EXPORTS = [
     "isx_set_option", "isx_mathprobe", "isx_trace_endstates", "isx_disc_sweep", "isx_detector_table",
     "isx_exit_dz_hist", "isx_fluxmap_per_position", "isx_trace_rays_detector", "isx_exit_directions",
     "isx_fluxmap_series", "isx_disc_sweep_per_position", "isx_last_kernel_ms",
+    "isx_default_exit_map_spec", "isx_exit_maps", "isx_exit_maps_device",
 ]
 
 
@@ -77,6 +78,30 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ExitMapSpec(C.Structure):
+    """isx_exit_map_spec (include/isx.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved0", C.c_uint32),
+        ("n_u", C.c_int32), ("n_v", C.c_int32), ("n_x", C.c_int32), ("n_y", C.c_int32),
+        ("plane_z", C.c_double), ("half_extent", C.c_double),
+    ]
+
+    def copy(self):
+        s = ExitMapSpec()
+        C.memmove(C.byref(s), C.byref(self), C.sizeof(ExitMapSpec))
+        return s
+
+
+class ExitMapCounts(C.Structure):
+    """isx_exit_map_counts (include/isx.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in ("dir_binned", "dir_outside", "pos_binned", "pos_outside", "upward")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -113,6 +138,10 @@ def load():
     L.isx_trace_rays_detector.argtypes = [P(Config), P(dbl), dbl, u64, u64, u64, P(u64), P(Stats)]
     L.isx_exit_directions.argtypes = [P(Config), u64, u64, u64, u64, P(u64), P(dbl), P(u64), P(Stats)]
     L.isx_fluxmap_series.argtypes = [P(Config), i32, u64, u64, u64, P(u64), P(Stats)]
+    L.isx_default_exit_map_spec.argtypes = [P(Config), P(ExitMapSpec)]
+    L.isx_default_exit_map_spec.restype = None
+    L.isx_exit_maps.argtypes = [P(Config), P(ExitMapSpec), u64, u64, u64, P(u64), P(u64), P(ExitMapCounts), P(Stats)]
+    L.isx_exit_maps_device.argtypes = [P(Config), P(ExitMapSpec), u64, u64, u64, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -256,6 +285,37 @@ def exit_directions(cfg, n_rays, seed, first_ray=0, capacity=None):
                                     _p(d, C.c_double), C.byref(cnt), C.byref(st)), "isx_exit_directions")
     k = min(int(cnt.value), cap)
     return ids[:k], d[:k], int(cnt.value), st
+
+
+def default_exit_map_spec(cfg):
+    """128 x 128 direction bins, 64 x 64 plane bins at the port plane over the port radius + 25 % (no GPU needed)."""
+    s = ExitMapSpec()
+    load().isx_default_exit_map_spec(C.byref(cfg), C.byref(s))
+    return s
+
+
+def exit_maps(cfg, n_rays, seed, spec=None, first_ray=0):
+    """-> (dir_map[n_v, n_u], pos_map[n_y, n_x] uint64, ExitMapCounts, Stats): the 2-D histogram of the exit direction
+    (dx, dy) and of the point where the exit line crosses the plane z = spec.plane_z (include/isx.h).  A map the spec
+    does not want comes back with shape (0, 0)."""
+    if spec is None:
+        spec = default_exit_map_spec(cfg)
+    dmap = np.zeros(max(spec.n_u * spec.n_v, 0), dtype=np.uint64)
+    pmap = np.zeros(max(spec.n_x * spec.n_y, 0), dtype=np.uint64)
+    cnt, st = ExitMapCounts(), Stats()
+    _chk(load().isx_exit_maps(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
+                              _p(dmap, C.c_uint64) if dmap.size else None, _p(pmap, C.c_uint64) if pmap.size else None,
+                              C.byref(cnt), C.byref(st)), "isx_exit_maps")
+    return (dmap.reshape(spec.n_v, spec.n_u) if dmap.size else dmap.reshape(0, 0),
+            pmap.reshape(spec.n_y, spec.n_x) if pmap.size else pmap.reshape(0, 0), cnt, st)
+
+
+def exit_maps_device(cfg, spec, n_rays, seed, first_ray, d_dir_ptr, d_pos_ptr, d_counts_ptr):
+    """Enqueue on the library stream, accumulating into device memory: uint64 maps at d_dir_ptr / d_pos_ptr (0 for a map
+    the spec does not want) and five uint64 counters at d_counts_ptr (e.g. torch tensors' data_ptr())."""
+    _chk(load().isx_exit_maps_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
+                                     C.c_void_p(int(d_dir_ptr) or None), C.c_void_p(int(d_pos_ptr) or None),
+                                     C.c_void_p(int(d_counts_ptr))), "isx_exit_maps_device")
 
 
 def fluxmap_series(cfgs, n_rays, seed, first_ray=0):

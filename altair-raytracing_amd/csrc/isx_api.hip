@@ -335,13 +335,29 @@ struct DiscClusters { size_t n = 0, off_ordered = 0, off_clusters = 0, off_perm 
 
 struct PerPos { uint64_t map_first = 0, rays_per_group = 0; int fold = 1; const double* d_table = nullptr; double width = 0; };
 struct LogSink { double* rec = nullptr; unsigned long long* count = nullptr; uint64_t cap = 0; };
+// isx_exit_maps: the checked spec and the device accumulators of the call (a map that is not wanted: nullptr)
+struct ExitSink { const isx_exit_map_spec* spec = nullptr; unsigned long long *dir = nullptr, *pos = nullptr, *counts = nullptr; };
+
+// isx.h: the limits of an exit-map spec (two u32 maps of at most 64 KiB each in a workgroup's LDS)
+int check_exit_spec(const isx_exit_map_spec* s) {
+  if (s->struct_size != (uint32_t)sizeof(isx_exit_map_spec)) return ISX_ERR_BAD_CONFIG;
+  auto axes = [](int32_t a, int32_t b, bool& wanted) {
+    wanted = !(a == 0 && b == 0);
+    return !wanted || (a >= 1 && a <= ISX_EXIT_MAP_MAX_AXIS && b >= 1 && b <= ISX_EXIT_MAP_MAX_AXIS &&
+                       (long long)a * b <= ISX_EXIT_MAP_MAX_BINS);
+  };
+  bool dir = false, pos = false;
+  if (!axes(s->n_u, s->n_v, dir) || !axes(s->n_x, s->n_y, pos) || !(dir || pos)) return ISX_ERR_BAD_CONFIG;
+  if (pos && !(std::isfinite(s->plane_z) && std::isfinite(s->half_extent) && s->half_extent > 0)) return ISX_ERR_BAD_CONFIG;
+  return ISX_OK;
+}
 
 // LDS of a workgroup's histogram: 4 B per bin, 16-byte aligned
 size_t hist_lds(int nbins) { return ((size_t)nbins * 4 + 15) & ~(size_t)15; }
 
 // The DetGrid of a call's sink, checked, and the dynamic LDS of its fused kernel (histogram + tables, census, Geom, DetGrid).
 int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d_discs, double disc_r, double disc_h,
-              const PerPos* pp, const LogSink* lg, DetGrid& d, size_t& lds) {
+              const PerPos* pp, const LogSink* lg, const ExitSink* xm, DetGrid& d, size_t& lds) {
   std::memset(&d, 0, sizeof(d));
   d.portz = c->exit_port_z;
   d.hit_line_mode = c->hit_line_mode;
@@ -387,6 +403,18 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
     d.nbins = 1;
     d.log_rec = lg->rec; d.log_count = lg->count; d.log_cap = lg->cap;
     lds = 16 + 64 + sizeof(Geom) + sizeof(DetGrid);
+  } else if (sink == SINK_EXITMAP) {
+    if (!xm || !xm->spec || !xm->counts) return ISX_ERR_BAD_ARG;
+    rc = check_exit_spec(xm->spec);
+    if (rc) return rc;
+    const isx_exit_map_spec& s = *xm->spec;
+    if ((s.n_u > 0 && !xm->dir) || (s.n_x > 0 && !xm->pos)) return ISX_ERR_BAD_ARG;
+    d.hit_line_mode = ISX_HITLINE_LAST_SEGMENT;   // (isx.h: the maps always see the real last segment)
+    d.xm_nu = s.n_u; d.xm_nv = s.n_v; d.xm_nx = s.n_x; d.xm_ny = s.n_y;
+    d.xm_plane_z = s.plane_z; d.xm_half = s.half_extent;
+    d.xm_dir = xm->dir; d.xm_pos = xm->pos; d.xm_counts = xm->counts;
+    d.nbins = s.n_u * s.n_v + s.n_x * s.n_y + 5;   // the workgroup's LDS block: direction map | plane map | the five counters
+    lds = hist_lds(d.nbins) + 64 + sizeof(Geom) + sizeof(DetGrid);
   } else {
     if (nbins_override < 1 || nbins_override > 36000) return ISX_ERR_BAD_ARG;
     d.nbins = nbins_override;
@@ -406,10 +434,11 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
 
 // ---- The launch plan of a call: the route, its kernel(s) and their workgroup shapes.
 //  ROUTE_FLUX_PIPE  flux maps: per chunk a trace kernel (exit lines -> HBM workspace) and a binning kernel
+//  ROUTE_EXIT_PIPE  exit maps: the flux pipeline's trace kernels, workspace and chunking; isx_bin_exitmaps_kernel streams the lines
 //  ROUTE_DISC_PIPE  the shared-ray disc sweep the same way: assist-wave trace kernel (exit segments) -> isx_bin_discs_kernel
 //  ROUTE_ASSIST     the per-position sinks: one assist-wave kernel, whose assist wave does the exact test per exiting ray
 //  ROUTE_FUSED      one kernel that traces and bins: everything the routes above do not serve
-enum Route { ROUTE_FUSED, ROUTE_ASSIST, ROUTE_FLUX_PIPE, ROUTE_DISC_PIPE };
+enum Route { ROUTE_FUSED, ROUTE_ASSIST, ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_DISC_PIPE };
 typedef void (*KernelFn)(const Geom, const DetGrid, const Work);
 typedef void (*BinFn)(const DetGrid, const Work);
 struct Plan {
@@ -480,8 +509,9 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
   // the line the binning kernel is to see) and, with the pencil source, the two other borders -- the chord identity is a property
   // of the Lambertian border, so trace_mode says nothing there.
   const bool flux_served = border == LAMBERT ? (!compat || (sp && S.assist)) && (pencil || !chord) : sp && S.assist && pencil;
-  if (sink == SINK_FLUX && flux_served && S.pipeline && S.bin_mode != 0) {
-    p.route = ROUTE_FLUX_PIPE;
+  // the trace kernel of a flux-map or exit-map pipeline and its shape
+  auto pipe_trace = [&](Route route) {
+    p.route = route;
     const bool assist = S.assist != 0;
     if (border == LOBE) p.fn = isx_trace_assist_lobe_kernel;
     else if (border == ROUGH) p.fn = isx_trace_assist_rough_kernel;
@@ -490,6 +520,9 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     else p.fn = assist ? isx_trace_assist_kernel : isx_trace_rec_kernel;
     trace_shape(p, assist ? small_shape(std::min(n, S.pipe_chunk), ablock) : Shape{S.trace_block, 4}, assist,
                 resident_unless(S.trace_blocks_per_cu));
+  };
+  if (sink == SINK_FLUX && flux_served && S.pipeline && S.bin_mode != 0) {
+    pipe_trace(ROUTE_FLUX_PIPE);
     // The binning kernel keeps the histogram and the detector tables in LDS.  With slot queues (1024-thread workgroups: 61 KB of
     // queues next to the histogram) if the grid fits their 32-bit slot records and the LDS, and then with COLUMN slots (default
     // for every source since round 4: grazing lines are column slots as well -- prep_band; bin_cols = 0 keeps the row slots of
@@ -508,6 +541,19 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     p.overlap = S.overlap > 1 && S.bin_mode == 1 && n >= (uint64_t)S.overlap * 65536;
     if (p.lds_bin <= S.lds_limit) return p;
     p = Plan();   // (a binning kernel whose LDS does not fit: the fused kernel below)
+  }
+
+  // The exit maps take the trace kernels as they are -- every one of them stores last point + final direction, which is the line
+  // the maps are defined on whatever hit_line_mode says (the rewrite kernel of the origin-compat line does not run here) -- and bin
+  // with isx_bin_exitmaps_kernel: 1024-thread workgroups, the two u32 maps and the five counters in LDS, what is resident.
+  const bool exit_served = border == LAMBERT ? (pencil || !chord) : sp && S.assist && pencil;
+  if (sink == SINK_EXITMAP && exit_served && S.pipeline) {
+    pipe_trace(ROUTE_EXIT_PIPE);
+    p.bin = isx_bin_exitmaps_kernel;
+    p.bblock = kBlock;
+    p.lds_bin = hist_lds(d.nbins);
+    if (p.lds_bin <= S.lds_limit) return p;
+    p = Plan();
   }
 
   // The disc pipeline's binning kernel keeps the histogram, the cluster table, the discs (up to kDiscsInLds) and per-wave lists in
@@ -541,6 +587,7 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     case SINK_FLUX: p.fn = lean && pencil ? (chord ? isx_trace_bin_chord_kernel : isx_trace_bin_kernel) :
                            lean && !chord ? isx_trace_bin_brdf_kernel : isx_trace_bin_full_kernel; break;
     case SINK_DZ: p.fn = lean_explicit ? isx_trace_dz_lean_kernel : isx_trace_dz_kernel; break;
+    case SINK_EXITMAP: p.fn = border == LAMBERT && pencil && !chord ? isx_trace_exitmap_lean_kernel : isx_trace_exitmap_kernel; break;
     case SINK_DISC: p.fn = lean_explicit ? isx_trace_disc_lean_kernel : isx_trace_disc_kernel; break;
     case SINK_PERPOS: p.fn = lean_explicit ? isx_trace_perpos_lean_kernel : isx_trace_perpos_kernel; break;
     case SINK_DISCPOS: p.fn = lean_explicit ? isx_trace_discpos_lean_kernel : isx_trace_discpos_kernel; break;
@@ -626,7 +673,7 @@ int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles) {
   return ISX_OK;
 }
 
-// ROUTE_FLUX_PIPE and ROUTE_DISC_PIPE: a trace launch and a binning launch per chunk of at most pipe_chunk rays
+// ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE and ROUTE_DISC_PIPE: a trace launch and a binning launch per chunk of at most pipe_chunk rays
 int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
   int rc = set_lds((const void*)p.fn, p.lds);
   if (rc == ISX_OK) rc = set_lds((const void*)p.bin, p.lds_bin);
@@ -635,7 +682,7 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
   const int bres = blocks_per_cu(p.bin, p.bblock, p.lds_bin, p.bin_per_cu);
   // what the two kernels see: a flux map's trace kernel keeps no histogram; the disc sweep's kernels walk the discs in cluster order
   DetGrid dt = d, db = d;
-  if (p.route == ROUTE_FLUX_PIPE) {
+  if (p.route != ROUTE_DISC_PIPE) {
     dt.nbins = 1; dt.n_theta = 0; dt.n_phi = 0;
   } else {
     db.discs = S.d_aux + g_disc_clusters.off_ordered;
@@ -716,7 +763,7 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
 // enqueue one call's launches, accumulating into d_hist (device) and S.d_stats (or d_stats)
 int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t first, unsigned long long* d_hist,
             int nbins_override, const double* d_discs, double disc_r, double disc_h, const PerPos* pp = nullptr,
-            const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr) {
+            const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr, const ExitSink* xm = nullptr) {
   Geom g;
   int rc = prepare_geom(c, &g);
   if (rc) return rc;
@@ -724,13 +771,13 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
   if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;   // first + n (the exclusive end of the index range) must be representable
   DetGrid d;
   size_t lds = 0;
-  rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, d, lds);
+  rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, xm, d, lds);
   if (rc || n == 0) return rc;
   Work wk;
   wk.seed = seed; wk.first = first; wk.n = n; wk.hist = d_hist; wk.stats = d_stats ? d_stats : S.d_stats;
   wk.ctr = nullptr; wk.sub = 0; wk.pad = 0;
   const Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n);
-  return p.route == ROUTE_FLUX_PIPE || p.route == ROUTE_DISC_PIPE ? run_pipeline(p, g, d, wk) : run_single(p, g, d, wk);
+  return p.route == ROUTE_FUSED || p.route == ROUTE_ASSIST ? run_single(p, g, d, wk) : run_pipeline(p, g, d, wk);
 }
 
 // device copy of a caller's detector / disc list in the pooled buffer (no hipMalloc/hipFree per call)
@@ -1276,6 +1323,54 @@ int isx_exit_dz_hist(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint
   if (rc == ISX_OK) rc = enqueue(SINK_DZ, cfg, n_rays, seed, first_ray, S.d_hist, nbins, nullptr, 0, 0);
   if (rc == ISX_OK) rc = copy_out(hist, S.d_hist, (size_t)nbins * sizeof(unsigned long long));
   return call_close(rc, stats);
+}
+
+void isx_default_exit_map_spec(const isx_config* cfg, isx_exit_map_spec* spec) {
+  if (!spec) return;
+  std::memset(spec, 0, sizeof(*spec));
+  spec->struct_size = (uint32_t)sizeof(isx_exit_map_spec);
+  spec->n_u = 128; spec->n_v = 128; spec->n_x = 64; spec->n_y = 64;
+  isx_config dflt;
+  if (!cfg) { isx_default_config(&dflt); cfg = &dflt; }
+  spec->plane_z = cfg->exit_port_z;
+  spec->half_extent = 1.25 * cfg->r_in * std::sin(cfg->theta_max_deg * M_PI / 180.0);   // the port radius + 25 %
+}
+
+int isx_exit_maps_device(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t n_rays, uint64_t seed,
+                         uint64_t first_ray, uint64_t* d_dir_map, uint64_t* d_pos_map, uint64_t* d_counts) {
+  if (!S.init) return ISX_ERR_NOT_INIT;
+  if (!cfg || !spec || !d_counts) return ISX_ERR_BAD_ARG;
+  const ExitSink xm{spec, (unsigned long long*)d_dir_map, (unsigned long long*)d_pos_map, (unsigned long long*)d_counts};
+  return enqueue(SINK_EXITMAP, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, &xm);
+}
+
+int isx_exit_maps(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                  uint64_t* dir_map, uint64_t* pos_map, isx_exit_map_counts* counts, isx_stats* stats) {
+  if (!S.init) return ISX_ERR_NOT_INIT;
+  if (!cfg || !spec) return ISX_ERR_BAD_ARG;
+  if (!config_abi_ok(cfg)) return ISX_ERR_BAD_CONFIG;
+  int rc = check_exit_spec(spec);
+  if (rc) return rc;
+  const size_t ndir = (size_t)spec->n_u * spec->n_v, npos = (size_t)spec->n_x * spec->n_y, words = ndir + npos + 5;
+  if ((ndir && !dir_map) || (npos && !pos_map)) return ISX_ERR_BAD_ARG;
+  rc = call_open(words);
+  if (rc) return rc;
+  // the call's accumulators in the pooled histogram: direction map | plane map | the five counters
+  const ExitSink xm{spec, ndir ? S.d_hist : nullptr, npos ? S.d_hist + ndir : nullptr, S.d_hist + ndir + npos};
+  rc = zero_hist(words);
+  if (rc == ISX_OK) rc = enqueue(SINK_EXITMAP, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, &xm);
+  if (rc == ISX_OK) rc = stage_result(S.d_hist, words * sizeof(unsigned long long));
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK) {
+    const unsigned long long* h = reinterpret_cast<const unsigned long long*>(S.h_pin + 64);
+    if (ndir) std::memcpy(dir_map, h, ndir * 8);
+    if (npos) std::memcpy(pos_map, h + ndir, npos * 8);
+    if (counts) {
+      const unsigned long long* k = h + ndir + npos;
+      counts->dir_binned = k[0]; counts->dir_outside = k[1]; counts->pos_binned = k[2]; counts->pos_outside = k[3]; counts->upward = k[4];
+    }
+  }
+  return rc;
 }
 
 #ifdef ISX_DIAG

@@ -60,6 +60,14 @@ struct DetGrid {
   double* log_rec;               // [log_cap][4]  (id bit-cast into the first double)
   unsigned long long* log_count;
   uint64_t log_cap;
+  // SINK_EXITMAP / isx_bin_exitmaps_kernel (isx.h: isx_exit_maps): the direction map (xm_nu x xm_nv bins over direction cosines
+  // dx, dy) and the plane map (xm_nx x xm_ny bins over [-xm_half, xm_half]^2 of the plane z = xm_plane_z) of every counted ray;
+  // 0 x 0 = map not wanted.  A workgroup's LDS holds u32[xm_nu * xm_nv | xm_nx * xm_ny | 5 counters] (nbins words).
+  int xm_nu, xm_nv, xm_nx, xm_ny;
+  double xm_plane_z, xm_half;
+  unsigned long long* xm_dir;    // [xm_nv][xm_nu]  global accumulators (+=)
+  unsigned long long* xm_pos;    // [xm_ny][xm_nx]
+  unsigned long long* xm_counts; // [5]: dir_binned, dir_outside, pos_binned, pos_outside, upward
 };
 
 // -DISX_DIAG (tuning builds only, never the shipped library): where the binning work goes.
@@ -98,7 +106,7 @@ __device__ unsigned long long g_diag[48];   // [32..47]: the assist wave of assi
 #define ISX_TD_FLUSH_AT(b_) do { } while (0)
 #endif
 
-enum : int { SINK_FLUX = 0, SINK_DZ = 1, SINK_DISC = 2, SINK_PERPOS = 3, SINK_LOG = 4, SINK_DISCPOS = 5, SINK_REC = 6 };
+enum : int { SINK_FLUX = 0, SINK_DZ = 1, SINK_DISC = 2, SINK_PERPOS = 3, SINK_LOG = 4, SINK_DISCPOS = 5, SINK_REC = 6, SINK_EXITMAP = 7 };
 
 struct Work {
   uint64_t seed, first, n;    // one launch traces rays [first, first + n), n < 2^31 (a lane keeps a 31-bit offset from `first`)
@@ -1954,10 +1962,67 @@ __device__ __forceinline__ void static_steps(F&& f) {
   }
 }
 
+// ------------------------------------------------------------------ exit maps (isx.h: isx_exit_maps)
+// The bins of one counted ray (last point p, final direction v), operation for operation as isx.h states them: IEEE double, a
+// multiply and then an add (no fma: -ffp-contract=off), the correctly rounded division.  floor(f) lies in [0, n) exactly when f does
+// (-0.0 included; NaN and inf compare false), so the index is only formed from a value that has one.  bd / bp: the ray's word in
+// the workgroup's LDS block (the plane map follows the direction map), -1 = not binned; up: the ray never reaches the plane.
+struct ExitBins { int bd, bp; bool dir_out, pos_out, up; };
+template <class D>
+__device__ __forceinline__ ExitBins exitmap_bins(const D& d, const V3& p, const V3& v) {
+  ExitBins e;
+  e.bd = -1; e.bp = -1; e.dir_out = false; e.pos_out = false; e.up = false;
+  const int nu = d.xm_nu, nv = d.xm_nv, nx = d.xm_nx, ny = d.xm_ny;
+  if (nu > 0) {
+    const double fu = (v.x + 1.0) * 0.5 * (double)nu;
+    const double fv = (v.y + 1.0) * 0.5 * (double)nv;
+    if (fu >= 0.0 && fu < (double)nu && fv >= 0.0 && fv < (double)nv) e.bd = (int)fv * nu + (int)fu;
+    else e.dir_out = true;
+  }
+  if (nx > 0) {
+    if (!(v.z < 0.0)) e.up = true;
+    else {
+      const double half = d.xm_half;
+      const double t = (d.xm_plane_z - p.z) / v.z;
+      const double x = p.x + t * v.x;
+      const double y = p.y + t * v.y;
+      const double fx = (x + half) / (2.0 * half) * (double)nx;
+      const double fy = (y + half) / (2.0 * half) * (double)ny;
+      if (fx >= 0.0 && fx < (double)nx && fy >= 0.0 && fy < (double)ny) e.bp = nu * nv + (int)fy * nx + (int)fx;
+      else e.pos_out = true;
+    }
+  }
+  return e;
+}
+// the five counters of a wave's batch: ballots and popcounts into wave-uniform words (cnt[5], order of isx_exit_map_counts)
+__device__ __forceinline__ void exitmap_count(const ExitBins& e, uint32_t* cnt) {
+  cnt[0] += (uint32_t)__popcll(__ballot(e.bd >= 0));
+  cnt[1] += (uint32_t)__popcll(__ballot(e.dir_out));
+  cnt[2] += (uint32_t)__popcll(__ballot(e.bp >= 0));
+  cnt[3] += (uint32_t)__popcll(__ballot(e.pos_out));
+  cnt[4] += (uint32_t)__popcll(__ballot(e.up));
+}
+// One flush of a workgroup's LDS block (after a barrier): the non-zero bins into the two u64 global maps, the five counters into
+// xm_counts.  Returns this thread's share of the increments (the sum of the map bins it flushed).
+__device__ __forceinline__ unsigned long long exitmap_flush(const DetGrid& d_arg, const uint32_t* hist, int tid, int nthr) {
+  const int ndir = d_arg.xm_nu * d_arg.xm_nv, nmap = ndir + d_arg.xm_nx * d_arg.xm_ny;
+  unsigned long long flushed = 0;
+  for (int b = tid; b < nmap + 5; b += nthr) {
+    const uint32_t c = hist[b];
+    if (!c) continue;
+    if (b < ndir) global_add_u64(d_arg.xm_dir + b, (unsigned long long)c);
+    else if (b < nmap) global_add_u64(d_arg.xm_pos + (b - ndir), (unsigned long long)c);
+    else global_add_u64(d_arg.xm_counts + (b - nmap), (unsigned long long)c);
+    if (b < nmap) flushed += c;
+  }
+  return flushed;
+}
+
 // ------------------------------------------------------------------ persistent trace kernel, one per sink
 //   SINK_FLUX: 180x90 detector flux map (the headline path)
 //   SINK_DZ  : histogram of the exit direction's z component (distributionSphereDetectorSweep.C:54,91)
 //   SINK_DISC: physical disc sweep (integratingSphereDetectorSweep.C)
+//   SINK_EXITMAP: direction map + plane map of the exit line (isx_exit_maps) -- the fused fallback of isx_bin_exitmaps_kernel
 template <int SINK, bool LEAN = false, int CH = 2, bool RESC = !LEAN>
 __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -2028,6 +2093,7 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
   unsigned long long n_inc = 0;                                                  // per wave (SINK_LOG; the histogram sinks count at flush)
   uint32_t n_taken = 0;                                                          // per wave: rays taken off the queue
   uint32_t reg_slot = 0, reg_left = 0, reg_id = 0xffffffffu;                     // per wave (SINK_REC): cursor in the open region
+  uint32_t n_xm[5] = {0u, 0u, 0u, 0u, 0u};                                       // per wave (SINK_EXITMAP): isx_exit_map_counts
   ISX_TD_DECL;
 
   for (;;) {
@@ -2240,6 +2306,16 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
         hit = segment_hits_tube_g(r.prev, r.v, tmax, d.discs + 6 * (size_t)b, d.disc_r, d.disc_h);
       }
       if (hit) atomicAdd(&hist[b], 1u);
+    } else if (SINK == SINK_EXITMAP) {
+      // per-lane: the two bins of the ray's exit line (the spec is read from the LDS copy when a ray left)
+      if (__ballot(bin_me)) {
+        ExitBins e;
+        e.bd = -1; e.bp = -1; e.dir_out = false; e.pos_out = false; e.up = false;
+        if (bin_me) e = exitmap_bins(d, r.p, r.v);
+        if (e.bd >= 0) atomicAdd(&hist[e.bd], 1u);
+        if (e.bp >= 0) atomicAdd(&hist[e.bp], 1u);
+        exitmap_count(e, n_xm);
+      }
     } else if (SINK == SINK_DZ) {
       // per-lane: TH1D(nbins,-1,1)->Fill(dz)
       bool hit = false;
@@ -2329,10 +2405,13 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
     atomicAdd(&sstat[4], (unsigned long long)n_susp);
     atomicAdd(&sstat[0], (unsigned long long)n_taken);                         // launched
     atomicAdd(&sstat[5], n_inc);
+    if (SINK == SINK_EXITMAP)   // (the counters are the last five words of the workgroup's block)
+      for (int k = 0; k < 5; ++k) if (n_xm[k]) atomicAdd(&hist[nbins - 5 + k], n_xm[k]);
   }
   __syncthreads();
   unsigned long long flushed = 0;   // increments of this block = sum of its LDS bins
-  for (int b = tid; b < nbins; b += nthr) {
+  if (SINK == SINK_EXITMAP) flushed = exitmap_flush(d_arg, hist, tid, nthr);
+  else for (int b = tid; b < nbins; b += nthr) {
     const uint32_t c = hist[b];
     if (c) { global_add_u64(&wk.hist[b], (unsigned long long)c); flushed += c; }
   }
@@ -2365,6 +2444,11 @@ extern "C" __global__ void ISX_KERNEL_ATTR
 isx_trace_dz_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_DZ>(g, d, wk); }
 extern "C" __global__ void ISX_KERNEL_ATTR
 isx_trace_dz_lean_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_DZ, true, 0>(g, d, wk); }
+// the exit maps where the two-kernel pipeline does not serve them (isx_api.hip: plan_launch)
+extern "C" __global__ void ISX_KERNEL_ATTR
+isx_trace_exitmap_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_EXITMAP>(g, d, wk); }
+extern "C" __global__ void ISX_KERNEL_ATTR
+isx_trace_exitmap_lean_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_EXITMAP, true, 0>(g, d, wk); }
 extern "C" __global__ void ISX_KERNEL_ATTR
 isx_trace_disc_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_DISC>(g, d, wk); }
 extern "C" __global__ void ISX_KERNEL_ATTR
@@ -3103,6 +3187,65 @@ isx_compat_lines_kernel(double* __restrict__ rec_lines, const uint32_t* __restri
       dst[0] = make_double2(P.x, P.y); dst[1] = make_double2(P.z, V.x); dst[2] = make_double2(V.y, V.z);
     }
   }
+}
+
+// ------------------------------------------------------------------ binning kernel of the exit maps (isx_exit_maps)
+// The pipeline's trace kernels leave the exit line (last point, final direction: 48 B) of every counted ray in the workspace; this
+// kernel streams them -- persistent waves take quarter regions off the launch's queue as the flux map's binning kernels do, one
+// lane per line, the loads of a unit's four batches (twelve 16-byte loads per lane) issued before the first is used -- and bins
+// each line twice (exitmap_bins): at most two ds_add_u32 per line into the workgroup's u32 maps, the five counters as ballots and
+// popcounts, one flush of the non-zero bins per workgroup.  No ray state, no tables: the work is the 48 B per line from HBM.
+extern "C" __global__ void __launch_bounds__(kBlock)
+isx_bin_exitmaps_kernel(const DetGrid d_arg, const Work wk) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  uint32_t* hist = reinterpret_cast<uint32_t*>(smem);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int nthr = (int)blockDim.x;
+  const int nmap = d_arg.xm_nu * d_arg.xm_nv + d_arg.xm_nx * d_arg.xm_ny;
+  for (int b = tid; b < nmap + 5; b += nthr) hist[b] = 0u;
+  __syncthreads();
+  uint32_t cnt[5] = {0u, 0u, 0u, 0u, 0u};
+  const uint32_t n_regions = wk.ctr[Q_REGIONS];   // (the trace kernel of this launch has completed)
+  const uint32_t ushift = 2u + wk.pad;            // a work unit = 1024 >> ushift exit lines of one region (Work::pad)
+#pragma unroll 1
+  for (;;) {
+    uint32_t unit = 0;
+    if (lane == 0) unit = atomicAdd(&wk.ctr[Q_BIN], 1u);
+    unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)unit);
+    const uint32_t region = unit >> ushift;
+    if (region >= n_regions) break;
+    const uint32_t r_lines = (uint32_t)__builtin_amdgcn_readfirstlane((int)d_arg.rec_counts[region]);
+    const uint32_t q_first = (unit & ((1u << ushift) - 1u)) * (kRegion >> ushift);
+    const uint32_t n_lines = r_lines < q_first + (kRegion >> ushift) ? r_lines : q_first + (kRegion >> ushift);
+    const double* rec = d_arg.rec_lines + 6ull * ((uint64_t)region * kRegion);
+#pragma unroll 1
+    for (uint32_t b0 = q_first; b0 < n_lines; b0 += 256u) {
+      V3 lp[4], lv[4];
+      bool have[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t i = b0 + 64u * (uint32_t)k + (uint32_t)lane;
+        have[k] = i < n_lines;
+        lp[k].x = lp[k].y = lp[k].z = 0.0; lv[k].x = lv[k].y = 0.0; lv[k].z = -1.0;
+        if (have[k]) load_line(rec + 6ull * i, lp[k], lv[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!__ballot(have[k])) continue;
+        ExitBins e;
+        e.bd = -1; e.bp = -1; e.dir_out = false; e.pos_out = false; e.up = false;
+        if (have[k]) e = exitmap_bins(d_arg, lp[k], lv[k]);
+        if (e.bd >= 0) atomicAdd(&hist[e.bd], 1u);
+        if (e.bp >= 0) atomicAdd(&hist[e.bp], 1u);
+        exitmap_count(e, cnt);
+      }
+    }
+  }
+  if (lane == 0)
+    for (int k = 0; k < 5; ++k) if (cnt[k]) atomicAdd(&hist[nmap + k], cnt[k]);
+  __syncthreads();
+  const unsigned long long flushed = exitmap_flush(d_arg, hist, tid, nthr);
+  if (flushed) atomicAdd(&wk.stats[5], flushed);
 }
 
 // ------------------------------------------------------------------ disc-binning kernel of the shared-ray disc sweep

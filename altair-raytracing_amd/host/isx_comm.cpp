@@ -624,4 +624,33 @@ int exit_dz_hist_all(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint
   return rc;
 }
 
+int exit_maps_all(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                  uint64_t* dir_map, uint64_t* pos_map, isx_exit_map_counts* counts, isx_stats* st) {
+  Comm& c = comm();
+  if (!c.active()) return isx_exit_maps(cfg, spec, n_rays, seed, first_ray, dir_map, pos_map, counts, st);
+  // (a spec the ABI refuses -- a map above ISX_EXIT_MAP_MAX_BINS -- leaves only the status word to exchange)
+  auto bins = [](long long a, long long b) { return a >= 1 && b >= 1 && a * b <= ISX_EXIT_MAP_MAX_BINS ? (size_t)(a * b) : (size_t)0; };
+  const size_t nd = spec ? bins(spec->n_u, spec->n_v) : 0, np = spec ? bins(spec->n_x, spec->n_y) : 0;
+  uint64_t f, cnt;
+  c.shard(n_rays, f, cnt);
+  isx_stats local{};
+  isx_exit_map_counts k{};
+  std::vector<uint64_t> buf(nd + np + 5, 0);   // direction map | plane map | the five counters: ONE sum
+  int rc = isx_exit_maps(cfg, spec, cnt, seed, first_ray + f, nd ? buf.data() : nullptr, np ? buf.data() + nd : nullptr, &k, &local);
+  if (rc == ISX_OK) {
+    uint64_t* w = buf.data() + nd + np;
+    w[0] = k.dir_binned; w[1] = k.dir_outside; w[2] = k.pos_binned; w[3] = k.pos_outside; w[4] = k.upward;
+  }
+  rc = c.reduce(rc, buf.data(), nd + np ? buf.size() : 0, &local);
+  if (rc != ISX_OK) return rc;
+  if (nd && dir_map) std::memcpy(dir_map, buf.data(), nd * sizeof(uint64_t));
+  if (np && pos_map) std::memcpy(pos_map, buf.data() + nd, np * sizeof(uint64_t));
+  if (counts) {
+    const uint64_t* w = buf.data() + nd + np;
+    counts->dir_binned = w[0]; counts->dir_outside = w[1]; counts->pos_binned = w[2]; counts->pos_outside = w[3]; counts->upward = w[4];
+  }
+  if (st) *st = local;
+  return rc;
+}
+
 }  // namespace isxhost

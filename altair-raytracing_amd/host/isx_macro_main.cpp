@@ -46,6 +46,7 @@ int main(int argc, char** argv) {
                  "  nonLambertianFlux::sweepDetector | nonLambertianFluxCopy::sweepDetector | nonLambertianFluxCopy::visualizeDetectorText [theta= phi=] |\n"
                  "  makeIntegratingSphereNRays |\n"
                  "  integratingSphereDetectorSweep |\n"
+                 "  exitMaps [--rays <n>] [--seed <s>] |\n"
                  "  distributionSphereDetectorSweep | --selftest-writer <file> | --unique <path> | --shard <n> | --analyze <csv>... | --analyze <folder> [average]\n";
     return 2;
   }
@@ -72,6 +73,13 @@ int main(int argc, char** argv) {
   }
   std::map<std::string, std::string> kv;
   for (int i = 2; i < argc; ++i) {
+    // --rays <n> / --seed <s>: the same as ISX_RAYS / ISX_SEED in the environment
+    if ((!std::strcmp(argv[i], "--rays") || !std::strcmp(argv[i], "--seed")) && i + 1 < argc) {
+      if (argv[i][2] == 'r') options().rays_override = std::atol(argv[i + 1]);
+      else options().seed = std::strtoull(argv[i + 1], nullptr, 0);
+      ++i;
+      continue;
+    }
     const char* eq = std::strchr(argv[i], '=');
     if (!eq) { std::cerr << "bad argument " << argv[i] << " (want key=value)\n"; return 2; }
     kv[std::string(argv[i], eq - argv[i])] = eq + 1;
@@ -92,6 +100,7 @@ int main(int argc, char** argv) {
   else if (entry == "makeIntegratingSphereNRays") rootMacros::makeIntegratingSphereNRays();
   else if (entry == "integratingSphereDetectorSweep") rootMacros::integratingSphereDetectorSweep();
   else if (entry == "distributionSphereDetectorSweep") rootMacros::distributionSphereDetectorSweep();
+  else if (entry == "exitMaps") rootMacros::exitMaps();
   else { std::cerr << "unknown entry point " << entry << "\n"; return 2; }
   const bool ok = ensure_device();  // false: the entry point printed its error and returned early
   comm().finalize();

@@ -1129,6 +1129,74 @@ void distributionSphereDetectorSweep() {
   for (uint64_t k = 0; k < count; ++k) lg << dirs[3 * k] << " " << dirs[3 * k + 1] << " " << dirs[3 * k + 2] << "\n";
 }
 
+// Far-field direction map and port-plane irradiance map of the sphere of distributionSphereDetectorSweep (isx.h: isx_exit_maps).
+void exitMaps() {
+  if (!ready_everywhere()) return;
+  isx_config c;
+  root_geometry(c, 101 * cm);
+  const long n = pick_n(1000000);
+  isx_exit_map_spec sp;
+  isx_default_exit_map_spec(&c, &sp);
+  std::vector<uint64_t> dmap((size_t)sp.n_u * sp.n_v), pmap((size_t)sp.n_x * sp.n_y);
+  isx_exit_map_counts k;
+  isx_stats st;
+  const uint64_t first = take_rays((uint64_t)n);
+  const int rc = exit_maps_all(&c, &sp, (uint64_t)n, options().seed, first, dmap.data(), pmap.data(), &k, &st);
+  if (rc != ISX_OK) {
+    err() << "Error: isx_exit_maps: " << isx_strerror(rc) << std::endl;
+    return;
+  }
+  std::cout << "Flux of rays through the exit port: " << st.counted_below_z << std::endl;
+  auto meta = [&](std::ofstream& f, const char* title) {
+    f << std::setprecision(17);
+    f << "# " << title << " - Generated: " << currentTimeString() << std::endl;
+    f << "# Number of rays: " << n << std::endl;
+    f << "# Seed: " << options().seed << std::endl;
+    f << "# First ray: " << first << std::endl;
+    f << "# Rays through the exit port: " << st.counted_below_z << std::endl;
+    f << "# Sphere inner radius: " << c.r_in << "cm" << std::endl;
+    f << "# Sphere outer radius: " << c.r_out << "cm" << std::endl;
+    f << "# Exit port angle: " << c.theta_max_deg << " degrees" << std::endl;
+    f << "# Exit port z: " << c.exit_port_z << "cm" << std::endl;
+    f << "# Direction bins (u x v): " << sp.n_u << " x " << sp.n_v << std::endl;
+    f << "# Plane bins (x x y): " << sp.n_x << " x " << sp.n_y << std::endl;
+    f << "# Plane z: " << sp.plane_z << "cm" << std::endl;
+    f << "# Plane half extent: " << sp.half_extent << "cm" << std::endl;
+    f << "# Direction binned: " << k.dir_binned << std::endl;
+    f << "# Direction outside: " << k.dir_outside << std::endl;
+    f << "# Plane binned: " << k.pos_binned << std::endl;
+    f << "# Plane outside: " << k.pos_outside << std::endl;
+    f << "# Upward: " << k.upward << std::endl;
+  };
+  {
+    // radiant intensity per steradian and launched ray: count / (N du dv / |dz|) at the bin centre (isx.h); a cell whose centre
+    // lies outside the unit disc has no solid angle there: 0
+    std::ofstream f(outputPath("exit_direction_map.csv"));
+    meta(f, "Exit Direction Map");
+    f << "u,v,count,intensity_per_sr\n";
+    const double du = 2.0 / sp.n_u, dv = 2.0 / sp.n_v;
+    for (int iv = 0; iv < sp.n_v; ++iv)
+      for (int iu = 0; iu < sp.n_u; ++iu) {
+        const double u = -1.0 + (iu + 0.5) * du, v = -1.0 + (iv + 0.5) * dv, w2 = 1.0 - u * u - v * v;
+        const uint64_t cnt = dmap[(size_t)iv * sp.n_u + iu];
+        const double inten = w2 > 0 ? (double)cnt / ((double)n * du * dv / std::sqrt(w2)) : 0.0;
+        f << u << "," << v << "," << cnt << "," << inten << "\n";
+      }
+  }
+  {
+    std::ofstream f(outputPath("exit_plane_map.csv"));
+    meta(f, "Exit Plane Map");
+    f << "x_cm,y_cm,count,fraction_per_cm2\n";
+    const double dx = 2.0 * sp.half_extent / sp.n_x, dy = 2.0 * sp.half_extent / sp.n_y;
+    for (int iy = 0; iy < sp.n_y; ++iy)
+      for (int ix = 0; ix < sp.n_x; ++ix) {
+        const uint64_t cnt = pmap[(size_t)iy * sp.n_x + ix];
+        f << (-sp.half_extent + (ix + 0.5) * dx) << "," << (-sp.half_extent + (iy + 0.5) * dy) << "," << cnt << ","
+          << (double)cnt / ((double)n * dx * dy) << "\n";
+      }
+  }
+}
+
 }  // namespace rootMacros
 
 }  // namespace isxhost

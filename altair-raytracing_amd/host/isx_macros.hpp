@@ -166,6 +166,9 @@ void integratingSphereDetectorSweep();                                     // in
 // disc placement of addDetectorDisk (:145-172): centre + tube axis after RotateZ(rotPhi), RotateY(rotTheta)
 void detectorDiskPlacement(double theta, double phi, double out6[6]);
 void distributionSphereDetectorSweep();                                    // distributionSphereDetectorSweep.C:26-130
+// the same geometry through isx_exit_maps (default spec): exit_direction_map.csv (u,v,count,intensity_per_sr) and
+// exit_plane_map.csv (x_cm,y_cm,count,fraction_per_cm2) -- what a hand-written loop over 3dRayLog.txt was for
+void exitMaps();
 }  // namespace rootMacros
 
 }  // namespace isxhost

@@ -3,7 +3,7 @@
 Rays are independent and ray i always draws from Philox stream (seed, i), so ANY partition of
 the index range gives the same summed histogram.  Rank r of P traces the
 contiguous range shard(n, r, P); the only exchange is one SUM all-reduce of the
-[n_theta*n_phi] int64 histogram (+ the 7-word census) — torch.distributed backend "nccl"
+[n_theta*n_phi] int64 histogram (+ the 7-word census; the exit maps: both maps + five counters + census) — torch.distributed backend "nccl"
 (= RCCL over xGMI) on GPUs, "gloo" in the CPU tests.
 
 The tracer itself is injected (`trace(cfg, count, seed, first) -> (hits, stats)`): on a GPU
@@ -67,3 +67,36 @@ def disc_sweep_sharded(sweep: Callable, cfg, discs, radius: float, half_thick: f
     single all-reduce as the flux map."""
     return fluxmap_sharded(lambda c, count, s, first: sweep(c, discs, radius, half_thick, count, s, first),
                            cfg, n_total, seed, first_ray, device)
+
+
+EXIT_COUNT_FIELDS = ("dir_binned", "dir_outside", "pos_binned", "pos_outside", "upward")
+
+
+def exit_maps_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, first_ray: int = 0, device=None):
+    """The exit maps (altair_raytracing_amd.exit_maps) ray-sharded: this rank's contiguous shard through
+    `trace(cfg, count, seed, spec, first) -> (dir_map, pos_map, counts, stats)`, then ONE SUM all-reduce that carries both
+    maps, the five counters and the census.  Returns (dir_map, pos_map, counts dict, census dict) -- identical on every rank."""
+    import torch
+    import torch.distributed as dist
+
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(), dist.get_world_size()
+    else:
+        rank, world = 0, 1
+    first, count = shard(n_total, rank, world)
+    dmap, pmap, cnt, st = trace(cfg, count, seed, spec, first_ray + first)
+    counts = np.array([getattr(cnt, k) for k in EXIT_COUNT_FIELDS], dtype=np.int64)
+    census = np.array([getattr(st, k) for k in CENSUS_FIELDS], dtype=np.int64)
+    if world > 1:
+        buf = torch.from_numpy(np.concatenate([dmap.reshape(-1).astype(np.int64), pmap.reshape(-1).astype(np.int64), counts, census]))
+        if device is not None:
+            buf = buf.to(device)
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+        buf = buf.cpu().numpy()
+        nd, npos = dmap.size, pmap.size
+        dmap = buf[:nd].astype(np.uint64).reshape(dmap.shape)
+        pmap = buf[nd:nd + npos].astype(np.uint64).reshape(pmap.shape)
+        counts = buf[nd + npos:nd + npos + len(EXIT_COUNT_FIELDS)]
+        census = buf[nd + npos + len(EXIT_COUNT_FIELDS):]
+    return (dmap, pmap, dict(zip(EXIT_COUNT_FIELDS, (int(x) for x in counts))),
+            dict(zip(CENSUS_FIELDS, (int(x) for x in census))))

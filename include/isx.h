@@ -169,7 +169,7 @@ int isx_take_stats(isx_stats* stats);
 /* The hipStream_t the library launches on (so callers can order work after it). */
 void* isx_stream(void);
 /* HIP-event times (ms) of the kernels collected by the last blocking call / isx_take_stats(), by kind: single-kernel
- * launches, the trace kernel of the two-kernel flux-map pipeline, its binning kernel.  Any pointer may be NULL. */
+ * launches, the trace kernel of a two-kernel pipeline (flux map, exit maps, disc sweep), its binning kernel.  Any pointer may be NULL. */
 int isx_last_kernel_ms(double* single_ms, double* trace_ms, double* bin_ms);
 
 /* Tuning/diagnostic switches.  None of them changes any result (a ray's history is a function of seed and index).
@@ -276,6 +276,63 @@ int isx_exit_dz_hist(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint
  */
 int isx_exit_directions(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t first_ray, uint64_t capacity,
                         uint64_t* ray_ids, double* directions, uint64_t* count, isx_stats* stats);
+
+/*
+ * Exit maps: what an observer FAR from the port sees, and the irradiance over a plane below it.  The flux map tests finite
+ * detector discs; the limit "detector -> point at infinity" of that map is the 2-D histogram of the exit direction (radiant
+ * intensity), which no finite detector reaches by Monte Carlo.  One call bins, for every traced ray that the census counts as
+ * "counted below z" (status EXITED and last_point.z < cfg->exit_port_z -- the rays of isx_exit_dz_hist / isx_exit_directions;
+ * for ISX_SOURCE_BRDF the scattered ray), with p = last point and v = final direction as isx_trace_endstates returns them
+ * (cfg->hit_line_mode is ignored: the maps always see the real last segment):
+ *
+ *   direction map (direction-cosine space; a Lambertian port gives a flat map inside the unit disc, radiant intensity per
+ *   steradian is count / (N du dv / |dz|)):
+ *       fu = (v.x + 1.0) * 0.5 * n_u ;  iu = (int)floor(fu)          (same with v.y, n_v -> iv)
+ *       0 <= iu < n_u and 0 <= iv < n_v :  dir_map[iv * n_u + iu] += 1 ,  dir_binned += 1
+ *       else                            :  dir_outside += 1           (|component| == 1 exactly)
+ *
+ *   plane map (where the exit LINE crosses the plane z = plane_z; free space -- the world box is no obstacle, a screen may lie
+ *   inside or beyond it):
+ *       v.z < 0.0 is false              :  upward += 1 , not binned   (-0.0 and +0.0 are "upward")
+ *       t = (plane_z - p.z) / v.z
+ *       x = p.x + t * v.x ;  y = p.y + t * v.y                        (a multiply, then an add: no fma)
+ *       fx = (x + half_extent) / (2.0 * half_extent) * n_x ;  ix = (int)floor(fx)     (same for y, n_y -> iy)
+ *       0 <= ix < n_x and 0 <= iy < n_y :  pos_map[iy * n_x + ix] += 1 ,  pos_binned += 1
+ *       else (NaN / inf included)       :  pos_outside += 1
+ *
+ * All operations are IEEE double, evaluated left to right as written, the division correctly rounded.  For every call and
+ * every map that is wanted: dir_binned + dir_outside == stats.counted_below_z == pos_binned + pos_outside + upward,
+ * dir_map sums to dir_binned, pos_map to pos_binned, stats.bin_increments == dir_binned + pos_binned.  The counters of a map
+ * that is not wanted stay 0.  The result does not depend on any isx_set_option switch nor on how a job is cut into calls.
+ *
+ * Limits (the two u32 maps of a workgroup live in its LDS): each map at most ISX_EXIT_MAP_MAX_BINS bins, each axis
+ * 1..ISX_EXIT_MAP_MAX_AXIS, at least one map wanted, plane_z and half_extent finite, half_extent > 0 -- else ISX_ERR_BAD_CONFIG.
+ */
+#define ISX_EXIT_MAP_MAX_BINS 16384
+#define ISX_EXIT_MAP_MAX_AXIS 1024
+typedef struct isx_exit_map_spec {
+  uint32_t struct_size;      /* sizeof(isx_exit_map_spec), set by isx_default_exit_map_spec(); a spec of another size is refused */
+  uint32_t reserved0;        /* 0 */
+  int32_t n_u, n_v;          /* direction map; 0,0 = not wanted (its pointer may then be NULL) */
+  int32_t n_x, n_y;          /* plane map;     0,0 = not wanted */
+  double plane_z;            /* plane map only */
+  double half_extent;        /* plane map only: it covers [-half_extent, half_extent] in x and in y */
+} isx_exit_map_spec;
+typedef struct isx_exit_map_counts {
+  uint64_t dir_binned, dir_outside, pos_binned, pos_outside, upward;
+} isx_exit_map_counts;
+
+/* 128 x 128 bins over the direction cosines, 64 x 64 bins at plane_z = cfg->exit_port_z with
+ * half_extent = 1.25 * r_in * sin(theta_max) (the port radius + 25 %).  No GPU needed. */
+void isx_default_exit_map_spec(const isx_config* cfg, isx_exit_map_spec* spec);
+
+/* Blocking: dir_map[n_v * n_u], pos_map[n_y * n_x], *counts (host, zeroed by the callee; counts and stats may be NULL). */
+int isx_exit_maps(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                  uint64_t* dir_map, uint64_t* pos_map, isx_exit_map_counts* counts, isx_stats* stats);
+/* ACCUMULATES (+=) into device-resident maps and five device counters (order of isx_exit_map_counts) on the library's
+ * stream and returns after enqueueing; isx_sync() / isx_take_stats() as for isx_fluxmap_device. */
+int isx_exit_maps_device(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t n_rays, uint64_t seed,
+                         uint64_t first_ray, uint64_t* d_dir_map, uint64_t* d_pos_map, uint64_t* d_counts /*[5]*/);
 
 /*
  * Series driver (sweepSeries, fluxAtObserverOptimize.C:892-921 / fluxAtObserverFast.C:1641-1673):
