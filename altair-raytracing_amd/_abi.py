@@ -25,6 +25,8 @@ SOURCE_BRDF = 1
 
 RAY_EXITED, RAY_ABSORBED, RAY_SUSPENDED = 1, 2, 3
 
+WALL_MAP_MAX_BINS, WALL_MAP_MAX_AXIS = 8192, 512   # ISX_WALL_MAP_MAX_BINS / ISX_WALL_MAP_MAX_AXIS
+
 # every symbol include/isx.h declares (tests check the .so exports exactly these)
 EXPORTS = [
     "isx_default_config", "isx_init", "isx_shutdown", "isx_strerror", "isx_last_hip_error", "isx_abi_version", "isx_stream_version",
@@ -33,6 +35,7 @@ EXPORTS = [
     "isx_exit_dz_hist", "isx_fluxmap_per_position", "isx_trace_rays_detector", "isx_exit_directions",
     "isx_fluxmap_series", "isx_disc_sweep_per_position", "isx_last_kernel_ms",
     "isx_default_exit_map_spec", "isx_exit_maps", "isx_exit_maps_device",
+    "isx_default_wall_map_spec", "isx_wall_map", "isx_wall_map_device",
 ]
 
 
@@ -102,6 +105,29 @@ class ExitMapCounts(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class WallMapSpec(C.Structure):
+    """isx_wall_map_spec (include/isx.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved0", C.c_uint32),
+        ("n_x", C.c_int32), ("n_y", C.c_int32), ("first_order", C.c_int32), ("reserved1", C.c_int32),
+    ]
+
+    def copy(self):
+        s = WallMapSpec()
+        C.memmove(C.byref(s), C.byref(self), C.sizeof(WallMapSpec))
+        return s
+
+
+class WallMapCounts(C.Structure):
+    """isx_wall_map_counts (include/isx.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in ("binned", "outside", "skipped", "other_surface")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -142,6 +168,10 @@ def load():
     L.isx_default_exit_map_spec.restype = None
     L.isx_exit_maps.argtypes = [P(Config), P(ExitMapSpec), u64, u64, u64, P(u64), P(u64), P(ExitMapCounts), P(Stats)]
     L.isx_exit_maps_device.argtypes = [P(Config), P(ExitMapSpec), u64, u64, u64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.isx_default_wall_map_spec.argtypes = [P(Config), P(WallMapSpec)]
+    L.isx_default_wall_map_spec.restype = None
+    L.isx_wall_map.argtypes = [P(Config), P(WallMapSpec), u64, u64, u64, P(u64), P(WallMapCounts), P(Stats)]
+    L.isx_wall_map_device.argtypes = [P(Config), P(WallMapSpec), u64, u64, u64, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -316,6 +346,32 @@ def exit_maps_device(cfg, spec, n_rays, seed, first_ray, d_dir_ptr, d_pos_ptr, d
     _chk(load().isx_exit_maps_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
                                      C.c_void_p(int(d_dir_ptr) or None), C.c_void_p(int(d_pos_ptr) or None),
                                      C.c_void_p(int(d_counts_ptr))), "isx_exit_maps_device")
+
+
+def default_wall_map_spec(cfg):
+    """64 x 64 bins, first_order 0 (no GPU needed)."""
+    s = WallMapSpec()
+    load().isx_default_wall_map_spec(C.byref(cfg), C.byref(s))
+    return s
+
+
+def wall_map(cfg, n_rays, seed, spec=None, first_ray=0):
+    """-> (wall_map[n_y, n_x] uint64, WallMapCounts, Stats): the equal-area map of every mirror interaction on the inner
+    sphere (include/isx.h)."""
+    if spec is None:
+        spec = default_wall_map_spec(cfg)
+    wmap = np.zeros(max(spec.n_x * spec.n_y, 1), dtype=np.uint64)
+    cnt, st = WallMapCounts(), Stats()
+    _chk(load().isx_wall_map(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray), _p(wmap, C.c_uint64),
+                             C.byref(cnt), C.byref(st)), "isx_wall_map")
+    return wmap.reshape(spec.n_y, spec.n_x), cnt, st
+
+
+def wall_map_device(cfg, spec, n_rays, seed, first_ray, d_map_ptr, d_counts_ptr):
+    """Enqueue on the library stream, accumulating into device memory: the uint64 map at d_map_ptr and four uint64 counters
+    at d_counts_ptr (e.g. torch tensors' data_ptr())."""
+    _chk(load().isx_wall_map_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
+                                    C.c_void_p(int(d_map_ptr) or None), C.c_void_p(int(d_counts_ptr) or None)), "isx_wall_map_device")
 
 
 def fluxmap_series(cfgs, n_rays, seed, first_ray=0):

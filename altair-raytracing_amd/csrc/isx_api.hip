@@ -352,12 +352,24 @@ int check_exit_spec(const isx_exit_map_spec* s) {
   return ISX_OK;
 }
 
+// isx_wall_map: the checked spec and the device accumulators of the call
+struct WallSink { const isx_wall_map_spec* spec = nullptr; unsigned long long *map = nullptr, *counts = nullptr; };
+
+// isx.h: the limits of a wall-map spec (one u32 map of at most 32 KiB in a workgroup's LDS)
+int check_wall_spec(const isx_wall_map_spec* s) {
+  if (s->struct_size != (uint32_t)sizeof(isx_wall_map_spec)) return ISX_ERR_BAD_CONFIG;
+  if (s->n_x < 1 || s->n_x > ISX_WALL_MAP_MAX_AXIS || s->n_y < 1 || s->n_y > ISX_WALL_MAP_MAX_AXIS ||
+      (long long)s->n_x * s->n_y > ISX_WALL_MAP_MAX_BINS || s->first_order < 0)
+    return ISX_ERR_BAD_CONFIG;
+  return ISX_OK;
+}
+
 // LDS of a workgroup's histogram: 4 B per bin, 16-byte aligned
 size_t hist_lds(int nbins) { return ((size_t)nbins * 4 + 15) & ~(size_t)15; }
 
 // The DetGrid of a call's sink, checked, and the dynamic LDS of its fused kernel (histogram + tables, census, Geom, DetGrid).
 int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d_discs, double disc_r, double disc_h,
-              const PerPos* pp, const LogSink* lg, const ExitSink* xm, DetGrid& d, size_t& lds) {
+              const PerPos* pp, const LogSink* lg, const ExitSink* xm, const WallSink* wm, DetGrid& d, size_t& lds) {
   std::memset(&d, 0, sizeof(d));
   d.portz = c->exit_port_z;
   d.hit_line_mode = c->hit_line_mode;
@@ -415,6 +427,18 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
     d.xm_dir = xm->dir; d.xm_pos = xm->pos; d.xm_counts = xm->counts;
     d.nbins = s.n_u * s.n_v + s.n_x * s.n_y + 5;   // the workgroup's LDS block: direction map | plane map | the five counters
     lds = hist_lds(d.nbins) + 64 + sizeof(Geom) + sizeof(DetGrid);
+  } else if (sink == SINK_WALL) {
+    if (!wm || !wm->spec || !wm->map || !wm->counts) return ISX_ERR_BAD_ARG;
+    rc = check_wall_spec(wm->spec);
+    if (rc) return rc;
+    const isx_wall_map_spec& s = *wm->spec;
+    d.hit_line_mode = ISX_HITLINE_LAST_SEGMENT;   // (isx.h: ignored -- no exit line is looked at)
+    // (the spec travels in the exit maps' words of DetGrid: isx_kernels.hpp)
+    d.xm_nx = s.n_x; d.xm_ny = s.n_y; d.xm_nu = s.first_order;
+    d.xm_plane_z = 1.0 / c->r_in;
+    d.xm_pos = wm->map; d.xm_counts = wm->counts;
+    d.nbins = s.n_x * s.n_y + 4;   // the workgroup's LDS block: the map | the four counters
+    lds = hist_lds(d.nbins) + 64 + sizeof(Geom) + sizeof(DetGrid);
   } else {
     if (nbins_override < 1 || nbins_override > 36000) return ISX_ERR_BAD_ARG;
     d.nbins = nbins_override;
@@ -436,7 +460,8 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
 //  ROUTE_FLUX_PIPE  flux maps: per chunk a trace kernel (exit lines -> HBM workspace) and a binning kernel
 //  ROUTE_EXIT_PIPE  exit maps: the flux pipeline's trace kernels, workspace and chunking; isx_bin_exitmaps_kernel streams the lines
 //  ROUTE_DISC_PIPE  the shared-ray disc sweep the same way: assist-wave trace kernel (exit segments) -> isx_bin_discs_kernel
-//  ROUTE_ASSIST     the per-position sinks: one assist-wave kernel, whose assist wave does the exact test per exiting ray
+//  ROUTE_ASSIST     the per-position sinks: one assist-wave kernel, whose assist wave does the exact test per exiting ray;
+//                   the wall map: one assist-wave kernel whose waves bin every interaction into the workgroup's LDS map
 //  ROUTE_FUSED      one kernel that traces and bins: everything the routes above do not serve
 enum Route { ROUTE_FUSED, ROUTE_ASSIST, ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_DISC_PIPE };
 typedef void (*KernelFn)(const Geom, const DetGrid, const Work);
@@ -582,12 +607,33 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     return p;
   }
 
+  // The wall map on the assist-wave kernels: every border with the pencil source, the Lambertian border with the BRDF source and
+  // explicit bounces (what those kernels are built for; hit_line_mode plays no part).  The workgroup's u32 map lies behind the rings:
+  // at the 8192-bin limit 72.6 KB per workgroup, two 768-thread workgroups per CU.  Should the device not hold two of them (the
+  // occupancy query of the grid), the 512-thread shape takes the call.
+  const bool wall_served = border == LAMBERT ? (pencil || !chord) : sp && pencil;
+  if (sink == SINK_WALL && wall_served && S.pipeline && S.assist) {
+    p.route = ROUTE_ASSIST;
+    p.fn = border == LOBE ? isx_trace_assist_wall_lobe_kernel : border == ROUGH ? isx_trace_assist_wall_rough_kernel :
+           !pencil ? isx_trace_assist_wall_brdf_kernel : chord ? isx_trace_assist_wall_chord_kernel : isx_trace_assist_wall_kernel;
+    Shape sh = small_shape(std::min(n, kLaunchMax), ablock);
+    trace_shape(p, sh, true, resident_unless(S.trace_blocks_per_cu));
+    p.lds += hist_lds(d.nbins);
+    if (sh.block > 512 && !S.assist_block_set && blocks_per_cu(p.fn, sh.block, p.lds, kResident) < 2) {
+      sh.block = 512;
+      trace_shape(p, sh, true, resident_unless(S.trace_blocks_per_cu));
+      p.lds += hist_lds(d.nbins);
+    }
+    return p;
+  }
+
   // the fused kernel: the lean build where there is one, the full-featured one for everything else
   switch (sink) {
     case SINK_FLUX: p.fn = lean && pencil ? (chord ? isx_trace_bin_chord_kernel : isx_trace_bin_kernel) :
                            lean && !chord ? isx_trace_bin_brdf_kernel : isx_trace_bin_full_kernel; break;
     case SINK_DZ: p.fn = lean_explicit ? isx_trace_dz_lean_kernel : isx_trace_dz_kernel; break;
     case SINK_EXITMAP: p.fn = border == LAMBERT && pencil && !chord ? isx_trace_exitmap_lean_kernel : isx_trace_exitmap_kernel; break;
+    case SINK_WALL: p.fn = border == LAMBERT && pencil && !chord ? isx_trace_wall_lean_kernel : isx_trace_wall_kernel; break;
     case SINK_DISC: p.fn = lean_explicit ? isx_trace_disc_lean_kernel : isx_trace_disc_kernel; break;
     case SINK_PERPOS: p.fn = lean_explicit ? isx_trace_perpos_lean_kernel : isx_trace_perpos_kernel; break;
     case SINK_DISCPOS: p.fn = lean_explicit ? isx_trace_discpos_lean_kernel : isx_trace_discpos_kernel; break;
@@ -763,7 +809,8 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
 // enqueue one call's launches, accumulating into d_hist (device) and S.d_stats (or d_stats)
 int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t first, unsigned long long* d_hist,
             int nbins_override, const double* d_discs, double disc_r, double disc_h, const PerPos* pp = nullptr,
-            const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr, const ExitSink* xm = nullptr) {
+            const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr, const ExitSink* xm = nullptr,
+            const WallSink* wm = nullptr) {
   Geom g;
   int rc = prepare_geom(c, &g);
   if (rc) return rc;
@@ -771,7 +818,7 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
   if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;   // first + n (the exclusive end of the index range) must be representable
   DetGrid d;
   size_t lds = 0;
-  rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, xm, d, lds);
+  rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, xm, wm, d, lds);
   if (rc || n == 0) return rc;
   Work wk;
   wk.seed = seed; wk.first = first; wk.n = n; wk.hist = d_hist; wk.stats = d_stats ? d_stats : S.d_stats;
@@ -1369,6 +1416,52 @@ int isx_exit_maps(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t
       const unsigned long long* k = h + ndir + npos;
       counts->dir_binned = k[0]; counts->dir_outside = k[1]; counts->pos_binned = k[2]; counts->pos_outside = k[3]; counts->upward = k[4];
     }
+  }
+  return rc;
+}
+
+// what an entry point answers before isx_init(): ISX_ERR_NO_DEVICE where no HIP device is to be had, else ISX_ERR_NOT_INIT
+static int not_initialised() {
+  int count = 0;
+  return (hipGetDeviceCount(&count) != hipSuccess || count <= 0) ? ISX_ERR_NO_DEVICE : ISX_ERR_NOT_INIT;
+}
+
+void isx_default_wall_map_spec(const isx_config* cfg, isx_wall_map_spec* spec) {
+  (void)cfg;   // (the default does not depend on the configuration: the map is scaled to the unit disc)
+  if (!spec) return;
+  std::memset(spec, 0, sizeof(*spec));
+  spec->struct_size = (uint32_t)sizeof(isx_wall_map_spec);
+  spec->n_x = 64; spec->n_y = 64; spec->first_order = 0;
+}
+
+int isx_wall_map_device(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                        uint64_t* d_wall_map, uint64_t* d_counts) {
+  if (!S.init) return not_initialised();
+  if (!cfg || !spec || !d_wall_map || !d_counts) return ISX_ERR_BAD_ARG;
+  const WallSink wm{spec, (unsigned long long*)d_wall_map, (unsigned long long*)d_counts};
+  return enqueue(SINK_WALL, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, &wm);
+}
+
+int isx_wall_map(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                 uint64_t* wall_map, isx_wall_map_counts* counts, isx_stats* stats) {
+  if (!S.init) return not_initialised();
+  if (!cfg || !spec || !wall_map) return ISX_ERR_BAD_ARG;
+  if (!config_abi_ok(cfg)) return ISX_ERR_BAD_CONFIG;
+  int rc = check_wall_spec(spec);
+  if (rc) return rc;
+  const size_t nmap = (size_t)spec->n_x * spec->n_y, words = nmap + 4;
+  rc = call_open(words);
+  if (rc) return rc;
+  // the call's accumulators in the pooled histogram: the map | the four counters
+  const WallSink wm{spec, S.d_hist, S.d_hist + nmap};
+  rc = zero_hist(words);
+  if (rc == ISX_OK) rc = enqueue(SINK_WALL, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, &wm);
+  if (rc == ISX_OK) rc = stage_result(S.d_hist, words * sizeof(unsigned long long));
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK) {
+    const unsigned long long* h = reinterpret_cast<const unsigned long long*>(S.h_pin + 64);
+    std::memcpy(wall_map, h, nmap * 8);
+    if (counts) { counts->binned = h[nmap]; counts->outside = h[nmap + 1]; counts->skipped = h[nmap + 2]; counts->other_surface = h[nmap + 3]; }
   }
   return rc;
 }

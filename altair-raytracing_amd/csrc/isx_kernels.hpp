@@ -68,6 +68,10 @@ struct DetGrid {
   unsigned long long* xm_dir;    // [xm_nv][xm_nu]  global accumulators (+=)
   unsigned long long* xm_pos;    // [xm_ny][xm_nx]
   unsigned long long* xm_counts; // [5]: dir_binned, dir_outside, pos_binned, pos_outside, upward
+  // SINK_WALL (isx.h: isx_wall_map) is never active together with the exit maps and takes its spec in the same words, so that no
+  // kernel's parameter block grows: xm_nx x xm_ny = the map's axes, xm_nu = first_order, xm_plane_z = 1 / r_in, xm_pos = the
+  // global map [xm_ny][xm_nx] (+=), xm_counts = [4]: binned, outside, skipped, other_surface.  A workgroup's LDS holds
+  // u32[xm_nx * xm_ny | 4 counters] (nbins words).
 };
 
 // -DISX_DIAG (tuning builds only, never the shipped library): where the binning work goes.
@@ -106,7 +110,7 @@ __device__ unsigned long long g_diag[48];   // [32..47]: the assist wave of assi
 #define ISX_TD_FLUSH_AT(b_) do { } while (0)
 #endif
 
-enum : int { SINK_FLUX = 0, SINK_DZ = 1, SINK_DISC = 2, SINK_PERPOS = 3, SINK_LOG = 4, SINK_DISCPOS = 5, SINK_REC = 6, SINK_EXITMAP = 7 };
+enum : int { SINK_FLUX = 0, SINK_DZ = 1, SINK_DISC = 2, SINK_PERPOS = 3, SINK_LOG = 4, SINK_DISCPOS = 5, SINK_REC = 6, SINK_EXITMAP = 7, SINK_WALL = 8 };
 
 struct Work {
   uint64_t seed, first, n;    // one launch traces rays [first, first + n), n < 2^31 (a lane keeps a 31-bit offset from `first`)
@@ -2018,11 +2022,80 @@ __device__ __forceinline__ unsigned long long exitmap_flush(const DetGrid& d_arg
   return flushed;
 }
 
+// ------------------------------------------------------------------ wall map (isx.h: isx_wall_map)
+// The spec of a call as the trace loops keep it: wave-uniform words (scalar registers).
+struct WallSpec { int nx; uint32_t first; double inv, fnx, fny; };
+// A wave-uniform value that a VALU instruction made (an int -> double conversion), moved into scalar registers.  (As inline
+// assembly: the compiler folds the builtin away for a value it knows to be uniform, and kept the doubles in four VGPRs for the
+// whole trace loop -- 20 B of scratch per lane in the assist-wave kernels, which sit at their 80 VGPRs.)
+__device__ __forceinline__ double uniform_f64(double x) {
+  const long long v = __double_as_longlong(x);
+  uint32_t lo, hi;
+  asm("v_readfirstlane_b32 %0, %1" : "=s"(lo) : "v"((uint32_t)v));
+  asm("v_readfirstlane_b32 %0, %1" : "=s"(hi) : "v"((uint32_t)(v >> 32)));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+template <bool ON>   // (false: a kernel of another sink -- nothing is computed, nothing is kept)
+__device__ __forceinline__ WallSpec wall_spec(const DetGrid& d) {
+  WallSpec s;
+  if (!ON) { s.nx = 0; s.first = 0u; s.inv = 0.0; s.fnx = 0.0; s.fny = 0.0; return s; }
+  s.nx = d.xm_nx; s.first = (uint32_t)d.xm_nu; s.inv = d.xm_plane_z;
+  s.fnx = uniform_f64((double)d.xm_nx); s.fny = uniform_f64((double)d.xm_ny);   // (the conversion is a VALU instruction)
+  return s;
+}
+// The bin of one point of the inner sphere, operation for operation as isx.h states it: IEEE double, left to right, no fma
+// (-ffp-contract=off), the correctly rounded division and square root.  -1 = outside (the in-range test is made on the value
+// floor() would see, as exitmap_bins does: NaN and inf compare false).
+__device__ __forceinline__ int wall_bin(const WallSpec& s, const V3& q) {
+  const double c = q.z * s.inv;
+  const double w = sqrt(0.5 / (1.0 + c));
+  const double X = (q.x * s.inv) * w;
+  const double Y = (q.y * s.inv) * w;
+  const double fx = (X + 1.0) * 0.5 * s.fnx;
+  const double fy = (Y + 1.0) * 0.5 * s.fny;
+  if (fx >= 0.0 && fx < s.fnx && fy >= 0.0 && fy < s.fny) return (int)fy * s.nx + (int)fx;
+  return -1;
+}
+// One interaction (or `inc` interactions at the same point with the same count j: the first strike of a wave's fresh rays) into
+// the workgroup's LDS block: hist[0, nmap) the map, then the four counters in the order of isx_wall_map_counts.  `binned` is not
+// kept while tracing (it is the sum of the map: wall_flush).  `skipped` is counted per wave -- the lanes that are here together,
+// one add by the first of them: per lane it would be a same-address add of up to 64 lanes, and a counter register per lane is
+// one more than the assist-wave kernels have.  outside and other_surface are rare.
+__device__ __forceinline__ void wall_record(const WallSpec& s, uint32_t* hist, int nmap, int kind, uint32_t j, const V3& q, uint32_t inc) {
+  const bool skip = kind == K_INNER && j < s.first;
+  const unsigned long long sm = __ballot(skip);
+  if (sm) {
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+    if (skip && rank == 0u) atomicAdd(&hist[nmap + 2], (uint32_t)__popcll(sm) * inc);   // (inc != 1: one lane is here alone)
+  }
+  if (kind != K_INNER) atomicAdd(&hist[nmap + 3], inc);
+  else if (!skip) {
+    const int b = wall_bin(s, q);
+    atomicAdd(&hist[b >= 0 ? b : nmap + 1], inc);
+  }
+}
+// One flush of a workgroup's LDS block (after a barrier): the non-zero bins into the u64 global map, outside / skipped /
+// other_surface into xm_counts[1..3].  Returns this thread's share of the increments (the sum of the map bins it flushed), which
+// the caller adds up to the workgroup's `binned`.
+__device__ __forceinline__ unsigned long long wall_flush(const DetGrid& d_arg, const uint32_t* hist, int tid, int nthr) {
+  const int nmap = d_arg.xm_nx * d_arg.xm_ny;
+  unsigned long long flushed = 0;
+  for (int b = tid; b < nmap + 4; b += nthr) {
+    const uint32_t c = hist[b];
+    if (!c) continue;
+    if (b < nmap) { global_add_u64(d_arg.xm_pos + b, (unsigned long long)c); flushed += c; }
+    else global_add_u64(d_arg.xm_counts + (b - nmap), (unsigned long long)c);
+  }
+  return flushed;
+}
+
 // ------------------------------------------------------------------ persistent trace kernel, one per sink
 //   SINK_FLUX: 180x90 detector flux map (the headline path)
 //   SINK_DZ  : histogram of the exit direction's z component (distributionSphereDetectorSweep.C:54,91)
 //   SINK_DISC: physical disc sweep (integratingSphereDetectorSweep.C)
 //   SINK_EXITMAP: direction map + plane map of the exit line (isx_exit_maps) -- the fused fallback of isx_bin_exitmaps_kernel
+//   SINK_WALL: equal-area map of the interaction points on the inner sphere (isx_wall_map), binned at the arrival -- every
+//              configuration; the assist-wave kernels (assist_body<.., WALL>) are the default route
 template <int SINK, bool LEAN = false, int CH = 2, bool RESC = !LEAN>
 __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -2094,6 +2167,8 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
   uint32_t n_taken = 0;                                                          // per wave: rays taken off the queue
   uint32_t reg_slot = 0, reg_left = 0, reg_id = 0xffffffffu;                     // per wave (SINK_REC): cursor in the open region
   uint32_t n_xm[5] = {0u, 0u, 0u, 0u, 0u};                                       // per wave (SINK_EXITMAP): isx_exit_map_counts
+  const WallSpec wspec = wall_spec<SINK == SINK_WALL>(d_arg);                    // SINK_WALL: the spec, the map's words
+  const int wall_nmap = d_arg.xm_nx * d_arg.xm_ny;
   ISX_TD_DECL;
 
   for (;;) {
@@ -2141,8 +2216,9 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
     // Philox block shared by two bounces (bounce_words): the lean kernels alternate compute / reuse steps
     constexpr bool kShare = LEAN;
     static_assert(!kShare || (kStepsPerTrip % 2) == 0, "block sharing needs an even number of steps per trip");
-    auto arrive = [&](int kind, const V3& q, auto ph) {
+    auto arrive = [&](int kind, const V3& q, auto ph, bool record = true) {
       constexpr int PH = kShare ? decltype(ph)::value : PH_DIRECT;
+      if (SINK == SINK_WALL && record && kind != K_BOX) wall_record(wspec, hist, wall_nmap, kind, r.j, q, 1u);
       const int st = ray_arrive<SINK == SINK_DISC || SINK == SINK_DISCPOS, LEAN, CH, PH>(h, g, r, seed, range_first, kind, q);
       if (st != 0) { run = false; pend = st; }   // census / re-scatter once per trip (below), not per bounce
     };
@@ -2155,12 +2231,13 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
       V3 q;
       int kind = K_NONE;
       bool arrived = false;
+      bool first_strike = false;   // SINK_WALL: the lane arrives at Geom::q0 with j = 0, as every fresh ray of the launch does
       if (run) {
         // a fresh ray (rays enter on step 0 only) goes straight to the launch's common first boundary (Geom::q0); a
         // re-scattered one that starts on the world box (on == K_NONE as well) is outside the ball: generic search
         const bool fresh = r.on == K_NONE && r.j == 0u && !r.scattered();
         if (fresh) {
-          if (g.q0_ok) { q.x = g.q0[0]; q.y = g.q0[1]; q.z = g.q0[2]; kind = K_INNER; arrived = true; }
+          if (g.q0_ok) { q.x = g.q0[0]; q.y = g.q0[1]; q.z = g.q0[2]; kind = K_INNER; arrived = true; first_strike = true; }
           else { parked = true; run = false; }
         } else if (hot_search(q)) { kind = K_INNER; arrived = true; }
         else { parked = true; run = false; }
@@ -2183,7 +2260,12 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
       }
       iter++;
       ISX_TD_MARK(2);
-      if (arrived) arrive(kind, q, std::integral_constant<int, PH_EVEN>());
+      if (SINK == SINK_WALL) {
+        // the first strikes of a wave's fresh rays are one point: counted per wave and added to its bin by one lane
+        const unsigned long long fm = __ballot(first_strike);
+        if (fm && lane == __builtin_ctzll(fm)) wall_record(wspec, hist, wall_nmap, K_INNER, 0u, q, (uint32_t)__popcll(fm));
+      }
+      if (arrived) arrive(kind, q, std::integral_constant<int, PH_EVEN>(), !first_strike);
       ISX_TD_MARK(3);
     }
     // extra bounces per loop trip (hot search only): amortises refill / flush / exit bookkeeping
@@ -2316,6 +2398,8 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
         if (e.bp >= 0) atomicAdd(&hist[e.bp], 1u);
         exitmap_count(e, n_xm);
       }
+    } else if (SINK == SINK_WALL) {
+      // (binned at every arrival: nothing is left to do for a ray that ended)
     } else if (SINK == SINK_DZ) {
       // per-lane: TH1D(nbins,-1,1)->Fill(dz)
       bool hit = false;
@@ -2411,6 +2495,7 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
   __syncthreads();
   unsigned long long flushed = 0;   // increments of this block = sum of its LDS bins
   if (SINK == SINK_EXITMAP) flushed = exitmap_flush(d_arg, hist, tid, nthr);
+  else if (SINK == SINK_WALL) flushed = wall_flush(d_arg, hist, tid, nthr);
   else for (int b = tid; b < nbins; b += nthr) {
     const uint32_t c = hist[b];
     if (c) { global_add_u64(&wk.hist[b], (unsigned long long)c); flushed += c; }
@@ -2425,6 +2510,7 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
     if (t2 < 7u) {
       const unsigned long long c = sstat[t2];
       if (c) atomicAdd(&wk.stats[t2], c);
+      if (SINK == SINK_WALL && t2 == 5u && c) global_add_u64(d_arg.xm_counts, c);   // binned = the workgroup's increments
     }
   }
 }
@@ -2449,6 +2535,11 @@ extern "C" __global__ void ISX_KERNEL_ATTR
 isx_trace_exitmap_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_EXITMAP>(g, d, wk); }
 extern "C" __global__ void ISX_KERNEL_ATTR
 isx_trace_exitmap_lean_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_EXITMAP, true, 0>(g, d, wk); }
+// the wall map where the assist-wave kernels do not serve it (isx_api.hip: plan_launch): every configuration
+extern "C" __global__ void ISX_KERNEL_ATTR
+isx_trace_wall_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_WALL>(g, d, wk); }
+extern "C" __global__ void ISX_KERNEL_ATTR
+isx_trace_wall_lean_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_WALL, true, 0>(g, d, wk); }
 extern "C" __global__ void ISX_KERNEL_ATTR
 isx_trace_disc_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_DISC>(g, d, wk); }
 extern "C" __global__ void ISX_KERNEL_ATTR
@@ -2563,7 +2654,11 @@ __device__ __forceinline__ void ray_unpack(const uint4& a, const uint4& b, const
 // whose try was rejected stays at its new point (Ray::k counts its tries) and tries again in the next step while its neighbours
 // go on to their next wall point.  The tries of an interaction are a function of (seed, ray, interaction, try index) alone, so
 // the schedule changes nothing: bit-equal to lobe_sample()'s loop (oracle: isxo lobe_sample).
-template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT>
+// WALL (isx_wall_map, SINK_WALL): every interaction is binned where it happens -- by the tracer waves at each arrival on the inner
+// sphere (wall_record: the projection and one ds_add_u32 into the workgroup's u32 map, which lies behind the rings), by the assist
+// wave for what it interacts with (rim and outer sphere: other_surface; a ray it brings back to the inner sphere: binned like a
+// tracer's).  A lobe interaction is binned at its arrival, once, not at its tries.  No exit lines, no second kernel.
+template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false>
 __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk) {
   constexpr bool LEAN = SURF == SURF_LAMBERT;
   static_assert(LEAN || (CH == 0 && !RESC), "the chord identity and the BRDF re-scatter pipeline are built for the Lambertian border");
@@ -2574,9 +2669,13 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   AssistQueues* Q = reinterpret_cast<AssistQueues*>(smem + ((reinterpret_cast<unsigned char*>(d_lds + 1) - smem + 15) & ~(size_t)15));
   uint4* resume_q = reinterpret_cast<uint4*>(Q + 1);               // [kResumeCap][4]
   uint4* pend_q = resume_q + 4 * kResumeCap;                       // [kPendCap][4]
+  uint32_t* hist = reinterpret_cast<uint32_t*>(pend_q + 4 * kPendCap);   // WALL: u32[xm_nx * xm_ny | 4 counters]
   const int tid = threadIdx.x, lane = tid & 63;
   const int nthr = (int)blockDim.x, wpb = nthr >> 6;
   const int n_tracers = wpb - 1;
+  const WallSpec wspec = wall_spec<WALL>(d_arg);
+  const int wall_nmap = d_arg.xm_nx * d_arg.xm_ny;
+  if (WALL) for (int b = tid; b < wall_nmap + 4; b += nthr) hist[b] = 0u;
   if (tid < 8) sstat[tid] = 0ull;
   if (tid == 64) {
     *g_lds = g_arg;
@@ -2705,7 +2804,8 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       // (the end of a ray as two flags -- lane masks in scalar registers -- instead of a status word per lane; a tracer lane's ray
       //  sits on the inner sphere unless it is fresh, so Ray::on is neither read nor written in the steps)
       bool ended = false, susp = false;
-      auto arrive = [&](const V3& q, auto ph) {
+      auto arrive = [&](const V3& q, auto ph, bool record = true) {
+        if (WALL && record) wall_record(wspec, hist, wall_nmap, K_INNER, r.j, q, 1u);
         const int st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(h, g, r, seed, first, K_INNER, q);
         if (st != 0) { run = false; ended = true; susp = st == ST_SUSPENDED; }
       };
@@ -2736,6 +2836,11 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
             else { hand = true; run = false; }
           } else if (next_hit_s1<false>(h, g, r.p, r.v, K_INNER, q)) arrived = true;
           else { hand = true; run = false; }
+          if (WALL) {   // (the first strikes of the wave's fresh rays: one point, added by one lane)
+            const unsigned long long fm = __ballot(arrived && fresh);
+            if (fm && lane == __builtin_ctzll(fm)) wall_record(wspec, hist, wall_nmap, K_INNER, 0u, q, (uint32_t)__popcll(fm));
+            if (arrived && !fresh) wall_record(wspec, hist, wall_nmap, K_INNER, r.j, q, 1u);
+          }
           if (arrived) {
             r.p = q;
             uint32_t w4[4];
@@ -2766,16 +2871,21 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       {
         V3 q;
         bool arrived = false;
+        bool first_strike = false;   // WALL: the lane arrives at Geom::q0 with j = 0, as every fresh ray of the launch does
         ISX_TD_ADD(4, __popcll(__ballot(run)));   // (-DISX_DIAG: lanes that attempt a bounce in this step)
         if (run) {
           const bool fresh = r.j == 0u && !r.scattered();   // (a ray that returns from the assist wave has interactions behind it)
           if (fresh) {
-            if (g.q0_ok) { q.x = g.q0[0]; q.y = g.q0[1]; q.z = g.q0[2]; arrived = true; }
+            if (g.q0_ok) { q.x = g.q0[0]; q.y = g.q0[1]; q.z = g.q0[2]; arrived = true; first_strike = true; }
             else { hand = true; run = false; }
           } else if (hot_search(q)) arrived = true;
           else { hand = true; run = false; }
         }
-        if (arrived) arrive(q, std::integral_constant<int, PH_EVEN>());
+        if (WALL) {   // the first strikes of a wave's fresh rays are one point: counted per wave and added to its bin by one lane
+          const unsigned long long fm = __ballot(first_strike);
+          if (fm && lane == __builtin_ctzll(fm)) wall_record(wspec, hist, wall_nmap, K_INNER, 0u, q, (uint32_t)__popcll(fm));
+        }
+        if (arrived) arrive(q, std::integral_constant<int, PH_EVEN>(), !first_strike);
       }
       static_steps<1, kStepsPerTrip>([&](auto rep) {
         V3 q;
@@ -2958,6 +3068,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           else if (r.on == K_INNER) unit_dir(r.v);   // handed over by a tracer whose rule S1' failed: unit direction from here on
           V3 q;
           const int kind = next_hit_generic(g, r.p, r.v, r.on, q);
+          if (WALL && kind != K_BOX) wall_record(wspec, hist, wall_nmap, kind, r.j, q, 1u);
           st = ray_arrive<DISC || PP == 2, LEAN, CH, PH_DIRECT, true, SURF>(h, g, r, seed, first, kind, q);   // (DISC: r.prev = start of this segment)
           if (RESC && st != 0 && h.source_model == 1 && !r.scattered()) {   // nonLambertianFlux.C:253-268
             n_wall += r.j;
@@ -3034,7 +3145,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         if (hit1) atomicAdd(&wk.hist[b1], 1ull);
         n_inc += (unsigned long long)__popcll(__ballot(hit0)) + (unsigned long long)__popcll(__ballot(hit1));
       }
-      const unsigned long long m = PP != 0 ? 0ull : __ballot(keep);
+      const unsigned long long m = (PP != 0 || WALL) ? 0ull : __ballot(keep);
       if (m) {
         const uint32_t cnt = (uint32_t)__popcll(m);
         if (cnt > reg_left) {   // close the open region, reserve the next one (kRegion)
@@ -3124,12 +3235,18 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   }
   __syncthreads();
   if (tid == 0 && Q->failed) atomicAdd(&wk.stats[7], (unsigned long long)Q->failed);
+  if (WALL) {   // one flush of the workgroup's map; binned = its increments
+    const unsigned long long flushed = wall_flush(d_arg, hist, tid, nthr);
+    if (flushed) atomicAdd(&sstat[5], flushed);
+    __syncthreads();
+  }
   {
     uint32_t t2 = threadIdx.x;
     asm volatile("" : "+v"(t2));
     if (t2 < 7u) {
       const unsigned long long c = sstat[t2];
       if (c) atomicAdd(&wk.stats[t2], c);
+      if (WALL && t2 == 5u && c) global_add_u64(d_arg.xm_counts, c);
     }
   }
 }
@@ -3150,6 +3267,13 @@ extern "C" __global__ void ISX_ASSIST_ATTR
 isx_trace_assist_perpos_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 1>(g, d, wk); }
 extern "C" __global__ void ISX_ASSIST_ATTR
 isx_trace_assist_discpos_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 2>(g, d, wk); }
+// the wall map (isx_wall_map): the same kernels with the binning at every arrival and the workgroup's u32 map behind the rings
+extern "C" __global__ void ISX_ASSIST_ATTR
+isx_trace_assist_wall_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_LAMBERT, true>(g, d, wk); }
+extern "C" __global__ void ISX_ASSIST_ATTR
+isx_trace_assist_wall_chord_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<1, false, false, 0, SURF_LAMBERT, true>(g, d, wk); }
+extern "C" __global__ void ISX_ASSIST_ATTR
+isx_trace_assist_wall_brdf_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, true, false, 0, SURF_LAMBERT, true>(g, d, wk); }
 // the other border models on the same pipeline (round 5; until then round 1's fused isx_trace_bin_full_kernel served them):
 // the cos^2 lobe of "nonLambertianFlux copy.C":31-70,188-221 and ROBAST's rough-specular border (EnableLambertian(false))
 #ifndef ISX_LOBE_WAVES
@@ -3168,6 +3292,10 @@ extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((am
 isx_trace_assist_perpos_lobe_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 1, SURF_LOBE>(g, d, wk); }
 extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_ROUGH_WAVES, ISX_ROUGH_WAVES)))
 isx_trace_assist_perpos_rough_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 1, SURF_ROUGH>(g, d, wk); }
+extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_LOBE_WAVES, ISX_LOBE_WAVES)))
+isx_trace_assist_wall_lobe_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_LOBE, true>(g, d, wk); }
+extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_ROUGH_WAVES, ISX_ROUGH_WAVES)))
+isx_trace_assist_wall_rough_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_ROUGH, true>(g, d, wk); }
 
 // ISX_HITLINE_ORIGIN_COMPAT on the pipeline (round 5): what fluxAtObserverFast.C:1181-1201,1285-1288 effectively tested is the line
 // from the origin along lastPoint/|lastPoint| (hit_line_compat).  The trace kernels write last point + final direction as always;

@@ -653,4 +653,32 @@ int exit_maps_all(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t
   return rc;
 }
 
+int wall_map_all(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                 uint64_t* wall_map, isx_wall_map_counts* counts, isx_stats* st) {
+  Comm& c = comm();
+  if (!c.active()) return isx_wall_map(cfg, spec, n_rays, seed, first_ray, wall_map, counts, st);
+  // (a spec the ABI refuses leaves only the status word to exchange)
+  const size_t nm = spec && spec->n_x >= 1 && spec->n_y >= 1 && (long long)spec->n_x * spec->n_y <= ISX_WALL_MAP_MAX_BINS
+                        ? (size_t)spec->n_x * spec->n_y : (size_t)0;
+  uint64_t f, cnt;
+  c.shard(n_rays, f, cnt);
+  isx_stats local{};
+  isx_wall_map_counts k{};
+  std::vector<uint64_t> buf(nm + 4, 0);   // the map | the four counters: ONE sum
+  int rc = isx_wall_map(cfg, spec, cnt, seed, first_ray + f, buf.data(), &k, &local);
+  if (rc == ISX_OK) {
+    uint64_t* w = buf.data() + nm;
+    w[0] = k.binned; w[1] = k.outside; w[2] = k.skipped; w[3] = k.other_surface;
+  }
+  rc = c.reduce(rc, buf.data(), nm ? buf.size() : 0, &local);
+  if (rc != ISX_OK) return rc;
+  if (nm && wall_map) std::memcpy(wall_map, buf.data(), nm * sizeof(uint64_t));
+  if (counts) {
+    const uint64_t* w = buf.data() + nm;
+    counts->binned = w[0]; counts->outside = w[1]; counts->skipped = w[2]; counts->other_surface = w[3];
+  }
+  if (st) *st = local;
+  return rc;
+}
+
 }  // namespace isxhost

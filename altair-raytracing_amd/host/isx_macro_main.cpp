@@ -47,6 +47,7 @@ int main(int argc, char** argv) {
                  "  makeIntegratingSphereNRays |\n"
                  "  integratingSphereDetectorSweep |\n"
                  "  exitMaps [--rays <n>] [--seed <s>] |\n"
+                 "  wallMap [--rays <n>] [--seed <s>] [--bins <n>] [--first-order <k>] |\n"
                  "  distributionSphereDetectorSweep | --selftest-writer <file> | --unique <path> | --shard <n> | --analyze <csv>... | --analyze <folder> [average]\n";
     return 2;
   }
@@ -80,6 +81,12 @@ int main(int argc, char** argv) {
       ++i;
       continue;
     }
+    if ((!std::strcmp(argv[i], "--bins") || !std::strcmp(argv[i], "--first-order")) && i + 1 < argc) {   // wallMap
+      if (argv[i][2] == 'b') options().wall_bins = std::atoi(argv[i + 1]);
+      else options().wall_first_order = std::atoi(argv[i + 1]);
+      ++i;
+      continue;
+    }
     const char* eq = std::strchr(argv[i], '=');
     if (!eq) { std::cerr << "bad argument " << argv[i] << " (want key=value)\n"; return 2; }
     kv[std::string(argv[i], eq - argv[i])] = eq + 1;
@@ -101,6 +108,7 @@ int main(int argc, char** argv) {
   else if (entry == "integratingSphereDetectorSweep") rootMacros::integratingSphereDetectorSweep();
   else if (entry == "distributionSphereDetectorSweep") rootMacros::distributionSphereDetectorSweep();
   else if (entry == "exitMaps") rootMacros::exitMaps();
+  else if (entry == "wallMap") rootMacros::wallMap();
   else { std::cerr << "unknown entry point " << entry << "\n"; return 2; }
   const bool ok = ensure_device();  // false: the entry point printed its error and returned early
   comm().finalize();

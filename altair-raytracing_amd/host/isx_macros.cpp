@@ -1197,6 +1197,62 @@ void exitMaps() {
   }
 }
 
+// Equal-area irradiance map of the inner sphere (isx.h: isx_wall_map) for the library's default configuration.
+void wallMap() {
+  if (!ready_everywhere()) return;
+  isx_config c;
+  isx_default_config(&c);
+  const long n = pick_n(1000000);
+  isx_wall_map_spec sp;
+  isx_default_wall_map_spec(&c, &sp);
+  sp.n_x = options().wall_bins; sp.n_y = options().wall_bins; sp.first_order = options().wall_first_order;
+  const size_t nmap = sp.n_x > 0 && sp.n_y > 0 ? (size_t)sp.n_x * sp.n_y : 1;
+  std::vector<uint64_t> wmap(nmap);
+  isx_wall_map_counts k;
+  isx_stats st;
+  const uint64_t first = take_rays((uint64_t)n);
+  const int rc = wall_map_all(&c, &sp, (uint64_t)n, options().seed, first, wmap.data(), &k, &st);
+  if (rc != ISX_OK) {
+    err() << "Error: isx_wall_map: " << isx_strerror(rc) << std::endl;
+    return;
+  }
+  std::cout << "Mirror interactions: " << st.wall_hits << ", binned: " << k.binned << std::endl;
+  std::ofstream f(outputPath("wall_map.csv"));
+  f << std::setprecision(17);
+  f << "# Wall Map - Generated: " << currentTimeString() << std::endl;
+  f << "# Number of rays: " << n << std::endl;
+  f << "# Seed: " << options().seed << std::endl;
+  f << "# First ray: " << first << std::endl;
+  f << "# Sphere inner radius: " << c.r_in << "cm" << std::endl;
+  f << "# Exit port angle: " << c.theta_max_deg << " degrees" << std::endl;
+  f << "# Reflectance: " << c.reflectance << std::endl;
+  f << "# Bins (x x y): " << sp.n_x << " x " << sp.n_y << std::endl;
+  f << "# First order: " << sp.first_order << std::endl;
+  f << "# Projection: Lambert azimuthal equal-area about +z, unit disc; wall radius " << std::sin(c.theta_max_deg * M_PI / 360.0) << std::endl;
+  f << "# Rays per cm2 = count / " << 4.0 * c.r_in * c.r_in * (2.0 / sp.n_x) * (2.0 / sp.n_y) << std::endl;
+  f << "ix,iy,X,Y,count\n";
+  // the bins whose four corners lie inside the wall disc (radius sin(theta_max / 2) of the unit disc)
+  const double rw = std::sin(c.theta_max_deg * M_PI / 360.0), dx = 2.0 / sp.n_x, dy = 2.0 / sp.n_y;
+  uint64_t lo = UINT64_MAX, hi = 0, sum = 0, inside = 0;
+  for (int iy = 0; iy < sp.n_y; ++iy)
+    for (int ix = 0; ix < sp.n_x; ++ix) {
+      const uint64_t cnt = wmap[(size_t)iy * sp.n_x + ix];
+      const double x0 = -1.0 + ix * dx, y0 = -1.0 + iy * dy;
+      f << ix << "," << iy << "," << (x0 + 0.5 * dx) << "," << (y0 + 0.5 * dy) << "," << cnt << "\n";
+      const double ax = std::max(std::fabs(x0), std::fabs(x0 + dx)), ay = std::max(std::fabs(y0), std::fabs(y0 + dy));
+      if (ax * ax + ay * ay <= rw * rw) {
+        lo = std::min(lo, cnt); hi = std::max(hi, cnt); sum += cnt; inside++;
+      }
+    }
+  f << "# Binned: " << k.binned << std::endl;
+  f << "# Outside: " << k.outside << std::endl;
+  f << "# Skipped: " << k.skipped << std::endl;
+  f << "# Other surface: " << k.other_surface << std::endl;
+  f << "# Bins inside the wall disc: " << inside << std::endl;
+  f << "# Count over those bins (min mean max): " << (inside ? lo : 0) << " " << (inside ? (double)sum / (double)inside : 0.0) << " "
+    << hi << std::endl;
+}
+
 }  // namespace rootMacros
 
 }  // namespace isxhost

@@ -51,6 +51,8 @@ struct RunOptions {
   uint64_t next_ray = 0;           // advances so successive sweeps use fresh Philox streams
   int device = 0;                  // env ISX_DEVICE
   long rays_override = -1;         // env ISX_RAYS: replaces the macros' hard-coded n (tests)
+  int wall_bins = 64;              // wallMap --bins: bins per axis of the wall map
+  int wall_first_order = 0;        // wallMap --first-order
   bool quiet = false;              // env ISX_QUIET
   int flush_rows = 0;              // env ISX_FLUSH_ROWS: theta rows per launch of the per-position sweep, written and flushed
                                    // before the next launch starts (0 = as many as hold ~4e9 rays: one launch for the reference's n)
@@ -169,6 +171,9 @@ void distributionSphereDetectorSweep();                                    // di
 // the same geometry through isx_exit_maps (default spec): exit_direction_map.csv (u,v,count,intensity_per_sr) and
 // exit_plane_map.csv (x_cm,y_cm,count,fraction_per_cm2) -- what a hand-written loop over 3dRayLog.txt was for
 void exitMaps();
+// the wall of the library's default sphere (isx_default_config: reflectance 0.99) through isx_wall_map, --bins x --bins bins:
+// wall_map.csv (ix,iy,X,Y,count) with the four counters and the min / mean / max count over the bins inside the wall disc
+void wallMap();
 }  // namespace rootMacros
 
 }  // namespace isxhost

@@ -3,7 +3,7 @@
 Rays are independent and ray i always draws from Philox stream (seed, i), so ANY partition of
 the index range gives the same summed histogram.  Rank r of P traces the
 contiguous range shard(n, r, P); the only exchange is one SUM all-reduce of the
-[n_theta*n_phi] int64 histogram (+ the 7-word census; the exit maps: both maps + five counters + census) — torch.distributed backend "nccl"
+[n_theta*n_phi] int64 histogram (+ the 7-word census; the exit maps: both maps + five counters + census; the wall map: map + four counters + census) — torch.distributed backend "nccl"
 (= RCCL over xGMI) on GPUs, "gloo" in the CPU tests.
 
 The tracer itself is injected (`trace(cfg, count, seed, first) -> (hits, stats)`): on a GPU
@@ -100,3 +100,34 @@ def exit_maps_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, first
         census = buf[nd + npos + len(EXIT_COUNT_FIELDS):]
     return (dmap, pmap, dict(zip(EXIT_COUNT_FIELDS, (int(x) for x in counts))),
             dict(zip(CENSUS_FIELDS, (int(x) for x in census))))
+
+
+WALL_COUNT_FIELDS = ("binned", "outside", "skipped", "other_surface")
+
+
+def wall_map_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, first_ray: int = 0, device=None):
+    """The wall map (altair_raytracing_amd.wall_map) ray-sharded: this rank's contiguous shard through
+    `trace(cfg, count, seed, spec, first) -> (wall_map, counts, stats)`, then ONE SUM all-reduce that carries the map, the
+    four counters and the census.  Returns (wall_map, counts dict, census dict) -- identical on every rank."""
+    import torch
+    import torch.distributed as dist
+
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(), dist.get_world_size()
+    else:
+        rank, world = 0, 1
+    first, count = shard(n_total, rank, world)
+    wmap, cnt, st = trace(cfg, count, seed, spec, first_ray + first)
+    counts = np.array([getattr(cnt, k) for k in WALL_COUNT_FIELDS], dtype=np.int64)
+    census = np.array([getattr(st, k) for k in CENSUS_FIELDS], dtype=np.int64)
+    if world > 1:
+        buf = torch.from_numpy(np.concatenate([wmap.reshape(-1).astype(np.int64), counts, census]))
+        if device is not None:
+            buf = buf.to(device)
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+        buf = buf.cpu().numpy()
+        nm = wmap.size
+        wmap = buf[:nm].astype(np.uint64).reshape(wmap.shape)
+        counts = buf[nm:nm + len(WALL_COUNT_FIELDS)]
+        census = buf[nm + len(WALL_COUNT_FIELDS):]
+    return (wmap, dict(zip(WALL_COUNT_FIELDS, (int(x) for x in counts))), dict(zip(CENSUS_FIELDS, (int(x) for x in census))))

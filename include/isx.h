@@ -335,6 +335,63 @@ int isx_exit_maps_device(const isx_config* cfg, const isx_exit_map_spec* spec, u
                          uint64_t first_ray, uint64_t* d_dir_map, uint64_t* d_pos_map, uint64_t* d_counts /*[5]*/);
 
 /*
+ * Wall map: where the light strikes the INSIDE of the sphere.  An integrating sphere exists to produce a spatially uniform
+ * irradiance on its wall; this call is the 2-D histogram of every mirror interaction on the inner sphere, in an equal-area
+ * projection, so that a uniformly irradiated wall gives a flat map.  For every mirror interaction that the census counts in
+ * isx_stats.wall_hits take q, the interaction point (the point isx_trace_endstates would report as last_point if the ray ended
+ * there; with ISX_TRACE_CHORD the sampled wall point), j, the ray's interaction count BEFORE this interaction (0-based; it
+ * restarts at 0 for the scattered trace of ISX_SOURCE_BRDF), and the kind of surface:
+ *
+ *       kind is not the inner sphere (rim cone, outer sphere)  :  other_surface += 1
+ *       j < spec.first_order                                   :  skipped += 1
+ *       inv = 1.0 / cfg->r_in                  (once, on the host)
+ *       c  = q.z * inv
+ *       w  = sqrt(0.5 / (1.0 + c))
+ *       X  = (q.x * inv) * w ;  Y = (q.y * inv) * w
+ *       fx = (X + 1.0) * 0.5 * n_x ;  ix = (int)floor(fx)       (same with Y, n_y -> iy)
+ *       0 <= ix < n_x and 0 <= iy < n_y  :  wall_map[iy * n_x + ix] += 1 ,  binned += 1
+ *       else (NaN / inf included)        :  outside += 1
+ *
+ * All operations are IEEE double, evaluated left to right as written, no fma, division and square root correctly rounded.
+ * (X, Y) is the Lambert azimuthal equal-area projection about +z scaled to the unit disc: the wall is the disc of radius
+ * sin(theta_max / 2), the port the ring outside it; equal areas of the sphere are equal areas of the map; the irradiance in
+ * rays per unit area is count / (4 pi r_in^2 * (2 / n_x) (2 / n_y) / pi).  first_order = 1 leaves out the first strike of
+ * every ray (the bright spot of the pencil source) and shows the diffuse field alone.
+ *
+ * For every call: binned + outside + skipped + other_surface == stats.wall_hits, wall_map sums to binned,
+ * stats.bin_increments == binned, and every other field of stats is what isx_fluxmap reports for the same (cfg, n_rays, seed,
+ * first_ray).  The result does not depend on any isx_set_option switch nor on how a job is cut into calls.  cfg->hit_line_mode
+ * and the detector-grid fields of cfg are ignored.
+ *
+ * Limits (a workgroup keeps the u32 map in its LDS next to the rings of its trace kernel): n_x * n_y at most
+ * ISX_WALL_MAP_MAX_BINS, each axis 1..ISX_WALL_MAP_MAX_AXIS, first_order >= 0 -- else ISX_ERR_BAD_CONFIG.
+ */
+#define ISX_WALL_MAP_MAX_BINS 8192
+#define ISX_WALL_MAP_MAX_AXIS 512
+typedef struct isx_wall_map_spec {
+  uint32_t struct_size;      /* sizeof(isx_wall_map_spec), set by isx_default_wall_map_spec(); a spec of another size is refused */
+  uint32_t reserved0;        /* 0 */
+  int32_t n_x, n_y;
+  int32_t first_order;       /* interactions with j < first_order are counted in `skipped`, not binned */
+  int32_t reserved1;         /* 0 */
+} isx_wall_map_spec;
+typedef struct isx_wall_map_counts {
+  uint64_t binned, outside, skipped, other_surface;
+} isx_wall_map_counts;
+
+/* 64 x 64 bins, first_order 0.  No GPU needed. */
+void isx_default_wall_map_spec(const isx_config* cfg, isx_wall_map_spec* spec);
+
+/* Blocking: wall_map[n_y * n_x], *counts (host, zeroed by the callee; counts and stats may be NULL).  Without a HIP device:
+ * ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT. */
+int isx_wall_map(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                 uint64_t* wall_map, isx_wall_map_counts* counts, isx_stats* stats);
+/* ACCUMULATES (+=) into a device-resident map and four device counters (order of isx_wall_map_counts) on the library's
+ * stream and returns after enqueueing; isx_sync() / isx_take_stats() as for isx_fluxmap_device. */
+int isx_wall_map_device(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t n_rays, uint64_t seed,
+                        uint64_t first_ray, uint64_t* d_wall_map, uint64_t* d_counts /*[4]*/);
+
+/*
  * Series driver (sweepSeries, fluxAtObserverOptimize.C:892-921 / fluxAtObserverFast.C:1641-1673):
  * n_cfg configurations sharing one detector grid, traced back to back on the device with ONE
  * host synchronisation; hits[n_cfg][n_theta*n_phi], stats[n_cfg] (t_kernel_ms = whole series).
