@@ -26,6 +26,7 @@ SOURCE_BRDF = 1
 RAY_EXITED, RAY_ABSORBED, RAY_SUSPENDED = 1, 2, 3
 
 WALL_MAP_MAX_BINS, WALL_MAP_MAX_AXIS = 8192, 512   # ISX_WALL_MAP_MAX_BINS / ISX_WALL_MAP_MAX_AXIS
+LIGHT_FIELD_MAX_BINS, LIGHT_FIELD_MAX_AXIS = 1 << 22, 1024   # ISX_LIGHT_FIELD_MAX_BINS / ISX_LIGHT_FIELD_MAX_AXIS
 
 # every symbol include/isx.h declares (tests check the .so exports exactly these)
 EXPORTS = [
@@ -36,6 +37,7 @@ EXPORTS = [
     "isx_fluxmap_series", "isx_disc_sweep_per_position", "isx_last_kernel_ms",
     "isx_default_exit_map_spec", "isx_exit_maps", "isx_exit_maps_device",
     "isx_default_wall_map_spec", "isx_wall_map", "isx_wall_map_device",
+    "isx_default_light_field_spec", "isx_light_field", "isx_light_field_device",
 ]
 
 
@@ -128,6 +130,15 @@ class WallMapCounts(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class LightFieldCounts(C.Structure):
+    """isx_light_field_counts (include/isx.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in ("binned", "pos_outside", "dir_outside", "upward")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -172,6 +183,10 @@ def load():
     L.isx_default_wall_map_spec.restype = None
     L.isx_wall_map.argtypes = [P(Config), P(WallMapSpec), u64, u64, u64, P(u64), P(WallMapCounts), P(Stats)]
     L.isx_wall_map_device.argtypes = [P(Config), P(WallMapSpec), u64, u64, u64, C.c_void_p, C.c_void_p]
+    L.isx_default_light_field_spec.argtypes = [P(Config), P(ExitMapSpec)]
+    L.isx_default_light_field_spec.restype = None
+    L.isx_light_field.argtypes = [P(Config), P(ExitMapSpec), u64, u64, u64, P(u64), P(LightFieldCounts), P(Stats)]
+    L.isx_light_field_device.argtypes = [P(Config), P(ExitMapSpec), u64, u64, u64, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -372,6 +387,35 @@ def wall_map_device(cfg, spec, n_rays, seed, first_ray, d_map_ptr, d_counts_ptr)
     at d_counts_ptr (e.g. torch tensors' data_ptr())."""
     _chk(load().isx_wall_map_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
                                     C.c_void_p(int(d_map_ptr) or None), C.c_void_p(int(d_counts_ptr) or None)), "isx_wall_map_device")
+
+
+def default_light_field_spec(cfg):
+    """32 x 32 position bins at the port plane over the exit maps' default extent, 32 x 32 direction bins (no GPU needed)."""
+    s = ExitMapSpec()
+    load().isx_default_light_field_spec(C.byref(cfg), C.byref(s))
+    return s
+
+
+def light_field(cfg, n_rays, seed, spec=None, first_ray=0):
+    """-> (field[n_y, n_x, n_v, n_u] uint64, LightFieldCounts, Stats): the 4-D position-direction histogram of the port light
+    over the plane z = spec.plane_z (include/isx.h); radiance = count / (N dx dy du dv)."""
+    if spec is None:
+        spec = default_light_field_spec(cfg)
+    axes = (spec.n_y, spec.n_x, spec.n_v, spec.n_u)
+    ok = all(1 <= a <= LIGHT_FIELD_MAX_AXIS for a in axes) and int(np.prod(axes, dtype=np.int64)) <= LIGHT_FIELD_MAX_BINS
+    field = np.zeros(int(np.prod(axes, dtype=np.int64)) if ok else 1, dtype=np.uint64)   # (a refused spec: the library says so)
+    cnt, st = LightFieldCounts(), Stats()
+    _chk(load().isx_light_field(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray), _p(field, C.c_uint64),
+                                C.byref(cnt), C.byref(st)), "isx_light_field")
+    return field.reshape(axes), cnt, st
+
+
+def light_field_device(cfg, spec, n_rays, seed, first_ray, d_field_ptr, d_counts_ptr):
+    """Enqueue on the library stream, accumulating into device memory: the uint64 field at d_field_ptr and four uint64 counters
+    at d_counts_ptr (e.g. torch tensors' data_ptr())."""
+    _chk(load().isx_light_field_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
+                                       C.c_void_p(int(d_field_ptr) or None), C.c_void_p(int(d_counts_ptr) or None)),
+         "isx_light_field_device")
 
 
 def fluxmap_series(cfgs, n_rays, seed, first_ray=0):

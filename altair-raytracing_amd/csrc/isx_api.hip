@@ -65,6 +65,7 @@ struct State {
   int assist = 1;                               // 1: trace kernels with an assist wave per workgroup (assist_body)
   int bin_cols = 1;                             // 1 (2: the same): isx_bin_cols_kernel ((line, column) slots) where bin_slots applies; 0: row slots
   int bin_slots = 1;                            // 1: isx_bin_slots_kernel (slot queues by window length) where the grid allows it
+  int lf_global = 0;                            // 1: isx_bin_lightfield_kernel's global form for a field that fits the LDS as well (diagnostic)
   int surface_pipeline = 1;                     // 1 (default): the lobe / rough-specular borders and the origin-compat hit line on the assist-wave
                                                 // pipeline (round 5); 0: round 1's fused isx_trace_bin_full_kernel
   // options
@@ -364,12 +365,29 @@ int check_wall_spec(const isx_wall_map_spec* s) {
   return ISX_OK;
 }
 
+// isx_light_field: the checked spec and the device accumulators of the call
+struct FieldSink { const isx_exit_map_spec* spec = nullptr; unsigned long long *field = nullptr, *counts = nullptr; };
+
+// isx.h: the limits of a light-field spec (all four axes wanted; the field lives in global memory, or in LDS if it fits)
+int check_field_spec(const isx_exit_map_spec* s) {
+  if (s->struct_size != (uint32_t)sizeof(isx_exit_map_spec)) return ISX_ERR_BAD_CONFIG;
+  long long words = 1;
+  for (int32_t a : {s->n_x, s->n_y, s->n_u, s->n_v}) {
+    if (a < 1 || a > ISX_LIGHT_FIELD_MAX_AXIS) return ISX_ERR_BAD_CONFIG;
+    words *= a;   // (at most 2^40)
+  }
+  if (words > ISX_LIGHT_FIELD_MAX_BINS) return ISX_ERR_BAD_CONFIG;
+  if (!(std::isfinite(s->plane_z) && std::isfinite(s->half_extent) && s->half_extent > 0)) return ISX_ERR_BAD_CONFIG;
+  return ISX_OK;
+}
+
 // LDS of a workgroup's histogram: 4 B per bin, 16-byte aligned
 size_t hist_lds(int nbins) { return ((size_t)nbins * 4 + 15) & ~(size_t)15; }
 
 // The DetGrid of a call's sink, checked, and the dynamic LDS of its fused kernel (histogram + tables, census, Geom, DetGrid).
 int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d_discs, double disc_r, double disc_h,
-              const PerPos* pp, const LogSink* lg, const ExitSink* xm, const WallSink* wm, DetGrid& d, size_t& lds) {
+              const PerPos* pp, const LogSink* lg, const ExitSink* xm, const WallSink* wm, const FieldSink* lf, DetGrid& d,
+              size_t& lds) {
   std::memset(&d, 0, sizeof(d));
   d.portz = c->exit_port_z;
   d.hit_line_mode = c->hit_line_mode;
@@ -427,6 +445,18 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
     d.xm_dir = xm->dir; d.xm_pos = xm->pos; d.xm_counts = xm->counts;
     d.nbins = s.n_u * s.n_v + s.n_x * s.n_y + 5;   // the workgroup's LDS block: direction map | plane map | the five counters
     lds = hist_lds(d.nbins) + 64 + sizeof(Geom) + sizeof(DetGrid);
+  } else if (sink == SINK_LIGHTFIELD) {
+    if (!lf || !lf->spec || !lf->field || !lf->counts) return ISX_ERR_BAD_ARG;
+    rc = check_field_spec(lf->spec);
+    if (rc) return rc;
+    const isx_exit_map_spec& s = *lf->spec;
+    d.hit_line_mode = ISX_HITLINE_LAST_SEGMENT;   // (isx.h: the field always sees the real last segment)
+    // (the spec travels in the exit maps' words of DetGrid: isx_kernels.hpp)
+    d.xm_nu = s.n_u; d.xm_nv = s.n_v; d.xm_nx = s.n_x; d.xm_ny = s.n_y;
+    d.xm_plane_z = s.plane_z; d.xm_half = s.half_extent;
+    d.xm_dir = lf->field; d.xm_counts = lf->counts;
+    d.nbins = 4;   // the LDS block of a fused kernel's workgroup: the four counters (the pipeline's binning kernel: plan_launch)
+    lds = hist_lds(d.nbins) + 64 + sizeof(Geom) + sizeof(DetGrid);
   } else if (sink == SINK_WALL) {
     if (!wm || !wm->spec || !wm->map || !wm->counts) return ISX_ERR_BAD_ARG;
     rc = check_wall_spec(wm->spec);
@@ -459,11 +489,12 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
 // ---- The launch plan of a call: the route, its kernel(s) and their workgroup shapes.
 //  ROUTE_FLUX_PIPE  flux maps: per chunk a trace kernel (exit lines -> HBM workspace) and a binning kernel
 //  ROUTE_EXIT_PIPE  exit maps: the flux pipeline's trace kernels, workspace and chunking; isx_bin_exitmaps_kernel streams the lines
+//  ROUTE_FIELD_PIPE the light field the same way; isx_bin_lightfield_kernel bins into LDS or, a field too large for it, into global memory
 //  ROUTE_DISC_PIPE  the shared-ray disc sweep the same way: assist-wave trace kernel (exit segments) -> isx_bin_discs_kernel
 //  ROUTE_ASSIST     the per-position sinks: one assist-wave kernel, whose assist wave does the exact test per exiting ray;
 //                   the wall map: one assist-wave kernel whose waves bin every interaction into the workgroup's LDS map
 //  ROUTE_FUSED      one kernel that traces and bins: everything the routes above do not serve
-enum Route { ROUTE_FUSED, ROUTE_ASSIST, ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_DISC_PIPE };
+enum Route { ROUTE_FUSED, ROUTE_ASSIST, ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_FIELD_PIPE, ROUTE_DISC_PIPE };
 typedef void (*KernelFn)(const Geom, const DetGrid, const Work);
 typedef void (*BinFn)(const DetGrid, const Work);
 struct Plan {
@@ -477,6 +508,7 @@ struct Plan {
   BinFn bin = nullptr;          // pipelines: the binning kernel, its workgroup size, workgroups per CU and dynamic LDS
   int bblock = 0, bin_per_cu = kResident;
   size_t lds_bin = 0;
+  int bin_words = 0;            // ROUTE_FIELD_PIPE: words of the binning workgroup's LDS block (DetGrid::nbins of that kernel)
   bool assist = true;           // the trace kernel has an assist wave (one writing wave per workgroup)
   bool compat_lines = false;    // isx_compat_lines_kernel runs between the two (ISX_HITLINE_ORIGIN_COMPAT)
   bool binning = true;          // false: bin_mode 2, a diagnostic: trace only
@@ -581,6 +613,20 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     p = Plan();
   }
 
+  // The light field goes the same way wherever the exit maps do.  Its binning kernel has two forms (isx_kernels.hpp): a field of at
+  // most kLightFieldLdsBins words is a u32 field in the workgroup's LDS; a larger one (or any, with lf_global = 1) takes one global
+  // u64 add per binned line, and the LDS holds the four counters only.  The form is the block's size, nothing else.
+  if (sink == SINK_LIGHTFIELD && exit_served && S.pipeline) {
+    pipe_trace(ROUTE_FIELD_PIPE);
+    p.bin = isx_bin_lightfield_kernel;
+    p.bblock = kBlock;
+    const long long field = (long long)d.xm_nu * d.xm_nv * d.xm_nx * d.xm_ny;
+    const bool in_lds = !S.lf_global && field <= kLightFieldLdsBins && hist_lds((int)field + 4) <= S.lds_limit;
+    p.bin_words = in_lds ? (int)field + 4 : 4;
+    p.lds_bin = hist_lds(p.bin_words);
+    return p;
+  }
+
   // The disc pipeline's binning kernel keeps the histogram, the cluster table, the discs (up to kDiscsInLds) and per-wave lists in
   // LDS; above ~16 000 discs on gfx950 they do not fit, and the fused SINK_DISC kernel, which needs the histogram only, takes the sweep.
   const size_t disc_lds = hist_lds(d.nbins) + (size_t)g_disc_clusters.n_clusters * 16 +
@@ -634,6 +680,7 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     case SINK_DZ: p.fn = lean_explicit ? isx_trace_dz_lean_kernel : isx_trace_dz_kernel; break;
     case SINK_EXITMAP: p.fn = border == LAMBERT && pencil && !chord ? isx_trace_exitmap_lean_kernel : isx_trace_exitmap_kernel; break;
     case SINK_WALL: p.fn = border == LAMBERT && pencil && !chord ? isx_trace_wall_lean_kernel : isx_trace_wall_kernel; break;
+    case SINK_LIGHTFIELD: p.fn = border == LAMBERT && pencil && !chord ? isx_trace_lightfield_lean_kernel : isx_trace_lightfield_kernel; break;
     case SINK_DISC: p.fn = lean_explicit ? isx_trace_disc_lean_kernel : isx_trace_disc_kernel; break;
     case SINK_PERPOS: p.fn = lean_explicit ? isx_trace_perpos_lean_kernel : isx_trace_perpos_kernel; break;
     case SINK_DISCPOS: p.fn = lean_explicit ? isx_trace_discpos_lean_kernel : isx_trace_discpos_kernel; break;
@@ -719,7 +766,7 @@ int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles) {
   return ISX_OK;
 }
 
-// ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE and ROUTE_DISC_PIPE: a trace launch and a binning launch per chunk of at most pipe_chunk rays
+// ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_FIELD_PIPE and ROUTE_DISC_PIPE: a trace launch and a binning launch per chunk of at most pipe_chunk rays
 int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
   int rc = set_lds((const void*)p.fn, p.lds);
   if (rc == ISX_OK) rc = set_lds((const void*)p.bin, p.lds_bin);
@@ -730,6 +777,7 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
   DetGrid dt = d, db = d;
   if (p.route != ROUTE_DISC_PIPE) {
     dt.nbins = 1; dt.n_theta = 0; dt.n_phi = 0;
+    if (p.route == ROUTE_FIELD_PIPE) db.nbins = p.bin_words;
   } else {
     db.discs = S.d_aux + g_disc_clusters.off_ordered;
     db.clusters = reinterpret_cast<const float*>(S.d_aux + g_disc_clusters.off_clusters);
@@ -810,7 +858,7 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
 int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t first, unsigned long long* d_hist,
             int nbins_override, const double* d_discs, double disc_r, double disc_h, const PerPos* pp = nullptr,
             const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr, const ExitSink* xm = nullptr,
-            const WallSink* wm = nullptr) {
+            const WallSink* wm = nullptr, const FieldSink* lf = nullptr) {
   Geom g;
   int rc = prepare_geom(c, &g);
   if (rc) return rc;
@@ -818,7 +866,7 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
   if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;   // first + n (the exclusive end of the index range) must be representable
   DetGrid d;
   size_t lds = 0;
-  rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, xm, wm, d, lds);
+  rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, xm, wm, lf, d, lds);
   if (rc || n == 0) return rc;
   Work wk;
   wk.seed = seed; wk.first = first; wk.n = n; wk.hist = d_hist; wk.stats = d_stats ? d_stats : S.d_stats;
@@ -1100,6 +1148,7 @@ int isx_set_option(const char* key, int64_t value) {
   if (!std::strcmp(key, "assist")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.assist = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "bin_cols")) { if (value < 0 || value > 2) return ISX_ERR_BAD_ARG; S.bin_cols = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "bin_slots")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.bin_slots = (int)value; return ISX_OK; }
+  if (!std::strcmp(key, "lf_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.lf_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "surface_pipeline")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.surface_pipeline = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "ray_sub")) { if (value < 0 || value > (1 << 20)) return ISX_ERR_BAD_ARG; S.ray_sub = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "pipeline")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.pipeline = (int)value; return ISX_OK; }
@@ -1462,6 +1511,48 @@ int isx_wall_map(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t 
     const unsigned long long* h = reinterpret_cast<const unsigned long long*>(S.h_pin + 64);
     std::memcpy(wall_map, h, nmap * 8);
     if (counts) { counts->binned = h[nmap]; counts->outside = h[nmap + 1]; counts->skipped = h[nmap + 2]; counts->other_surface = h[nmap + 3]; }
+  }
+  return rc;
+}
+
+void isx_default_light_field_spec(const isx_config* cfg, isx_exit_map_spec* spec) {
+  if (!spec) return;
+  isx_default_exit_map_spec(cfg, spec);   // (plane_z = exit_port_z and the exit maps' half_extent)
+  spec->n_u = 32; spec->n_v = 32; spec->n_x = 32; spec->n_y = 32;
+}
+
+int isx_light_field_device(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                           uint64_t* d_field, uint64_t* d_counts) {
+  // (what needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one)
+  if (!cfg || !spec || !d_field || !d_counts) return ISX_ERR_BAD_ARG;
+  const int bad = check_field_spec(spec);
+  if (bad) return bad;
+  if (!S.init) return not_initialised();
+  const FieldSink lf{spec, (unsigned long long*)d_field, (unsigned long long*)d_counts};
+  return enqueue(SINK_LIGHTFIELD, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &lf);
+}
+
+int isx_light_field(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                    uint64_t* field, isx_light_field_counts* counts, isx_stats* stats) {
+  if (!cfg || !spec || !field) return ISX_ERR_BAD_ARG;
+  if (!config_abi_ok(cfg)) return ISX_ERR_BAD_CONFIG;
+  int rc = check_field_spec(spec);
+  if (rc) return rc;
+  if (!S.init) return not_initialised();
+  const size_t nfield = (size_t)spec->n_x * spec->n_y * spec->n_u * spec->n_v;
+  rc = call_open(nfield + 4);   // (the pooled histogram: at most 32 MiB + the counters)
+  if (rc) return rc;
+  // the call's accumulators in the pooled histogram: the field | the four counters.  The field goes straight into the caller's
+  // memory (up to 32 MiB: not through the staging buffer), the counters through the staging buffer.
+  const FieldSink lf{spec, S.d_hist, S.d_hist + nfield};
+  rc = zero_hist(nfield + 4);
+  if (rc == ISX_OK) rc = enqueue(SINK_LIGHTFIELD, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &lf);
+  if (rc == ISX_OK) rc = copy_out(field, S.d_hist, nfield * sizeof(unsigned long long));
+  if (rc == ISX_OK) rc = stage_result(S.d_hist + nfield, 4 * sizeof(unsigned long long));
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK && counts) {
+    const unsigned long long* k = reinterpret_cast<const unsigned long long*>(S.h_pin + 64);
+    counts->binned = k[0]; counts->pos_outside = k[1]; counts->dir_outside = k[2]; counts->upward = k[3];
   }
   return rc;
 }

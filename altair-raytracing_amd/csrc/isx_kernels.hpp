@@ -72,6 +72,10 @@ struct DetGrid {
   // kernel's parameter block grows: xm_nx x xm_ny = the map's axes, xm_nu = first_order, xm_plane_z = 1 / r_in, xm_pos = the
   // global map [xm_ny][xm_nx] (+=), xm_counts = [4]: binned, outside, skipped, other_surface.  A workgroup's LDS holds
   // u32[xm_nx * xm_ny | 4 counters] (nbins words).
+  // SINK_LIGHTFIELD / isx_bin_lightfield_kernel (isx.h: isx_light_field) likewise: the four axes, xm_plane_z and xm_half as the exit
+  // maps have them, xm_dir = the global field [xm_ny][xm_nx][xm_nv][xm_nu] (+=), xm_counts = [4]: binned, pos_outside, dir_outside,
+  // upward.  A workgroup's LDS holds u32[field | 4 counters] (LDS form) or u32[4 counters] (global form, and the fused kernels):
+  // nbins words either way.
 };
 
 // -DISX_DIAG (tuning builds only, never the shipped library): where the binning work goes.
@@ -110,7 +114,8 @@ __device__ unsigned long long g_diag[48];   // [32..47]: the assist wave of assi
 #define ISX_TD_FLUSH_AT(b_) do { } while (0)
 #endif
 
-enum : int { SINK_FLUX = 0, SINK_DZ = 1, SINK_DISC = 2, SINK_PERPOS = 3, SINK_LOG = 4, SINK_DISCPOS = 5, SINK_REC = 6, SINK_EXITMAP = 7, SINK_WALL = 8 };
+enum : int { SINK_FLUX = 0, SINK_DZ = 1, SINK_DISC = 2, SINK_PERPOS = 3, SINK_LOG = 4, SINK_DISCPOS = 5, SINK_REC = 6, SINK_EXITMAP = 7, SINK_WALL = 8,
+              SINK_LIGHTFIELD = 9 };
 
 struct Work {
   uint64_t seed, first, n;    // one launch traces rays [first, first + n), n < 2^31 (a lane keeps a 31-bit offset from `first`)
@@ -2022,6 +2027,40 @@ __device__ __forceinline__ unsigned long long exitmap_flush(const DetGrid& d_arg
   return flushed;
 }
 
+// ------------------------------------------------------------------ light field (isx.h: isx_light_field)
+// The word of one counted ray in the 4-D field, from the exit maps' two bins (exitmap_bins: the formulas are stated once), in the
+// order of isx.h: upward, then the position bin, then the direction bin.  >= 0: ((iy nx + ix) nv + iv) nu + iu; < 0: the counter.
+enum : int { LF_POS_OUT = -1, LF_DIR_OUT = -2, LF_UP = -3, LF_NONE = -4 /* a lane without a ray */ };
+template <class D>
+__device__ __forceinline__ int lightfield_bin(const D& d, const V3& p, const V3& v) {
+  const ExitBins e = exitmap_bins(d, p, v);
+  if (e.up) return LF_UP;
+  if (e.pos_out) return LF_POS_OUT;
+  if (e.dir_out) return LF_DIR_OUT;
+  const int ndir = d.xm_nu * d.xm_nv;
+  return (e.bp - ndir) * ndir + e.bd;   // (at most ISX_LIGHT_FIELD_MAX_BINS = 2^22 words)
+}
+// the four counters of a wave's batch: ballots and popcounts into wave-uniform words (cnt[4], order of isx_light_field_counts)
+__device__ __forceinline__ void lightfield_count(int b, uint32_t* cnt) {
+  cnt[0] += (uint32_t)__popcll(__ballot(b >= 0));
+  cnt[1] += (uint32_t)__popcll(__ballot(b == LF_POS_OUT));
+  cnt[2] += (uint32_t)__popcll(__ballot(b == LF_DIR_OUT));
+  cnt[3] += (uint32_t)__popcll(__ballot(b == LF_UP));
+}
+// One flush of a workgroup's LDS block (after a barrier): the non-zero words of the u32 field, if the block holds one (nfield > 0),
+// into the u64 global field, the four counters into xm_counts.  Returns the workgroup's `binned` in the thread that flushed it.
+__device__ __forceinline__ unsigned long long lightfield_flush(const DetGrid& d_arg, const uint32_t* hist, int nfield, int tid, int nthr) {
+  unsigned long long binned = 0;
+  for (int b = tid; b < nfield + 4; b += nthr) {
+    const uint32_t c = hist[b];
+    if (!c) continue;
+    if (b < nfield) global_add_u64(d_arg.xm_dir + b, (unsigned long long)c);
+    else global_add_u64(d_arg.xm_counts + (b - nfield), (unsigned long long)c);
+    if (b == nfield) binned = c;
+  }
+  return binned;
+}
+
 // ------------------------------------------------------------------ wall map (isx.h: isx_wall_map)
 // The spec of a call as the trace loops keep it: wave-uniform words (scalar registers).
 struct WallSpec { int nx; uint32_t first; double inv, fnx, fny; };
@@ -2094,6 +2133,8 @@ __device__ __forceinline__ unsigned long long wall_flush(const DetGrid& d_arg, c
 //   SINK_DZ  : histogram of the exit direction's z component (distributionSphereDetectorSweep.C:54,91)
 //   SINK_DISC: physical disc sweep (integratingSphereDetectorSweep.C)
 //   SINK_EXITMAP: direction map + plane map of the exit line (isx_exit_maps) -- the fused fallback of isx_bin_exitmaps_kernel
+//   SINK_LIGHTFIELD: 4-D position-direction field of the exit line (isx_light_field) -- the fused fallback of
+//              isx_bin_lightfield_kernel: one global u64 add per binned ray, the four counters in LDS (nbins = 4)
 //   SINK_WALL: equal-area map of the interaction points on the inner sphere (isx_wall_map), binned at the arrival -- every
 //              configuration; the assist-wave kernels (assist_body<.., WALL>) are the default route
 template <int SINK, bool LEAN = false, int CH = 2, bool RESC = !LEAN>
@@ -2167,6 +2208,7 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
   uint32_t n_taken = 0;                                                          // per wave: rays taken off the queue
   uint32_t reg_slot = 0, reg_left = 0, reg_id = 0xffffffffu;                     // per wave (SINK_REC): cursor in the open region
   uint32_t n_xm[5] = {0u, 0u, 0u, 0u, 0u};                                       // per wave (SINK_EXITMAP): isx_exit_map_counts
+                                                                                 // (SINK_LIGHTFIELD: [0..3] isx_light_field_counts)
   const WallSpec wspec = wall_spec<SINK == SINK_WALL>(d_arg);                    // SINK_WALL: the spec, the map's words
   const int wall_nmap = d_arg.xm_nx * d_arg.xm_ny;
   ISX_TD_DECL;
@@ -2398,6 +2440,14 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
         if (e.bp >= 0) atomicAdd(&hist[e.bp], 1u);
         exitmap_count(e, n_xm);
       }
+    } else if (SINK == SINK_LIGHTFIELD) {
+      // per-lane: the ray's word of the 4-D field, straight into the global field (the spec is read from the LDS copy when a ray left)
+      if (__ballot(bin_me)) {
+        int b = LF_NONE;
+        if (bin_me) b = lightfield_bin(d, r.p, r.v);
+        if (b >= 0) global_add_u64(d_arg.xm_dir + b, 1ull);
+        lightfield_count(b, n_xm);
+      }
     } else if (SINK == SINK_WALL) {
       // (binned at every arrival: nothing is left to do for a ray that ended)
     } else if (SINK == SINK_DZ) {
@@ -2491,11 +2541,14 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
     atomicAdd(&sstat[5], n_inc);
     if (SINK == SINK_EXITMAP)   // (the counters are the last five words of the workgroup's block)
       for (int k = 0; k < 5; ++k) if (n_xm[k]) atomicAdd(&hist[nbins - 5 + k], n_xm[k]);
+    if (SINK == SINK_LIGHTFIELD)   // (the workgroup's block is the four counters)
+      for (int k = 0; k < 4; ++k) if (n_xm[k]) atomicAdd(&hist[k], n_xm[k]);
   }
   __syncthreads();
   unsigned long long flushed = 0;   // increments of this block = sum of its LDS bins
   if (SINK == SINK_EXITMAP) flushed = exitmap_flush(d_arg, hist, tid, nthr);
   else if (SINK == SINK_WALL) flushed = wall_flush(d_arg, hist, tid, nthr);
+  else if (SINK == SINK_LIGHTFIELD) flushed = lightfield_flush(d_arg, hist, 0, tid, nthr);
   else for (int b = tid; b < nbins; b += nthr) {
     const uint32_t c = hist[b];
     if (c) { global_add_u64(&wk.hist[b], (unsigned long long)c); flushed += c; }
@@ -2535,6 +2588,11 @@ extern "C" __global__ void ISX_KERNEL_ATTR
 isx_trace_exitmap_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_EXITMAP>(g, d, wk); }
 extern "C" __global__ void ISX_KERNEL_ATTR
 isx_trace_exitmap_lean_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_EXITMAP, true, 0>(g, d, wk); }
+// the light field where the two-kernel pipeline does not serve it (isx_api.hip: plan_launch)
+extern "C" __global__ void ISX_KERNEL_ATTR
+isx_trace_lightfield_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_LIGHTFIELD>(g, d, wk); }
+extern "C" __global__ void ISX_KERNEL_ATTR
+isx_trace_lightfield_lean_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_LIGHTFIELD, true, 0>(g, d, wk); }
 // the wall map where the assist-wave kernels do not serve it (isx_api.hip: plan_launch): every configuration
 extern "C" __global__ void ISX_KERNEL_ATTR
 isx_trace_wall_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_WALL>(g, d, wk); }
@@ -3374,6 +3432,72 @@ isx_bin_exitmaps_kernel(const DetGrid d_arg, const Work wk) {
   __syncthreads();
   const unsigned long long flushed = exitmap_flush(d_arg, hist, tid, nthr);
   if (flushed) atomicAdd(&wk.stats[5], flushed);
+}
+
+// ------------------------------------------------------------------ binning kernel of the light field (isx_light_field)
+// The exit maps' streaming structure -- persistent waves, quarter regions off the launch's queue, one lane per 48-byte line, the
+// loads of a unit's four batches issued before the first is used -- with ONE word per line (lightfield_bin) in a field of up to
+// 2^22 bins, which no longer fits the LDS.  Two forms, chosen by the plan through the words of the workgroup's LDS block (nbins):
+//   LDS form    (nbins = field + 4, field <= kLightFieldLdsBins): a u32 field in LDS, one ds_add_u32 per binned line, one flush of
+//               the non-zero words per workgroup with u64 atomics -- the exit maps' structure;
+//   global form (nbins = 4): one no-return device-scope u64 atomic add per binned line straight into the destination field.  The
+//               adds of a wave are scattered (same-word multiplicity within a wave: 1.016 for the flux map, docs/LOG.md 4.3), so
+//               nothing is combined across lanes.
+// The four counters are ballots and popcounts, through LDS, one flush per workgroup, in both forms.
+constexpr int kLightFieldLdsBins = 32768;   // largest field of the LDS form: (32768 + 4) x 4 B = 128 KiB + 16 B of the CU's 160 KiB
+extern "C" __global__ void __launch_bounds__(kBlock)
+isx_bin_lightfield_kernel(const DetGrid d_arg, const Work wk) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  uint32_t* hist = reinterpret_cast<uint32_t*>(smem);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int nthr = (int)blockDim.x;
+  const int nfield = d_arg.nbins - 4;   // words of the field in LDS; 0: global form
+  const bool in_lds = nfield > 0;
+  for (int b = tid; b < nfield + 4; b += nthr) hist[b] = 0u;
+  __syncthreads();
+  uint32_t cnt[4] = {0u, 0u, 0u, 0u};
+  const uint32_t n_regions = wk.ctr[Q_REGIONS];   // (the trace kernel of this launch has completed)
+  const uint32_t ushift = 2u + wk.pad;            // a work unit = 1024 >> ushift exit lines of one region (Work::pad)
+#pragma unroll 1
+  for (;;) {
+    uint32_t unit = 0;
+    if (lane == 0) unit = atomicAdd(&wk.ctr[Q_BIN], 1u);
+    unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)unit);
+    const uint32_t region = unit >> ushift;
+    if (region >= n_regions) break;
+    const uint32_t r_lines = (uint32_t)__builtin_amdgcn_readfirstlane((int)d_arg.rec_counts[region]);
+    const uint32_t q_first = (unit & ((1u << ushift) - 1u)) * (kRegion >> ushift);
+    const uint32_t n_lines = r_lines < q_first + (kRegion >> ushift) ? r_lines : q_first + (kRegion >> ushift);
+    const double* rec = d_arg.rec_lines + 6ull * ((uint64_t)region * kRegion);
+#pragma unroll 1
+    for (uint32_t b0 = q_first; b0 < n_lines; b0 += 256u) {
+      V3 lp[4], lv[4];
+      bool have[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t i = b0 + 64u * (uint32_t)k + (uint32_t)lane;
+        have[k] = i < n_lines;
+        lp[k].x = lp[k].y = lp[k].z = 0.0; lv[k].x = lv[k].y = 0.0; lv[k].z = -1.0;
+        if (have[k]) load_line(rec + 6ull * i, lp[k], lv[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!__ballot(have[k])) continue;
+        int b = LF_NONE;
+        if (have[k]) b = lightfield_bin(d_arg, lp[k], lv[k]);
+        if (b >= 0) {
+          if (in_lds) atomicAdd(&hist[b], 1u);
+          else global_add_u64(d_arg.xm_dir + b, 1ull);
+        }
+        lightfield_count(b, cnt);
+      }
+    }
+  }
+  if (lane == 0)
+    for (int k = 0; k < 4; ++k) if (cnt[k]) atomicAdd(&hist[nfield + k], cnt[k]);
+  __syncthreads();
+  const unsigned long long binned = lightfield_flush(d_arg, hist, nfield, tid, nthr);
+  if (binned) atomicAdd(&wk.stats[5], binned);
 }
 
 // ------------------------------------------------------------------ disc-binning kernel of the shared-ray disc sweep

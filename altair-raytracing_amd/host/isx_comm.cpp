@@ -681,4 +681,35 @@ int wall_map_all(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t 
   return rc;
 }
 
+int light_field_all(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                    uint64_t* field, isx_light_field_counts* counts, isx_stats* st) {
+  Comm& c = comm();
+  if (!c.active()) return isx_light_field(cfg, spec, n_rays, seed, first_ray, field, counts, st);
+  // (a spec the ABI refuses leaves only the status word to exchange)
+  long long words = spec ? 1 : 0;
+  if (spec)
+    for (long long a : {(long long)spec->n_x, (long long)spec->n_y, (long long)spec->n_u, (long long)spec->n_v})
+      words = a >= 1 && a <= ISX_LIGHT_FIELD_MAX_AXIS && words > 0 ? words * a : 0;
+  const size_t nf = words <= ISX_LIGHT_FIELD_MAX_BINS ? (size_t)words : (size_t)0;
+  uint64_t f, cnt;
+  c.shard(n_rays, f, cnt);
+  isx_stats local{};
+  isx_light_field_counts k{};
+  std::vector<uint64_t> buf(nf + 4, 0);   // the field | the four counters: ONE sum
+  int rc = isx_light_field(cfg, spec, cnt, seed, first_ray + f, buf.data(), &k, &local);
+  if (rc == ISX_OK) {
+    uint64_t* w = buf.data() + nf;
+    w[0] = k.binned; w[1] = k.pos_outside; w[2] = k.dir_outside; w[3] = k.upward;
+  }
+  rc = c.reduce(rc, buf.data(), nf ? buf.size() : 0, &local);
+  if (rc != ISX_OK) return rc;
+  if (nf && field) std::memcpy(field, buf.data(), nf * sizeof(uint64_t));
+  if (counts) {
+    const uint64_t* w = buf.data() + nf;
+    counts->binned = w[0]; counts->pos_outside = w[1]; counts->dir_outside = w[2]; counts->upward = w[3];
+  }
+  if (st) *st = local;
+  return rc;
+}
+
 }  // namespace isxhost

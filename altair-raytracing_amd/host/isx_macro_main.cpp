@@ -48,6 +48,7 @@ int main(int argc, char** argv) {
                  "  integratingSphereDetectorSweep |\n"
                  "  exitMaps [--rays <n>] [--seed <s>] |\n"
                  "  wallMap [--rays <n>] [--seed <s>] [--bins <n>] [--first-order <k>] |\n"
+                 "  lightField [--rays <n>] [--seed <s>] |\n"
                  "  distributionSphereDetectorSweep | --selftest-writer <file> | --unique <path> | --shard <n> | --analyze <csv>... | --analyze <folder> [average]\n";
     return 2;
   }
@@ -109,6 +110,7 @@ int main(int argc, char** argv) {
   else if (entry == "distributionSphereDetectorSweep") rootMacros::distributionSphereDetectorSweep();
   else if (entry == "exitMaps") rootMacros::exitMaps();
   else if (entry == "wallMap") rootMacros::wallMap();
+  else if (entry == "lightField") rootMacros::lightField();
   else { std::cerr << "unknown entry point " << entry << "\n"; return 2; }
   const bool ok = ensure_device();  // false: the entry point printed its error and returned early
   comm().finalize();

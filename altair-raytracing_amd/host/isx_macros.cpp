@@ -1253,6 +1253,54 @@ void wallMap() {
     << hi << std::endl;
 }
 
+// Position-direction radiance field of the port of the library's default sphere (isx.h: isx_light_field), default spec.
+void lightField() {
+  if (!ready_everywhere()) return;
+  isx_config c;
+  isx_default_config(&c);
+  const long n = pick_n(1000000);
+  isx_exit_map_spec sp;
+  isx_default_light_field_spec(&c, &sp);
+  std::vector<uint64_t> field((size_t)sp.n_x * sp.n_y * sp.n_u * sp.n_v);
+  isx_light_field_counts k;
+  isx_stats st;
+  const uint64_t first = take_rays((uint64_t)n);
+  const int rc = light_field_all(&c, &sp, (uint64_t)n, options().seed, first, field.data(), &k, &st);
+  if (rc != ISX_OK) {
+    err() << "Error: isx_light_field: " << isx_strerror(rc) << std::endl;
+    return;
+  }
+  std::cout << "Flux of rays through the exit port: " << st.counted_below_z << ", binned: " << k.binned << std::endl;
+  std::ofstream f(outputPath("light_field.csv"));
+  f << std::setprecision(17);
+  f << "# Port Light Field - Generated: " << currentTimeString() << std::endl;
+  f << "# Number of rays: " << n << std::endl;
+  f << "# Seed: " << options().seed << std::endl;
+  f << "# First ray: " << first << std::endl;
+  f << "# Rays through the exit port: " << st.counted_below_z << std::endl;
+  f << "# Sphere inner radius: " << c.r_in << "cm" << std::endl;
+  f << "# Exit port angle: " << c.theta_max_deg << " degrees" << std::endl;
+  f << "# Exit port z: " << c.exit_port_z << "cm" << std::endl;
+  f << "# Position bins (x x y): " << sp.n_x << " x " << sp.n_y << std::endl;
+  f << "# Direction bins (u x v): " << sp.n_u << " x " << sp.n_v << std::endl;
+  f << "# Plane z: " << sp.plane_z << "cm" << std::endl;
+  f << "# Plane half extent: " << sp.half_extent << "cm" << std::endl;
+  f << "# Binned: " << k.binned << std::endl;
+  f << "# Position outside: " << k.pos_outside << std::endl;
+  f << "# Direction outside: " << k.dir_outside << std::endl;
+  f << "# Upward: " << k.upward << std::endl;
+  // radiance per launched ray = count / (N dx dy du dv) in direction-cosine space (isx.h)
+  const double dx = 2.0 * sp.half_extent / sp.n_x, dy = 2.0 * sp.half_extent / sp.n_y, du = 2.0 / sp.n_u, dv = 2.0 / sp.n_v;
+  f << "# Radiance normalisation (count / N dx dy du dv), N dx dy du dv: " << (double)n * dx * dy * du * dv << std::endl;
+  f << "ix,iy,iu,iv,count\n";
+  size_t w = 0;
+  for (int iy = 0; iy < sp.n_y; ++iy)
+    for (int ix = 0; ix < sp.n_x; ++ix)
+      for (int iv = 0; iv < sp.n_v; ++iv)
+        for (int iu = 0; iu < sp.n_u; ++iu, ++w)
+          if (field[w]) f << ix << "," << iy << "," << iu << "," << iv << "," << field[w] << "\n";
+}
+
 }  // namespace rootMacros
 
 }  // namespace isxhost

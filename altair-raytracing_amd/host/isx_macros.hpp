@@ -174,6 +174,10 @@ void exitMaps();
 // the wall of the library's default sphere (isx_default_config: reflectance 0.99) through isx_wall_map, --bins x --bins bins:
 // wall_map.csv (ix,iy,X,Y,count) with the four counters and the min / mean / max count over the bins inside the wall disc
 void wallMap();
+// the port of the same sphere through isx_light_field (default spec: 32 x 32 position bins x 32 x 32 direction bins):
+// light_field.csv, sparse -- the non-zero bins (ix,iy,iu,iv,count) in index order under '#' lines with the spec, the counters and
+// the radiance normalisation N dx dy du dv
+void lightField();
 }  // namespace rootMacros
 
 }  // namespace isxhost

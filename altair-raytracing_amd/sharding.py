@@ -131,3 +131,34 @@ def wall_map_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, first_
         counts = buf[nm:nm + len(WALL_COUNT_FIELDS)]
         census = buf[nm + len(WALL_COUNT_FIELDS):]
     return (wmap, dict(zip(WALL_COUNT_FIELDS, (int(x) for x in counts))), dict(zip(CENSUS_FIELDS, (int(x) for x in census))))
+
+
+FIELD_COUNT_FIELDS = ("binned", "pos_outside", "dir_outside", "upward")
+
+
+def light_field_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, first_ray: int = 0, device=None):
+    """The port light field (altair_raytracing_amd.light_field) ray-sharded: this rank's contiguous shard through
+    `trace(cfg, count, seed, spec, first) -> (field, counts, stats)`, then ONE SUM all-reduce that carries the field, the
+    four counters and the census.  Returns (field, counts dict, census dict) -- identical on every rank."""
+    import torch
+    import torch.distributed as dist
+
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(), dist.get_world_size()
+    else:
+        rank, world = 0, 1
+    first, count = shard(n_total, rank, world)
+    field, cnt, st = trace(cfg, count, seed, spec, first_ray + first)
+    counts = np.array([getattr(cnt, k) for k in FIELD_COUNT_FIELDS], dtype=np.int64)
+    census = np.array([getattr(st, k) for k in CENSUS_FIELDS], dtype=np.int64)
+    if world > 1:
+        buf = torch.from_numpy(np.concatenate([field.reshape(-1).astype(np.int64), counts, census]))
+        if device is not None:
+            buf = buf.to(device)
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+        buf = buf.cpu().numpy()
+        nf = field.size
+        field = buf[:nf].astype(np.uint64).reshape(field.shape)
+        counts = buf[nf:nf + len(FIELD_COUNT_FIELDS)]
+        census = buf[nf + len(FIELD_COUNT_FIELDS):]
+    return (field, dict(zip(FIELD_COUNT_FIELDS, (int(x) for x in counts))), dict(zip(CENSUS_FIELDS, (int(x) for x in census))))

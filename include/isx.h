@@ -190,6 +190,8 @@ int isx_last_kernel_ms(double* single_ms, double* trace_ms, double* bin_ms);
  *                  line run on the assist-wave pipeline too (isx_trace_assist_lobe_kernel / ..._rough_kernel; the compat lines are
  *                  rewritten by isx_compat_lines_kernel between the trace and the binning kernel); 0: round 1's fused
  *                  isx_trace_bin_full_kernel
+ *   "lf_global"    0 (default): isx_light_field bins a field of at most 32 768 words in the workgroup's LDS and a larger one with
+ *                  one global atomic add per ray; 1: the global form for every field (a diagnostic)
  *   "bin_block", "bin_blocks_per_cu"  shape of round 2's binning kernel (0 workgroups per CU = what is resident)
  *                  (round 5: "assist_block" 0 = the default again -- 768 threads, 256 for launches below 1e6 rays, 512 for the lobe /
  *                  rough-specular kernels; "rays_per_lane" > 0 sizes every grid for that many rays per tracer lane, 0 = by launch
@@ -390,6 +392,55 @@ int isx_wall_map(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t 
  * stream and returns after enqueueing; isx_sync() / isx_take_stats() as for isx_fluxmap_device. */
 int isx_wall_map_device(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t n_rays, uint64_t seed,
                         uint64_t first_ray, uint64_t* d_wall_map, uint64_t* d_counts /*[4]*/);
+
+/*
+ * Port light field: the radiance of the port as a function of position AND direction.  The exit maps are its two marginals (the
+ * direction map summed over the port, the plane map summed over all directions); what says whether the port is a uniform source
+ * from every viewing angle, and what any camera or detector in free space would read, is the joint quantity L(x, y, u, v) over
+ * the plane z = plane_z.  In direction-cosine space (u, v) = (v.x, v.y) the cos(theta) of the projected area and the solid angle
+ * cancel: radiance = count / (N dx dy du dv) with dx = 2 half_extent / n_x, dy = 2 half_extent / n_y, du = 2 / n_u, dv = 2 / n_v,
+ * and a Lambertian, uniform port gives a flat 4-D field.
+ *
+ * The spec is an isx_exit_map_spec: the same six fields with the same meaning, all four axes >= 1.  For every ray the census
+ * counts in counted_below_z, with p = last point and v = final direction as isx_trace_endstates returns them
+ * (cfg->hit_line_mode is ignored; for ISX_SOURCE_BRDF the scattered ray), in this order:
+ *
+ *       v.z < 0.0 is false                        :  upward += 1                     (as in the plane map)
+ *       (ix, iy) by the plane map's formulas above, operation for operation (t, x, y, fx, fy, floor)
+ *       not (0 <= ix < n_x and 0 <= iy < n_y)     :  pos_outside += 1                (NaN / inf included)
+ *       (iu, iv) by the direction map's formulas above, operation for operation
+ *       not (0 <= iu < n_u and 0 <= iv < n_v)     :  dir_outside += 1                (only rays that have a position bin)
+ *       else  field[((iy * n_x + ix) * n_v + iv) * n_u + iu] += 1 ,  binned += 1
+ *
+ * All operations are IEEE double, evaluated left to right as written, no fma.  For every call:
+ * binned + pos_outside + dir_outside + upward == stats.counted_below_z, field sums to binned, stats.bin_increments == binned,
+ * every other field of stats is what isx_fluxmap reports for the same (cfg, n_rays, seed, first_ray), and upward and pos_outside
+ * equal those of isx_exit_maps for the same (n_x, n_y, plane_z, half_extent).  The result does not depend on any
+ * isx_set_option switch nor on how a job is cut into calls.
+ *
+ * Limits: each axis 1..ISX_LIGHT_FIELD_MAX_AXIS, n_x * n_y * n_u * n_v at most ISX_LIGHT_FIELD_MAX_BINS (32 MiB of uint64),
+ * plane_z and half_extent finite, half_extent > 0, struct_size == sizeof(isx_exit_map_spec) -- else ISX_ERR_BAD_CONFIG; a NULL
+ * spec or field: ISX_ERR_BAD_ARG.  Both are answered whether or not a device is present.  A field of at most 32 768 words is
+ * binned in the workgroups' LDS, a larger one with one global atomic add per binned ray ("lf_global").
+ */
+#define ISX_LIGHT_FIELD_MAX_BINS (1 << 22)
+#define ISX_LIGHT_FIELD_MAX_AXIS 1024
+typedef struct isx_light_field_counts {
+  uint64_t binned, pos_outside, dir_outside, upward;
+} isx_light_field_counts;
+
+/* 32 x 32 position bins at plane_z = cfg->exit_port_z with the exit maps' default half_extent, 32 x 32 direction bins.
+ * No GPU needed. */
+void isx_default_light_field_spec(const isx_config* cfg, isx_exit_map_spec* spec);
+
+/* Blocking: field[n_y * n_x * n_v * n_u], *counts (host, zeroed by the callee; counts and stats may be NULL).  Without a HIP
+ * device: ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT (as isx_wall_map). */
+int isx_light_field(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                    uint64_t* field, isx_light_field_counts* counts, isx_stats* stats);
+/* ACCUMULATES (+=) into a device-resident field and four device counters (order of isx_light_field_counts) on the library's
+ * stream and returns after enqueueing; isx_sync() / isx_take_stats() as for isx_fluxmap_device. */
+int isx_light_field_device(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t n_rays, uint64_t seed,
+                           uint64_t first_ray, uint64_t* d_field, uint64_t* d_counts /*[4]*/);
 
 /*
  * Series driver (sweepSeries, fluxAtObserverOptimize.C:892-921 / fluxAtObserverFast.C:1641-1673):

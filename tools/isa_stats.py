@@ -23,6 +23,7 @@ SRC = os.path.join(ROOT, "altair-raytracing_amd", "csrc", "isx_api.hip")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function"]
 # kernels that must not spill: the binning kernels and the trace kernels the BASELINE configurations run
 NO_SCRATCH = ("isx_bin_cols_kernel", "isx_bin_slots_kernel", "isx_bin_lines_kernel", "isx_bin_discs_kernel", "isx_bin_exitmaps_kernel",
+              "isx_bin_lightfield_kernel", "isx_trace_lightfield_kernel", "isx_trace_lightfield_lean_kernel",
               "isx_trace_assist_kernel", "isx_trace_assist_brdf_kernel", "isx_trace_assist_chord_kernel",
               "isx_trace_assist_perpos_kernel", "isx_trace_assist_lobe_kernel", "isx_trace_assist_rough_kernel",
               "isx_trace_wall_kernel", "isx_trace_wall_lean_kernel", "isx_trace_assist_wall_kernel", "isx_trace_assist_wall_chord_kernel",
