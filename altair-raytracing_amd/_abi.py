@@ -27,6 +27,7 @@ RAY_EXITED, RAY_ABSORBED, RAY_SUSPENDED = 1, 2, 3
 
 WALL_MAP_MAX_BINS, WALL_MAP_MAX_AXIS = 8192, 512   # ISX_WALL_MAP_MAX_BINS / ISX_WALL_MAP_MAX_AXIS
 LIGHT_FIELD_MAX_BINS, LIGHT_FIELD_MAX_AXIS = 1 << 22, 1024   # ISX_LIGHT_FIELD_MAX_BINS / ISX_LIGHT_FIELD_MAX_AXIS
+ORDER_HIST_MAX_ORDERS, ORDER_HIST_MAX_WORDS, ORDER_HIST_MAX_DZ = 2048, 8192, 64   # ISX_ORDER_HIST_MAX_ORDERS / _MAX_WORDS, n_dz <= 64
 
 # every symbol include/isx.h declares (tests check the .so exports exactly these)
 EXPORTS = [
@@ -38,6 +39,7 @@ EXPORTS = [
     "isx_default_exit_map_spec", "isx_exit_maps", "isx_exit_maps_device",
     "isx_default_wall_map_spec", "isx_wall_map", "isx_wall_map_device",
     "isx_default_light_field_spec", "isx_light_field", "isx_light_field_device",
+    "isx_default_order_hist_spec", "isx_order_hist", "isx_order_hist_device", "isx_order_reweight",
 ]
 
 
@@ -139,6 +141,26 @@ class LightFieldCounts(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class OrderHistSpec(C.Structure):
+    """isx_order_hist_spec (include/isx.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("n_orders", C.c_int32), ("n_dz", C.c_int32)]
+
+    def copy(self):
+        s = OrderHistSpec()
+        C.memmove(C.byref(s), C.byref(self), C.sizeof(OrderHistSpec))
+        return s
+
+
+class OrderHistCounts(C.Structure):
+    """isx_order_hist_counts (include/isx.h): overflow per class (port, exited otherwise, absorbed, suspended), dz_outside."""
+
+    _fields_ = [("overflow", C.c_uint64 * 4), ("dz_outside", C.c_uint64)]
+
+    def as_dict(self):
+        return {"overflow": [int(x) for x in self.overflow], "dz_outside": int(self.dz_outside)}
+
+
 _lib = None
 
 
@@ -187,6 +209,12 @@ def load():
     L.isx_default_light_field_spec.restype = None
     L.isx_light_field.argtypes = [P(Config), P(ExitMapSpec), u64, u64, u64, P(u64), P(LightFieldCounts), P(Stats)]
     L.isx_light_field_device.argtypes = [P(Config), P(ExitMapSpec), u64, u64, u64, C.c_void_p, C.c_void_p]
+    L.isx_default_order_hist_spec.argtypes = [P(Config), P(OrderHistSpec)]
+    L.isx_default_order_hist_spec.restype = None
+    L.isx_order_hist.argtypes = [P(Config), P(OrderHistSpec), u64, u64, u64, P(u64), P(u64), P(OrderHistCounts), P(Stats)]
+    L.isx_order_hist_device.argtypes = [P(Config), P(OrderHistSpec), u64, u64, u64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.isx_order_reweight.argtypes = [P(Config), P(OrderHistSpec), P(u64), P(OrderHistCounts), u64, P(C.c_double), C.c_int32,
+                                     P(C.c_double), P(C.c_double)]
     _lib = L
     return L
 
@@ -416,6 +444,58 @@ def light_field_device(cfg, spec, n_rays, seed, first_ray, d_field_ptr, d_counts
     _chk(load().isx_light_field_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
                                        C.c_void_p(int(d_field_ptr) or None), C.c_void_p(int(d_counts_ptr) or None)),
          "isx_light_field_device")
+
+
+def default_order_hist_spec(cfg):
+    """512 orders, 8 dz bins (no GPU needed)."""
+    s = OrderHistSpec()
+    load().isx_default_order_hist_spec(C.byref(cfg), C.byref(s))
+    return s
+
+
+def _order_sizes(spec):
+    """(n_orders, n_dz) of the arrays a call may write; (1, 0) for a spec the library refuses (it says so itself)."""
+    ok = (1 <= spec.n_orders <= ORDER_HIST_MAX_ORDERS and 0 <= spec.n_dz <= ORDER_HIST_MAX_DZ and
+          spec.n_orders * (4 + spec.n_dz) <= ORDER_HIST_MAX_WORDS)
+    return (spec.n_orders, spec.n_dz) if ok else (1, 0)
+
+
+def order_hist(cfg, n_rays, seed, spec=None, first_ray=0):
+    """-> (hist[4, n_orders] uint64, port_dz[n_orders, n_dz] uint64, OrderHistCounts, Stats): the bounce order at which every ray
+    ended, by class -- 0 counted below z, 1 exited otherwise, 2 absorbed, 3 suspended -- and, for the counted rays, by the z of
+    the final direction (include/isx.h)."""
+    if spec is None:
+        spec = default_order_hist_spec(cfg)
+    no, nz = _order_sizes(spec)
+    hist = np.zeros(4 * no, dtype=np.uint64)
+    dz = np.zeros(max(no * nz, 1), dtype=np.uint64)
+    cnt, st = OrderHistCounts(), Stats()
+    _chk(load().isx_order_hist(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray), _p(hist, C.c_uint64),
+                               _p(dz, C.c_uint64), C.byref(cnt), C.byref(st)), "isx_order_hist")
+    return hist.reshape(4, no), dz[:no * nz].reshape(no, nz), cnt, st
+
+
+def order_hist_device(cfg, spec, n_rays, seed, first_ray, d_hist_ptr, d_port_dz_ptr, d_counts_ptr):
+    """Enqueue on the library stream, accumulating into device memory: the uint64 histograms [4][n_orders] at d_hist_ptr, the
+    port's [n_orders][n_dz] at d_port_dz_ptr (0 / None where n_dz == 0) and five uint64 counters at d_counts_ptr (e.g. torch
+    tensors' data_ptr())."""
+    _chk(load().isx_order_hist_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
+                                      C.c_void_p(int(d_hist_ptr or 0) or None), C.c_void_p(int(d_port_dz_ptr or 0) or None),
+                                      C.c_void_p(int(d_counts_ptr or 0) or None)), "isx_order_hist_device")
+
+
+def order_reweight(cfg, spec, hist, counts, launched, rho):
+    """-> (fraction[n_rho], sigma[n_rho]): the port fraction at the wall reflectances `rho` from the histories traced at
+    cfg.reflectance, each with weight (rho / cfg.reflectance)^k (include/isx.h: isx_order_reweight; host only, no GPU needed)."""
+    h = np.ascontiguousarray(np.asarray(hist, dtype=np.uint64).reshape(-1))
+    no, _ = _order_sizes(spec)
+    if h.size < 4 * no:
+        raise ValueError("hist has %d words, the spec wants %d" % (h.size, 4 * no))
+    r = np.ascontiguousarray(np.atleast_1d(rho), dtype=np.float64)
+    frac, sig = np.zeros(max(r.size, 1)), np.zeros(max(r.size, 1))
+    _chk(load().isx_order_reweight(C.byref(cfg), C.byref(spec), _p(h, C.c_uint64), C.byref(counts), int(launched),
+                                   _p(r, C.c_double), int(r.size), _p(frac, C.c_double), _p(sig, C.c_double)), "isx_order_reweight")
+    return frac[:r.size], sig[:r.size]
 
 
 def fluxmap_series(cfgs, n_rays, seed, first_ray=0):

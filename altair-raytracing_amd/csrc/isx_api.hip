@@ -381,13 +381,25 @@ int check_field_spec(const isx_exit_map_spec* s) {
   return ISX_OK;
 }
 
+// isx_order_hist: the checked spec and the device accumulators of the call (port_dz: nullptr where n_dz == 0)
+struct OrderSink { const isx_order_hist_spec* spec = nullptr; unsigned long long *hist = nullptr, *port_dz = nullptr, *counts = nullptr; };
+
+// isx.h: the limits of an order-histogram spec (one u32 block of at most 32 KiB + the counters in a workgroup's LDS)
+int check_order_spec(const isx_order_hist_spec* s) {
+  if (s->struct_size != (uint32_t)sizeof(isx_order_hist_spec)) return ISX_ERR_BAD_CONFIG;
+  if (s->n_orders < 1 || s->n_orders > ISX_ORDER_HIST_MAX_ORDERS || s->n_dz < 0 || s->n_dz > 64 ||
+      4ll * s->n_orders + (long long)s->n_orders * s->n_dz > ISX_ORDER_HIST_MAX_WORDS)
+    return ISX_ERR_BAD_CONFIG;
+  return ISX_OK;
+}
+
 // LDS of a workgroup's histogram: 4 B per bin, 16-byte aligned
 size_t hist_lds(int nbins) { return ((size_t)nbins * 4 + 15) & ~(size_t)15; }
 
 // The DetGrid of a call's sink, checked, and the dynamic LDS of its fused kernel (histogram + tables, census, Geom, DetGrid).
 int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d_discs, double disc_r, double disc_h,
-              const PerPos* pp, const LogSink* lg, const ExitSink* xm, const WallSink* wm, const FieldSink* lf, DetGrid& d,
-              size_t& lds) {
+              const PerPos* pp, const LogSink* lg, const ExitSink* xm, const WallSink* wm, const FieldSink* lf, const OrderSink* oh,
+              DetGrid& d, size_t& lds) {
   std::memset(&d, 0, sizeof(d));
   d.portz = c->exit_port_z;
   d.hit_line_mode = c->hit_line_mode;
@@ -469,6 +481,18 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
     d.xm_pos = wm->map; d.xm_counts = wm->counts;
     d.nbins = s.n_x * s.n_y + 4;   // the workgroup's LDS block: the map | the four counters
     lds = hist_lds(d.nbins) + 64 + sizeof(Geom) + sizeof(DetGrid);
+  } else if (sink == SINK_ORDER) {
+    if (!oh || !oh->spec || !oh->hist || !oh->counts) return ISX_ERR_BAD_ARG;
+    rc = check_order_spec(oh->spec);
+    if (rc) return rc;
+    const isx_order_hist_spec& s = *oh->spec;
+    if (s.n_dz > 0 && !oh->port_dz) return ISX_ERR_BAD_ARG;
+    d.hit_line_mode = ISX_HITLINE_LAST_SEGMENT;   // (isx.h: ignored -- no exit line is looked at)
+    // (the spec travels in the exit maps' words of DetGrid: isx_kernels.hpp)
+    d.xm_nx = s.n_orders; d.xm_ny = s.n_dz;
+    d.xm_dir = oh->hist; d.xm_pos = oh->port_dz; d.xm_counts = oh->counts;
+    d.nbins = 4 * s.n_orders + s.n_orders * s.n_dz + 5;   // the workgroup's LDS block: the histograms | the port's dz | the five counters
+    lds = hist_lds(d.nbins) + 64 + sizeof(Geom) + sizeof(DetGrid);
   } else {
     if (nbins_override < 1 || nbins_override > 36000) return ISX_ERR_BAD_ARG;
     d.nbins = nbins_override;
@@ -492,7 +516,8 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
 //  ROUTE_FIELD_PIPE the light field the same way; isx_bin_lightfield_kernel bins into LDS or, a field too large for it, into global memory
 //  ROUTE_DISC_PIPE  the shared-ray disc sweep the same way: assist-wave trace kernel (exit segments) -> isx_bin_discs_kernel
 //  ROUTE_ASSIST     the per-position sinks: one assist-wave kernel, whose assist wave does the exact test per exiting ray;
-//                   the wall map: one assist-wave kernel whose waves bin every interaction into the workgroup's LDS map
+//                   the wall map: one assist-wave kernel whose waves bin every interaction into the workgroup's LDS map;
+//                   the order histograms: one assist-wave kernel whose waves bin every ray where it ends
 //  ROUTE_FUSED      one kernel that traces and bins: everything the routes above do not serve
 enum Route { ROUTE_FUSED, ROUTE_ASSIST, ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_FIELD_PIPE, ROUTE_DISC_PIPE };
 typedef void (*KernelFn)(const Geom, const DetGrid, const Work);
@@ -673,6 +698,23 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     return p;
   }
 
+  // The bounce-order histograms go the wall map's way, with its kernels' shapes and its occupancy rule: the workgroup's u32 block
+  // (at most 8192 words + the five counters) lies behind the rings.
+  if (sink == SINK_ORDER && wall_served && S.pipeline && S.assist) {
+    p.route = ROUTE_ASSIST;
+    p.fn = border == LOBE ? isx_trace_assist_order_lobe_kernel : border == ROUGH ? isx_trace_assist_order_rough_kernel :
+           !pencil ? isx_trace_assist_order_brdf_kernel : chord ? isx_trace_assist_order_chord_kernel : isx_trace_assist_order_kernel;
+    Shape sh = small_shape(std::min(n, kLaunchMax), ablock);
+    trace_shape(p, sh, true, resident_unless(S.trace_blocks_per_cu));
+    p.lds += hist_lds(d.nbins);
+    if (sh.block > 512 && !S.assist_block_set && blocks_per_cu(p.fn, sh.block, p.lds, kResident) < 2) {
+      sh.block = 512;
+      trace_shape(p, sh, true, resident_unless(S.trace_blocks_per_cu));
+      p.lds += hist_lds(d.nbins);
+    }
+    return p;
+  }
+
   // the fused kernel: the lean build where there is one, the full-featured one for everything else
   switch (sink) {
     case SINK_FLUX: p.fn = lean && pencil ? (chord ? isx_trace_bin_chord_kernel : isx_trace_bin_kernel) :
@@ -681,6 +723,7 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     case SINK_EXITMAP: p.fn = border == LAMBERT && pencil && !chord ? isx_trace_exitmap_lean_kernel : isx_trace_exitmap_kernel; break;
     case SINK_WALL: p.fn = border == LAMBERT && pencil && !chord ? isx_trace_wall_lean_kernel : isx_trace_wall_kernel; break;
     case SINK_LIGHTFIELD: p.fn = border == LAMBERT && pencil && !chord ? isx_trace_lightfield_lean_kernel : isx_trace_lightfield_kernel; break;
+    case SINK_ORDER: p.fn = border == LAMBERT && pencil && !chord ? isx_trace_order_lean_kernel : isx_trace_order_kernel; break;
     case SINK_DISC: p.fn = lean_explicit ? isx_trace_disc_lean_kernel : isx_trace_disc_kernel; break;
     case SINK_PERPOS: p.fn = lean_explicit ? isx_trace_perpos_lean_kernel : isx_trace_perpos_kernel; break;
     case SINK_DISCPOS: p.fn = lean_explicit ? isx_trace_discpos_lean_kernel : isx_trace_discpos_kernel; break;
@@ -858,7 +901,7 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
 int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t first, unsigned long long* d_hist,
             int nbins_override, const double* d_discs, double disc_r, double disc_h, const PerPos* pp = nullptr,
             const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr, const ExitSink* xm = nullptr,
-            const WallSink* wm = nullptr, const FieldSink* lf = nullptr) {
+            const WallSink* wm = nullptr, const FieldSink* lf = nullptr, const OrderSink* oh = nullptr) {
   Geom g;
   int rc = prepare_geom(c, &g);
   if (rc) return rc;
@@ -866,7 +909,7 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
   if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;   // first + n (the exclusive end of the index range) must be representable
   DetGrid d;
   size_t lds = 0;
-  rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, xm, wm, lf, d, lds);
+  rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, xm, wm, lf, oh, d, lds);
   if (rc || n == 0) return rc;
   Work wk;
   wk.seed = seed; wk.first = first; wk.n = n; wk.hist = d_hist; wk.stats = d_stats ? d_stats : S.d_stats;
@@ -1555,6 +1598,87 @@ int isx_light_field(const isx_config* cfg, const isx_exit_map_spec* spec, uint64
     counts->binned = k[0]; counts->pos_outside = k[1]; counts->dir_outside = k[2]; counts->upward = k[3];
   }
   return rc;
+}
+
+void isx_default_order_hist_spec(const isx_config* cfg, isx_order_hist_spec* spec) {
+  (void)cfg;   // (the default does not depend on the configuration: orders are counted, not scaled)
+  if (!spec) return;
+  std::memset(spec, 0, sizeof(*spec));
+  spec->struct_size = (uint32_t)sizeof(isx_order_hist_spec);
+  spec->n_orders = 512; spec->n_dz = 8;
+}
+
+int isx_order_hist_device(const isx_config* cfg, const isx_order_hist_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                          uint64_t* d_hist, uint64_t* d_port_dz, uint64_t* d_counts) {
+  // (what needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one)
+  if (!cfg || !spec || !d_hist || !d_counts) return ISX_ERR_BAD_ARG;
+  const int bad = check_order_spec(spec);
+  if (bad) return bad;
+  if (spec->n_dz > 0 && !d_port_dz) return ISX_ERR_BAD_ARG;
+  if (!S.init) return not_initialised();
+  const OrderSink oh{spec, (unsigned long long*)d_hist, spec->n_dz > 0 ? (unsigned long long*)d_port_dz : nullptr,
+                     (unsigned long long*)d_counts};
+  return enqueue(SINK_ORDER, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                 nullptr, &oh);
+}
+
+int isx_order_hist(const isx_config* cfg, const isx_order_hist_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                   uint64_t* hist, uint64_t* port_dz, isx_order_hist_counts* counts, isx_stats* stats) {
+  if (!cfg || !spec || !hist) return ISX_ERR_BAD_ARG;
+  if (!config_abi_ok(cfg)) return ISX_ERR_BAD_CONFIG;
+  int rc = check_order_spec(spec);
+  if (rc) return rc;
+  if (spec->n_dz > 0 && !port_dz) return ISX_ERR_BAD_ARG;
+  if (!S.init) return not_initialised();
+  const size_t nh = 4 * (size_t)spec->n_orders, nd = (size_t)spec->n_orders * spec->n_dz, words = nh + nd + 5;
+  rc = call_open(words);
+  if (rc) return rc;
+  // the call's accumulators in the pooled histogram: the four histograms | the port's dz | the five counters
+  const OrderSink oh{spec, S.d_hist, nd ? S.d_hist + nh : nullptr, S.d_hist + nh + nd};
+  rc = zero_hist(words);
+  if (rc == ISX_OK) rc = enqueue(SINK_ORDER, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, &oh);
+  if (rc == ISX_OK) rc = stage_result(S.d_hist, words * sizeof(unsigned long long));
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK) {
+    const unsigned long long* h = reinterpret_cast<const unsigned long long*>(S.h_pin + 64);
+    std::memcpy(hist, h, nh * 8);
+    if (nd) std::memcpy(port_dz, h + nh, nd * 8);
+    if (counts) {
+      for (int c = 0; c < 4; ++c) counts->overflow[c] = h[nh + nd + c];
+      counts->dz_outside = h[nh + nd + 4];
+    }
+  }
+  return rc;
+}
+
+int isx_order_reweight(const isx_config* cfg, const isx_order_hist_spec* spec, const uint64_t* hist,
+                       const isx_order_hist_counts* counts, uint64_t launched, const double* rho, int32_t n_rho, double* fraction,
+                       double* sigma) {
+  if (!cfg || !spec || !hist || !counts || n_rho < 0 || (n_rho > 0 && (!rho || !fraction))) return ISX_ERR_BAD_ARG;
+  if (!config_abi_ok(cfg)) return ISX_ERR_BAD_CONFIG;
+  const int rc = check_order_spec(spec);
+  if (rc) return rc;
+  const double rho0 = cfg->reflectance;
+  if (cfg->source_model != ISX_SOURCE_PENCIL || counts->overflow[0] != 0 || !(rho0 > 0) || launched == 0) return ISX_ERR_BAD_CONFIG;
+  for (int32_t i = 0; i < n_rho; ++i)
+    if (!(std::isfinite(rho[i]) && rho[i] >= 0)) return ISX_ERR_BAD_ARG;
+  const double n = (double)launched;
+  for (int32_t i = 0; i < n_rho; ++i) {
+    const double q = rho[i] / rho0;
+    double s1 = 0, s2 = 0;
+    for (int32_t k = 0; k < spec->n_orders; ++k) {
+      const double w = std::pow(q, (double)k), h = (double)hist[k];
+      s1 += h * w;
+      s2 += h * w * w;
+    }
+    fraction[i] = s1 / n;
+    if (sigma) {
+      const double var = s2 - s1 * s1 / n;
+      sigma[i] = std::sqrt(var > 0 ? var : 0.0) / n;
+    }
+  }
+  return ISX_OK;
 }
 
 #ifdef ISX_DIAG

@@ -76,6 +76,9 @@ struct DetGrid {
   // maps have them, xm_dir = the global field [xm_ny][xm_nx][xm_nv][xm_nu] (+=), xm_counts = [4]: binned, pos_outside, dir_outside,
   // upward.  A workgroup's LDS holds u32[field | 4 counters] (LDS form) or u32[4 counters] (global form, and the fused kernels):
   // nbins words either way.
+  // SINK_ORDER (isx.h: isx_order_hist) likewise: xm_nx = n_orders, xm_ny = n_dz, xm_dir = the global histograms [4][xm_nx] (+=),
+  // xm_pos = the port's [xm_nx][xm_ny] (+=; not read where xm_ny = 0), xm_counts = [5]: overflow[4], dz_outside.  A workgroup's LDS
+  // holds u32[4 * xm_nx | xm_nx * xm_ny | 5 counters] (nbins words).
 };
 
 // -DISX_DIAG (tuning builds only, never the shipped library): where the binning work goes.
@@ -115,7 +118,7 @@ __device__ unsigned long long g_diag[48];   // [32..47]: the assist wave of assi
 #endif
 
 enum : int { SINK_FLUX = 0, SINK_DZ = 1, SINK_DISC = 2, SINK_PERPOS = 3, SINK_LOG = 4, SINK_DISCPOS = 5, SINK_REC = 6, SINK_EXITMAP = 7, SINK_WALL = 8,
-              SINK_LIGHTFIELD = 9 };
+              SINK_LIGHTFIELD = 9, SINK_ORDER = 10 };
 
 struct Work {
   uint64_t seed, first, n;    // one launch traces rays [first, first + n), n < 2^31 (a lane keeps a 31-bit offset from `first`)
@@ -2128,6 +2131,48 @@ __device__ __forceinline__ unsigned long long wall_flush(const DetGrid& d_arg, c
   return flushed;
 }
 
+// ------------------------------------------------------------------ bounce-order histograms (isx.h: isx_order_hist)
+// The spec of a call as the trace loops keep it: wave-uniform words (scalar registers).
+struct OrderSpec { int n_orders, n_dz; double fdz; };
+template <bool ON>   // (false: a kernel of another sink -- nothing is computed, nothing is kept)
+__device__ __forceinline__ OrderSpec order_spec(const DetGrid& d) {
+  OrderSpec s;
+  if (!ON) { s.n_orders = 0; s.n_dz = 0; s.fdz = 0.0; return s; }
+  s.n_orders = d.xm_nx; s.n_dz = d.xm_ny;
+  s.fdz = uniform_f64((double)d.xm_ny);   // (the conversion is a VALU instruction)
+  return s;
+}
+// The end of one ray into the workgroup's LDS block, as isx.h states it: the class from the ray's end status (exited: counted
+// below z or not; else suspended or absorbed), the order k = Ray::j at the end (an integer every kernel carries: nothing is
+// computed in a bounce step for it).  hist[0, 4 * n_orders) the four histograms, then the port's [n_orders][n_dz], then overflow[4]
+// and dz_outside.  The dz bin is isx_exit_dz_hist's arithmetic (SINK_DZ); the in-range test is made on the value floor() would
+// see, as exitmap_bins does (NaN and inf compare false).  One ds_add_u32 per ray, a second one for a counted ray.
+__device__ __forceinline__ void order_record(const OrderSpec& s, uint32_t* hist, bool exited, bool below, bool susp, uint32_t k, double vz) {
+  const int c = exited ? (below ? 0 : 1) : (susp ? 3 : 2);
+  const int nh = 4 * s.n_orders, nd = s.n_orders * s.n_dz;
+  if (k >= (uint32_t)s.n_orders) { atomicAdd(&hist[nh + nd + c], 1u); return; }
+  atomicAdd(&hist[c * s.n_orders + (int)k], 1u);
+  if (c == 0 && s.n_dz > 0) {
+    const double f = (vz + 1.0) * 0.5 * s.fdz;
+    const bool in = f >= 0.0 && f < s.fdz;
+    atomicAdd(&hist[in ? nh + (int)k * s.n_dz + (int)f : nh + nd + 4], 1u);
+  }
+}
+// One flush of a workgroup's LDS block (after a barrier): the non-zero words into the u64 global arrays.  Returns this thread's
+// share of the increments (the sum of the histogram words it flushed: isx.h, stats.bin_increments).
+__device__ __forceinline__ unsigned long long order_flush(const DetGrid& d_arg, const uint32_t* hist, int tid, int nthr) {
+  const int nh = 4 * d_arg.xm_nx, nd = d_arg.xm_nx * d_arg.xm_ny;
+  unsigned long long flushed = 0;
+  for (int b = tid; b < nh + nd + 5; b += nthr) {
+    const uint32_t c = hist[b];
+    if (!c) continue;
+    if (b < nh) { global_add_u64(d_arg.xm_dir + b, (unsigned long long)c); flushed += c; }
+    else if (b < nh + nd) global_add_u64(d_arg.xm_pos + (b - nh), (unsigned long long)c);
+    else global_add_u64(d_arg.xm_counts + (b - nh - nd), (unsigned long long)c);
+  }
+  return flushed;
+}
+
 // ------------------------------------------------------------------ persistent trace kernel, one per sink
 //   SINK_FLUX: 180x90 detector flux map (the headline path)
 //   SINK_DZ  : histogram of the exit direction's z component (distributionSphereDetectorSweep.C:54,91)
@@ -2137,6 +2182,8 @@ __device__ __forceinline__ unsigned long long wall_flush(const DetGrid& d_arg, c
 //              isx_bin_lightfield_kernel: one global u64 add per binned ray, the four counters in LDS (nbins = 4)
 //   SINK_WALL: equal-area map of the interaction points on the inner sphere (isx_wall_map), binned at the arrival -- every
 //              configuration; the assist-wave kernels (assist_body<.., WALL>) are the default route
+//   SINK_ORDER: histograms of the bounce order at which rays end, by class (isx_order_hist), binned once per ended ray at the
+//              census -- every configuration; the assist-wave kernels (assist_body<.., ORDER>) are the default route
 template <int SINK, bool LEAN = false, int CH = 2, bool RESC = !LEAN>
 __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -2211,6 +2258,7 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
                                                                                  // (SINK_LIGHTFIELD: [0..3] isx_light_field_counts)
   const WallSpec wspec = wall_spec<SINK == SINK_WALL>(d_arg);                    // SINK_WALL: the spec, the map's words
   const int wall_nmap = d_arg.xm_nx * d_arg.xm_ny;
+  const OrderSpec ospec = order_spec<SINK == SINK_ORDER>(d_arg);                 // SINK_ORDER: the spec
   ISX_TD_DECL;
 
   for (;;) {
@@ -2347,6 +2395,7 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
         n_susp += (uint32_t)__popcll(__ballot(pend == ST_SUSPENDED));
         ISX_TD_ADD(12, __popcll(me));
       }
+      if (SINK == SINK_ORDER && ended) order_record(ospec, hist, exited, below, pend == ST_SUSPENDED, r.j, r.v.z);
     }
     ISX_TD_MARK(5);
     if (SINK == SINK_LOG) {
@@ -2450,6 +2499,8 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
       }
     } else if (SINK == SINK_WALL) {
       // (binned at every arrival: nothing is left to do for a ray that ended)
+    } else if (SINK == SINK_ORDER) {
+      // (binned with the census above: every ended ray, not only the counted ones)
     } else if (SINK == SINK_DZ) {
       // per-lane: TH1D(nbins,-1,1)->Fill(dz)
       bool hit = false;
@@ -2549,6 +2600,7 @@ __device__ __forceinline__ void persistent_body(const Geom& g_arg, const DetGrid
   if (SINK == SINK_EXITMAP) flushed = exitmap_flush(d_arg, hist, tid, nthr);
   else if (SINK == SINK_WALL) flushed = wall_flush(d_arg, hist, tid, nthr);
   else if (SINK == SINK_LIGHTFIELD) flushed = lightfield_flush(d_arg, hist, 0, tid, nthr);
+  else if (SINK == SINK_ORDER) flushed = order_flush(d_arg, hist, tid, nthr);
   else for (int b = tid; b < nbins; b += nthr) {
     const uint32_t c = hist[b];
     if (c) { global_add_u64(&wk.hist[b], (unsigned long long)c); flushed += c; }
@@ -2598,6 +2650,11 @@ extern "C" __global__ void ISX_KERNEL_ATTR
 isx_trace_wall_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_WALL>(g, d, wk); }
 extern "C" __global__ void ISX_KERNEL_ATTR
 isx_trace_wall_lean_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_WALL, true, 0>(g, d, wk); }
+// the bounce-order histograms where the assist-wave kernels do not serve them (isx_api.hip: plan_launch): every configuration
+extern "C" __global__ void ISX_KERNEL_ATTR
+isx_trace_order_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_ORDER>(g, d, wk); }
+extern "C" __global__ void ISX_KERNEL_ATTR
+isx_trace_order_lean_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_ORDER, true, 0>(g, d, wk); }
 extern "C" __global__ void ISX_KERNEL_ATTR
 isx_trace_disc_kernel(const Geom g, const DetGrid d, const Work wk) { persistent_body<SINK_DISC>(g, d, wk); }
 extern "C" __global__ void ISX_KERNEL_ATTR
@@ -2716,7 +2773,12 @@ __device__ __forceinline__ void ray_unpack(const uint4& a, const uint4& b, const
 // sphere (wall_record: the projection and one ds_add_u32 into the workgroup's u32 map, which lies behind the rings), by the assist
 // wave for what it interacts with (rim and outer sphere: other_surface; a ray it brings back to the inner sphere: binned like a
 // tracer's).  A lobe interaction is binned at its arrival, once, not at its tries.  No exit lines, no second kernel.
-template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false>
+// ORDER (isx_order_hist, SINK_ORDER): every ray is binned once, where it ends, by the wave that takes its census -- the tracer
+// waves for what the inner sphere absorbs or suspends (in the per-trip block of the ended lanes, not in a bounce step), the assist
+// wave for the exits and for what ends on the rim or the outer sphere.  A BRDF primary's end is not a ray's end: both waves hand it
+// to ray_rescatter before their census, so only the scattered ray's end is seen.  The workgroup's u32 block lies behind the rings,
+// as WALL's map does.  No exit lines, no second kernel.
+template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false, bool ORDER = false>
 __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk) {
   constexpr bool LEAN = SURF == SURF_LAMBERT;
   static_assert(LEAN || (CH == 0 && !RESC), "the chord identity and the BRDF re-scatter pipeline are built for the Lambertian border");
@@ -2727,13 +2789,16 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   AssistQueues* Q = reinterpret_cast<AssistQueues*>(smem + ((reinterpret_cast<unsigned char*>(d_lds + 1) - smem + 15) & ~(size_t)15));
   uint4* resume_q = reinterpret_cast<uint4*>(Q + 1);               // [kResumeCap][4]
   uint4* pend_q = resume_q + 4 * kResumeCap;                       // [kPendCap][4]
-  uint32_t* hist = reinterpret_cast<uint32_t*>(pend_q + 4 * kPendCap);   // WALL: u32[xm_nx * xm_ny | 4 counters]
+  uint32_t* hist = reinterpret_cast<uint32_t*>(pend_q + 4 * kPendCap);   // WALL: u32[xm_nx * xm_ny | 4 counters]; ORDER: DetGrid
   const int tid = threadIdx.x, lane = tid & 63;
   const int nthr = (int)blockDim.x, wpb = nthr >> 6;
   const int n_tracers = wpb - 1;
   const WallSpec wspec = wall_spec<WALL>(d_arg);
   const int wall_nmap = d_arg.xm_nx * d_arg.xm_ny;
   if (WALL) for (int b = tid; b < wall_nmap + 4; b += nthr) hist[b] = 0u;
+  static_assert(!(WALL && ORDER), "one LDS block behind the rings");
+  const OrderSpec ospec = order_spec<ORDER>(d_arg);
+  if (ORDER) for (int b = tid; b < d_arg.nbins; b += nthr) hist[b] = 0u;
   if (tid < 8) sstat[tid] = 0ull;
   if (tid == 64) {
     *g_lds = g_arg;
@@ -2969,6 +3034,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         if (ended) {
           n_wall += r.j;
           if (n_wall > 0x7fffffffu) { atomicAdd(&sstat[6], (unsigned long long)n_wall); n_wall = 0; }
+          if (ORDER) order_record(ospec, hist, false, false, susp, r.j, 0.0);
         }
         const unsigned long long me = __ballot(ended);
         if (me) {
@@ -3165,6 +3231,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       const bool below = exited && (r.p.z < portz);                   // isRayPassingThroughExitPort, fluxAtObserver.C:162-166
       if (ended) n_wall += r.j;
       if (n_wall > 0x7fffffffu) { atomicAdd(&sstat[6], (unsigned long long)n_wall); n_wall = 0; }
+      if (ORDER && ended) order_record(ospec, hist, exited, below, st == ST_SUSPENDED, r.j, r.v.z);
       const uint32_t c_ended = (uint32_t)__popcll(__ballot(ended));
       n_ended += c_ended;
       n_exited += (uint32_t)__popcll(__ballot(exited));
@@ -3203,7 +3270,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         if (hit1) atomicAdd(&wk.hist[b1], 1ull);
         n_inc += (unsigned long long)__popcll(__ballot(hit0)) + (unsigned long long)__popcll(__ballot(hit1));
       }
-      const unsigned long long m = (PP != 0 || WALL) ? 0ull : __ballot(keep);
+      const unsigned long long m = (PP != 0 || WALL || ORDER) ? 0ull : __ballot(keep);
       if (m) {
         const uint32_t cnt = (uint32_t)__popcll(m);
         if (cnt > reg_left) {   // close the open region, reserve the next one (kRegion)
@@ -3298,6 +3365,11 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     if (flushed) atomicAdd(&sstat[5], flushed);
     __syncthreads();
   }
+  if (ORDER) {   // one flush of the workgroup's block; bin_increments = the histograms' increments
+    const unsigned long long flushed = order_flush(d_arg, hist, tid, nthr);
+    if (flushed) atomicAdd(&sstat[5], flushed);
+    __syncthreads();
+  }
   {
     uint32_t t2 = threadIdx.x;
     asm volatile("" : "+v"(t2));
@@ -3332,6 +3404,14 @@ extern "C" __global__ void ISX_ASSIST_ATTR
 isx_trace_assist_wall_chord_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<1, false, false, 0, SURF_LAMBERT, true>(g, d, wk); }
 extern "C" __global__ void ISX_ASSIST_ATTR
 isx_trace_assist_wall_brdf_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, true, false, 0, SURF_LAMBERT, true>(g, d, wk); }
+// the bounce-order histograms (isx_order_hist): the same kernels with one LDS add per ended ray and the workgroup's u32 block
+// behind the rings
+extern "C" __global__ void ISX_ASSIST_ATTR
+isx_trace_assist_order_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_LAMBERT, false, true>(g, d, wk); }
+extern "C" __global__ void ISX_ASSIST_ATTR
+isx_trace_assist_order_chord_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<1, false, false, 0, SURF_LAMBERT, false, true>(g, d, wk); }
+extern "C" __global__ void ISX_ASSIST_ATTR
+isx_trace_assist_order_brdf_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, true, false, 0, SURF_LAMBERT, false, true>(g, d, wk); }
 // the other border models on the same pipeline (round 5; until then round 1's fused isx_trace_bin_full_kernel served them):
 // the cos^2 lobe of "nonLambertianFlux copy.C":31-70,188-221 and ROBAST's rough-specular border (EnableLambertian(false))
 #ifndef ISX_LOBE_WAVES
@@ -3354,6 +3434,10 @@ extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((am
 isx_trace_assist_wall_lobe_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_LOBE, true>(g, d, wk); }
 extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_ROUGH_WAVES, ISX_ROUGH_WAVES)))
 isx_trace_assist_wall_rough_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_ROUGH, true>(g, d, wk); }
+extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_LOBE_WAVES, ISX_LOBE_WAVES)))
+isx_trace_assist_order_lobe_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_LOBE, false, true>(g, d, wk); }
+extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_ROUGH_WAVES, ISX_ROUGH_WAVES)))
+isx_trace_assist_order_rough_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_ROUGH, false, true>(g, d, wk); }
 
 // ISX_HITLINE_ORIGIN_COMPAT on the pipeline (round 5): what fluxAtObserverFast.C:1181-1201,1285-1288 effectively tested is the line
 // from the origin along lastPoint/|lastPoint| (hit_line_compat).  The trace kernels write last point + final direction as always;

@@ -712,4 +712,36 @@ int light_field_all(const isx_config* cfg, const isx_exit_map_spec* spec, uint64
   return rc;
 }
 
+int order_hist_all(const isx_config* cfg, const isx_order_hist_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                   uint64_t* hist, uint64_t* port_dz, isx_order_hist_counts* counts, isx_stats* st) {
+  Comm& c = comm();
+  if (!c.active()) return isx_order_hist(cfg, spec, n_rays, seed, first_ray, hist, port_dz, counts, st);
+  // (a spec the ABI refuses leaves only the status word to exchange)
+  const bool ok = spec && spec->n_orders >= 1 && spec->n_orders <= ISX_ORDER_HIST_MAX_ORDERS && spec->n_dz >= 0 && spec->n_dz <= 64 &&
+                  (long long)spec->n_orders * (4 + spec->n_dz) <= ISX_ORDER_HIST_MAX_WORDS;
+  const size_t nh = ok ? 4 * (size_t)spec->n_orders : 0, nd = ok ? (size_t)spec->n_orders * spec->n_dz : 0;
+  uint64_t f, cnt;
+  c.shard(n_rays, f, cnt);
+  isx_stats local{};
+  isx_order_hist_counts k{};
+  std::vector<uint64_t> buf(nh + nd + 5, 0);   // the histograms | the port's dz | the five counters: ONE sum
+  int rc = isx_order_hist(cfg, spec, cnt, seed, first_ray + f, buf.data(), buf.data() + nh, &k, &local);
+  if (rc == ISX_OK) {
+    uint64_t* w = buf.data() + nh + nd;
+    for (int i = 0; i < 4; ++i) w[i] = k.overflow[i];
+    w[4] = k.dz_outside;
+  }
+  rc = c.reduce(rc, buf.data(), nh ? buf.size() : 0, &local);
+  if (rc != ISX_OK) return rc;
+  if (nh && hist) std::memcpy(hist, buf.data(), nh * sizeof(uint64_t));
+  if (nd && port_dz) std::memcpy(port_dz, buf.data() + nh, nd * sizeof(uint64_t));
+  if (counts) {
+    const uint64_t* w = buf.data() + nh + nd;
+    for (int i = 0; i < 4; ++i) counts->overflow[i] = w[i];
+    counts->dz_outside = w[4];
+  }
+  if (st) *st = local;
+  return rc;
+}
+
 }  // namespace isxhost

@@ -80,6 +80,9 @@ int exit_dz_hist_all(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint
 // the port light field (isx_light_field): the field and the four counters travel in the one collective of the call
 int light_field_all(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
                     uint64_t* field, isx_light_field_counts* counts, isx_stats* st);
+// the bounce-order histograms (isx_order_hist): both arrays and the five counters travel in the one collective of the call
+int order_hist_all(const isx_config* cfg, const isx_order_hist_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                   uint64_t* hist, uint64_t* port_dz, isx_order_hist_counts* counts, isx_stats* st);
 // the wall map (isx_wall_map): the map and the four counters travel in the one collective of the call
 int wall_map_all(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
                  uint64_t* wall_map, isx_wall_map_counts* counts, isx_stats* st);

@@ -49,6 +49,7 @@ int main(int argc, char** argv) {
                  "  exitMaps [--rays <n>] [--seed <s>] |\n"
                  "  wallMap [--rays <n>] [--seed <s>] [--bins <n>] [--first-order <k>] |\n"
                  "  lightField [--rays <n>] [--seed <s>] |\n"
+                 "  orderHist [--rays <n>] [--seed <s>] [--orders <n>] [--dz <n>] [--reflectances <a,b,...>] |\n"
                  "  distributionSphereDetectorSweep | --selftest-writer <file> | --unique <path> | --shard <n> | --analyze <csv>... | --analyze <folder> [average]\n";
     return 2;
   }
@@ -88,6 +89,13 @@ int main(int argc, char** argv) {
       ++i;
       continue;
     }
+    if ((!std::strcmp(argv[i], "--orders") || !std::strcmp(argv[i], "--dz") || !std::strcmp(argv[i], "--reflectances")) && i + 1 < argc) {   // orderHist
+      if (argv[i][2] == 'o') options().order_orders = std::atoi(argv[i + 1]);
+      else if (argv[i][2] == 'd') options().order_dz = std::atoi(argv[i + 1]);
+      else options().order_reflectances = argv[i + 1];
+      ++i;
+      continue;
+    }
     const char* eq = std::strchr(argv[i], '=');
     if (!eq) { std::cerr << "bad argument " << argv[i] << " (want key=value)\n"; return 2; }
     kv[std::string(argv[i], eq - argv[i])] = eq + 1;
@@ -111,6 +119,7 @@ int main(int argc, char** argv) {
   else if (entry == "exitMaps") rootMacros::exitMaps();
   else if (entry == "wallMap") rootMacros::wallMap();
   else if (entry == "lightField") rootMacros::lightField();
+  else if (entry == "orderHist") rootMacros::orderHist();
   else { std::cerr << "unknown entry point " << entry << "\n"; return 2; }
   const bool ok = ensure_device();  // false: the entry point printed its error and returned early
   comm().finalize();

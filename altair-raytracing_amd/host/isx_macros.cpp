@@ -1301,6 +1301,79 @@ void lightField() {
           if (field[w]) f << ix << "," << iy << "," << iu << "," << iv << "," << field[w] << "\n";
 }
 
+// Bounce-order histograms of the library's default sphere (isx.h: isx_order_hist), and the port fraction reweighted to other wall
+// reflectances (isx_order_reweight).
+void orderHist() {
+  if (!ready_everywhere()) return;
+  isx_config c;
+  isx_default_config(&c);
+  const long n = pick_n(1000000);
+  isx_order_hist_spec sp;
+  isx_default_order_hist_spec(&c, &sp);
+  sp.n_orders = options().order_orders; sp.n_dz = options().order_dz;
+  const bool sized = sp.n_orders >= 1 && sp.n_orders <= ISX_ORDER_HIST_MAX_ORDERS && sp.n_dz >= 0 && sp.n_dz <= 64;   // (else the library refuses)
+  const size_t no = sized ? (size_t)sp.n_orders : 1, nz = sized ? (size_t)sp.n_dz : 0;
+  std::vector<uint64_t> hist(4 * no), dz(no * nz + 1);
+  isx_order_hist_counts k;
+  isx_stats st;
+  const uint64_t first = take_rays((uint64_t)n);
+  const int rc = order_hist_all(&c, &sp, (uint64_t)n, options().seed, first, hist.data(), dz.data(), &k, &st);
+  if (rc != ISX_OK) {
+    err() << "Error: isx_order_hist: " << isx_strerror(rc) << std::endl;
+    return;
+  }
+  std::cout << "Flux of rays through the exit port: " << st.counted_below_z << ", mean order: "
+            << (st.launched ? (double)st.wall_hits / (double)st.launched : 0.0) << std::endl;
+  {
+    std::ofstream f(outputPath("order_hist.csv"));
+    f << std::setprecision(17);
+    f << "# Bounce-Order Histograms - Generated: " << currentTimeString() << std::endl;
+    f << "# Number of rays: " << n << std::endl;
+    f << "# Seed: " << options().seed << std::endl;
+    f << "# First ray: " << first << std::endl;
+    f << "# Sphere inner radius: " << c.r_in << "cm" << std::endl;
+    f << "# Exit port angle: " << c.theta_max_deg << " degrees" << std::endl;
+    f << "# Reflectance: " << c.reflectance << std::endl;
+    f << "# Orders: " << sp.n_orders << std::endl;
+    f << "# dz bins: " << sp.n_dz << std::endl;
+    f << "# Mean path per order (4 r_in / 3): " << 4.0 * c.r_in / 3.0 << "cm" << std::endl;
+    f << "k,port,exited_other,absorbed,suspended";
+    for (size_t b = 0; b < nz; ++b) f << ",dz_" << b;
+    f << "\n";
+    for (size_t kk = 0; kk < no; ++kk) {
+      f << kk << "," << hist[kk] << "," << hist[no + kk] << "," << hist[2 * no + kk] << "," << hist[3 * no + kk];
+      for (size_t b = 0; b < nz; ++b) f << "," << dz[kk * nz + b];
+      f << "\n";
+    }
+    f << "# Launched: " << st.launched << std::endl;
+    f << "# Overflow port: " << k.overflow[0] << std::endl;
+    f << "# Overflow exited other: " << k.overflow[1] << std::endl;
+    f << "# Overflow absorbed: " << k.overflow[2] << std::endl;
+    f << "# Overflow suspended: " << k.overflow[3] << std::endl;
+    f << "# dz outside: " << k.dz_outside << std::endl;
+  }
+  if (options().order_reflectances.empty()) return;
+  std::vector<double> rho;
+  {
+    std::stringstream ss(options().order_reflectances);
+    std::string tok;
+    while (std::getline(ss, tok, ',')) if (!tok.empty()) rho.push_back(std::atof(tok.c_str()));
+  }
+  std::vector<double> frac(rho.size() + 1), sig(rho.size() + 1);
+  const int rw = isx_order_reweight(&c, &sp, hist.data(), &k, st.launched, rho.data(), (int32_t)rho.size(), frac.data(), sig.data());
+  if (rw != ISX_OK) {
+    err() << "Error: isx_order_reweight: " << isx_strerror(rw) << std::endl;
+    return;
+  }
+  std::ofstream f(outputPath("order_reweight.csv"));
+  f << std::setprecision(17);
+  f << "# Port fraction reweighted from reflectance " << c.reflectance << " - Generated: " << currentTimeString() << std::endl;
+  f << "# Number of rays: " << n << std::endl;
+  f << "# Seed: " << options().seed << std::endl;
+  f << "rho,fraction,sigma\n";
+  for (size_t i = 0; i < rho.size(); ++i) f << rho[i] << "," << frac[i] << "," << sig[i] << "\n";
+}
+
 }  // namespace rootMacros
 
 }  // namespace isxhost

@@ -53,6 +53,9 @@ struct RunOptions {
   long rays_override = -1;         // env ISX_RAYS: replaces the macros' hard-coded n (tests)
   int wall_bins = 64;              // wallMap --bins: bins per axis of the wall map
   int wall_first_order = 0;        // wallMap --first-order
+  int order_orders = 512;          // orderHist --orders: orders 0 .. n - 1 of the bounce-order histograms
+  int order_dz = 8;                // orderHist --dz: dz bins per order of the port's rays
+  std::string order_reflectances;  // orderHist --reflectances a,b,...: wall reflectances to reweight the port fraction to
   bool quiet = false;              // env ISX_QUIET
   int flush_rows = 0;              // env ISX_FLUSH_ROWS: theta rows per launch of the per-position sweep, written and flushed
                                    // before the next launch starts (0 = as many as hold ~4e9 rays: one launch for the reference's n)
@@ -178,6 +181,10 @@ void wallMap();
 // light_field.csv, sparse -- the non-zero bins (ix,iy,iu,iv,count) in index order under '#' lines with the spec, the counters and
 // the radiance normalisation N dx dy du dv
 void lightField();
+// the same sphere through isx_order_hist (--orders orders, --dz dz bins): order_hist.csv (k,port,exited_other,absorbed,suspended,
+// dz_0 .. dz_{n_dz-1}) with the five counters in the footer; with --reflectances a,b,... also order_reweight.csv
+// (rho,fraction,sigma: isx_order_reweight, the port fraction at other wall reflectances from this one trace)
+void orderHist();
 }  // namespace rootMacros
 
 }  // namespace isxhost

@@ -3,7 +3,7 @@
 Rays are independent and ray i always draws from Philox stream (seed, i), so ANY partition of
 the index range gives the same summed histogram.  Rank r of P traces the
 contiguous range shard(n, r, P); the only exchange is one SUM all-reduce of the
-[n_theta*n_phi] int64 histogram (+ the 7-word census; the exit maps: both maps + five counters + census; the wall map: map + four counters + census) — torch.distributed backend "nccl"
+[n_theta*n_phi] int64 histogram (+ the 7-word census; the exit maps: both maps + five counters + census; the wall map: map + four counters + census; the order histograms: both arrays + five counters + census) — torch.distributed backend "nccl"
 (= RCCL over xGMI) on GPUs, "gloo" in the CPU tests.
 
 The tracer itself is injected (`trace(cfg, count, seed, first) -> (hits, stats)`): on a GPU
@@ -162,3 +162,36 @@ def light_field_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, fir
         counts = buf[nf:nf + len(FIELD_COUNT_FIELDS)]
         census = buf[nf + len(FIELD_COUNT_FIELDS):]
     return (field, dict(zip(FIELD_COUNT_FIELDS, (int(x) for x in counts))), dict(zip(CENSUS_FIELDS, (int(x) for x in census))))
+
+
+ORDER_COUNT_FIELDS = ("overflow_port", "overflow_exited_other", "overflow_absorbed", "overflow_suspended", "dz_outside")
+
+
+def order_hist_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, first_ray: int = 0, device=None):
+    """The bounce-order histograms (altair_raytracing_amd.order_hist) ray-sharded: this rank's contiguous shard through
+    `trace(cfg, count, seed, spec, first) -> (hist, port_dz, counts, stats)`, then ONE SUM all-reduce that carries both arrays,
+    the five counters (overflow[0..3], dz_outside) and the census.  Returns (hist, port_dz, counts dict, census dict) --
+    identical on every rank."""
+    import torch
+    import torch.distributed as dist
+
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(), dist.get_world_size()
+    else:
+        rank, world = 0, 1
+    first, count = shard(n_total, rank, world)
+    hist, dz, cnt, st = trace(cfg, count, seed, spec, first_ray + first)
+    counts = np.array([int(x) for x in cnt.overflow] + [int(cnt.dz_outside)], dtype=np.int64)
+    census = np.array([getattr(st, k) for k in CENSUS_FIELDS], dtype=np.int64)
+    if world > 1:
+        buf = torch.from_numpy(np.concatenate([hist.reshape(-1).astype(np.int64), dz.reshape(-1).astype(np.int64), counts, census]))
+        if device is not None:
+            buf = buf.to(device)
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+        buf = buf.cpu().numpy()
+        nh, nd, nc = hist.size, dz.size, len(ORDER_COUNT_FIELDS)
+        hist = buf[:nh].astype(np.uint64).reshape(hist.shape)
+        dz = buf[nh:nh + nd].astype(np.uint64).reshape(dz.shape)
+        counts = buf[nh + nd:nh + nd + nc]
+        census = buf[nh + nd + nc:]
+    return (hist, dz, dict(zip(ORDER_COUNT_FIELDS, (int(x) for x in counts))), dict(zip(CENSUS_FIELDS, (int(x) for x in census))))

@@ -443,6 +443,84 @@ int isx_light_field_device(const isx_config* cfg, const isx_exit_map_spec* spec,
                            uint64_t first_ray, uint64_t* d_field, uint64_t* d_counts /*[4]*/);
 
 /*
+ * Bounce-order histograms: how long the light stayed in the sphere before it ended.  A ray that ends after k mirror
+ * interactions survived k absorption tests, so the histories traced at reflectance rho0 = cfg->reflectance are the histories at
+ * any rho <= rho0 with weight (rho / rho0)^k: one trace gives the port throughput along a whole reflectance curve
+ * (isx_order_reweight).  The mean path per bounce is 4 r_in / 3, so the same histogram is the sphere's time response at the
+ * resolution of one mean chord; the census reports only its mean, wall_hits / launched.  No path length is measured.
+ *
+ * For every traced ray take status and n_points as isx_trace_endstates reports them for that ray index (for ISX_SOURCE_BRDF
+ * the scattered ray, as there) and v, its final direction:
+ *
+ *       k = n_points - 2 if EXITED, else n_points - 1     (the mirror interactions of the ray: its own count at its end)
+ *       c = 0  EXITED and counted below z (the census's counted_below_z)
+ *           1  EXITED otherwise
+ *           2  ABSORBED
+ *           3  SUSPENDED
+ *       k >= n_orders                    :  overflow[c] += 1 , nothing else
+ *       else                             :  hist[c * n_orders + k] += 1
+ *       and for c == 0 with n_dz > 0     :  f = (v.z + 1.0) * 0.5 * n_dz ;  b = (int)floor(f)     (isx_exit_dz_hist's arithmetic)
+ *           0 <= b < n_dz                :  port_dz[k * n_dz + b] += 1
+ *           else (NaN / inf included)    :  dz_outside += 1
+ *
+ * For every call: hist[0] sums to counted_below_z - overflow[0], hist[1] to exited - counted_below_z - overflow[1], hist[2] to
+ * absorbed - overflow[2], hist[3] to suspended - overflow[3]; with n_dz > 0, port_dz + dz_outside sums to the sum of hist[0];
+ * stats.bin_increments == the sum of hist, and every other field of stats is what isx_fluxmap reports for the same (cfg, n_rays,
+ * seed, first_ray).  For ISX_SOURCE_PENCIL with all overflow zero, sum over c and k of k * hist[c][k] == stats.wall_hits (with
+ * ISX_SOURCE_BRDF wall_hits counts the primaries' interactions as well, k does not).  The result does not depend on any
+ * isx_set_option switch nor on how a job is cut into calls.  cfg->hit_line_mode and the detector-grid fields of cfg are ignored.
+ *
+ * Limits (a workgroup keeps the u32 block [4 * n_orders | n_orders * n_dz | 5 counters] in its LDS next to the rings of its trace
+ * kernel, as ISX_WALL_MAP_MAX_BINS): n_orders 1..ISX_ORDER_HIST_MAX_ORDERS, n_dz 0..64, 4 * n_orders + n_orders * n_dz at most
+ * ISX_ORDER_HIST_MAX_WORDS, struct_size == sizeof(isx_order_hist_spec) -- else ISX_ERR_BAD_CONFIG; a NULL cfg, spec or hist, or a
+ * NULL port_dz with n_dz > 0: ISX_ERR_BAD_ARG.  Both are answered whether or not a device is present.
+ */
+#define ISX_ORDER_HIST_MAX_ORDERS 2048
+#define ISX_ORDER_HIST_MAX_WORDS  8192
+typedef struct isx_order_hist_spec {
+  uint32_t struct_size;      /* sizeof(isx_order_hist_spec), set by isx_default_order_hist_spec(); a spec of another size is refused */
+  uint32_t reserved0;        /* 0 */
+  int32_t n_orders;          /* orders 0 .. n_orders - 1; a ray of a higher order is counted in overflow[] */
+  int32_t n_dz;              /* bins of the final direction's z over [-1, 1) per order, counted rays only; 0 = not wanted */
+} isx_order_hist_spec;
+typedef struct isx_order_hist_counts {
+  uint64_t overflow[4];      /* per class: rays with k >= n_orders */
+  uint64_t dz_outside;
+} isx_order_hist_counts;
+
+/* 512 orders, 8 dz bins.  No GPU needed. */
+void isx_default_order_hist_spec(const isx_config* cfg, isx_order_hist_spec* spec);
+
+/* Blocking: hist[4 * n_orders], port_dz[n_orders * n_dz] (may be NULL iff n_dz == 0), *counts (host, zeroed by the callee;
+ * counts and stats may be NULL).  Without a HIP device: ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT
+ * (as isx_light_field). */
+int isx_order_hist(const isx_config* cfg, const isx_order_hist_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                   uint64_t* hist, uint64_t* port_dz, isx_order_hist_counts* counts, isx_stats* stats);
+/* ACCUMULATES (+=) into device-resident arrays and five device counters (order of isx_order_hist_counts) on the library's
+ * stream and returns after enqueueing; isx_sync() / isx_take_stats() as for isx_wall_map_device. */
+int isx_order_hist_device(const isx_config* cfg, const isx_order_hist_spec* spec, uint64_t n_rays, uint64_t seed,
+                          uint64_t first_ray, uint64_t* d_hist, uint64_t* d_port_dz, uint64_t* d_counts /*[5]*/);
+
+/*
+ * The port fraction at other wall reflectances from one isx_order_hist result.  Host only, no GPU needed.  With
+ * rho0 = cfg->reflectance and, for each i < n_rho, w_k = pow(rho[i] / rho0, (double)k):
+ *
+ *       S1 = sum over k of hist[0][k] * w_k ;  S2 = sum over k of hist[0][k] * w_k * w_k      (in increasing k)
+ *       fraction[i] = S1 / launched
+ *       sigma[i]    = sqrt(S2 - S1 * S1 / launched) / launched       (the standard error of the weighted mean)
+ *
+ * `launched` is stats.launched of the call(s) that made hist.  At rho[i] == rho0 fraction is counted_below_z / launched exactly.
+ * rho > rho0 is accepted, but its weights grow with k, and so does the variance: the estimate is then carried by the few
+ * long-lived rays of the tail.  (Only the wall's absorption is reweighted; the histories themselves -- geometry, border model --
+ * are those of cfg.)  Refused with ISX_ERR_BAD_CONFIG: a wrong spec, cfg->source_model != ISX_SOURCE_PENCIL (the primary's
+ * interactions are not in k), counts->overflow[0] != 0 (the tail is lost), rho0 <= 0, launched == 0.  ISX_ERR_BAD_ARG: a NULL
+ * cfg, spec, hist, counts, rho or fraction, n_rho < 0, a rho[i] that is negative or not finite.  sigma may be NULL.
+ */
+int isx_order_reweight(const isx_config* cfg, const isx_order_hist_spec* spec, const uint64_t* hist,
+                       const isx_order_hist_counts* counts, uint64_t launched, const double* rho, int32_t n_rho,
+                       double* fraction, double* sigma);
+
+/*
  * Series driver (sweepSeries, fluxAtObserverOptimize.C:892-921 / fluxAtObserverFast.C:1641-1673):
  * n_cfg configurations sharing one detector grid, traced back to back on the device with ONE
  * host synchronisation; hits[n_cfg][n_theta*n_phi], stats[n_cfg] (t_kernel_ms = whole series).
