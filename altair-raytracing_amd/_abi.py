@@ -28,6 +28,7 @@ RAY_EXITED, RAY_ABSORBED, RAY_SUSPENDED = 1, 2, 3
 WALL_MAP_MAX_BINS, WALL_MAP_MAX_AXIS = 8192, 512   # ISX_WALL_MAP_MAX_BINS / ISX_WALL_MAP_MAX_AXIS
 LIGHT_FIELD_MAX_BINS, LIGHT_FIELD_MAX_AXIS = 1 << 22, 1024   # ISX_LIGHT_FIELD_MAX_BINS / ISX_LIGHT_FIELD_MAX_AXIS
 ORDER_HIST_MAX_ORDERS, ORDER_HIST_MAX_WORDS, ORDER_HIST_MAX_DZ = 2048, 8192, 64   # ISX_ORDER_HIST_MAX_ORDERS / _MAX_WORDS, n_dz <= 64
+MAX_WALL_PATCHES = 8   # ISX_MAX_WALL_PATCHES
 
 # every symbol include/isx.h declares (tests check the .so exports exactly these)
 EXPORTS = [
@@ -40,6 +41,7 @@ EXPORTS = [
     "isx_default_wall_map_spec", "isx_wall_map", "isx_wall_map_device",
     "isx_default_light_field_spec", "isx_light_field", "isx_light_field_device",
     "isx_default_order_hist_spec", "isx_order_hist", "isx_order_hist_device", "isx_order_reweight",
+    "isx_default_wall_patch_spec", "isx_wall_patch_cap", "isx_wall_patches", "isx_wall_patches_device",
 ]
 
 
@@ -161,6 +163,24 @@ class OrderHistCounts(C.Structure):
         return {"overflow": [int(x) for x in self.overflow], "dz_outside": int(self.dz_outside)}
 
 
+class WallPatch(C.Structure):
+    """isx_wall_patch (include/isx.h): a cap of the inner wall -- q . axis >= min_dot -- with a reflectance of its own."""
+
+    _fields_ = [("axis", C.c_double * 3), ("min_dot", C.c_double), ("reflectance", C.c_double)]
+
+
+class WallPatchSpec(C.Structure):
+    """isx_wall_patch_spec (include/isx.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("n_patches", C.c_int32), ("reserved1", C.c_int32),
+                ("patch", WallPatch * MAX_WALL_PATCHES)]
+
+    def copy(self):
+        s = WallPatchSpec()
+        C.memmove(C.byref(s), C.byref(self), C.sizeof(WallPatchSpec))
+        return s
+
+
 _lib = None
 
 
@@ -215,6 +235,11 @@ def load():
     L.isx_order_hist_device.argtypes = [P(Config), P(OrderHistSpec), u64, u64, u64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.isx_order_reweight.argtypes = [P(Config), P(OrderHistSpec), P(u64), P(OrderHistCounts), u64, P(C.c_double), C.c_int32,
                                      P(C.c_double), P(C.c_double)]
+    L.isx_default_wall_patch_spec.argtypes = [P(Config), P(WallPatchSpec)]
+    L.isx_default_wall_patch_spec.restype = None
+    L.isx_wall_patch_cap.argtypes = [P(Config), P(dbl), dbl, dbl, P(WallPatch)]
+    L.isx_wall_patches.argtypes = [P(Config), P(WallPatchSpec), u64, u64, u64, P(u64), P(u64), P(Stats)]
+    L.isx_wall_patches_device.argtypes = [P(Config), P(WallPatchSpec), u64, u64, u64, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -496,6 +521,60 @@ def order_reweight(cfg, spec, hist, counts, launched, rho):
     _chk(load().isx_order_reweight(C.byref(cfg), C.byref(spec), _p(h, C.c_uint64), C.byref(counts), int(launched),
                                    _p(r, C.c_double), int(r.size), _p(frac, C.c_double), _p(sig, C.c_double)), "isx_order_reweight")
     return frac[:r.size], sig[:r.size]
+
+
+def default_wall_patch_spec(cfg):
+    """No patches (no GPU needed)."""
+    s = WallPatchSpec()
+    load().isx_default_wall_patch_spec(C.byref(cfg), C.byref(s))
+    return s
+
+
+def wall_patch_cap(cfg, direction, half_angle_deg, reflectance):
+    """-> WallPatch: the cap of half-angle `half_angle_deg` about `direction` (include/isx.h: isx_wall_patch_cap; host only)."""
+    d = (C.c_double * 3)(*[float(x) for x in direction])
+    out = WallPatch()
+    _chk(load().isx_wall_patch_cap(C.byref(cfg), d, float(half_angle_deg), float(reflectance), C.byref(out)), "isx_wall_patch_cap")
+    return out
+
+
+def wall_patch_spec(cfg, patches):
+    """-> WallPatchSpec of a list of WallPatch (at most MAX_WALL_PATCHES; where caps overlap the first wins)."""
+    patches = list(patches)
+    if len(patches) > MAX_WALL_PATCHES:
+        raise ValueError("at most %d wall patches" % MAX_WALL_PATCHES)
+    s = default_wall_patch_spec(cfg)
+    s.n_patches = len(patches)
+    for k, p in enumerate(patches):
+        C.memmove(C.byref(s.patch[k]), C.byref(p), C.sizeof(WallPatch))
+    return s
+
+
+def _patch_classes(spec):
+    """entries of the arrays a call may write; 2 for a spec the library refuses (it says so itself)"""
+    return (spec.n_patches if 0 <= spec.n_patches <= MAX_WALL_PATCHES else 0) + 2
+
+
+def wall_patches(cfg, n_rays, seed, spec=None, first_ray=0):
+    """-> (arrivals[P + 2] uint64, absorbed[P + 2] uint64, Stats): the trace with the spec's caps of the inner wall at their own
+    reflectance; per class -- the P patches, the rest of the inner sphere, rim and outer sphere -- the interactions that arrived
+    and the rays absorbed there (include/isx.h)."""
+    if spec is None:
+        spec = default_wall_patch_spec(cfg)
+    nc = _patch_classes(spec)
+    arr, ab = np.zeros(nc, dtype=np.uint64), np.zeros(nc, dtype=np.uint64)
+    st = Stats()
+    _chk(load().isx_wall_patches(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray), _p(arr, C.c_uint64),
+                                 _p(ab, C.c_uint64), C.byref(st)), "isx_wall_patches")
+    return arr, ab, st
+
+
+def wall_patches_device(cfg, spec, n_rays, seed, first_ray, d_arrivals_ptr, d_absorbed_ptr):
+    """Enqueue on the library stream, accumulating into device memory: n_patches + 2 uint64 counters each at d_arrivals_ptr and
+    d_absorbed_ptr (e.g. torch tensors' data_ptr())."""
+    _chk(load().isx_wall_patches_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
+                                        C.c_void_p(int(d_arrivals_ptr or 0) or None), C.c_void_p(int(d_absorbed_ptr or 0) or None)),
+         "isx_wall_patches_device")
 
 
 def fluxmap_series(cfgs, n_rays, seed, first_ray=0):

@@ -115,6 +115,19 @@ int hip_rc(hipError_t e) {
 // ABI v3: the caller's struct must be the library's (isx.h: struct_size)
 bool config_abi_ok(const isx_config* c) { return c->struct_size == (uint32_t)sizeof(isx_config); }
 
+// What the absorb test and the azimuth need of a reflectance (Geom / Hot, and per patch PatchTab): stated once.
+struct RhoConsts { unsigned long long rho_thr; double inv_thr, psi_k1, psi_k0; };
+RhoConsts reflectance_consts(double rho) {
+  RhoConsts k;
+  // (w + 0.5) * 2^-32 < rho  <=>  w < rho * 2^32 - 0.5 =: x (both scalings exact)  <=>  w < ceil(x) for integer w
+  const double x = std::ldexp(rho, 32) - 0.5;
+  k.rho_thr = !(x > 0.0) ? 0ull : (x >= 4294967296.0 ? 4294967296ull : (unsigned long long)std::ceil(x));
+  k.inv_thr = k.rho_thr ? 1.0 / (double)k.rho_thr : 0.0;
+  k.psi_k1 = k.inv_thr * 1.57079632679489655800e+00;
+  k.psi_k0 = (0.5 * k.inv_thr - 0.5) * 1.57079632679489655800e+00;
+  return k;
+}
+
 int prepare_geom(const isx_config* c, Geom* g) {
   if (!config_abi_ok(c)) return ISX_ERR_BAD_CONFIG;
   if (!(c->r_in > 0) || !(c->r_out > c->r_in)) return ISX_ERR_BAD_CONFIG;
@@ -135,12 +148,8 @@ int prepare_geom(const isx_config* c, Geom* g) {
   g->H = c->box_half;
   g->rho = c->reflectance;
   {
-    // (w + 0.5) * 2^-32 < rho  <=>  w < rho * 2^32 - 0.5 =: x (both scalings exact)  <=>  w < ceil(x) for integer w
-    const double x = std::ldexp(c->reflectance, 32) - 0.5;
-    g->rho_thr = !(x > 0.0) ? 0ull : (x >= 4294967296.0 ? 4294967296ull : (unsigned long long)std::ceil(x));
-    g->inv_thr = g->rho_thr ? 1.0 / (double)g->rho_thr : 0.0;
-    g->psi_k1 = g->inv_thr * 1.57079632679489655800e+00;
-    g->psi_k0 = (0.5 * g->inv_thr - 0.5) * 1.57079632679489655800e+00;
+    const RhoConsts k = reflectance_consts(c->reflectance);
+    g->rho_thr = k.rho_thr; g->inv_thr = k.inv_thr; g->psi_k1 = k.psi_k1; g->psi_k0 = k.psi_k0;
   }
   g->sigma = c->roughness_rad;
   g->lambertian = c->lambertian;
@@ -393,13 +402,50 @@ int check_order_spec(const isx_order_hist_spec* s) {
   return ISX_OK;
 }
 
+// isx_wall_patches: the checked spec and the device accumulators of the call
+struct PatchSink { const isx_wall_patch_spec* spec = nullptr; unsigned long long *arrivals = nullptr, *absorbed = nullptr; };
+
+bool patch_ok(const isx_wall_patch& p) {
+  return std::isfinite(p.axis[0]) && std::isfinite(p.axis[1]) && std::isfinite(p.axis[2]) && std::isfinite(p.min_dot) &&
+         p.reflectance >= 0.0 && p.reflectance <= 1.0;   // (a NaN compares false)
+}
+// isx.h: the limits of a wall-patch spec and the scope of the call (the explicit Lambertian lean path)
+int check_patch_call(const isx_config* c, const isx_wall_patch_spec* s) {
+  if (!config_abi_ok(c) || s->struct_size != (uint32_t)sizeof(isx_wall_patch_spec)) return ISX_ERR_BAD_CONFIG;
+  if (s->n_patches < 0 || s->n_patches > ISX_MAX_WALL_PATCHES) return ISX_ERR_BAD_CONFIG;
+  for (int k = 0; k < s->n_patches; ++k)
+    if (!patch_ok(s->patch[k])) return ISX_ERR_BAD_CONFIG;
+  if (c->source_model != ISX_SOURCE_PENCIL || c->surface_model != ISX_SURFACE_ROBAST || c->lambertian == 0 ||
+      c->trace_mode != ISX_TRACE_EXPLICIT)
+    return ISX_ERR_BAD_CONFIG;
+  return ISX_OK;
+}
+static_assert(ISX_MAX_WALL_PATCHES == kMaxPatches, "isx.h and PatchTab");
+// the kernel's table of a checked spec: the caps, and per class the constants of its reflectance (classes P and P + 1: the wall's)
+PatchTab patch_table(const isx_config& c, const isx_wall_patch_spec& s) {
+  PatchTab t;
+  std::memset(&t, 0, sizeof(t));
+  t.n = s.n_patches;
+  for (int k = 0; k < s.n_patches + 2; ++k) {
+    const RhoConsts rc = reflectance_consts(k < s.n_patches ? s.patch[k].reflectance : c.reflectance);
+    t.rho_thr[k] = rc.rho_thr; t.psi_k1[k] = rc.psi_k1; t.psi_k0[k] = rc.psi_k0;
+    if (k < s.n_patches) {
+      const isx_wall_patch& p = s.patch[k];
+      t.cap[k][0] = p.axis[0]; t.cap[k][1] = p.axis[1]; t.cap[k][2] = p.axis[2]; t.cap[k][3] = p.min_dot;
+    }
+  }
+  return t;
+}
+// LDS of the patch kernel's block behind the rings: the table and its 2 (P + 2) u32 counters
+size_t patch_lds() { return (sizeof(PatchTab) + 2 * (kMaxPatches + 2) * sizeof(uint32_t) + 15) & ~(size_t)15; }
+
 // LDS of a workgroup's histogram: 4 B per bin, 16-byte aligned
 size_t hist_lds(int nbins) { return ((size_t)nbins * 4 + 15) & ~(size_t)15; }
 
 // The DetGrid of a call's sink, checked, and the dynamic LDS of its fused kernel (histogram + tables, census, Geom, DetGrid).
 int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d_discs, double disc_r, double disc_h,
               const PerPos* pp, const LogSink* lg, const ExitSink* xm, const WallSink* wm, const FieldSink* lf, const OrderSink* oh,
-              DetGrid& d, size_t& lds) {
+              const PatchSink* wp, DetGrid& d, size_t& lds) {
   std::memset(&d, 0, sizeof(d));
   d.portz = c->exit_port_z;
   d.hit_line_mode = c->hit_line_mode;
@@ -493,6 +539,16 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
     d.xm_dir = oh->hist; d.xm_pos = oh->port_dz; d.xm_counts = oh->counts;
     d.nbins = 4 * s.n_orders + s.n_orders * s.n_dz + 5;   // the workgroup's LDS block: the histograms | the port's dz | the five counters
     lds = hist_lds(d.nbins) + 64 + sizeof(Geom) + sizeof(DetGrid);
+  } else if (sink == SINK_PATCH) {
+    if (!wp || !wp->spec || !wp->arrivals || !wp->absorbed) return ISX_ERR_BAD_ARG;
+    rc = check_patch_call(c, wp->spec);
+    if (rc) return rc;
+    d.hit_line_mode = ISX_HITLINE_LAST_SEGMENT;   // (isx.h: ignored -- no exit line is looked at)
+    // (the spec travels in the exit maps' words of DetGrid: isx_kernels.hpp)
+    d.xm_nx = wp->spec->n_patches;
+    d.xm_dir = wp->arrivals; d.xm_pos = wp->absorbed;
+    d.nbins = 2 * (wp->spec->n_patches + 2);
+    lds = patch_lds() + 64 + sizeof(Geom) + sizeof(DetGrid);
   } else {
     if (nbins_override < 1 || nbins_override > 36000) return ISX_ERR_BAD_ARG;
     d.nbins = nbins_override;
@@ -522,6 +578,7 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
 enum Route { ROUTE_FUSED, ROUTE_ASSIST, ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_FIELD_PIPE, ROUTE_DISC_PIPE };
 typedef void (*KernelFn)(const Geom, const DetGrid, const Work);
 typedef void (*BinFn)(const DetGrid, const Work);
+typedef void (*PatchFn)(const Geom, const DetGrid, const Work, const PatchTab);
 struct Plan {
   Route route = ROUTE_FUSED;
   KernelFn fn = nullptr;        // the kernel (a pipeline's trace kernel)
@@ -539,6 +596,9 @@ struct Plan {
   bool binning = true;          // false: bin_mode 2, a diagnostic: trace only
   bool overlap = false;         // chunks alternate over two streams (S.overlap)
   size_t slot_doubles = 6;      // doubles per exit record in the workspace
+  PatchFn patch_fn = nullptr;   // SINK_PATCH: the kernel (it takes the patches as a fourth argument: patch_tab) instead of fn
+  PatchTab patch_tab{};
+  uint64_t launch_max = 0;      // ROUTE_FUSED / ROUTE_ASSIST: rays per launch (0: kLaunchMax)
 };
 
 // workgroups of a launch of n rays: enough for p.rays_per_lane rays per tracer lane, no more than `per_cu` per CU
@@ -715,6 +775,18 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     return p;
   }
 
+  // The wall patches have one route whatever the switches say: the assist-wave kernel of the explicit Lambertian lean path (the
+  // call is refused for anything else: check_patch_call) in the wall map's shapes, the table and the counters behind the rings.
+  // Launches are cut at pipeline_chunk, which bounds what a workgroup's u32 counters can see.
+  if (sink == SINK_PATCH) {
+    p.route = ROUTE_ASSIST;
+    p.patch_fn = isx_trace_assist_patch_kernel;
+    p.launch_max = std::min(kLaunchMax, S.pipe_chunk);
+    trace_shape(p, small_shape(std::min(n, p.launch_max), S.assist_block), true, resident_unless(S.trace_blocks_per_cu));
+    p.lds += patch_lds();
+    return p;
+  }
+
   // the fused kernel: the lean build where there is one, the full-featured one for everything else
   switch (sink) {
     case SINK_FLUX: p.fn = lean && pencil ? (chord ? isx_trace_bin_chord_kernel : isx_trace_bin_kernel) :
@@ -779,14 +851,17 @@ int span(int kind, size_t* from) {
 
 // ROUTE_FUSED and ROUTE_ASSIST: launches of at most kLaunchMax rays, one span
 int run_single(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
-  int rc = set_lds((const void*)p.fn, p.lds); if (rc) return rc;
-  const int per_cu = blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
+  const void* fn = p.patch_fn ? (const void*)p.patch_fn : (const void*)p.fn;
+  int rc = set_lds(fn, p.lds); if (rc) return rc;
+  const int per_cu = p.patch_fn ? blocks_per_cu(p.patch_fn, p.block, p.lds, p.per_cu) : blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
+  const uint64_t launch_max = p.launch_max ? p.launch_max : kLaunchMax;
   size_t t;
   rc = mark(S.stream, &t); if (rc) return rc;
-  for (uint64_t off = 0; off < wk.n; off += kLaunchMax) {
+  for (uint64_t off = 0; off < wk.n; off += launch_max) {
     Work w;
-    rc = launch_work(wk, off, std::min(wk.n - off, kLaunchMax), 0, S.stream, &w); if (rc) return rc;
-    hipLaunchKernelGGL(p.fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w);
+    rc = launch_work(wk, off, std::min(wk.n - off, launch_max), 0, S.stream, &w); if (rc) return rc;
+    if (p.patch_fn) hipLaunchKernelGGL(p.patch_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab);
+    else hipLaunchKernelGGL(p.fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w);
     HIPCHK(hipGetLastError());
   }
   return span(0, &t);
@@ -901,7 +976,8 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
 int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t first, unsigned long long* d_hist,
             int nbins_override, const double* d_discs, double disc_r, double disc_h, const PerPos* pp = nullptr,
             const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr, const ExitSink* xm = nullptr,
-            const WallSink* wm = nullptr, const FieldSink* lf = nullptr, const OrderSink* oh = nullptr) {
+            const WallSink* wm = nullptr, const FieldSink* lf = nullptr, const OrderSink* oh = nullptr,
+            const PatchSink* wp = nullptr) {
   Geom g;
   int rc = prepare_geom(c, &g);
   if (rc) return rc;
@@ -909,12 +985,13 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
   if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;   // first + n (the exclusive end of the index range) must be representable
   DetGrid d;
   size_t lds = 0;
-  rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, xm, wm, lf, oh, d, lds);
+  rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, xm, wm, lf, oh, wp, d, lds);
   if (rc || n == 0) return rc;
   Work wk;
   wk.seed = seed; wk.first = first; wk.n = n; wk.hist = d_hist; wk.stats = d_stats ? d_stats : S.d_stats;
   wk.ctr = nullptr; wk.sub = 0; wk.pad = 0;
-  const Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n);
+  Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n);
+  if (sink == SINK_PATCH) p.patch_tab = patch_table(*c, *wp->spec);
   return p.route == ROUTE_FUSED || p.route == ROUTE_ASSIST ? run_single(p, g, d, wk) : run_pipeline(p, g, d, wk);
 }
 
@@ -1679,6 +1756,62 @@ int isx_order_reweight(const isx_config* cfg, const isx_order_hist_spec* spec, c
     }
   }
   return ISX_OK;
+}
+
+void isx_default_wall_patch_spec(const isx_config* cfg, isx_wall_patch_spec* spec) {
+  (void)cfg;   // (the default does not depend on the configuration: no patches)
+  if (!spec) return;
+  std::memset(spec, 0, sizeof(*spec));
+  spec->struct_size = (uint32_t)sizeof(isx_wall_patch_spec);
+}
+
+int isx_wall_patch_cap(const isx_config* cfg, const double dir[3], double half_angle_deg, double reflectance, isx_wall_patch* out) {
+  if (!cfg || !dir || !out) return ISX_ERR_BAD_ARG;
+  if (!config_abi_ok(cfg)) return ISX_ERR_BAD_CONFIG;
+  const double mag = std::sqrt(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
+  if (!(mag > 0) || !std::isfinite(mag) || !(half_angle_deg >= 0.0 && half_angle_deg <= 180.0) ||
+      !(reflectance >= 0.0 && reflectance <= 1.0))
+    return ISX_ERR_BAD_CONFIG;
+  for (int k = 0; k < 3; ++k) out->axis[k] = dir[k] / mag;
+  out->min_dot = cfg->r_in * std::cos(half_angle_deg * M_PI / 180.0);
+  out->reflectance = reflectance;
+  return ISX_OK;
+}
+
+int isx_wall_patches_device(const isx_config* cfg, const isx_wall_patch_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                            uint64_t* d_arrivals, uint64_t* d_absorbed) {
+  // (what needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one)
+  if (!cfg || !spec || !d_arrivals || !d_absorbed) return ISX_ERR_BAD_ARG;
+  const int bad = check_patch_call(cfg, spec);
+  if (bad) return bad;
+  if (!S.init) return not_initialised();
+  const PatchSink wp{spec, (unsigned long long*)d_arrivals, (unsigned long long*)d_absorbed};
+  return enqueue(SINK_PATCH, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                 nullptr, nullptr, &wp);
+}
+
+int isx_wall_patches(const isx_config* cfg, const isx_wall_patch_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                     uint64_t* arrivals, uint64_t* absorbed, isx_stats* stats) {
+  if (!cfg || !spec || !arrivals || !absorbed) return ISX_ERR_BAD_ARG;
+  int rc = check_patch_call(cfg, spec);
+  if (rc) return rc;
+  if (!S.init) return not_initialised();
+  const size_t nc = (size_t)spec->n_patches + 2, words = 2 * nc;
+  rc = call_open(words);
+  if (rc) return rc;
+  // the call's accumulators in the pooled histogram: arrivals | absorbed
+  const PatchSink wp{spec, S.d_hist, S.d_hist + nc};
+  rc = zero_hist(words);
+  if (rc == ISX_OK) rc = enqueue(SINK_PATCH, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, &wp);
+  if (rc == ISX_OK) rc = stage_result(S.d_hist, words * sizeof(unsigned long long));
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK) {
+    const unsigned long long* h = reinterpret_cast<const unsigned long long*>(S.h_pin + 64);
+    std::memcpy(arrivals, h, nc * 8);
+    std::memcpy(absorbed, h + nc, nc * 8);
+  }
+  return rc;
 }
 
 #ifdef ISX_DIAG

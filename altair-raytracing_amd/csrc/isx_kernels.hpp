@@ -79,6 +79,9 @@ struct DetGrid {
   // SINK_ORDER (isx.h: isx_order_hist) likewise: xm_nx = n_orders, xm_ny = n_dz, xm_dir = the global histograms [4][xm_nx] (+=),
   // xm_pos = the port's [xm_nx][xm_ny] (+=; not read where xm_ny = 0), xm_counts = [5]: overflow[4], dz_outside.  A workgroup's LDS
   // holds u32[4 * xm_nx | xm_nx * xm_ny | 5 counters] (nbins words).
+  // SINK_PATCH (isx.h: isx_wall_patches) likewise: xm_nx = n_patches, xm_dir = arrivals [xm_nx + 2] (+=), xm_pos = absorbed
+  // [xm_nx + 2] (+=).  The patches themselves are a kernel argument of their own (PatchTab); a workgroup's LDS holds a copy of
+  // it and u32[2 * (xm_nx + 2)] counters behind the rings.
 };
 
 // -DISX_DIAG (tuning builds only, never the shipped library): where the binning work goes.
@@ -118,7 +121,7 @@ __device__ unsigned long long g_diag[48];   // [32..47]: the assist wave of assi
 #endif
 
 enum : int { SINK_FLUX = 0, SINK_DZ = 1, SINK_DISC = 2, SINK_PERPOS = 3, SINK_LOG = 4, SINK_DISCPOS = 5, SINK_REC = 6, SINK_EXITMAP = 7, SINK_WALL = 8,
-              SINK_LIGHTFIELD = 9, SINK_ORDER = 10 };
+              SINK_LIGHTFIELD = 9, SINK_ORDER = 10, SINK_PATCH = 11 };
 
 struct Work {
   uint64_t seed, first, n;    // one launch traces rays [first, first + n), n < 2^31 (a lane keeps a 31-bit offset from `first`)
@@ -2173,6 +2176,72 @@ __device__ __forceinline__ unsigned long long order_flush(const DetGrid& d_arg, 
   return flushed;
 }
 
+// ------------------------------------------------------------------ wall patches (isx.h: isx_wall_patches)
+// The patches of a call as the trace kernel gets them (a kernel argument of its own, copied into the workgroup's LDS): per patch
+// the cap (axis, min_dot: used as given) and the three constants of its reflectance that the bounce needs (Hot: rho_thr, psi_k1,
+// psi_k0 -- made by the host with the expressions that make the wall's own, isx_api.hip: reflectance_consts), by class: entries n
+// and n + 1 of the constants are the wall's.  8 x 4 + 10 x 3 doubles.
+constexpr int kMaxPatches = 8;
+struct PatchTab {
+  double cap[kMaxPatches][4];             // axis[3], min_dot
+  unsigned long long rho_thr[kMaxPatches + 2];
+  double psi_k1[kMaxPatches + 2], psi_k0[kMaxPatches + 2];
+  int n, pad;
+};
+// One arrival at q on a surface of `kind` (INNER: known to be the inner sphere -- the tracer waves): its class, the arrivals of
+// the lanes that are here together, and in `hp` the constants of the class's reflectance.  Class k < n: the lowest patch with
+// (q.x a0 + q.y a1) + q.z a2 >= min_dot (IEEE double, left to right, no fma: -ffp-contract=off); n: the inner sphere outside every
+// patch; n + 1: rim and outer sphere (the wall's reflectance).  The loop over the table is uniform (scalar counter, LDS reads at a
+// wave-uniform address) and selects the lane's class -- one register; the class then selects the three constants from the LDS
+// table where they are used (selecting the constants themselves in the loop kept six more VGPRs alive through it: 16 B of scratch
+// in a kernel that sits at its 80).  No branch depends on the class.  Arrivals are counted per wave: a ballot per class, its
+// popcount added to the workgroup's u32 counter cnt[class] by the first lane of the ballot (per lane it would be a same-address
+// add of up to 64 lanes per bounce).  That lane is told by its rank in the ballot, as wall_record does: a lane index kept for the
+// purpose is a register more than the kernel has (the thread index went to scratch for the whole trace loop).
+__device__ __forceinline__ void patch_count(uint32_t* word, bool mine) {
+  const unsigned long long m = __ballot(mine);
+  if (m) {
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (mine && rank == 0u) atomicAdd(word, (uint32_t)__popcll(m));
+  }
+}
+template <bool INNER>
+__device__ __forceinline__ int patch_arrive(const PatchTab* tab, int np, uint32_t* cnt, int kind, const V3& q, Hot& hp) {
+  const bool inner = INNER || kind == K_INNER;
+  bool open = inner;                      // no patch holds q so far
+  int cls = np;
+  for (int k = 0; k < np; ++k) {
+    const double dq = (q.x * tab->cap[k][0] + q.y * tab->cap[k][1]) + q.z * tab->cap[k][2];
+    const bool hit = open && dq >= tab->cap[k][3];
+    cls = hit ? k : cls;
+    open = open && !hit;
+    patch_count(&cnt[k], hit);
+  }
+  patch_count(&cnt[np], open);
+  if (!INNER) {
+    cls = inner ? cls : np + 1;
+    patch_count(&cnt[np + 1], !inner);
+  }
+  hp.rho_thr = tab->rho_thr[cls]; hp.psi_k1 = tab->psi_k1[cls]; hp.psi_k0 = tab->psi_k0[cls];
+  return cls;
+}
+// One flush of a workgroup's counters (after a barrier): arrivals into xm_dir, absorbed into xm_pos.  Returns this thread's share
+// of stats.bin_increments (isx.h: the arrivals on the patches).
+__device__ __forceinline__ unsigned long long patch_flush(const DetGrid& d_arg, const uint32_t* cnt) {
+  // (the thread index afresh, as the census below takes it: the address of cnt[tid] that zeroed the counter at the kernel's start
+  //  would otherwise be kept for this one read -- through the whole trace loop, in scratch)
+  uint32_t t2 = threadIdx.x;
+  asm volatile("" : "+v"(t2));
+  const int tid = (int)t2;
+  const int np = d_arg.xm_nx, nc = np + 2;
+  if (tid >= 2 * nc) return 0ull;
+  const uint32_t c = cnt[tid];
+  if (!c) return 0ull;
+  if (tid < nc) global_add_u64(d_arg.xm_dir + tid, (unsigned long long)c);
+  else global_add_u64(d_arg.xm_pos + (tid - nc), (unsigned long long)c);
+  return tid < np ? (unsigned long long)c : 0ull;
+}
+
 // ------------------------------------------------------------------ persistent trace kernel, one per sink
 //   SINK_FLUX: 180x90 detector flux map (the headline path)
 //   SINK_DZ  : histogram of the exit direction's z component (distributionSphereDetectorSweep.C:54,91)
@@ -2778,10 +2847,17 @@ __device__ __forceinline__ void ray_unpack(const uint4& a, const uint4& b, const
 // wave for the exits and for what ends on the rim or the outer sphere.  A BRDF primary's end is not a ray's end: both waves hand it
 // to ray_rescatter before their census, so only the scattered ray's end is seen.  The workgroup's u32 block lies behind the rings,
 // as WALL's map does.  No exit lines, no second kernel.
-template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false, bool ORDER = false>
-__device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk) {
+// PATCH (isx_wall_patches, SINK_PATCH): caps of the inner sphere with a reflectance of their own.  Wherever a ray arrives on the
+// inner sphere -- a tracer's bounce step, the first strike Geom::q0 included (every fresh ray arrives there: it is classified like
+// any other arrival), or the assist wave when it brings a ray back -- patch_arrive() finds the class, counts the arrival and
+// selects the lane's (rho_thr, psi_k1, psi_k0), with which the unchanged interaction runs; rim and outer sphere are class P + 1 at
+// the wall's reflectance.  An absorbed ray adds one to its class's counter where it ends.  The table and the workgroup's u32
+// counters lie behind the rings.  Explicit Lambertian lean path only; no exit lines, no second kernel.
+template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false, bool ORDER = false, bool PATCH = false>
+__device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk, const PatchTab* tab_arg = nullptr) {
   constexpr bool LEAN = SURF == SURF_LAMBERT;
   static_assert(LEAN || (CH == 0 && !RESC), "the chord identity and the BRDF re-scatter pipeline are built for the Lambertian border");
+  static_assert(!PATCH || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER), "wall patches: the explicit Lambertian lean path, no other sink");
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned long long* sstat = reinterpret_cast<unsigned long long*>(smem);
   Geom* g_lds = reinterpret_cast<Geom*>(sstat + 8);
@@ -2799,6 +2875,14 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   static_assert(!(WALL && ORDER), "one LDS block behind the rings");
   const OrderSpec ospec = order_spec<ORDER>(d_arg);
   if (ORDER) for (int b = tid; b < d_arg.nbins; b += nthr) hist[b] = 0u;
+  // PATCH: the table | u32[arrivals (n_patch + 2) | absorbed (n_patch + 2)]
+  PatchTab* ptab = reinterpret_cast<PatchTab*>(hist);
+  uint32_t* pcnt = reinterpret_cast<uint32_t*>(ptab + 1);
+  const int n_patch = PATCH ? d_arg.xm_nx : 0;
+  if constexpr (PATCH) {
+    if (tid == 65) *ptab = *tab_arg;
+    if (tid < 2 * (n_patch + 2)) pcnt[tid] = 0u;
+  }
   if (tid < 8) sstat[tid] = 0ull;
   if (tid == 64) {
     *g_lds = g_arg;
@@ -2929,7 +3013,13 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       bool ended = false, susp = false;
       auto arrive = [&](const V3& q, auto ph, bool record = true) {
         if (WALL && record) wall_record(wspec, hist, wall_nmap, K_INNER, r.j, q, 1u);
-        const int st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(h, g, r, seed, first, K_INNER, q);
+        int st;
+        if constexpr (PATCH) {
+          Hot hp = h;
+          const int cls = patch_arrive<true>(ptab, n_patch, pcnt, K_INNER, q, hp);
+          st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(hp, g, r, seed, first, K_INNER, q);
+          if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
+        } else st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(h, g, r, seed, first, K_INNER, q);
         if (st != 0) { run = false; ended = true; susp = st == ST_SUSPENDED; }
       };
       // SURF_LOBE: one TRY of the lobe's rejection sampler for every lane that is in an interaction (Ray::k != 0)
@@ -3193,6 +3283,13 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           V3 q;
           const int kind = next_hit_generic(g, r.p, r.v, r.on, q);
           if (WALL && kind != K_BOX) wall_record(wspec, hist, wall_nmap, kind, r.j, q, 1u);
+          if constexpr (PATCH) {
+            Hot hp = h;
+            int cls = 0;
+            if (kind != K_BOX) cls = patch_arrive<false>(ptab, n_patch, pcnt, kind, q, hp);
+            st = ray_arrive<false, LEAN, CH, PH_DIRECT, true, SURF>(hp, g, r, seed, first, kind, q);
+            if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
+          } else
           st = ray_arrive<DISC || PP == 2, LEAN, CH, PH_DIRECT, true, SURF>(h, g, r, seed, first, kind, q);   // (DISC: r.prev = start of this segment)
           if (RESC && st != 0 && h.source_model == 1 && !r.scattered()) {   // nonLambertianFlux.C:253-268
             n_wall += r.j;
@@ -3270,7 +3367,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         if (hit1) atomicAdd(&wk.hist[b1], 1ull);
         n_inc += (unsigned long long)__popcll(__ballot(hit0)) + (unsigned long long)__popcll(__ballot(hit1));
       }
-      const unsigned long long m = (PP != 0 || WALL || ORDER) ? 0ull : __ballot(keep);
+      const unsigned long long m = (PP != 0 || WALL || ORDER || PATCH) ? 0ull : __ballot(keep);
       if (m) {
         const uint32_t cnt = (uint32_t)__popcll(m);
         if (cnt > reg_left) {   // close the open region, reserve the next one (kRegion)
@@ -3370,6 +3467,11 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     if (flushed) atomicAdd(&sstat[5], flushed);
     __syncthreads();
   }
+  if constexpr (PATCH) {   // one flush of the workgroup's counters; bin_increments = the arrivals on the patches
+    const unsigned long long flushed = patch_flush(d_arg, pcnt);
+    if (flushed) atomicAdd(&sstat[5], flushed);
+    __syncthreads();
+  }
   {
     uint32_t t2 = threadIdx.x;
     asm volatile("" : "+v"(t2));
@@ -3412,6 +3514,12 @@ extern "C" __global__ void ISX_ASSIST_ATTR
 isx_trace_assist_order_chord_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<1, false, false, 0, SURF_LAMBERT, false, true>(g, d, wk); }
 extern "C" __global__ void ISX_ASSIST_ATTR
 isx_trace_assist_order_brdf_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, true, false, 0, SURF_LAMBERT, false, true>(g, d, wk); }
+// the wall patches (isx_wall_patches): the lean explicit kernel with a class and a reflectance per arrival; the patches are a
+// fourth argument
+extern "C" __global__ void ISX_ASSIST_ATTR
+isx_trace_assist_patch_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab) {
+  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true>(g, d, wk, &tab);
+}
 // the other border models on the same pipeline (round 5; until then round 1's fused isx_trace_bin_full_kernel served them):
 // the cos^2 lobe of "nonLambertianFlux copy.C":31-70,188-221 and ROBAST's rough-specular border (EnableLambertian(false))
 #ifndef ISX_LOBE_WAVES

@@ -744,4 +744,24 @@ int order_hist_all(const isx_config* cfg, const isx_order_hist_spec* spec, uint6
   return rc;
 }
 
+int wall_patches_all(const isx_config* cfg, const isx_wall_patch_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                     uint64_t* arrivals, uint64_t* absorbed, isx_stats* st) {
+  Comm& c = comm();
+  if (!c.active()) return isx_wall_patches(cfg, spec, n_rays, seed, first_ray, arrivals, absorbed, st);
+  // (a spec the ABI refuses leaves only the status word to exchange)
+  const bool ok = spec && spec->n_patches >= 0 && spec->n_patches <= ISX_MAX_WALL_PATCHES;
+  const size_t nc = ok ? (size_t)spec->n_patches + 2 : 0;
+  uint64_t f, cnt;
+  c.shard(n_rays, f, cnt);
+  isx_stats local{};
+  std::vector<uint64_t> buf(2 * (size_t)(ISX_MAX_WALL_PATCHES + 2), 0);   // arrivals | absorbed: ONE sum
+  int rc = isx_wall_patches(cfg, spec, cnt, seed, first_ray + f, buf.data(), buf.data() + nc, &local);
+  rc = c.reduce(rc, buf.data(), nc ? 2 * nc : 0, &local);
+  if (rc != ISX_OK) return rc;
+  if (nc && arrivals) std::memcpy(arrivals, buf.data(), nc * sizeof(uint64_t));
+  if (nc && absorbed) std::memcpy(absorbed, buf.data() + nc, nc * sizeof(uint64_t));
+  if (st) *st = local;
+  return rc;
+}
+
 }  // namespace isxhost

@@ -50,6 +50,7 @@ int main(int argc, char** argv) {
                  "  wallMap [--rays <n>] [--seed <s>] [--bins <n>] [--first-order <k>] |\n"
                  "  lightField [--rays <n>] [--seed <s>] |\n"
                  "  orderHist [--rays <n>] [--seed <s>] [--orders <n>] [--dz <n>] [--reflectances <a,b,...>] |\n"
+                 "  wallPatches [--rays <n>] [--seed <s>] [--patch <ax,ay,az,half_angle_deg,rho>]... |\n"
                  "  distributionSphereDetectorSweep | --selftest-writer <file> | --unique <path> | --shard <n> | --analyze <csv>... | --analyze <folder> [average]\n";
     return 2;
   }
@@ -96,6 +97,11 @@ int main(int argc, char** argv) {
       ++i;
       continue;
     }
+    if (!std::strcmp(argv[i], "--patch") && i + 1 < argc) {   // wallPatches (repeatable)
+      options().patches.push_back(argv[i + 1]);
+      ++i;
+      continue;
+    }
     const char* eq = std::strchr(argv[i], '=');
     if (!eq) { std::cerr << "bad argument " << argv[i] << " (want key=value)\n"; return 2; }
     kv[std::string(argv[i], eq - argv[i])] = eq + 1;
@@ -120,6 +126,7 @@ int main(int argc, char** argv) {
   else if (entry == "wallMap") rootMacros::wallMap();
   else if (entry == "lightField") rootMacros::lightField();
   else if (entry == "orderHist") rootMacros::orderHist();
+  else if (entry == "wallPatches") rootMacros::wallPatches();
   else { std::cerr << "unknown entry point " << entry << "\n"; return 2; }
   const bool ok = ensure_device();  // false: the entry point printed its error and returned early
   comm().finalize();

@@ -1374,6 +1374,78 @@ void orderHist() {
   for (size_t i = 0; i < rho.size(); ++i) f << rho[i] << "," << frac[i] << "," << sig[i] << "\n";
 }
 
+// Wall patches of the library's default sphere (isx.h: isx_wall_patches): what arrived on each cap and what it absorbed.
+void wallPatches() {
+  if (!ready_everywhere()) return;
+  isx_config c;
+  isx_default_config(&c);
+  const long n = pick_n(1000000);
+  isx_wall_patch_spec sp;
+  isx_default_wall_patch_spec(&c, &sp);
+  std::vector<double> half;   // per patch, as given
+  for (const std::string& arg : options().patches) {
+    double v[5];
+    int got = 0;
+    std::stringstream ss(arg);
+    std::string tok;
+    while (got < 5 && std::getline(ss, tok, ',')) v[got++] = std::atof(tok.c_str());
+    if (got != 5 || sp.n_patches >= ISX_MAX_WALL_PATCHES) {
+      err() << "Error: --patch wants ax,ay,az,half_angle_deg,rho, at most " << ISX_MAX_WALL_PATCHES << " times: " << arg << std::endl;
+      return;
+    }
+    const int rc = isx_wall_patch_cap(&c, v, v[3], v[4], &sp.patch[sp.n_patches]);
+    if (rc != ISX_OK) {
+      err() << "Error: isx_wall_patch_cap(" << arg << "): " << isx_strerror(rc) << std::endl;
+      return;
+    }
+    half.push_back(v[3]);
+    sp.n_patches++;
+  }
+  const size_t nc = (size_t)sp.n_patches + 2;
+  std::vector<uint64_t> arrivals(nc), absorbed(nc);
+  isx_stats st;
+  const uint64_t first = take_rays((uint64_t)n);
+  const int rc = wall_patches_all(&c, &sp, (uint64_t)n, options().seed, first, arrivals.data(), absorbed.data(), &st);
+  if (rc != ISX_OK) {
+    err() << "Error: isx_wall_patches: " << isx_strerror(rc) << std::endl;
+    return;
+  }
+  const double fraction = st.launched ? (double)st.counted_below_z / (double)st.launched : 0.0;
+  std::cout << "Flux of rays through the exit port: " << st.counted_below_z << ", port fraction: " << fraction << std::endl;
+  std::ofstream f(outputPath("wall_patches.csv"));
+  f << std::setprecision(17);
+  f << "# Wall Patches - Generated: " << currentTimeString() << std::endl;
+  f << "# Number of rays: " << n << std::endl;
+  f << "# Seed: " << options().seed << std::endl;
+  f << "# First ray: " << first << std::endl;
+  f << "# Sphere inner radius: " << c.r_in << "cm" << std::endl;
+  f << "# Exit port angle: " << c.theta_max_deg << " degrees" << std::endl;
+  f << "# Wall reflectance: " << c.reflectance << std::endl;
+  for (int k = 0; k < sp.n_patches; ++k)
+    f << "# Patch " << k << ": axis " << sp.patch[k].axis[0] << " " << sp.patch[k].axis[1] << " " << sp.patch[k].axis[2] << ", half angle "
+      << half[(size_t)k] << " degrees, min_dot " << sp.patch[k].min_dot << ", reflectance " << sp.patch[k].reflectance << std::endl;
+  f << "# Classes: 0.." << sp.n_patches - 1 << " the patches (the first cap that holds a point wins), " << sp.n_patches
+    << " the rest of the inner sphere, " << sp.n_patches + 1 << " rim and outer sphere" << std::endl;
+  f << "class,arrivals,absorbed,arrivals_per_sr\n";
+  for (size_t k = 0; k < nc; ++k) {
+    f << k << "," << arrivals[k] << "," << absorbed[k] << ",";
+    if (k < (size_t)sp.n_patches) {
+      // the cap as given, seen from the centre: 2 pi (1 - cos(half angle)), cos from the struct the library uses
+      const double cosa = std::max(-1.0, std::min(1.0, sp.patch[k].min_dot / c.r_in));
+      const double sr = 2.0 * M_PI * (1.0 - cosa);
+      if (sr > 0) f << (double)arrivals[k] / sr;
+    }
+    f << "\n";
+  }
+  f << "# Launched: " << st.launched << std::endl;
+  f << "# Exited: " << st.exited << std::endl;
+  f << "# Counted below z: " << st.counted_below_z << std::endl;
+  f << "# Absorbed: " << st.absorbed << std::endl;
+  f << "# Suspended: " << st.suspended << std::endl;
+  f << "# Wall hits: " << st.wall_hits << std::endl;
+  f << "# Port fraction: " << fraction << std::endl;
+}
+
 }  // namespace rootMacros
 
 }  // namespace isxhost

@@ -56,6 +56,7 @@ struct RunOptions {
   int order_orders = 512;          // orderHist --orders: orders 0 .. n - 1 of the bounce-order histograms
   int order_dz = 8;                // orderHist --dz: dz bins per order of the port's rays
   std::string order_reflectances;  // orderHist --reflectances a,b,...: wall reflectances to reweight the port fraction to
+  std::vector<std::string> patches;   // wallPatches --patch ax,ay,az,half_angle_deg,rho (repeatable, in order: the first cap wins)
   bool quiet = false;              // env ISX_QUIET
   int flush_rows = 0;              // env ISX_FLUSH_ROWS: theta rows per launch of the per-position sweep, written and flushed
                                    // before the next launch starts (0 = as many as hold ~4e9 rays: one launch for the reference's n)
@@ -185,6 +186,11 @@ void lightField();
 // dz_0 .. dz_{n_dz-1}) with the five counters in the footer; with --reflectances a,b,... also order_reweight.csv
 // (rho,fraction,sigma: isx_order_reweight, the port fraction at other wall reflectances from this one trace)
 void orderHist();
+// the same sphere with caps of its inner wall at a reflectance of their own (--patch ax,ay,az,half_angle_deg,rho, repeatable;
+// isx_wall_patch_cap makes each) through isx_wall_patches: wall_patches.csv, one row per class (class,arrivals,absorbed,
+// arrivals_per_sr -- per steradian of the cap as given, seen from the centre; empty for the two classes that are no cap) with
+// the census and the port fraction in the footer
+void wallPatches();
 }  // namespace rootMacros
 
 }  // namespace isxhost

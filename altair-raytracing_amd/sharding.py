@@ -195,3 +195,30 @@ def order_hist_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, firs
         counts = buf[nh + nd:nh + nd + nc]
         census = buf[nh + nd + nc:]
     return (hist, dz, dict(zip(ORDER_COUNT_FIELDS, (int(x) for x in counts))), dict(zip(CENSUS_FIELDS, (int(x) for x in census))))
+
+
+def wall_patches_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, first_ray: int = 0, device=None):
+    """The wall patches (altair_raytracing_amd.wall_patches) ray-sharded: this rank's contiguous shard through
+    `trace(cfg, count, seed, spec, first) -> (arrivals, absorbed, stats)`, then ONE SUM all-reduce that carries the 2 (P + 2)
+    counters and the census.  Returns (arrivals, absorbed, census dict) -- identical on every rank."""
+    import torch
+    import torch.distributed as dist
+
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(), dist.get_world_size()
+    else:
+        rank, world = 0, 1
+    first, count = shard(n_total, rank, world)
+    arr, ab, st = trace(cfg, count, seed, spec, first_ray + first)
+    census = np.array([getattr(st, k) for k in CENSUS_FIELDS], dtype=np.int64)
+    if world > 1:
+        buf = torch.from_numpy(np.concatenate([arr.astype(np.int64), ab.astype(np.int64), census]))
+        if device is not None:
+            buf = buf.to(device)
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+        buf = buf.cpu().numpy()
+        nc = arr.size
+        arr = buf[:nc].astype(np.uint64)
+        ab = buf[nc:2 * nc].astype(np.uint64)
+        census = buf[2 * nc:]
+    return arr, ab, dict(zip(CENSUS_FIELDS, (int(x) for x in census)))

@@ -521,6 +521,69 @@ int isx_order_reweight(const isx_config* cfg, const isx_order_hist_spec* spec, c
                        double* fraction, double* sigma);
 
 /*
+ * Wall patches: up to ISX_MAX_WALL_PATCHES spherical caps of the inner wall with a reflectance of their own -- a wall-mounted
+ * detector (reflectance 0: `absorbed` of its cap is its signal), a sample or a reference standard over a port, a patch of aged
+ * coating.  Unlike isx_order_reweight and isx_wall_map this CHANGES the ray histories: a ray that arrives on a patch is absorbed
+ * or re-emitted at the patch's reflectance.
+ *
+ * arrivals and absorbed have P + 2 entries, P = spec->n_patches: class k < P is patch k, class P the inner sphere outside every
+ * patch, class P + 1 the rim cone and the outer sphere.  For every mirror interaction the census counts in wall_hits, at the
+ * point q (the last point isx_trace_endstates would report if the ray ended there), in this order:
+ *
+ *       class = P + 1 if the surface is not the inner sphere, else the LOWEST k with
+ *               (q.x * axis[0] + q.y * axis[1]) + q.z * axis[2] >= min_dot      (IEEE double, left to right, no fma; axis and
+ *               min_dot are used as given, nothing is normalised), else P
+ *       arrivals[class] += 1
+ *       rho_eff = patch[class].reflectance for class < P, else cfg->reflectance
+ *       the interaction's word b survives iff b < rho_thr(rho_eff), rho_thr(rho) = ceil(rho * 2^32 - 0.5) clamped to [0, 2^32];
+ *               otherwise absorbed[class] += 1 and the ray ends ABSORBED
+ *       a surviving ray is re-emitted as the library re-emits at reflectance rho_eff: the azimuth's uniform is
+ *               (b + 1/2) / rho_thr(rho_eff); the interaction count and the bounce limit follow as always
+ *
+ * The random words, their layout and everything else of a ray's history are unchanged.  For every call: arrivals sums to
+ * stats.wall_hits, absorbed sums to stats.absorbed, stats.bin_increments == the sum of arrivals[k] over k < P.  With
+ * n_patches == 0, or every patch's reflectance equal to cfg->reflectance bit for bit, every other field of stats except
+ * t_kernel_ms is what isx_fluxmap reports for the same (cfg, n_rays, seed, first_ray).  The result does not depend on any
+ * isx_set_option switch nor on how a job is cut into calls.  The detector-grid fields and hit_line_mode of cfg are ignored.
+ *
+ * Scope: the pencil source, the Lambertian ROBAST border, explicit bounces.  Refused with ISX_ERR_BAD_CONFIG: n_patches outside
+ * 0..ISX_MAX_WALL_PATCHES, struct_size != sizeof(isx_wall_patch_spec), an axis component or min_dot that is not finite, a
+ * reflectance that is NaN or outside [0, 1], cfg->source_model != ISX_SOURCE_PENCIL, cfg->surface_model != ISX_SURFACE_ROBAST,
+ * cfg->lambertian == 0, cfg->trace_mode != ISX_TRACE_EXPLICIT; with ISX_ERR_BAD_ARG: a NULL cfg, spec, arrivals or absorbed.
+ * Both are answered whether or not a device is present.
+ */
+#define ISX_MAX_WALL_PATCHES 8
+typedef struct isx_wall_patch {
+  double axis[3];            /* the cap's axis (isx_wall_patch_cap: a unit vector) */
+  double min_dot;            /* a point q of the inner sphere lies in the cap iff q . axis >= min_dot */
+  double reflectance;        /* in [0, 1] */
+} isx_wall_patch;
+typedef struct isx_wall_patch_spec {
+  uint32_t struct_size;      /* sizeof(isx_wall_patch_spec), set by isx_default_wall_patch_spec(); a spec of another size is refused */
+  uint32_t reserved0;        /* 0 */
+  int32_t n_patches;         /* 0 .. ISX_MAX_WALL_PATCHES; where caps overlap the lowest index wins */
+  int32_t reserved1;         /* 0 */
+  isx_wall_patch patch[ISX_MAX_WALL_PATCHES];
+} isx_wall_patch_spec;
+
+/* n_patches 0.  No GPU needed. */
+void isx_default_wall_patch_spec(const isx_config* cfg, isx_wall_patch_spec* spec);
+/* Host only, no GPU needed: the cap of half-angle half_angle_deg (as seen from the sphere's centre) about dir --
+ * axis = dir / |dir|, min_dot = cfg->r_in * cos(half_angle_deg * pi / 180), reflectance as given.  ISX_ERR_BAD_ARG: a NULL
+ * argument; ISX_ERR_BAD_CONFIG: dir of zero or non-finite length, half_angle_deg not in [0, 180], a reflectance that is NaN or
+ * outside [0, 1]. */
+int isx_wall_patch_cap(const isx_config* cfg, const double dir[3], double half_angle_deg, double reflectance, isx_wall_patch* out);
+
+/* Blocking: arrivals[n_patches + 2], absorbed[n_patches + 2] (host, zeroed by the callee; stats may be NULL).  Without a HIP
+ * device: ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT (as isx_wall_map). */
+int isx_wall_patches(const isx_config* cfg, const isx_wall_patch_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                     uint64_t* arrivals, uint64_t* absorbed, isx_stats* stats);
+/* ACCUMULATES (+=) into two device-resident arrays of n_patches + 2 counters on the library's stream and returns after
+ * enqueueing; isx_sync() / isx_take_stats() as for isx_wall_map_device. */
+int isx_wall_patches_device(const isx_config* cfg, const isx_wall_patch_spec* spec, uint64_t n_rays, uint64_t seed,
+                            uint64_t first_ray, uint64_t* d_arrivals, uint64_t* d_absorbed);
+
+/*
  * Series driver (sweepSeries, fluxAtObserverOptimize.C:892-921 / fluxAtObserverFast.C:1641-1673):
  * n_cfg configurations sharing one detector grid, traced back to back on the device with ONE
  * host synchronisation; hits[n_cfg][n_theta*n_phi], stats[n_cfg] (t_kernel_ms = whole series).
