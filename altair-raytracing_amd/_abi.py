@@ -29,6 +29,9 @@ WALL_MAP_MAX_BINS, WALL_MAP_MAX_AXIS = 8192, 512   # ISX_WALL_MAP_MAX_BINS / ISX
 LIGHT_FIELD_MAX_BINS, LIGHT_FIELD_MAX_AXIS = 1 << 22, 1024   # ISX_LIGHT_FIELD_MAX_BINS / ISX_LIGHT_FIELD_MAX_AXIS
 ORDER_HIST_MAX_ORDERS, ORDER_HIST_MAX_WORDS, ORDER_HIST_MAX_DZ = 2048, 8192, 64   # ISX_ORDER_HIST_MAX_ORDERS / _MAX_WORDS, n_dz <= 64
 MAX_WALL_PATCHES = 8   # ISX_MAX_WALL_PATCHES
+INJECT_FLUX, INJECT_EXIT_MAPS, INJECT_LIGHT_FIELD = 0, 1, 2   # ISX_INJECT_*: the sink of isx_bin_injected_lines
+INJECT_UNIT_AUTO = -1                                          # ISX_INJECT_UNIT_AUTO (else 0: 256-line work units, 2: 64-line units)
+INJECT_MAX_LINES, INJECT_MAX_REGIONS = 1 << 20, 1024   # (the flux sink also wants |P| <= sqrt(3) cfg.box_half)
 
 # every symbol include/isx.h declares (tests check the .so exports exactly these)
 EXPORTS = [
@@ -39,7 +42,7 @@ EXPORTS = [
     "isx_fluxmap_series", "isx_disc_sweep_per_position", "isx_last_kernel_ms",
     "isx_default_exit_map_spec", "isx_exit_maps", "isx_exit_maps_device",
     "isx_default_wall_map_spec", "isx_wall_map", "isx_wall_map_device",
-    "isx_default_light_field_spec", "isx_light_field", "isx_light_field_device",
+    "isx_default_light_field_spec", "isx_light_field", "isx_light_field_device", "isx_bin_injected_lines",
     "isx_default_order_hist_spec", "isx_order_hist", "isx_order_hist_device", "isx_order_reweight",
     "isx_default_wall_patch_spec", "isx_wall_patch_cap", "isx_wall_patches", "isx_wall_patches_device",
 ]
@@ -229,6 +232,8 @@ def load():
     L.isx_default_light_field_spec.restype = None
     L.isx_light_field.argtypes = [P(Config), P(ExitMapSpec), u64, u64, u64, P(u64), P(LightFieldCounts), P(Stats)]
     L.isx_light_field_device.argtypes = [P(Config), P(ExitMapSpec), u64, u64, u64, C.c_void_p, C.c_void_p]
+    L.isx_bin_injected_lines.argtypes = [P(Config), i32, P(ExitMapSpec), P(dbl), u64, P(C.c_uint32), i32, i32, P(u64), P(u64), P(u64),
+                                         P(u64)]
     L.isx_default_order_hist_spec.argtypes = [P(Config), P(OrderHistSpec)]
     L.isx_default_order_hist_spec.restype = None
     L.isx_order_hist.argtypes = [P(Config), P(OrderHistSpec), u64, u64, u64, P(u64), P(u64), P(OrderHistCounts), P(Stats)]
@@ -469,6 +474,38 @@ def light_field_device(cfg, spec, n_rays, seed, first_ray, d_field_ptr, d_counts
     _chk(load().isx_light_field_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
                                        C.c_void_p(int(d_field_ptr) or None), C.c_void_p(int(d_counts_ptr) or None)),
          "isx_light_field_device")
+
+
+def bin_injected_lines(cfg, sink, P, V, spec=None, region_counts=None, unit=INJECT_UNIT_AUTO, into=None):
+    """The binning kernel of `sink` alone on the caller's exit lines (P[k], V[k]) (include/isx.h: isx_bin_injected_lines; parity
+    tests).  -> (out_a, out_b, counts, bin_increments): INJECT_FLUX hits[n_theta, n_phi], None, None; INJECT_EXIT_MAPS
+    dir_map[n_v, n_u], pos_map[n_y, n_x], counts[5]; INJECT_LIGHT_FIELD field[n_y, n_x, n_v, n_u], None, counts[4].
+    region_counts: lines per 1024-slot region of the workspace (None: full regions); into: (out_a, out_b, counts) of an earlier
+    call to accumulate into."""
+    lines = np.ascontiguousarray(np.concatenate([np.asarray(P, dtype=np.float64).reshape(-1, 3),
+                                                 np.asarray(V, dtype=np.float64).reshape(-1, 3)], axis=1))
+    n = lines.shape[0]
+    if sink == INJECT_FLUX:
+        shapes = ((cfg.n_theta, cfg.n_phi), None, 0)
+    elif sink == INJECT_EXIT_MAPS:
+        shapes = ((spec.n_v, spec.n_u), (spec.n_y, spec.n_x), 5)
+    else:
+        shapes = ((spec.n_y, spec.n_x, spec.n_v, spec.n_u), None, 4)
+    if into is not None:
+        a, b, k = into
+    else:
+        a = np.zeros(shapes[0], dtype=np.uint64)
+        b = np.zeros(shapes[1], dtype=np.uint64) if shapes[1] is not None else None
+        k = np.zeros(shapes[2], dtype=np.uint64) if shapes[2] else None
+    rc_arr = None if region_counts is None else np.ascontiguousarray(region_counts, dtype=np.uint32)
+    inc = C.c_uint64(0)
+    ptr = lambda x: _p(x, C.c_uint64) if x is not None and x.size else None
+    _chk(load().isx_bin_injected_lines(C.byref(cfg), int(sink), C.byref(spec) if spec is not None else None,
+                                       _p(lines, C.c_double) if n else None, n,
+                                       _p(rc_arr, C.c_uint32) if rc_arr is not None else None,
+                                       0 if rc_arr is None else rc_arr.size, int(unit), ptr(a), ptr(b), ptr(k), C.byref(inc)),
+         "isx_bin_injected_lines")
+    return a, b, k, int(inc.value)
 
 
 def default_order_hist_spec(cfg):

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <algorithm>
 #include <map>
+#include <new>
 #include <tuple>
 #include <vector>
 
@@ -867,10 +868,8 @@ int run_single(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
   return span(0, &t);
 }
 
-// workspace of the two-kernel pipeline for a chunk of `rays` rays traced by `waves` waves: every region but a wave's last is
-// closed with more than kRegion - 64 lines in it, and a launch cannot have more lines than rays (isx_kernels.hpp: kRegion)
-int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles) {
-  const size_t regions = (rays / (kRegion - 63) + waves + 1) * slot_doubles / 6 + 1;   // (capacity is counted in 6-double slots)
+// workspace `buf` of the two-kernel pipeline with room for `regions` regions of kRegion 6-double slots and their line counts
+int ensure_regions(size_t regions, int buf) {
   if (regions > S.cap_regions[buf]) {
     HIPCHK(hipStreamSynchronize(S.stream));
     if (S.stream2) HIPCHK(hipStreamSynchronize(S.stream2));
@@ -882,6 +881,11 @@ int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles) {
     S.cap_regions[buf] = regions;
   }
   return ISX_OK;
+}
+// ... for a chunk of `rays` rays traced by `waves` waves: every region but a wave's last is closed with more than kRegion - 64
+// lines in it, and a launch cannot have more lines than rays (isx_kernels.hpp: kRegion)
+int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles) {
+  return ensure_regions((rays / (kRegion - 63) + waves + 1) * slot_doubles / 6 + 1, buf);   // (capacity is counted in 6-double slots)
 }
 
 // ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_FIELD_PIPE and ROUTE_DISC_PIPE: a trace launch and a binning launch per chunk of at most pipe_chunk rays
@@ -1129,6 +1133,46 @@ int call_open(size_t bins) {
 }
 int zero_hist(size_t bins) { return hip_rc(hipMemsetAsync(S.d_hist, 0, bins * sizeof(unsigned long long), S.stream)); }
 int call_close(int rc, isx_stats* stats) { const int rc2 = collect_stats(stats); return rc ? rc : rc2; }
+
+// isx_bin_injected_lines: the binning kernel of plan `p` on `n` caller-supplied lines laid out as `counts` says (one entry per
+// region), through the pipeline's own workspace, queue words and launch helpers -- what run_pipeline's launch_pair does after its
+// trace kernel, with the host in the trace kernel's place.  The slots of a region that hold no line carry `loud`.
+int run_injected(const Plan& p, const DetGrid& d, const double* lines, uint64_t n, const std::vector<uint32_t>& counts,
+                 uint32_t pad, const double loud[6], unsigned long long* d_hist) {
+  const size_t regions = counts.size();
+  int rc = set_lds((const void*)p.bin, p.lds_bin); if (rc) return rc;
+  const int bres = blocks_per_cu(p.bin, p.bblock, p.lds_bin, p.bin_per_cu);
+  rc = ensure_regions(regions + 1, 0); if (rc) return rc;
+  std::vector<double> rec(regions * (size_t)kRegion * 6);
+  for (size_t s = 0; s < rec.size(); s += 6) std::memcpy(&rec[s], loud, 6 * sizeof(double));
+  uint64_t at = 0;
+  for (size_t r = 0; r < regions; ++r) {
+    if (counts[r]) std::memcpy(&rec[r * (size_t)kRegion * 6], lines + 6 * at, (size_t)counts[r] * 6 * sizeof(double));
+    at += counts[r];
+  }
+  if (at != n) return ISX_ERR_BAD_ARG;
+  // (blocking copies from pageable memory: whatever the stream held has completed first)
+  HIPCHK(hipStreamSynchronize(S.stream));
+  HIPCHK(hipMemcpy(S.d_rec[0], rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(S.d_rec_counts[0], counts.data(), regions * sizeof(uint32_t), hipMemcpyHostToDevice));
+  Work wk;
+  wk.seed = 0; wk.first = 0; wk.n = n; wk.hist = d_hist; wk.stats = S.d_stats; wk.ctr = nullptr; wk.sub = 0; wk.pad = 0;
+  Work w;
+  rc = launch_work(wk, 0, n, pad, S.stream, &w); if (rc) return rc;                       // (the queue words, zeroed)
+  HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(w.ctr + Q_REGIONS), (int)regions, 1, S.stream));   // (what the trace kernel would have counted)
+  DetGrid db = d;
+  if (p.route == ROUTE_FIELD_PIPE) db.nbins = p.bin_words;
+  db.rec_lines = S.d_rec[0]; db.rec_counts = S.d_rec_counts[0];
+  size_t t;
+  rc = mark(S.stream, &t); if (rc) return rc;
+  if (p.compat_lines) {
+    hipLaunchKernelGGL(isx_compat_lines_kernel, dim3(S.cu_count * 8), dim3(256), 0, S.stream, S.d_rec[0], S.d_rec_counts[0], w.ctr);
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(p.bin, dim3(bin_grid(p, n, w.pad, (uint64_t)regions, bres)), dim3(p.bblock), p.lds_bin, S.stream, db, w);
+  HIPCHK(hipGetLastError());
+  return span(2, &t);
+}
 
 }  // namespace
 
@@ -1675,6 +1719,114 @@ int isx_light_field(const isx_config* cfg, const isx_exit_map_spec* spec, uint64
     counts->binned = k[0]; counts->pos_outside = k[1]; counts->dir_outside = k[2]; counts->upward = k[3];
   }
   return rc;
+}
+
+static int bin_injected_lines(const isx_config* cfg, int32_t sink, const isx_exit_map_spec* spec, const double* lines, uint64_t n,
+                           const uint32_t* region_counts, int32_t n_regions, int32_t unit, uint64_t* out_a, uint64_t* out_b,
+                           uint64_t* counts, uint64_t* bin_increments) {
+  // ---- what needs no device (isx.h: the refusals)
+  if (!cfg || (n && !lines)) return ISX_ERR_BAD_ARG;
+  if (sink != ISX_INJECT_FLUX && sink != ISX_INJECT_EXIT_MAPS && sink != ISX_INJECT_LIGHT_FIELD) return ISX_ERR_BAD_ARG;
+  if (unit != ISX_INJECT_UNIT_AUTO && unit != 0 && unit != 2) return ISX_ERR_BAD_ARG;
+  if (n > ISX_INJECT_MAX_LINES) return ISX_ERR_TOO_LARGE;
+  if (!config_abi_ok(cfg)) return ISX_ERR_BAD_CONFIG;
+  std::vector<uint32_t> layout;
+  if (region_counts) {
+    if (n_regions < 1 || n_regions > ISX_INJECT_MAX_REGIONS) return ISX_ERR_BAD_ARG;
+    uint64_t sum = 0;
+    for (int32_t r = 0; r < n_regions; ++r) {
+      if (region_counts[r] > kRegion) return ISX_ERR_BAD_ARG;
+      sum += region_counts[r];
+    }
+    if (sum != n) return ISX_ERR_BAD_ARG;
+    layout.assign(region_counts, region_counts + n_regions);
+  } else {
+    if (n_regions != 0) return ISX_ERR_BAD_ARG;
+    for (uint64_t left = n; left > 0; left -= layout.back()) layout.push_back((uint32_t)std::min<uint64_t>(left, kRegion));
+  }
+  size_t na = 0, nb = 0, nc = 0;   // words of out_a, out_b, counts
+  int rc;
+  {
+    Geom g;
+    rc = prepare_geom(cfg, &g);   // (the geometry is not used, but a config the public calls refuse is refused here too)
+    if (rc) return rc;
+  }
+  if (sink == ISX_INJECT_FLUX) {
+    rc = check_grid(cfg);
+    if (rc) return rc;
+    if (!out_a) return ISX_ERR_BAD_ARG;
+    na = (size_t)cfg->n_theta * cfg->n_phi;
+    for (uint64_t i = 0; i < n; ++i) {
+      const double* l = lines + 6 * i;
+      for (int k = 0; k < 6; ++k) if (!std::isfinite(l[k])) return ISX_ERR_BAD_ARG;
+      const double p2 = l[0] * l[0] + l[1] * l[1] + l[2] * l[2];
+      if (p2 > 3.0 * cfg->box_half * cfg->box_half) return ISX_ERR_BAD_ARG;   // (beyond the world box: no traced ray ends there)
+      const double vn = std::sqrt(l[3] * l[3] + l[4] * l[4] + l[5] * l[5]);
+      if (!(std::fabs(vn - 1.0) <= 1e-12)) return ISX_ERR_BAD_ARG;
+    }
+  } else {
+    if (!spec || !counts) return ISX_ERR_BAD_ARG;
+    if (sink == ISX_INJECT_EXIT_MAPS) {
+      rc = check_exit_spec(spec);
+      if (rc) return rc;
+      na = (size_t)spec->n_u * spec->n_v; nb = (size_t)spec->n_x * spec->n_y; nc = 5;
+      if ((na && !out_a) || (nb && !out_b)) return ISX_ERR_BAD_ARG;
+    } else {
+      rc = check_field_spec(spec);
+      if (rc) return rc;
+      na = (size_t)spec->n_x * spec->n_y * spec->n_u * spec->n_v; nc = 4;
+      if (!out_a) return ISX_ERR_BAD_ARG;
+    }
+  }
+  if (!S.init) return not_initialised();
+  if (bin_increments) *bin_increments = 0;
+  if (n == 0) return ISX_OK;
+  // ---- the call's accumulators in the pooled histogram (out_a | out_b | counts), its DetGrid and its plan as the sink's public
+  // call has them
+  const size_t words = na + nb + nc;
+  rc = call_open(words);
+  if (rc) return rc;
+  std::vector<unsigned long long> host(words);
+  isx_stats st;
+  std::memset(&st, 0, sizeof(st));
+  rc = zero_hist(words);
+  if (rc == ISX_OK) {
+    const int ksink = sink == ISX_INJECT_FLUX ? SINK_FLUX : sink == ISX_INJECT_EXIT_MAPS ? SINK_EXITMAP : SINK_LIGHTFIELD;
+    const ExitSink xm{spec, na ? S.d_hist : nullptr, nb ? S.d_hist + na : nullptr, S.d_hist + na + nb};
+    const FieldSink lf{spec, S.d_hist, S.d_hist + na};
+    DetGrid d;
+    size_t lds = 0;
+    rc = sink_grid(ksink, cfg, 0, nullptr, 0, 0, nullptr, nullptr, &xm, nullptr, &lf, nullptr, nullptr, d, lds);
+    if (rc == ISX_OK) {
+      const Plan p = plan_launch(ksink, cfg, d, lds, false, n);
+      const Route want = sink == ISX_INJECT_FLUX ? ROUTE_FLUX_PIPE : sink == ISX_INJECT_EXIT_MAPS ? ROUTE_EXIT_PIPE : ROUTE_FIELD_PIPE;
+      if (p.route != want || !p.bin || !p.binning || p.slot_doubles != 6) rc = ISX_ERR_BAD_CONFIG;   // (no binning kernel answers this call)
+      else {
+        const double loud[6] = {0.0, 0.0, cfg->exit_port_z + 0.5 * cfg->det_distance, 0.0, 0.0, -1.0};
+        const uint32_t pad = unit == ISX_INJECT_UNIT_AUTO ? (n < 1000000ull ? 2u : 0u) : (uint32_t)unit;
+        rc = run_injected(p, d, lines, n, layout, pad, loud, S.d_hist);
+      }
+    }
+  }
+  if (rc == ISX_OK) rc = copy_out(host.data(), S.d_hist, words * sizeof(unsigned long long));
+  rc = call_close(rc, &st);
+  if (rc) return rc;
+  for (size_t k = 0; k < na; ++k) out_a[k] += host[k];
+  for (size_t k = 0; k < nb; ++k) out_b[k] += host[na + k];
+  for (size_t k = 0; k < nc; ++k) counts[k] += host[na + nb + k];
+  if (bin_increments) *bin_increments = st.bin_increments;
+  return ISX_OK;
+}
+
+int isx_bin_injected_lines(const isx_config* cfg, int32_t sink, const isx_exit_map_spec* spec, const double* lines, uint64_t n,
+                           const uint32_t* region_counts, int32_t n_regions, int32_t unit, uint64_t* out_a, uint64_t* out_b,
+                           uint64_t* counts, uint64_t* bin_increments) {
+  // (the staging copies are std::vectors: no exception crosses the ABI)
+  try {
+    return bin_injected_lines(cfg, sink, spec, lines, n, region_counts, n_regions, unit, out_a, out_b, counts, bin_increments);
+  } catch (const std::bad_alloc&) {
+    return ISX_ERR_TOO_LARGE;
+  }
 }
 
 void isx_default_order_hist_spec(const isx_config* cfg, isx_order_hist_spec* spec) {

@@ -1317,7 +1317,10 @@ __device__ __forceinline__ void cap_rows(float fx, float fy, float a, float cosw
   ilo = 0; cnt = 0;
   const float b = fmaf(c32, fx, s32 * fy);
   const float rho2 = fmaf(a, a, b * b);
-  if (!(rho2 > 1e-12f)) return;
+  // (the cap's axis is perpendicular to the meridian's plane: every point of the meridian is at 90 degrees from it, to 1e-6 --
+  //  outside a cap narrower than a hemisphere, which is every cap of prep_cols; inside one that is wider, which the cap about h^ of
+  //  a grazing line can be, prep_band: every row.  1e-5: that 1e-6 and the 4e-6 of slack in cos w)
+  if (!(rho2 > 1e-12f)) { if (cosw < 1e-5f) cnt = n_theta; return; }
   const float x = cosw * __builtin_amdgcn_rsqf(rho2);
   if (x > 1.0f) return;                                               // the column misses the cap
   // (a cap wider than a quarter turn in the meridian's plane -- only the cap about h^ of a grazing line can be, prep_band: the caps

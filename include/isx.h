@@ -443,6 +443,54 @@ int isx_light_field_device(const isx_config* cfg, const isx_exit_map_spec* spec,
                            uint64_t first_ray, uint64_t* d_field, uint64_t* d_counts /*[4]*/);
 
 /*
+ * The binning kernels alone, on exit lines the CALLER supplies (parity tests: lines placed on a detector's rim, on the parallel
+ * cut, on the thresholds of the cull -- what traced rays do not reach in a test-sized run).  No ray is traced: the lines are
+ * laid into the pipeline's workspace exactly as a trace kernel leaves them -- regions of 1024 slots, a line count per region --
+ * and the binning kernel that the launch plan selects for (cfg, sink, the current isx_set_option switches) runs on them, with the
+ * plan's workgroup shape, LDS and grid ("bin_cols", "bin_slots", "bin_block", "bin_blocks_per_cu", "grid_blocks", "lf_global" keep
+ * their meaning); with ISX_HITLINE_ORIGIN_COMPAT and the flux sink the pipeline's line-rewriting kernel runs first.
+ *
+ *   sink  ISX_INJECT_FLUX         hits of isx_fluxmap:      out_a = hits[n_theta * n_phi], out_b and counts unused (may be NULL)
+ *         ISX_INJECT_EXIT_MAPS    maps of isx_exit_maps:    out_a = dir_map[n_v * n_u], out_b = pos_map[n_y * n_x] (NULL for a map
+ *                                 that is not wanted), counts[5] in the order of isx_exit_map_counts
+ *         ISX_INJECT_LIGHT_FIELD  field of isx_light_field: out_a = field[n_y * n_x * n_v * n_u], counts[4] in the order of
+ *                                 isx_light_field_counts
+ *   spec  the isx_exit_map_spec of the latter two sinks (ignored, may be NULL, for the flux sink)
+ *   lines[n][6]  last point, direction.  Every line counts as "counted below z": no census is taken, cfg's geometry and source
+ *         are looked at only where the launch plan does
+ *   region_counts[n_regions]  how the lines are laid out: region r holds the next region_counts[r] lines (each 0..1024, their
+ *         sum n, n_regions 1..ISX_INJECT_MAX_REGIONS).  NULL with n_regions 0: full regions, the rest in the last.  The slots of a
+ *         region that hold no line are filled with one valid line straight down the axis through (0, 0, exit_port_z), which hits
+ *         every detector of the rows about the axis: a kernel that reads past a region's count shows up as extra counts
+ *   unit  ISX_INJECT_UNIT_AUTO: work units as the pipeline sizes them (64 lines below 1e6 lines, else 256); 0: 256 lines; 2: 64 lines
+ *
+ * out_a, out_b and counts are HOST arrays and ACCUMULATE (+=); *bin_increments (may be NULL) is set to what this call added.
+ * Blocking.  The result does not depend on the layout, the unit, the order of the lines or any switch.
+ *
+ * Domain of the flux sink: the flux binners are written for unit directions (the foot of the line is h = P - (P.V) V) and for
+ * points within the reach of a traced ray -- the world box, |P| <= sqrt(3) cfg->box_half (520 cm for the reference's 300) -- which
+ * is what the float32 margins of their cull are written and tested for; their loops must never see anything else.  Refused with ISX_ERR_BAD_ARG, before
+ * any device is asked for: a NULL cfg, lines (with n > 0) or accumulator the sink writes; a sink or unit that is none of the
+ * above; n above ISX_INJECT_MAX_LINES (ISX_ERR_TOO_LARGE, as is host memory that cannot be had for the staging copy); n_regions or a region count out of range, counts that do not sum to n;
+ * and for the flux sink any coordinate that is not finite, a direction with | |V| - 1 | > 1e-12, a point with
+ * |P|^2 > 3 cfg->box_half^2.  ISX_ERR_BAD_CONFIG, likewise before the device: a config or spec that the sink's public call
+ * refuses.  The exit-map and light-field sinks take any doubles: their contract defines NaN and inf as "outside".
+ * With a device, ISX_ERR_BAD_CONFIG as well where the plan has no binning kernel for the call: a flux grid whose histogram and
+ * tables do not fit the binning kernels' LDS (isx_fluxmap then runs the fused kernel), "pipeline" 0, "bin_mode" 0 or 2, a border /
+ * source combination that the pipeline does not serve.  The disc sweep's binning kernel (8-double segments) is not reachable here.
+ */
+#define ISX_INJECT_FLUX 0
+#define ISX_INJECT_EXIT_MAPS 1
+#define ISX_INJECT_LIGHT_FIELD 2
+#define ISX_INJECT_UNIT_AUTO (-1)
+/* (a diagnostic entry: the lines are staged once on the host and once on the device, 48 KiB per region -- 48 MiB at the most) */
+#define ISX_INJECT_MAX_LINES (1u << 20)
+#define ISX_INJECT_MAX_REGIONS 1024
+int isx_bin_injected_lines(const isx_config* cfg, int32_t sink, const isx_exit_map_spec* spec, const double* lines /*[n][6]*/,
+                           uint64_t n, const uint32_t* region_counts, int32_t n_regions, int32_t unit, uint64_t* out_a,
+                           uint64_t* out_b, uint64_t* counts, uint64_t* bin_increments);
+
+/*
  * Bounce-order histograms: how long the light stayed in the sphere before it ended.  A ray that ends after k mirror
  * interactions survived k absorption tests, so the histories traced at reflectance rho0 = cfg->reflectance are the histories at
  * any rho <= rho0 with weight (rho / rho0)^k: one trace gives the port throughput along a whole reflectance curve

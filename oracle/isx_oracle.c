@@ -772,17 +772,22 @@ static double now_ms(void) {
   return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
 }
 
+/* ISX_HITLINE_ORIGIN_COMPAT: the line fluxAtObserverFast.C:1181-1201 effectively tested for a ray whose last point is p --
+ * secondLastPoint stays (0,0,0); dir = (last-0)/|last-0|; then the ARay constructor (:1285) normalises the direction once more */
+static inline void compat_line(const double p[3], double lp[3], double d[3]) {
+  double dx = p[0] - 0.0, dy = p[1] - 0.0, dz = p[2] - 0.0;
+  double mag = sqrt(dx * dx + dy * dy + dz * dz);
+  double ex = dx / mag, ey = dy / mag, ez = dz / mag;
+  double m2 = sqrt(ex * ex + ey * ey + ez * ez);
+  lp[0] = 0.0; lp[1] = 0.0; lp[2] = 0.0;
+  d[0] = ex / m2; d[1] = ey / m2; d[2] = ez / m2;
+}
+
 /* the line handed to Detector::checkIntersection */
 static inline void hit_line(const isxo_config* c, const endstate* es, double lp[3], double d[3]) {
   if (c->hit_line_mode == 1) {
-    /* fluxAtObserverFast.C:1181-1201: secondLastPoint stays (0,0,0); dir = (last-0)/|last-0|; then the
-     * ARay constructor (:1285) normalises the direction once more */
-    double dx = es->p.x - 0.0, dy = es->p.y - 0.0, dz = es->p.z - 0.0;
-    double mag = sqrt(dx * dx + dy * dy + dz * dz);
-    double ex = dx / mag, ey = dy / mag, ez = dz / mag;
-    double m2 = sqrt(ex * ex + ey * ey + ez * ez);
-    lp[0] = 0.0; lp[1] = 0.0; lp[2] = 0.0;
-    d[0] = ex / m2; d[1] = ey / m2; d[2] = ez / m2;
+    const double p[3] = { es->p.x, es->p.y, es->p.z };
+    compat_line(p, lp, d);
   } else {
     lp[0] = es->p.x; lp[1] = es->p.y; lp[2] = es->p.z;
     d[0] = es->v.x; d[1] = es->v.y; d[2] = es->v.z;
@@ -874,6 +879,43 @@ int isxo_fluxmap(const isxo_config* c, uint64_t n, uint64_t seed, uint64_t first
   }
   tot.t_kernel_ms = now_ms() - t0;
   if (stats) *stats = tot;
+  free(tab);
+  return 0;
+}
+
+/* The detector test alone: every line (last point, direction) against every bin of isxo_detector_table, in table order --
+ * what isxo_fluxmap does with the exit line of a counted ray, for lines the caller supplies (tests: lines placed on a detector's
+ * rim, on the parallel cut, ...).  hit_line_mode 1: the line is first rewritten as hit_line() rewrites an end state. */
+int isxo_bin_lines(const isxo_config* c, const double* lines, uint64_t n, uint64_t* hits, int nthreads) {
+  if (!c || !hits || (n && !lines)) return -3;
+  if (c->n_theta < 1 || c->n_phi < 1) return -2;
+  size_t nb = (size_t)c->n_theta * c->n_phi;
+  double* tab = (double*)malloc(nb * 6 * sizeof(double));
+  if (!tab) return -3;
+  isxo_detector_table(c, tab);
+  memset(hits, 0, nb * sizeof(uint64_t));
+#ifdef _OPENMP
+  if (nthreads > 0) omp_set_num_threads(nthreads);
+  else omp_set_num_threads(omp_get_num_procs());
+#endif
+#pragma omp parallel
+  {
+    uint64_t* h = (uint64_t*)calloc(nb, sizeof(uint64_t));
+#pragma omp for schedule(dynamic, 16)
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+      double lp[3], d[3];
+      if (c->hit_line_mode == 1) compat_line(lines + 6 * i, lp, d);
+      else {
+        lp[0] = lines[6 * i]; lp[1] = lines[6 * i + 1]; lp[2] = lines[6 * i + 2];
+        d[0] = lines[6 * i + 3]; d[1] = lines[6 * i + 4]; d[2] = lines[6 * i + 5];
+      }
+      for (size_t k = 0; k < nb; k++)
+        if (isxo_check_intersection(tab + 6 * k, c->det_diameter, lp, d)) h[k]++;
+    }
+#pragma omp critical
+    for (size_t k = 0; k < nb; k++) hits[k] += h[k];
+    free(h);
+  }
   free(tab);
   return 0;
 }

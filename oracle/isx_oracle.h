@@ -67,6 +67,11 @@ int isxo_trace_endstates(const isxo_config* cfg, uint64_t n_rays, uint64_t seed,
 int isxo_fluxmap(const isxo_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
                  uint64_t* hits, isxo_stats* stats, int nthreads);
 
+/* The detector test alone on caller-supplied lines[n][6] (last point, direction): isxo_check_intersection against every bin of
+ * isxo_detector_table, in table order; hit_line_mode 1 rewrites each line first as the flux map rewrites an end state.
+ * hits[n_theta*n_phi] zeroed then filled. nthreads<=0: all cores. */
+int isxo_bin_lines(const isxo_config* cfg, const double* lines, uint64_t n, uint64_t* hits, int nthreads);
+
 /* Per-position maps (fluxAtObserverOptimize.C:542-579; fold=2: fluxAtObserverFast.C:336-408). */
 int isxo_fluxmap_per_position(const isxo_config* cfg, uint64_t rays_per_position, int32_t fold, uint64_t first_group,
                               uint64_t n_groups, uint64_t seed, uint64_t first_ray, uint64_t* hits, isxo_stats* stats,

@@ -41,6 +41,8 @@ def cap_rows(fx, fy, a, cosw, c32, s32, inv_dth, n_theta):
     hi = np.minimum(np.floor(thi * inv_dth - f32(0.5) + f32(1e-3)).astype(int), n_theta - 1)
     cnt = np.where(ok & (hi >= lo), hi - lo + 1, 0)
     wide = ok0 & (x < 0)                                              # wider than a quarter turn in the meridian's plane: every row
+    # ... and so is the meridian whose plane the cap's axis is perpendicular to, where the cap is wider than a hemisphere
+    wide = wide | (~(rho2 > f32(1e-12)) & (cosw < f32(1e-5)))
     cnt = np.where(wide, n_theta, cnt)
     return np.where((cnt > 0) & ~wide, lo, 0), cnt
 

@@ -82,6 +82,7 @@ def lib():
         L.isxo_check_intersection.argtypes = [P(dbl), dbl, P(dbl), P(dbl)]
         L.isxo_trace_endstates.argtypes = [P(Config), u64, u64, u64, P(i32), P(i32), P(dbl), P(dbl)]
         L.isxo_fluxmap.argtypes = [P(Config), u64, u64, u64, P(u64), P(Stats), C.c_int]
+        L.isxo_bin_lines.argtypes = [P(Config), P(dbl), u64, P(u64), C.c_int]
         L.isxo_disc_sweep.argtypes = [P(Config), P(dbl), i32, dbl, dbl, u64, u64, u64, P(u64), P(Stats), C.c_int]
         L.isxo_disc_sweep_per_position.argtypes = [P(Config), P(dbl), i32, dbl, dbl, u64, u64, u64, P(u64), P(Stats), C.c_int]
         L.isxo_exit_dz_hist.argtypes = [P(Config), u64, u64, u64, i32, P(u64), P(Stats), C.c_int]
@@ -185,6 +186,16 @@ def fluxmap(cfg, n, seed, first=0, nthreads=0):
     rc = lib().isxo_fluxmap(C.byref(cfg), n, seed, first, _p(hits, C.c_uint64), C.byref(st), nthreads)
     assert rc == 0, rc
     return hits.reshape(cfg.n_theta, cfg.n_phi), st
+
+
+def bin_lines(cfg, P, V, nthreads=0):
+    """-> hits[n_theta, n_phi]: isxo_check_intersection of the lines (P[k], V[k]) against every bin, in table order."""
+    lines = np.ascontiguousarray(np.concatenate([np.asarray(P, dtype=np.float64).reshape(-1, 3),
+                                                 np.asarray(V, dtype=np.float64).reshape(-1, 3)], axis=1))
+    hits = np.zeros(cfg.n_theta * cfg.n_phi, dtype=np.uint64)
+    rc = lib().isxo_bin_lines(C.byref(cfg), _p(lines, C.c_double), lines.shape[0], _p(hits, C.c_uint64), nthreads)
+    assert rc == 0, rc
+    return hits.reshape(cfg.n_theta, cfg.n_phi)
 
 
 def disc_sweep(cfg, centers_axes, radius, half_thick, n, seed, first=0, nthreads=0):
