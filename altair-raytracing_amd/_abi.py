@@ -29,6 +29,7 @@ WALL_MAP_MAX_BINS, WALL_MAP_MAX_AXIS = 8192, 512   # ISX_WALL_MAP_MAX_BINS / ISX
 LIGHT_FIELD_MAX_BINS, LIGHT_FIELD_MAX_AXIS = 1 << 22, 1024   # ISX_LIGHT_FIELD_MAX_BINS / ISX_LIGHT_FIELD_MAX_AXIS
 ORDER_HIST_MAX_ORDERS, ORDER_HIST_MAX_WORDS, ORDER_HIST_MAX_DZ = 2048, 8192, 64   # ISX_ORDER_HIST_MAX_ORDERS / _MAX_WORDS, n_dz <= 64
 MAX_WALL_PATCHES = 8   # ISX_MAX_WALL_PATCHES
+BEAM_UNIFORM, BEAM_LAMBERT = 0, 1   # ISX_BEAM_UNIFORM / ISX_BEAM_LAMBERT
 INJECT_FLUX, INJECT_EXIT_MAPS, INJECT_LIGHT_FIELD = 0, 1, 2   # ISX_INJECT_*: the sink of isx_bin_injected_lines
 INJECT_UNIT_AUTO = -1                                          # ISX_INJECT_UNIT_AUTO (else 0: 256-line work units, 2: 64-line units)
 INJECT_MAX_LINES, INJECT_MAX_REGIONS = 1 << 20, 1024   # (the flux sink also wants |P| <= sqrt(3) cfg.box_half)
@@ -45,6 +46,7 @@ EXPORTS = [
     "isx_default_light_field_spec", "isx_light_field", "isx_light_field_device", "isx_bin_injected_lines",
     "isx_default_order_hist_spec", "isx_order_hist", "isx_order_hist_device", "isx_order_reweight",
     "isx_default_wall_patch_spec", "isx_wall_patch_cap", "isx_wall_patches", "isx_wall_patches_device",
+    "isx_default_beam_spec", "isx_beam_cone", "isx_beam_endstates", "isx_fluxmap_beam", "isx_fluxmap_beam_device",
 ]
 
 
@@ -184,6 +186,19 @@ class WallPatchSpec(C.Structure):
         return s
 
 
+class BeamSpec(C.Structure):
+    """isx_beam_spec (include/isx.h): the emitting disc, the frame (used as given), the cone and the angular law."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("origin", C.c_double * 3), ("axis", C.c_double * 3),
+                ("e1", C.c_double * 3), ("e2", C.c_double * 3), ("radius", C.c_double), ("cos_min", C.c_double),
+                ("angular_law", C.c_int32), ("reserved1", C.c_int32)]
+
+    def copy(self):
+        s = BeamSpec()
+        C.memmove(C.byref(s), C.byref(self), C.sizeof(BeamSpec))
+        return s
+
+
 _lib = None
 
 
@@ -245,6 +260,12 @@ def load():
     L.isx_wall_patch_cap.argtypes = [P(Config), P(dbl), dbl, dbl, P(WallPatch)]
     L.isx_wall_patches.argtypes = [P(Config), P(WallPatchSpec), u64, u64, u64, P(u64), P(u64), P(Stats)]
     L.isx_wall_patches_device.argtypes = [P(Config), P(WallPatchSpec), u64, u64, u64, C.c_void_p, C.c_void_p]
+    L.isx_default_beam_spec.argtypes = [P(Config), P(BeamSpec)]
+    L.isx_default_beam_spec.restype = None
+    L.isx_beam_cone.argtypes = [P(Config), P(dbl), P(dbl), dbl, dbl, i32, P(BeamSpec)]
+    L.isx_beam_endstates.argtypes = [P(Config), P(BeamSpec), u64, u64, u64, P(i32), P(i32), P(dbl), P(dbl), P(dbl), P(dbl)]
+    L.isx_fluxmap_beam.argtypes = [P(Config), P(BeamSpec), u64, u64, u64, P(u64), P(Stats)]
+    L.isx_fluxmap_beam_device.argtypes = [P(Config), P(BeamSpec), u64, u64, u64, C.c_void_p]
     _lib = L
     return L
 
@@ -612,6 +633,51 @@ def wall_patches_device(cfg, spec, n_rays, seed, first_ray, d_arrivals_ptr, d_ab
     _chk(load().isx_wall_patches_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
                                         C.c_void_p(int(d_arrivals_ptr or 0) or None), C.c_void_p(int(d_absorbed_ptr or 0) or None)),
          "isx_wall_patches_device")
+
+
+def default_beam_spec(cfg):
+    """The pencil of `cfg` as a beam: origin src, axis dir / |dir|, radius 0, cos_min 1 (no GPU needed)."""
+    s = BeamSpec()
+    load().isx_default_beam_spec(C.byref(cfg), C.byref(s))
+    return s
+
+
+def beam_cone(cfg, origin, direction, radius, half_angle_deg, law=BEAM_UNIFORM):
+    """-> BeamSpec: the disc of `radius` about `origin` emitting into the cone of `half_angle_deg` about `direction`
+    (include/isx.h: isx_beam_cone; host only)."""
+    o = (C.c_double * 3)(*[float(x) for x in origin])
+    d = (C.c_double * 3)(*[float(x) for x in direction])
+    out = BeamSpec()
+    _chk(load().isx_beam_cone(C.byref(cfg), o, d, float(radius), float(half_angle_deg), int(law), C.byref(out)), "isx_beam_cone")
+    return out
+
+
+def beam_endstates(cfg, spec, n, seed, first_ray=0):
+    """-> (status, n_points, last_point, direction, start_point, start_dir): trace_endstates for the beam, with every ray's
+    sampled start."""
+    n = int(n)
+    status = np.zeros(n, dtype=np.int32)
+    npts = np.zeros(n, dtype=np.int32)
+    lp, d, sp, sd = (np.zeros((n, 3), dtype=np.float64) for _ in range(4))
+    _chk(load().isx_beam_endstates(C.byref(cfg), C.byref(spec), n, int(seed), int(first_ray), _p(status, C.c_int32),
+                                   _p(npts, C.c_int32), _p(lp, C.c_double), _p(d, C.c_double), _p(sp, C.c_double),
+                                   _p(sd, C.c_double)), "isx_beam_endstates")
+    return status, npts, lp, d, sp, sd
+
+
+def fluxmap_beam(cfg, spec, n_rays, seed, first_ray=0):
+    """-> (hits[n_theta, n_phi] uint64, Stats): the flux map of the beam source `spec` (include/isx.h: isx_fluxmap_beam)."""
+    hits = np.zeros(max(cfg.n_theta, 0) * max(cfg.n_phi, 0), dtype=np.uint64)
+    st = Stats()
+    _chk(load().isx_fluxmap_beam(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray), _p(hits, C.c_uint64),
+                                 C.byref(st)), "isx_fluxmap_beam")
+    return hits.reshape(cfg.n_theta, cfg.n_phi), st
+
+
+def fluxmap_beam_device(cfg, spec, n_rays, seed, first_ray, d_hits_ptr):
+    """Enqueue on the library stream, accumulating into device memory at d_hits_ptr ([n_theta * n_phi] uint64)."""
+    _chk(load().isx_fluxmap_beam_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
+                                        C.c_void_p(int(d_hits_ptr or 0) or None)), "isx_fluxmap_beam_device")
 
 
 def fluxmap_series(cfgs, n_rays, seed, first_ray=0):

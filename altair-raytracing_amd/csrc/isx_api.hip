@@ -440,13 +440,73 @@ PatchTab patch_table(const isx_config& c, const isx_wall_patch_spec& s) {
 // LDS of the patch kernel's block behind the rings: the table and its 2 (P + 2) u32 counters
 size_t patch_lds() { return (sizeof(PatchTab) + 2 * (kMaxPatches + 2) * sizeof(uint32_t) + 15) & ~(size_t)15; }
 
+// isx.h: the limits of a beam spec and the scope of the call (the explicit Lambertian lean path, either hit line)
+int check_beam_call(const isx_config* c, const isx_beam_spec* s) {
+  if (!config_abi_ok(c) || s->struct_size != (uint32_t)sizeof(isx_beam_spec)) return ISX_ERR_BAD_CONFIG;
+  if (c->source_model != ISX_SOURCE_PENCIL || c->surface_model != ISX_SURFACE_ROBAST || c->lambertian == 0 ||
+      c->trace_mode != ISX_TRACE_EXPLICIT)
+    return ISX_ERR_BAD_CONFIG;
+  const double* vec[4] = {s->origin, s->axis, s->e1, s->e2};
+  for (int k = 0; k < 4; ++k)
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(vec[k][i])) return ISX_ERR_BAD_CONFIG;
+  if (!std::isfinite(s->radius) || !std::isfinite(s->cos_min) || s->radius < 0.0) return ISX_ERR_BAD_CONFIG;
+  if (s->angular_law != ISX_BEAM_UNIFORM && s->angular_law != ISX_BEAM_LAMBERT) return ISX_ERR_BAD_CONFIG;
+  if (s->cos_min > 1.0 || s->cos_min < (s->angular_law == ISX_BEAM_LAMBERT ? 0.0 : -1.0)) return ISX_ERR_BAD_CONFIG;
+  auto dot = [](const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+  for (int k = 1; k < 4; ++k) {
+    if (!(std::fabs(std::sqrt(dot(vec[k], vec[k])) - 1.0) <= 1e-12)) return ISX_ERR_BAD_CONFIG;
+    const double* o = vec[k == 3 ? 1 : k + 1];
+    if (!(std::fabs(dot(vec[k], o)) <= 1e-12)) return ISX_ERR_BAD_CONFIG;
+  }
+  // (the disc's centre strictly inside the inner sphere, every start point strictly inside the world box; a start outside the
+  //  inner sphere -- a disc that overhangs the wall -- takes the generic search, as a pencil there does)
+  const double ro = std::sqrt(dot(s->origin, s->origin));
+  if (!(ro * (1.0 + 1e-12) < c->r_in) || !((ro + s->radius) * (1.0 + 1e-12) < c->box_half)) return ISX_ERR_BAD_CONFIG;
+  return ISX_OK;
+}
+// the kernels' source of a checked spec
+// isx.h: cfg->src and cfg->dir are ignored -- the configuration the beam calls prepare has the spec's origin and axis in their place
+isx_config beam_config(const isx_config& c, const isx_beam_spec& s) {
+  isx_config b = c;
+  for (int i = 0; i < 3; ++i) { b.src[i] = s.origin[i]; b.dir[i] = s.axis[i]; }
+  return b;
+}
+BeamSrc beam_source(const isx_beam_spec& s) {
+  BeamSrc b;
+  std::memset(&b, 0, sizeof(b));
+  for (int i = 0; i < 3; ++i) { b.origin[i] = s.origin[i]; b.axis[i] = s.axis[i]; b.e1[i] = s.e1[i]; b.e2[i] = s.e2[i]; }
+  b.radius = s.radius; b.cos_min = s.cos_min; b.law = s.angular_law;
+  return b;
+}
+// LDS of the beam kernel's block behind the rings: the source and the tracer waves' parked starts
+size_t beam_lds(int tracers) { return kBeamSrcBytes + (size_t)tracers * kBeamParkBytes; }
+// isx_beam_cone's frame about `dir` (isx.h states the rule); false: dir has no length
+bool beam_frame(const double dir[3], double axis[3], double e1[3], double e2[3]) {
+  const double dx = dir[0], dy = dir[1], dz = dir[2];
+  const double mag = std::sqrt(dx * dx + dy * dy + dz * dz);   // (prepare_geom's expression for the pencil)
+  if (!(mag > 0) || !std::isfinite(mag)) return false;
+  axis[0] = dx / mag; axis[1] = dy / mag; axis[2] = dz / mag;
+  int k = 0;
+  for (int i = 1; i < 3; ++i)
+    if (std::fabs(axis[i]) < std::fabs(axis[k])) k = i;
+  double u[3];
+  for (int i = 0; i < 3; ++i) u[i] = (i == k ? 1.0 : 0.0) - axis[k] * axis[i];
+  const double mu = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+  for (int i = 0; i < 3; ++i) e1[i] = u[i] / mu;
+  const double w[3] = {axis[1] * e1[2] - axis[2] * e1[1], axis[2] * e1[0] - axis[0] * e1[2], axis[0] * e1[1] - axis[1] * e1[0]};
+  const double mw = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+  for (int i = 0; i < 3; ++i) e2[i] = w[i] / mw;
+  return true;
+}
+
 // LDS of a workgroup's histogram: 4 B per bin, 16-byte aligned
 size_t hist_lds(int nbins) { return ((size_t)nbins * 4 + 15) & ~(size_t)15; }
 
 // The DetGrid of a call's sink, checked, and the dynamic LDS of its fused kernel (histogram + tables, census, Geom, DetGrid).
 int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d_discs, double disc_r, double disc_h,
               const PerPos* pp, const LogSink* lg, const ExitSink* xm, const WallSink* wm, const FieldSink* lf, const OrderSink* oh,
-              const PatchSink* wp, DetGrid& d, size_t& lds) {
+              const PatchSink* wp, const isx_beam_spec* bs, DetGrid& d, size_t& lds) {
   std::memset(&d, 0, sizeof(d));
   d.portz = c->exit_port_z;
   d.hit_line_mode = c->hit_line_mode;
@@ -456,7 +516,9 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
     if (rc) return rc;
     rc = ensure_tables(c);
     if (rc) return rc;
+    if (bs && (rc = check_beam_call(c, bs))) return rc;
     d.n_theta = c->n_theta; d.n_phi = c->n_phi; d.nbins = c->n_theta * c->n_phi; d.bin_mode = S.bin_mode;
+    if (bs && S.bin_mode == 2) d.bin_mode = 1;   // (isx.h: the trace-only diagnostic does not apply to the beam)
     d.half_w2 = (c->det_diameter / 2) * (c->det_diameter / 2);
     d.rho_d = c->det_diameter / 2;
     d.R = c->det_distance;
@@ -580,6 +642,7 @@ enum Route { ROUTE_FUSED, ROUTE_ASSIST, ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_
 typedef void (*KernelFn)(const Geom, const DetGrid, const Work);
 typedef void (*BinFn)(const DetGrid, const Work);
 typedef void (*PatchFn)(const Geom, const DetGrid, const Work, const PatchTab);
+typedef void (*BeamFn)(const Geom, const DetGrid, const Work, const BeamSrc);
 struct Plan {
   Route route = ROUTE_FUSED;
   KernelFn fn = nullptr;        // the kernel (a pipeline's trace kernel)
@@ -600,6 +663,8 @@ struct Plan {
   PatchFn patch_fn = nullptr;   // SINK_PATCH: the kernel (it takes the patches as a fourth argument: patch_tab) instead of fn
   PatchTab patch_tab{};
   uint64_t launch_max = 0;      // ROUTE_FUSED / ROUTE_ASSIST: rays per launch (0: kLaunchMax)
+  BeamFn beam_fn = nullptr;     // isx_fluxmap_beam: the pipeline's trace kernel (it takes the source as a fourth argument: beam) instead of fn
+  BeamSrc beam{};
 };
 
 // workgroups of a launch of n rays: enough for p.rays_per_lane rays per tracer lane, no more than `per_cu` per CU
@@ -631,7 +696,7 @@ void trace_shape(Plan& p, Shape sh, bool assist, int per_cu) {
   p.assist = assist;
 }
 
-Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bool discs_in_aux, uint64_t n) {
+Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bool discs_in_aux, uint64_t n, bool beam = false) {
   enum { LAMBERT, LOBE, ROUGH } const border =
       c->surface_model == ISX_SURFACE_LOBE ? LOBE : c->lambertian ? LAMBERT : ROUGH;   // (ISX_SURFACE_ROBAST: Lambertian or rough-specular)
   const bool pencil = c->source_model == ISX_SOURCE_PENCIL;   // (else ISX_SOURCE_BRDF)
@@ -664,7 +729,16 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     trace_shape(p, assist ? small_shape(std::min(n, S.pipe_chunk), ablock) : Shape{S.trace_block, 4}, assist,
                 resident_unless(S.trace_blocks_per_cu));
   };
-  if (sink == SINK_FLUX && flux_served && S.pipeline && S.bin_mode != 0) {
+  // The beam source (isx_fluxmap_beam) has one route whatever the switches say: its assist-wave trace kernel (the call is refused
+  // outside the explicit Lambertian lean path: check_beam_call), the source behind the rings, and isx_fluxmap's binning kernels
+  // (bin_mode 0: the brute-force form of isx_bin_lines_kernel).
+  if (sink == SINK_FLUX && (beam || (flux_served && S.pipeline && S.bin_mode != 0))) {
+    if (beam) {
+      p.route = ROUTE_FLUX_PIPE;
+      p.beam_fn = isx_trace_assist_beam_kernel;
+      trace_shape(p, small_shape(std::min(n, S.pipe_chunk), S.assist_block), true, resident_unless(S.trace_blocks_per_cu));
+      p.lds += beam_lds(p.tracers);
+    } else
     pipe_trace(ROUTE_FLUX_PIPE);
     // The binning kernel keeps the histogram and the detector tables in LDS.  With slot queues (1024-thread workgroups: 61 KB of
     // queues next to the histogram) if the grid fits their 32-bit slot records and the LDS, and then with COLUMN slots (default
@@ -673,16 +747,16 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     const size_t tables = hist_lds(d.nbins) + (size_t)(4 * d.n_theta) * 8 + (size_t)(2 * d.n_phi) * sizeof(ColX) + sizeof(DetGrid) + 16;
     const size_t slots_lds = tables + (size_t)(2 * d.n_phi) * sizeof(ColP) + (size_t)(kBlock / 64) * kSlotWaveWords * 4;
     const size_t cols_lds = tables + (size_t)(d.n_theta + 4) * sizeof(RowX) + (size_t)(kBlock / 64) * kColWaveWords * 4;
-    const bool slots = S.bin_slots && S.bin_mode == 1 && d.n_theta <= 256 && d.n_phi <= 255 && slots_lds <= S.lds_limit;
+    const bool slots = S.bin_slots && d.bin_mode == 1 && d.n_theta <= 256 && d.n_phi <= 255 && slots_lds <= S.lds_limit;
     const bool cols = slots && S.bin_cols && cols_lds <= S.lds_limit;
     p.bin = cols ? isx_bin_cols_kernel : slots ? isx_bin_slots_kernel : isx_bin_lines_kernel;
     p.bblock = slots ? kBlock : S.bin_block;
     p.lds_bin = cols ? cols_lds : slots ? slots_lds : tables + (size_t)(p.bblock / 64) * 128 * 4;
     p.bin_per_cu = resident_unless(S.bin_blocks_per_cu);
-    p.compat_lines = compat && S.bin_mode != 2;
-    p.binning = S.bin_mode != 2;
-    p.overlap = S.overlap > 1 && S.bin_mode == 1 && n >= (uint64_t)S.overlap * 65536;
-    if (p.lds_bin <= S.lds_limit) return p;
+    p.compat_lines = compat && d.bin_mode != 2;
+    p.binning = d.bin_mode != 2;
+    p.overlap = S.overlap > 1 && d.bin_mode == 1 && n >= (uint64_t)S.overlap * 65536;
+    if (p.lds_bin <= S.lds_limit || beam) return p;   // (beam: enqueue refuses a binning kernel whose LDS does not fit)
     p = Plan();   // (a binning kernel whose LDS does not fit: the fused kernel below)
   }
 
@@ -890,10 +964,10 @@ int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles) {
 
 // ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_FIELD_PIPE and ROUTE_DISC_PIPE: a trace launch and a binning launch per chunk of at most pipe_chunk rays
 int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
-  int rc = set_lds((const void*)p.fn, p.lds);
+  int rc = set_lds(p.beam_fn ? (const void*)p.beam_fn : (const void*)p.fn, p.lds);
   if (rc == ISX_OK) rc = set_lds((const void*)p.bin, p.lds_bin);
   if (rc) return rc;
-  const int tres = blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
+  const int tres = p.beam_fn ? blocks_per_cu(p.beam_fn, p.block, p.lds, p.per_cu) : blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
   const int bres = blocks_per_cu(p.bin, p.bblock, p.lds_bin, p.bin_per_cu);
   // what the two kernels see: a flux map's trace kernel keeps no histogram; the disc sweep's kernels walk the discs in cluster order
   DetGrid dt = d, db = d;
@@ -918,7 +992,8 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     dt.rec_lines = db.rec_lines = S.d_rec[buf];
     dt.rec_counts = db.rec_counts = S.d_rec_counts[buf];
     const int tgrid = pick_grid(p, cnt, tres);
-    hipLaunchKernelGGL(p.fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w);
+    if (p.beam_fn) hipLaunchKernelGGL(p.beam_fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w, p.beam);
+    else hipLaunchKernelGGL(p.fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w);
     HIPCHK(hipGetLastError());
     size_t traced;
     if (t) r = span(1, t);
@@ -981,21 +1056,27 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
             int nbins_override, const double* d_discs, double disc_r, double disc_h, const PerPos* pp = nullptr,
             const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr, const ExitSink* xm = nullptr,
             const WallSink* wm = nullptr, const FieldSink* lf = nullptr, const OrderSink* oh = nullptr,
-            const PatchSink* wp = nullptr) {
+            const PatchSink* wp = nullptr, const isx_beam_spec* bs = nullptr) {
   Geom g;
+  isx_config cb;
+  if (bs && config_abi_ok(c) && bs->struct_size == (uint32_t)sizeof(isx_beam_spec)) { cb = beam_config(*c, *bs); c = &cb; }
   int rc = prepare_geom(c, &g);
   if (rc) return rc;
   if (n > ISX_MAX_RAYS_PER_CALL) return ISX_ERR_TOO_LARGE;
   if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;   // first + n (the exclusive end of the index range) must be representable
   DetGrid d;
   size_t lds = 0;
-  rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, xm, wm, lf, oh, wp, d, lds);
+  rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, xm, wm, lf, oh, wp, bs, d, lds);
   if (rc || n == 0) return rc;
   Work wk;
   wk.seed = seed; wk.first = first; wk.n = n; wk.hist = d_hist; wk.stats = d_stats ? d_stats : S.d_stats;
   wk.ctr = nullptr; wk.sub = 0; wk.pad = 0;
-  Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n);
+  Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n, bs != nullptr);
   if (sink == SINK_PATCH) p.patch_tab = patch_table(*c, *wp->spec);
+  if (bs) {
+    if (p.lds_bin > S.lds_limit) return ISX_ERR_BAD_CONFIG;   // (isx.h: a grid whose tables do not fit the binning kernels' LDS)
+    p.beam = beam_source(*bs);
+  }
   return p.route == ROUTE_FUSED || p.route == ROUTE_ASSIST ? run_single(p, g, d, wk) : run_pipeline(p, g, d, wk);
 }
 
@@ -1796,7 +1877,7 @@ static int bin_injected_lines(const isx_config* cfg, int32_t sink, const isx_exi
     const FieldSink lf{spec, S.d_hist, S.d_hist + na};
     DetGrid d;
     size_t lds = 0;
-    rc = sink_grid(ksink, cfg, 0, nullptr, 0, 0, nullptr, nullptr, &xm, nullptr, &lf, nullptr, nullptr, d, lds);
+    rc = sink_grid(ksink, cfg, 0, nullptr, 0, 0, nullptr, nullptr, &xm, nullptr, &lf, nullptr, nullptr, nullptr, d, lds);
     if (rc == ISX_OK) {
       const Plan p = plan_launch(ksink, cfg, d, lds, false, n);
       const Route want = sink == ISX_INJECT_FLUX ? ROUTE_FLUX_PIPE : sink == ISX_INJECT_EXIT_MAPS ? ROUTE_EXIT_PIPE : ROUTE_FIELD_PIPE;
@@ -1963,6 +2044,105 @@ int isx_wall_patches(const isx_config* cfg, const isx_wall_patch_spec* spec, uin
     std::memcpy(arrivals, h, nc * 8);
     std::memcpy(absorbed, h + nc, nc * 8);
   }
+  return rc;
+}
+
+void isx_default_beam_spec(const isx_config* cfg, isx_beam_spec* spec) {
+  if (!spec) return;
+  std::memset(spec, 0, sizeof(*spec));
+  spec->struct_size = (uint32_t)sizeof(isx_beam_spec);
+  spec->cos_min = 1.0;
+  spec->angular_law = ISX_BEAM_UNIFORM;
+  if (!cfg) return;
+  for (int k = 0; k < 3; ++k) spec->origin[k] = cfg->src[k];
+  if (!beam_frame(cfg->dir, spec->axis, spec->e1, spec->e2))
+    for (int k = 0; k < 3; ++k) spec->axis[k] = spec->e1[k] = spec->e2[k] = 0.0;
+}
+
+int isx_beam_cone(const isx_config* cfg, const double origin[3], const double dir[3], double radius, double half_angle_deg,
+                  int32_t law, isx_beam_spec* out) {
+  if (!cfg || !origin || !dir || !out) return ISX_ERR_BAD_ARG;
+  if (!config_abi_ok(cfg)) return ISX_ERR_BAD_CONFIG;
+  if (law != ISX_BEAM_UNIFORM && law != ISX_BEAM_LAMBERT) return ISX_ERR_BAD_CONFIG;
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(origin[k]) || !std::isfinite(dir[k])) return ISX_ERR_BAD_CONFIG;
+  if (!std::isfinite(radius) || radius < 0.0) return ISX_ERR_BAD_CONFIG;
+  if (!(half_angle_deg >= 0.0 && half_angle_deg <= (law == ISX_BEAM_LAMBERT ? 90.0 : 180.0))) return ISX_ERR_BAD_CONFIG;
+  isx_beam_spec s;
+  std::memset(&s, 0, sizeof(s));
+  s.struct_size = (uint32_t)sizeof(isx_beam_spec);
+  if (!beam_frame(dir, s.axis, s.e1, s.e2)) return ISX_ERR_BAD_CONFIG;
+  for (int k = 0; k < 3; ++k) s.origin[k] = origin[k];
+  s.radius = radius;
+  s.cos_min = half_angle_deg == 0.0 ? 1.0 : half_angle_deg == 90.0 ? 0.0 : half_angle_deg == 180.0 ? -1.0 :
+              std::cos(half_angle_deg * M_PI / 180.0);
+  s.angular_law = law;
+  *out = s;
+  return ISX_OK;
+}
+
+int isx_beam_endstates(const isx_config* cfg, const isx_beam_spec* spec, uint64_t n, uint64_t seed, uint64_t first, int32_t* status,
+                       int32_t* n_points, double* last_point, double* direction, double* start_point, double* start_dir) {
+  // (what needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one)
+  if (!cfg || !spec || !status || !n_points || !last_point || !direction) return ISX_ERR_BAD_ARG;
+  int rc = check_beam_call(cfg, spec);
+  if (rc) return rc;
+  if (!S.init) return not_initialised();
+  if (n == 0) return ISX_OK;
+  if (n > (1ull << 28)) return ISX_ERR_TOO_LARGE;
+  if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;
+  Geom g;
+  const isx_config cb = beam_config(*cfg, *spec);
+  rc = prepare_geom(&cb, &g);
+  if (rc) return rc;
+  const BeamSrc b = beam_source(*spec);
+  DevBuf<int32_t> b_st, b_np;
+  DevBuf<double> b_lp, b_dir, b_sp, b_sd;
+  HIPCHK(b_st.alloc(n)); HIPCHK(b_np.alloc(n)); HIPCHK(b_lp.alloc(n * 3)); HIPCHK(b_dir.alloc(n * 3));
+  if (start_point) HIPCHK(b_sp.alloc(n * 3));
+  if (start_dir) HIPCHK(b_sd.alloc(n * 3));
+  const int blk = 256;
+  const unsigned grid = (unsigned)((n + blk - 1) / blk);
+  hipLaunchKernelGGL(isx_beam_endstates_kernel, dim3(grid), dim3(blk), 0, S.stream, g, b, seed, first, n, b_st.p, b_np.p, b_lp.p,
+                     b_dir.p, b_sp.p, b_sd.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(status, b_st.p, n * 4, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipMemcpyAsync(n_points, b_np.p, n * 4, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipMemcpyAsync(last_point, b_lp.p, n * 24, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipMemcpyAsync(direction, b_dir.p, n * 24, hipMemcpyDeviceToHost, S.stream));
+  if (start_point) HIPCHK(hipMemcpyAsync(start_point, b_sp.p, n * 24, hipMemcpyDeviceToHost, S.stream));
+  if (start_dir) HIPCHK(hipMemcpyAsync(start_dir, b_sd.p, n * 24, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipStreamSynchronize(S.stream));
+  return ISX_OK;
+}
+
+int isx_fluxmap_beam_device(const isx_config* cfg, const isx_beam_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                            uint64_t* d_hits) {
+  if (!cfg || !spec || !d_hits) return ISX_ERR_BAD_ARG;
+  const int bad = check_beam_call(cfg, spec);
+  if (bad) return bad;
+  if (!S.init) return not_initialised();
+  return enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, (unsigned long long*)d_hits, 0, nullptr, 0, 0, nullptr, nullptr, nullptr,
+                 nullptr, nullptr, nullptr, nullptr, nullptr, spec);
+}
+
+int isx_fluxmap_beam(const isx_config* cfg, const isx_beam_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                     uint64_t* hits, isx_stats* stats) {
+  if (!cfg || !spec || !hits) return ISX_ERR_BAD_ARG;
+  int rc = check_beam_call(cfg, spec);
+  if (rc) return rc;
+  if (!S.init) return not_initialised();
+  rc = check_grid(cfg);
+  if (rc) return rc;
+  const size_t nb = (size_t)cfg->n_theta * cfg->n_phi, bytes = nb * sizeof(unsigned long long);
+  rc = call_open(nb);
+  if (rc) return rc;
+  rc = zero_hist(nb);
+  if (rc == ISX_OK) rc = enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, S.d_hist, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, spec);
+  if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK) fetch_result(hits, bytes);
   return rc;
 }
 

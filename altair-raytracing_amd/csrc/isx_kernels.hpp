@@ -2245,6 +2245,56 @@ __device__ __forceinline__ unsigned long long patch_flush(const DetGrid& d_arg, 
   return tid < np ? (unsigned long long)c : 0ull;
 }
 
+// ------------------------------------------------------------------ beam source (isx.h: isx_fluxmap_beam, isx_beam_endstates)
+// The source of a call as the kernels get it (a kernel argument of its own; the trace kernel copies it into the workgroup's LDS
+// behind the rings): the checked isx_beam_spec, field for field.  14 doubles + the law.
+struct BeamSrc {
+  double origin[3], axis[3], e1[3], e2[3];
+  double radius, cos_min;
+  int law, pad;
+};
+// LDS of the beam kernel's block behind the rings: the source, then per tracer wave the parked starts of 64 fresh rays
+constexpr size_t kBeamSrcBytes = (sizeof(BeamSrc) + 15) & ~(size_t)15;
+constexpr size_t kBeamParkBytes = 6 * 64 * sizeof(double);
+// The start of ray `ido` of the launch: isx.h's per-ray contract, operation for operation (IEEE double, left to right, no fma:
+// -ffp-contract=off; sqrt and / are the correctly rounded ones).  The words are block 0 of Philox stream 3 of the ray.  `b` is the
+// kernel argument (isx_beam_endstates_kernel) or the workgroup's LDS copy (assist_body<.., BEAM>); both kernels call this and
+// nothing else states the sampling.  The ray sits on no surface.
+template <class B>
+__device__ __forceinline__ void beam_start(const B& b, Ray& r, uint64_t seed, uint64_t id_base, uint32_t ido) {
+  r.ido = ido; r.j = 0; r.on = K_NONE; r.tgt = false; r.k = 0;
+  uint32_t w[4];
+  draw_block(seed, id_base + (uint64_t)ido, 0u, 3u, w);
+  const double cos_min = b.cos_min;
+  const double rr = b.radius * sqrt(u01(w[0]));
+  double s1, c1, s3, c3;
+  sincos2pi(u01(w[1]), s1, c1);
+  const double a = rr * c1, bb = rr * s1;
+  const double u2 = u01(w[2]);
+  double ct, st;
+  if (b.law == 1) {   // ISX_BEAM_LAMBERT
+    const double s2 = u2 * (1.0 - cos_min * cos_min);
+    st = sqrt(s2);
+    ct = sqrt(1.0 - s2);
+  } else {            // ISX_BEAM_UNIFORM
+    ct = 1.0 - u2 * (1.0 - cos_min);
+    st = sqrt(1.0 - ct * ct);
+  }
+  sincos2pi(u01(w[3]), s3, c3);
+  const double k1 = st * c3, k2 = st * s3;
+  double e1[3], e2[3];
+  e1[0] = b.e1[0]; e1[1] = b.e1[1]; e1[2] = b.e1[2];
+  e2[0] = b.e2[0]; e2[1] = b.e2[1]; e2[2] = b.e2[2];
+  r.p.x = (b.origin[0] + a * e1[0]) + bb * e2[0];
+  r.p.y = (b.origin[1] + a * e1[1]) + bb * e2[1];
+  r.p.z = (b.origin[2] + a * e1[2]) + bb * e2[2];
+  const double dx = (ct * b.axis[0] + k1 * e1[0]) + k2 * e2[0];
+  const double dy = (ct * b.axis[1] + k1 * e1[1]) + k2 * e2[1];
+  const double dz = (ct * b.axis[2] + k1 * e1[2]) + k2 * e2[2];
+  const double mag = sqrt((dx * dx + dy * dy) + dz * dz);
+  r.v.x = dx / mag; r.v.y = dy / mag; r.v.z = dz / mag;
+}
+
 // ------------------------------------------------------------------ persistent trace kernel, one per sink
 //   SINK_FLUX: 180x90 detector flux map (the headline path)
 //   SINK_DZ  : histogram of the exit direction's z component (distributionSphereDetectorSweep.C:54,91)
@@ -2856,11 +2906,20 @@ __device__ __forceinline__ void ray_unpack(const uint4& a, const uint4& b, const
 // selects the lane's (rho_thr, psi_k1, psi_k0), with which the unchanged interaction runs; rim and outer sphere are class P + 1 at
 // the wall's reflectance.  An absorbed ray adds one to its class's counter where it ends.  The table and the workgroup's u32
 // counters lie behind the rings.  Explicit Lambertian lean path only; no exit lines, no second kernel.
-template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false, bool ORDER = false, bool PATCH = false>
-__device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk, const PatchTab* tab_arg = nullptr) {
+// BEAM (isx_fluxmap_beam): a source of finite aperture and divergence instead of the pencil.  The tracer lane that takes a fresh
+// ray off the launch's queue samples its start (beam_start: at refill, never inside a bounce step) and does the ray's own first
+// segment on step 0 of the trip -- rule S1 with rin2 from the LDS geometry: the far root on the wall is a normal arrival with
+// PH_EVEN, anything else goes to the assist wave with K_NONE, as a pencil whose Geom::q0_ok is 0 does.  The workgroup's one-thread
+// evaluation of Geom::q0 is skipped; the source lies behind the rings.  Exit lines, chunks, workspace and the kernels that follow
+// are isx_trace_assist_kernel's.  Explicit Lambertian lean path only.
+template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false, bool ORDER = false, bool PATCH = false,
+          bool BEAM = false>
+__device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk, const PatchTab* tab_arg = nullptr,
+                                            const BeamSrc* beam_arg = nullptr) {
   constexpr bool LEAN = SURF == SURF_LAMBERT;
   static_assert(LEAN || (CH == 0 && !RESC), "the chord identity and the BRDF re-scatter pipeline are built for the Lambertian border");
   static_assert(!PATCH || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER), "wall patches: the explicit Lambertian lean path, no other sink");
+  static_assert(!BEAM || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && !PATCH), "beam source: the explicit Lambertian lean path, no other sink");
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned long long* sstat = reinterpret_cast<unsigned long long*>(smem);
   Geom* g_lds = reinterpret_cast<Geom*>(sstat + 8);
@@ -2886,17 +2945,33 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     if (tid == 65) *ptab = *tab_arg;
     if (tid < 2 * (n_patch + 2)) pcnt[tid] = 0u;
   }
+  // BEAM: the source
+  typedef __attribute__((address_space(3))) BeamSrc LdsBeam;
+  if constexpr (BEAM) {
+    if (tid == 65) *reinterpret_cast<BeamSrc*>(hist) = *beam_arg;
+  }
+  const volatile LdsBeam& beam = *(const volatile LdsBeam*)hist;
+  // ... and behind it, per tracer wave, the parked starts of 64 fresh rays: double[6][64] (kBeamParkBytes)
+  typedef __attribute__((address_space(3))) double LdsDouble;
+  const uint32_t beam_wave = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform: a scalar register)
+  volatile LdsDouble* park = (volatile LdsDouble*)(reinterpret_cast<unsigned char*>(hist) + kBeamSrcBytes) +
+                              (size_t)beam_wave * (6 * 64);
   if (tid < 8) sstat[tid] = 0ull;
   if (tid == 64) {
     *g_lds = g_arg;
-    const Hot h0 = make_hot(g_arg);
-    V3 s0, d0, q0;
-    s0.x = g_arg.src[0]; s0.y = g_arg.src[1]; s0.z = g_arg.src[2];
-    d0.x = g_arg.dir0[0]; d0.y = g_arg.dir0[1]; d0.z = g_arg.dir0[2];
-    q0 = s0;
-    const bool ok = next_hit_s1<true>(h0, g_arg, s0, d0, K_NONE, q0);
-    g_lds->q0[0] = q0.x; g_lds->q0[1] = q0.y; g_lds->q0[2] = q0.z;
-    g_lds->q0_ok = ok ? 1 : 0;
+    if constexpr (BEAM) {   // (fresh rays have no common first boundary)
+      g_lds->q0[0] = 0.0; g_lds->q0[1] = 0.0; g_lds->q0[2] = 0.0;
+      g_lds->q0_ok = 0;
+    } else {
+      const Hot h0 = make_hot(g_arg);
+      V3 s0, d0, q0;
+      s0.x = g_arg.src[0]; s0.y = g_arg.src[1]; s0.z = g_arg.src[2];
+      d0.x = g_arg.dir0[0]; d0.y = g_arg.dir0[1]; d0.z = g_arg.dir0[2];
+      q0 = s0;
+      const bool ok = next_hit_s1<true>(h0, g_arg, s0, d0, K_NONE, q0);
+      g_lds->q0[0] = q0.x; g_lds->q0[1] = q0.y; g_lds->q0[2] = q0.z;
+      g_lds->q0_ok = ok ? 1 : 0;
+    }
   }
   if (tid == 0) { *d_lds = d_arg; AssistQueues z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, (uint32_t)n_tracers}; *Q = z; }
   __syncthreads();
@@ -2915,6 +2990,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     // =============================================================== tracer waves
     constexpr uint32_t kDry = 0xffffffffu;
     uint32_t next = 0, end = 0, spins = 0, beat_seen = 0;
+    uint32_t park_base = 0, park_end = 0;   // BEAM: the wave's parked fresh rays are [park_base, park_end) of the launch
     bool drained = false;
     Ray r;
     ray_start(g, r, 0);
@@ -2975,8 +3051,44 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b64);
           if (bhi == 0u && b < n32) { next = b; end = n32 - b > want ? b + want : n32; }
           else next = kDry;
+          park_base = park_end = next;   // (BEAM: nothing of the new sub-range is parked yet)
         }
-        if (next < end) {
+        if constexpr (BEAM) {
+          // The source is paid per RAY, not per trip: the next 64 rays of the wave's sub-range are sampled by the whole wave at
+          // once -- beam_start and the ray's own first segment (rule S1, rin2 from the LDS geometry), one ray per lane -- and parked
+          // in the wave's LDS block; a lane that refills copies its ray from there.  A parked ray is its first wall point q with a
+          // NaN in the direction's x (the far root lies on the wall: step 0 lets it arrive there) or its start (p, v) (anything
+          // else: step 0 hands it over with K_NONE).  (Sampled where it is needed -- by the few lanes of a trip that refill -- the
+          // wave issued the whole sampling in nearly every trip: 1.31 of the pencil's trace time, docs/LOG.md section 15.5.)
+          while (next < end && dead) {
+            if (next == park_end) {
+              park_base = next; park_end = end - next > 64u ? next + 64u : end;
+              if (park_base + (uint32_t)lane < park_end) {
+                Ray t;
+                beam_start(beam, t, seed, first, park_base + (uint32_t)lane);
+                V3 q;
+                if (next_hit_s1<true>(h, g, t.p, t.v, K_NONE, q)) { t.p = q; t.v.x = __builtin_nan(""); }
+                park[0 * 64 + lane] = t.p.x; park[1 * 64 + lane] = t.p.y; park[2 * 64 + lane] = t.p.z;
+                park[3 * 64 + lane] = t.v.x; park[4 * 64 + lane] = t.v.y; park[5 * 64 + lane] = t.v.z;
+              }
+              __builtin_amdgcn_wave_barrier();
+            }
+            const uint32_t left = park_end - next;
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(dead >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dead, 0u));
+            if (!(run || hand) && rank < left) {
+              const uint32_t slot = next - park_base + rank;
+              r.ido = next + rank; r.j = 0; r.on = K_NONE; r.tgt = false; r.k = 0;
+              r.p.x = park[0 * 64 + slot]; r.p.y = park[1 * 64 + slot]; r.p.z = park[2 * 64 + slot];
+              r.v.x = park[3 * 64 + slot]; r.v.y = park[4 * 64 + slot]; r.v.z = park[5 * 64 + slot];
+              run = true;
+            }
+            __builtin_amdgcn_wave_barrier();
+            const uint32_t want = (uint32_t)__popcll(dead);
+            const uint32_t take = want < left ? want : left;
+            next += take; n_taken += take;
+            dead = __ballot(!(run || hand));
+          }
+        } else if (next < end) {
           const uint32_t left = end - next;
           const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(dead >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dead, 0u));
           if (!(run || hand) && rank < left) { ray_start(g, r, next + rank); run = true; }
@@ -3092,8 +3204,13 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         if (run) {
           const bool fresh = r.j == 0u && !r.scattered();   // (a ray that returns from the assist wave has interactions behind it)
           if (fresh) {
-            if (g.q0_ok) { q.x = g.q0[0]; q.y = g.q0[1]; q.z = g.q0[2]; arrived = true; first_strike = true; }
-            else { hand = true; run = false; }
+            if constexpr (BEAM) {   // parked with its first segment done: at its first wall point (NaN in v.x), or to be handed over
+              if (r.v.x != r.v.x) { q = r.p; arrived = true; }
+              else { hand = true; run = false; }
+            } else {
+              if (g.q0_ok) { q.x = g.q0[0]; q.y = g.q0[1]; q.z = g.q0[2]; arrived = true; first_strike = true; }
+              else { hand = true; run = false; }
+            }
           } else if (hot_search(q)) arrived = true;
           else { hand = true; run = false; }
         }
@@ -3459,7 +3576,11 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     atomicAdd(&sstat[0], (unsigned long long)n_taken);
   }
   __syncthreads();
-  if (tid == 0 && Q->failed) atomicAdd(&wk.stats[7], (unsigned long long)Q->failed);
+  // (BEAM: the thread index rebuilt from the wave's number -- a scalar -- and the lane's rank in the wave: kept from the kernel's
+  //  entry for these last lines it is the one register more than the parking of the fresh rays leaves, and went to scratch)
+  uint32_t tid_end = (uint32_t)tid;
+  if constexpr (BEAM) tid_end = beam_wave * 64u + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  if (tid_end == 0u && Q->failed) atomicAdd(&wk.stats[7], (unsigned long long)Q->failed);
   if (WALL) {   // one flush of the workgroup's map; binned = its increments
     const unsigned long long flushed = wall_flush(d_arg, hist, tid, nthr);
     if (flushed) atomicAdd(&sstat[5], flushed);
@@ -3477,6 +3598,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   }
   {
     uint32_t t2 = threadIdx.x;
+    if constexpr (BEAM) t2 = tid_end;
     asm volatile("" : "+v"(t2));
     if (t2 < 7u) {
       const unsigned long long c = sstat[t2];
@@ -3522,6 +3644,11 @@ isx_trace_assist_order_brdf_kernel(const Geom g, const DetGrid d, const Work wk)
 extern "C" __global__ void ISX_ASSIST_ATTR
 isx_trace_assist_patch_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab) {
   assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true>(g, d, wk, &tab);
+}
+// the beam source (isx_fluxmap_beam): isx_trace_assist_kernel with a sampled start per fresh ray; the source is a fourth argument
+extern "C" __global__ void ISX_ASSIST_ATTR
+isx_trace_assist_beam_kernel(const Geom g, const DetGrid d, const Work wk, const BeamSrc beam) {
+  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, false, true>(g, d, wk, nullptr, &beam);
 }
 // the other border models on the same pipeline (round 5; until then round 1's fused isx_trace_bin_full_kernel served them):
 // the cos^2 lobe of "nonLambertianFlux copy.C":31-70,188-221 and ROBAST's rough-specular border (EnableLambertian(false))
@@ -4262,6 +4389,29 @@ isx_endstates_kernel(const Geom g, uint64_t seed, uint64_t first, uint64_t n, in
   for (;;) {
     st = ray_step<false>(h, g, r, seed, first);
     if (st != 0 && h.source_model == 1 && !r.scattered()) { ray_rescatter(g, r, seed, first); st = 0; }
+    if (st != 0) break;
+  }
+  status[i] = st;
+  npts[i] = (int)r.j + 1 + (st == ST_EXITED ? 1 : 0);
+  lp[3 * i] = r.p.x; lp[3 * i + 1] = r.p.y; lp[3 * i + 2] = r.p.z;
+  dir[3 * i] = r.v.x; dir[3 * i + 1] = r.v.y; dir[3 * i + 2] = r.v.z;
+}
+
+// isx_beam_endstates: the same with a sampled start per ray (beam_start), which is reported as well (either array may be NULL)
+extern "C" __global__ void __launch_bounds__(256)
+isx_beam_endstates_kernel(const Geom g, const BeamSrc beam, uint64_t seed, uint64_t first, uint64_t n, int32_t* __restrict__ status,
+                          int32_t* __restrict__ npts, double* __restrict__ lp, double* __restrict__ dir, double* __restrict__ sp,
+                          double* __restrict__ sd) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Hot h = make_hot(g);
+  Ray r;
+  beam_start(beam, r, seed, first, (uint32_t)i);
+  if (sp) { sp[3 * i] = r.p.x; sp[3 * i + 1] = r.p.y; sp[3 * i + 2] = r.p.z; }
+  if (sd) { sd[3 * i] = r.v.x; sd[3 * i + 1] = r.v.y; sd[3 * i + 2] = r.v.z; }
+  int st;
+  for (;;) {
+    st = ray_step<false>(h, g, r, seed, first);
     if (st != 0) break;
   }
   status[i] = st;

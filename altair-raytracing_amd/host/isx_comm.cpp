@@ -764,4 +764,17 @@ int wall_patches_all(const isx_config* cfg, const isx_wall_patch_spec* spec, uin
   return rc;
 }
 
+int fluxmap_beam_all(const isx_config* cfg, const isx_beam_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                     uint64_t* hits, isx_stats* st) {
+  Comm& c = comm();
+  if (!c.active()) return isx_fluxmap_beam(cfg, spec, n_rays, seed, first_ray, hits, st);
+  uint64_t f, cnt;
+  c.shard(n_rays, f, cnt);
+  isx_stats local{};
+  int rc = isx_fluxmap_beam(cfg, spec, cnt, seed, first_ray + f, hits, &local);
+  rc = c.reduce(rc, hits, grid_bins(cfg), &local);
+  if (rc == ISX_OK && st) *st = local;
+  return rc;
+}
+
 }  // namespace isxhost

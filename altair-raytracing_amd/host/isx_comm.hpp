@@ -86,6 +86,9 @@ int order_hist_all(const isx_config* cfg, const isx_order_hist_spec* spec, uint6
 // the wall patches (isx_wall_patches): the 2 (P + 2) counters travel in the one collective of the call
 int wall_patches_all(const isx_config* cfg, const isx_wall_patch_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
                      uint64_t* arrivals, uint64_t* absorbed, isx_stats* st);
+// the beam-source flux map (isx_fluxmap_beam): contiguous ray ranges, histogram plus census in the one collective of the call
+int fluxmap_beam_all(const isx_config* cfg, const isx_beam_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                     uint64_t* hits, isx_stats* st);
 // the wall map (isx_wall_map): the map and the four counters travel in the one collective of the call
 int wall_map_all(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
                  uint64_t* wall_map, isx_wall_map_counts* counts, isx_stats* st);

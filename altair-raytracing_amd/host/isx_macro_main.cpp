@@ -51,6 +51,7 @@ int main(int argc, char** argv) {
                  "  lightField [--rays <n>] [--seed <s>] |\n"
                  "  orderHist [--rays <n>] [--seed <s>] [--orders <n>] [--dz <n>] [--reflectances <a,b,...>] |\n"
                  "  wallPatches [--rays <n>] [--seed <s>] [--patch <ax,ay,az,half_angle_deg,rho>]... |\n"
+                 "  beamFlux [--rays <n>] [--seed <s>] [--origin <x,y,z>] [--axis <x,y,z>] [--radius <r>] [--half-angle <deg>] [--law uniform|lambert] |\n"
                  "  distributionSphereDetectorSweep | --selftest-writer <file> | --unique <path> | --shard <n> | --analyze <csv>... | --analyze <folder> [average]\n";
     return 2;
   }
@@ -102,6 +103,20 @@ int main(int argc, char** argv) {
       ++i;
       continue;
     }
+    if ((!std::strcmp(argv[i], "--origin") || !std::strcmp(argv[i], "--axis") || !std::strcmp(argv[i], "--radius") ||
+         !std::strcmp(argv[i], "--half-angle") || !std::strcmp(argv[i], "--law")) && i + 1 < argc) {   // beamFlux
+      const std::string key = argv[i] + 2;
+      if (key == "origin") options().beam_origin = argv[i + 1];
+      else if (key == "axis") options().beam_axis = argv[i + 1];
+      else if (key == "radius" || key == "half-angle") {   // a number, the whole token
+        char* rest = nullptr;
+        const double v = std::strtod(argv[i + 1], &rest);
+        if (rest == argv[i + 1] || *rest != '\0') { std::cerr << "bad number for --" << key << ": " << argv[i + 1] << "\n"; return 2; }
+        (key == "radius" ? options().beam_radius : options().beam_half_angle) = v;
+      } else options().beam_law = argv[i + 1];
+      ++i;
+      continue;
+    }
     const char* eq = std::strchr(argv[i], '=');
     if (!eq) { std::cerr << "bad argument " << argv[i] << " (want key=value)\n"; return 2; }
     kv[std::string(argv[i], eq - argv[i])] = eq + 1;
@@ -127,6 +142,7 @@ int main(int argc, char** argv) {
   else if (entry == "lightField") rootMacros::lightField();
   else if (entry == "orderHist") rootMacros::orderHist();
   else if (entry == "wallPatches") rootMacros::wallPatches();
+  else if (entry == "beamFlux") rootMacros::beamFlux();
   else { std::cerr << "unknown entry point " << entry << "\n"; return 2; }
   const bool ok = ensure_device();  // false: the entry point printed its error and returned early
   comm().finalize();

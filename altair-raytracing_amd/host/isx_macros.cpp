@@ -1446,6 +1446,94 @@ void wallPatches() {
   f << "# Port fraction: " << fraction << std::endl;
 }
 
+// Flux map of the library's default sphere lit by a beam source (isx.h: isx_fluxmap_beam) instead of the pencil.
+void beamFlux() {
+  if (!ready_everywhere()) return;
+  isx_config c;
+  isx_default_config(&c);
+  const long n = pick_n(1000000);
+  // exactly three numbers, each the whole of its token ("1,x,0" and "1,,0" are errors, not other beams)
+  auto triple = [](const std::string& arg, double v[3]) {
+    int got = 0;
+    std::stringstream ss(arg);
+    std::string tok;
+    while (std::getline(ss, tok, ',')) {
+      char* rest = nullptr;
+      const double x = std::strtod(tok.c_str(), &rest);
+      if (got == 3 || rest == tok.c_str() || *rest != '\0') return false;
+      v[got++] = x;
+    }
+    return got == 3 && arg.back() != ',';
+  };
+  double origin[3] = {c.src[0], c.src[1], c.src[2]}, axis[3] = {c.dir[0], c.dir[1], c.dir[2]};
+  if ((!options().beam_origin.empty() && !triple(options().beam_origin, origin)) ||
+      (!options().beam_axis.empty() && !triple(options().beam_axis, axis))) {
+    err() << "Error: --origin and --axis want x,y,z" << std::endl;
+    return;
+  }
+  const std::string& law = options().beam_law;
+  if (law != "uniform" && law != "lambert") {
+    err() << "Error: --law wants uniform or lambert: " << law << std::endl;
+    return;
+  }
+  isx_beam_spec sp;
+  int rc = isx_beam_cone(&c, origin, axis, options().beam_radius, options().beam_half_angle,
+                         law == "lambert" ? ISX_BEAM_LAMBERT : ISX_BEAM_UNIFORM, &sp);
+  if (rc != ISX_OK) {
+    err() << "Error: isx_beam_cone: " << isx_strerror(rc) << std::endl;
+    return;
+  }
+  std::vector<uint64_t> hits((size_t)c.n_theta * c.n_phi);
+  isx_stats st;
+  const uint64_t first = take_rays((uint64_t)n);
+  rc = fluxmap_beam_all(&c, &sp, (uint64_t)n, options().seed, first, hits.data(), &st);
+  if (rc != ISX_OK) {
+    err() << "Error: isx_fluxmap_beam: " << isx_strerror(rc) << std::endl;
+    return;
+  }
+  std::cout << "Total rays exiting port: " << st.counted_below_z << " out of " << n << std::endl;
+  FluxMapMeta mm;
+  mm.title = "Flux Map Data (Beam Source)";
+  mm.n_label = "Number of rays";
+  mm.method_line = "Trace-Once (single trace, multiple detector positions)";
+  mm.n = n; mm.det_w = mm.det_h = c.det_diameter; mm.r_in = c.r_in; mm.r_out = c.r_out; mm.thetaMax = c.theta_max_deg;
+  mm.nTheta = c.n_theta; mm.nPhi = c.n_phi; mm.reflectance = c.reflectance; mm.roughness = c.roughness_rad; mm.maxReflections = c.max_points;
+  for (int k = 0; k < 3; ++k) { mm.src[k] = sp.origin[k]; mm.dir[k] = sp.axis[k]; }
+  // the flux maps' header with the beam's lines ahead of the column line
+  std::string head = fluxmap_header(mm, currentTimeString());
+  const std::string cols = "theta,phi,fraction\n";
+  if (head.size() < cols.size() || head.compare(head.size() - cols.size(), cols.size(), cols) != 0) {
+    err() << "Error: the flux-map header does not end with its column line" << std::endl;
+    return;
+  }
+  head.erase(head.size() - cols.size());
+  std::ofstream f(outputPath("beam_flux.csv"));
+  f << head;
+  {
+    std::ostringstream o;
+    o << std::setprecision(17);
+    o << "# Seed: " << options().seed << std::endl;
+    o << "# First ray: " << first << std::endl;
+    o << "# Beam origin (x,y,z): " << sp.origin[0] << "cm, " << sp.origin[1] << "cm, " << sp.origin[2] << "cm" << std::endl;
+    o << "# Beam axis (x,y,z): " << sp.axis[0] << ", " << sp.axis[1] << ", " << sp.axis[2] << std::endl;
+    o << "# Beam e1 (x,y,z): " << sp.e1[0] << ", " << sp.e1[1] << ", " << sp.e1[2] << std::endl;
+    o << "# Beam e2 (x,y,z): " << sp.e2[0] << ", " << sp.e2[1] << ", " << sp.e2[2] << std::endl;
+    o << "# Beam radius: " << sp.radius << "cm" << std::endl;
+    o << "# Beam half angle: " << options().beam_half_angle << " degrees, cos_min " << sp.cos_min << std::endl;
+    o << "# Beam angular law: " << law << std::endl;
+    f << o.str();
+  }
+  f << cols;
+  f << fluxmap_rows(hits.data(), n, c.n_theta, c.n_phi, 1);
+  f << "# Launched: " << st.launched << std::endl;
+  f << "# Exited: " << st.exited << std::endl;
+  f << "# Total rays exiting port: " << st.counted_below_z << " out of " << n << std::endl;
+  f << "# Absorbed: " << st.absorbed << std::endl;
+  f << "# Suspended: " << st.suspended << std::endl;
+  f << "# Wall hits: " << st.wall_hits << std::endl;
+  f << "# Detector hits: " << st.bin_increments << std::endl;
+}
+
 }  // namespace rootMacros
 
 }  // namespace isxhost

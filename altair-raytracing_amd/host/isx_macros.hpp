@@ -57,6 +57,9 @@ struct RunOptions {
   int order_dz = 8;                // orderHist --dz: dz bins per order of the port's rays
   std::string order_reflectances;  // orderHist --reflectances a,b,...: wall reflectances to reweight the port fraction to
   std::vector<std::string> patches;   // wallPatches --patch ax,ay,az,half_angle_deg,rho (repeatable, in order: the first cap wins)
+  // beamFlux --origin x,y,z --axis x,y,z --radius r --half-angle deg --law uniform|lambert (defaults: the pencil of the default config)
+  std::string beam_origin, beam_axis, beam_law = "uniform";
+  double beam_radius = 0.0, beam_half_angle = 0.0;
   bool quiet = false;              // env ISX_QUIET
   int flush_rows = 0;              // env ISX_FLUSH_ROWS: theta rows per launch of the per-position sweep, written and flushed
                                    // before the next launch starts (0 = as many as hold ~4e9 rays: one launch for the reference's n)
@@ -191,6 +194,9 @@ void orderHist();
 // arrivals_per_sr -- per steradian of the cap as given, seen from the centre; empty for the two classes that are no cap) with
 // the census and the port fraction in the footer
 void wallPatches();
+// the flux map of the default sphere lit by a beam source (--origin, --axis, --radius, --half-angle, --law; isx_beam_cone makes
+// the spec) through isx_fluxmap_beam: beam_flux.csv in the flux maps' format (theta,phi,fraction), the beam in the # metadata
+void beamFlux();
 }  // namespace rootMacros
 
 }  // namespace isxhost

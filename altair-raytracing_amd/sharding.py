@@ -222,3 +222,10 @@ def wall_patches_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, fi
         ab = buf[nc:2 * nc].astype(np.uint64)
         census = buf[2 * nc:]
     return arr, ab, dict(zip(CENSUS_FIELDS, (int(x) for x in census)))
+
+
+def fluxmap_beam_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, first_ray: int = 0, device=None):
+    """The beam-source flux map (altair_raytracing_amd.fluxmap_beam) ray-sharded: this rank's contiguous shard through
+    `trace(cfg, spec, count, seed, first) -> (hits, stats)`, then the flux map's ONE SUM all-reduce of histogram plus census.
+    Returns (hits[n_theta, n_phi] uint64, census dict) -- identical on every rank."""
+    return fluxmap_sharded(lambda c, count, s, first: trace(c, spec, count, s, first), cfg, n_total, seed, first_ray, device)

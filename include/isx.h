@@ -632,6 +632,90 @@ int isx_wall_patches_device(const isx_config* cfg, const isx_wall_patch_spec* sp
                             uint64_t first_ray, uint64_t* d_arrivals, uint64_t* d_absorbed);
 
 /*
+ * Beam source: a flux map whose rays start on a disc of finite radius and leave inside a cone -- a collimated beam of finite
+ * diameter (radius > 0, cos_min = 1), a fibre or an LED with a numerical aperture (ISX_BEAM_UNIFORM / ISX_BEAM_LAMBERT inside
+ * the cone of half-angle acos(cos_min)), a lamp inside the sphere (radius 0, cos_min = -1) -- instead of the pencil, whose rays
+ * all share one start point and one direction.  cfg->src and cfg->dir are ignored -- they need not even be a valid pencil (the
+ * library puts the spec's origin and axis in their place before it looks at cfg); everything else of cfg means what it means for
+ * isx_fluxmap.
+ *
+ * Per ray (index `ray` of stream `seed`), in IEEE double, every expression evaluated left to right as written, no fma; sqrt and
+ * / are the correctly rounded ones; sincos2pi(u) = (sin 2 pi u, cos 2 pi u) and u01(w) = (w + 1/2) 2^-32 are the library's own
+ * (isx_mathprobe ops 4 / 5; the oracle's isxo_sincos2pi / isxo_u01):
+ *
+ *       w[0..3] = block 0 of Philox4x32-10 stream 3 of the ray: counter (ray lo, ray hi, 0, 3), key (seed lo, seed hi)
+ *       u_i = u01(w[i])
+ *       rr = radius * sqrt(u_0);  (s1, c1) = sincos2pi(u_1);  a = rr * c1;  b = rr * s1
+ *       p.x = (origin[0] + a * e1[0]) + b * e2[0]                                  (p.y, p.z likewise with [1], [2])
+ *       ISX_BEAM_UNIFORM:  ct = 1.0 - u_2 * (1.0 - cos_min);  st = sqrt(1.0 - ct * ct)
+ *       ISX_BEAM_LAMBERT:  s2 = u_2 * (1.0 - cos_min * cos_min);  st = sqrt(s2);  ct = sqrt(1.0 - s2)
+ *       (s3, c3) = sincos2pi(u_3)
+ *       d.x = (ct * axis[0] + (st * c3) * e1[0]) + (st * s3) * e2[0]               (d.y, d.z likewise)
+ *       mag = sqrt((d.x * d.x + d.y * d.y) + d.z * d.z);  v = (d.x / mag, d.y / mag, d.z / mag)
+ *
+ * The ray starts at p along v, on no surface, and is traced from there exactly as a pencil ray is: Philox stream 0 of the ray
+ * for its interactions, the same words per interaction, the same bounce limit, the same census.  Stream 3 is used for nothing
+ * else.  With the spec of isx_default_beam_spec() on a configuration whose normalised dir is an exact unit vector (the default's
+ * (5, 0, 0)), p == src and v == dir / |dir| for every ray: the results are isx_fluxmap's / isx_trace_endstates', bit for bit.
+ *
+ * Scope: ISX_SOURCE_PENCIL (the source model of cfg is otherwise unused), ISX_SURFACE_ROBAST with `lambertian` set,
+ * ISX_TRACE_EXPLICIT, both hit-line modes.  Refused with ISX_ERR_BAD_CONFIG, whether or not a device is present: anything
+ * outside that scope; struct_size != sizeof(isx_beam_spec) (or a cfg of the wrong size); any field of origin, axis, e1, e2,
+ * radius, cos_min that is not finite; radius < 0; cos_min outside [-1, 1], or outside [0, 1] for ISX_BEAM_LAMBERT; an
+ * angular_law that is neither; (axis, e1, e2) not orthonormal to 1e-12 -- | sqrt(x . x) - 1 | <= 1e-12 for each of the three and
+ * | x . y | <= 1e-12 for each of the three pairs (plain products summed left to right); unless
+ * sqrt(origin . origin) * (1 + 1e-12) < cfg->r_in -- the disc's centre lies strictly inside the inner sphere -- and
+ * (sqrt(origin . origin) + radius) * (1 + 1e-12) < cfg->box_half -- every start point lies strictly inside the world box.  The
+ * disc MAY overhang the wall, on purpose: a ray that starts inside the inner sphere meets it from the inside (rule S1 of the first
+ * segment); one that starts outside it -- the part of a disc that reaches through the wall -- takes the general boundary search, as
+ * a pencil placed there does.  A source wholly inside the wall shell or outside the sphere is refused.  With
+ * ISX_ERR_BAD_ARG: a NULL pointer (start_point and start_dir of
+ * isx_beam_endstates excepted).  The axes are USED AS GIVEN, nothing is normalised or re-orthogonalised.
+ */
+#define ISX_BEAM_UNIFORM 0   /* directions uniform in solid angle inside the cone (fibre NA; cos_min = -1: isotropic lamp) */
+#define ISX_BEAM_LAMBERT 1   /* cosine-weighted inside the cone (flat emitter, LED die); cos_min >= 0 */
+typedef struct isx_beam_spec {
+  uint32_t struct_size;      /* sizeof(isx_beam_spec), set by isx_default_beam_spec() / isx_beam_cone() */
+  uint32_t reserved0;        /* 0 */
+  double origin[3];          /* centre of the emitting disc */
+  double axis[3], e1[3], e2[3]; /* beam axis and the disc's two in-plane axes: USED AS GIVEN */
+  double radius;             /* >= 0: start points uniform over the disc */
+  double cos_min;            /* cosine of the cone's half-angle */
+  int32_t angular_law;       /* ISX_BEAM_UNIFORM / ISX_BEAM_LAMBERT */
+  int32_t reserved1;         /* 0 */
+} isx_beam_spec;
+
+/* The pencil as a beam: origin = cfg->src, the frame of isx_beam_cone() about cfg->dir (axis = dir / |dir| as the library
+ * normalises the pencil's direction: mag = sqrt(dx*dx + dy*dy + dz*dz), three divisions), radius 0, cos_min 1, ISX_BEAM_UNIFORM.
+ * No GPU needed.  (A dir of zero length leaves a zero frame, which every call refuses.) */
+void isx_default_beam_spec(const isx_config* cfg, isx_beam_spec* spec);
+/* Host only, no GPU needed: the beam from the disc of `radius` about `origin` into the cone of half-angle half_angle_deg about
+ * dir.  axis = dir / |dir| (as above).  The frame: t = the coordinate axis k with the smallest |axis[k]| (the lowest k on a tie);
+ * u = t - axis[k] * axis;  e1 = u / |u|;  w = axis x e1;  e2 = w / |w| -- right-handed (e1 x e2 = axis), orthonormal to rounding.
+ * cos_min = cos(half_angle_deg * pi / 180), with 0 and 180 degrees mapped to exactly 1 and -1 (and 90 to exactly 0).
+ * ISX_ERR_BAD_ARG: a NULL argument; ISX_ERR_BAD_CONFIG: a cfg of the wrong size, origin or dir not finite, dir of zero length,
+ * radius not finite or < 0, half_angle_deg not in [0, 180] (ISX_BEAM_LAMBERT: [0, 90]), an unknown law.  Whether the beam lies
+ * inside the sphere is checked by the calls that trace it. */
+int isx_beam_cone(const isx_config* cfg, const double origin[3], const double dir[3], double radius, double half_angle_deg,
+                  int32_t law, isx_beam_spec* out);
+
+/* isx_trace_endstates for the beam, plus the sampled start of every ray: start_point / start_dir [n][3] (either may be NULL).
+ * Without a HIP device: ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT. */
+int isx_beam_endstates(const isx_config* cfg, const isx_beam_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                       int32_t* status, int32_t* n_points, double* last_point /*[n][3]*/, double* direction /*[n][3]*/,
+                       double* start_point /*[n][3]*/, double* start_dir /*[n][3]*/);
+/* isx_fluxmap / isx_fluxmap_device for the beam: hits [n_theta * n_phi], zeroed by the callee (the device form ACCUMULATES and
+ * returns after enqueueing; isx_sync() / isx_take_stats() as for isx_fluxmap_device).  One route whatever the switches say: the
+ * assist-wave trace kernel with the sampled start (isx_trace_assist_beam_kernel), then the binning kernels of isx_fluxmap
+ * ("pipeline" 0, "assist" 0 and "bin_mode" 2 do not apply; "bin_mode" 0 bins by brute force).  The result does not depend on any
+ * isx_set_option switch nor on how a job is cut into calls.  A detector grid whose tables do not fit the binning kernels' LDS
+ * is refused with ISX_ERR_BAD_CONFIG (the default 180 x 90 grid fits). */
+int isx_fluxmap_beam(const isx_config* cfg, const isx_beam_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                     uint64_t* hits, isx_stats* stats);
+int isx_fluxmap_beam_device(const isx_config* cfg, const isx_beam_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                            uint64_t* d_hits);
+
+/*
  * Series driver (sweepSeries, fluxAtObserverOptimize.C:892-921 / fluxAtObserverFast.C:1641-1673):
  * n_cfg configurations sharing one detector grid, traced back to back on the device with ONE
  * host synchronisation; hits[n_cfg][n_theta*n_phi], stats[n_cfg] (t_kernel_ms = whole series).
