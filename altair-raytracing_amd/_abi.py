@@ -38,7 +38,7 @@ INJECT_MAX_LINES, INJECT_MAX_REGIONS = 1 << 20, 1024   # (the flux sink also wan
 EXPORTS = [
     "isx_default_config", "isx_init", "isx_shutdown", "isx_strerror", "isx_last_hip_error", "isx_abi_version", "isx_stream_version",
     "isx_device_info", "isx_fluxmap", "isx_fluxmap_device", "isx_sync", "isx_take_stats", "isx_stream",
-    "isx_set_option", "isx_mathprobe", "isx_trace_endstates", "isx_disc_sweep", "isx_detector_table",
+    "isx_set_option", "isx_mathprobe", "isx_trace_endstates", "isx_fate_scan", "isx_fate_scan_launches", "isx_disc_sweep", "isx_detector_table",
     "isx_exit_dz_hist", "isx_fluxmap_per_position", "isx_trace_rays_detector", "isx_exit_directions",
     "isx_fluxmap_series", "isx_disc_sweep_per_position", "isx_last_kernel_ms",
     "isx_default_exit_map_spec", "isx_exit_maps", "isx_exit_maps_device",
@@ -226,6 +226,8 @@ def load():
     L.isx_set_option.argtypes = [C.c_char_p, i64]
     L.isx_mathprobe.argtypes = [C.c_int, P(dbl), P(dbl), P(dbl), P(dbl), i32]
     L.isx_trace_endstates.argtypes = [P(Config), u64, u64, u64, P(i32), P(i32), P(dbl), P(dbl)]
+    L.isx_fate_scan.argtypes = [P(Config), u64, u64, u64, P(i32), P(i32)]
+    L.isx_fate_scan_launches.argtypes = [P(u64)]
     L.isx_disc_sweep.argtypes = [P(Config), P(dbl), i32, dbl, dbl, u64, u64, u64, P(u64), P(Stats)]
     L.isx_disc_sweep_per_position.argtypes = [P(Config), P(dbl), i32, dbl, dbl, u64, u64, u64, P(u64), P(Stats)]
     L.isx_last_kernel_ms.argtypes = [P(dbl), P(dbl), P(dbl)]
@@ -338,6 +340,23 @@ def trace_endstates(cfg, n, seed, first_ray=0):
     _chk(load().isx_trace_endstates(C.byref(cfg), int(n), int(seed), int(first_ray), _p(status, C.c_int32),
                                     _p(npts, C.c_int32), _p(lp, C.c_double), _p(d, C.c_double)), "isx_trace_endstates")
     return status, npts, lp, d
+
+
+def fate_scan(cfg, n, seed, first_ray=0):
+    """-> (fate, order): the "fate_scan" rule per ray (include/isx.h: isx_fate_scan) -- fate 2: settled as absorbed at interaction
+    order; fate 0: left to the trace kernel, undecided at interaction order."""
+    fate = np.zeros(n, dtype=np.int32)
+    order = np.zeros(n, dtype=np.int32)
+    _chk(load().isx_fate_scan(C.byref(cfg), int(n), int(seed), int(first_ray), _p(fate, C.c_int32), _p(order, C.c_int32)),
+         "isx_fate_scan")
+    return fate, order
+
+
+def fate_scan_launches():
+    """chunks that took the fate scan since init() (include/isx.h: isx_fate_scan_launches)"""
+    n = C.c_uint64(0)
+    _chk(load().isx_fate_scan_launches(C.byref(n)), "isx_fate_scan_launches")
+    return int(n.value)
 
 
 def disc_sweep(cfg, centers_axes, radius, half_thick, n_rays, seed, first_ray=0):

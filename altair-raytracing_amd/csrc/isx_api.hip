@@ -45,6 +45,11 @@ struct State {
   double* d_rec[kRecBufs] = {nullptr, nullptr, nullptr};
   uint32_t* d_rec_counts[kRecBufs] = {nullptr, nullptr, nullptr};
   size_t cap_regions[kRecBufs] = {0, 0, 0};
+  // fate scan: the rays of a chunk that the scan leaves to the trace kernel, 4 B per ray of the largest chunk
+  uint32_t* d_list = nullptr;
+  size_t cap_list = 0;
+  unsigned long long fate_launches = 0;   // isx_fate_scan_kernel launches enqueued since isx_init (isx_fate_scan_launches)
+  int fate_scan = -1;                     // 0 off, 1 on wherever eligible, -1 (default) automatic: fate_scan_auto()
   // overlap > 1: a flux-map call is cut into that many chunks and the binning kernel of chunk k runs on a second stream
   // while the trace kernel of chunk k+1 runs on the first
   int overlap = 0;
@@ -129,7 +134,35 @@ RhoConsts reflectance_consts(double rho) {
   return k;
 }
 
-int prepare_geom(const isx_config* c, Geom* g) {
+// The fate scan's integer thresholds (isx_device.hpp: FateConsts; DESIGN.md section 4.2d has the bound behind MARG and SEP).
+//   W_leave = (1 - 2^-32 - zcut_in / r_in) 2^31: r_in sphere_z(wa) >= zcut_in  <=>  wa <= W_leave
+//   MARG = 2^16 words: the landing point's z differs from r_in sphere_z(wa) by at most 130 words over J_CAP bounces (worst-case bound, 500x under MARG); measured 9.5e-4
+//   SEP  = 2^17 words: consecutive words at least this far apart in z give |v| >= r_in SEP 2^-31 (6e-3 cm at the headline)
+// ok = the configuration is served: pencil source inside the ball whose first strike q0 (next_hit_s1<true>'s arithmetic in plain
+// operations -- the scan only needs it to a margin) lies on the mirror patch by more than MARG, Lambertian border, explicit bounces.
+constexpr uint32_t kFateMarg = 1u << 16, kFateSep = 1u << 17, kFateJCap = 1024u;
+FateConsts fate_consts(const isx_config* c, const Geom& g) {
+  FateConsts f{};
+  f.rho_thr = g.rho_thr; f.sep = kFateSep; f.j_cap = kFateJCap; f.limit = g.limit;
+  const double w_leave = (1.0 - 0x1.0p-32 - g.zcut_in / g.r_in) * 0x1.0p31 - (double)kFateMarg;
+  const double px = g.src[0], py = g.src[1], pz = g.src[2], vx = g.dir0[0], vy = g.dir0[1], vz = g.dir0[2];
+  const double b = px * vx + py * vy + pz * vz;
+  const double ci = (px * px + py * py + pz * pz) - g.rin2;
+  const double di = b * b - ci;
+  bool ok = c->source_model == ISX_SOURCE_PENCIL && c->surface_model == ISX_SURFACE_ROBAST && c->lambertian != 0 &&
+            c->trace_mode == ISX_TRACE_EXPLICIT && w_leave >= 0.0 && w_leave < 4294967296.0 && ci < -1e-9 * g.rin2 && di >= 0.0;
+  if (ok) {
+    f.w_leave = (uint32_t)std::floor(w_leave);
+    const double q0z = pz + (std::sqrt(di) - b) * vz;
+    const double wq = std::floor((1.0 - 0x1.0p-32 - q0z / g.r_in) * 0x1.0p31 + 0.5);
+    ok = wq >= 0.0 && wq <= (double)f.w_leave;
+    if (ok) f.w_q0 = (uint32_t)wq;
+  }
+  f.ok = ok ? 1 : 0;
+  return f;
+}
+
+int prepare_geom(const isx_config* c, Geom* g, FateConsts* fate = nullptr) {
   if (!config_abi_ok(c)) return ISX_ERR_BAD_CONFIG;
   if (!(c->r_in > 0) || !(c->r_out > c->r_in)) return ISX_ERR_BAD_CONFIG;
   if (!(c->theta_max_deg > 90.0) || !(c->theta_max_deg < 180.0)) return ISX_ERR_BAD_CONFIG;
@@ -172,6 +205,7 @@ int prepare_geom(const isx_config* c, Geom* g) {
   g->brdf_theta_scale = c->brdf[0] * M_PI / 6;
   const double sum = c->brdf[1] + c->brdf[2];
   g->brdf_spec = sum != 0 ? c->brdf[1] / sum : 0.0;
+  if (fate) *fate = fate_consts(c, *g);
   return ISX_OK;
 }
 
@@ -643,6 +677,7 @@ typedef void (*KernelFn)(const Geom, const DetGrid, const Work);
 typedef void (*BinFn)(const DetGrid, const Work);
 typedef void (*PatchFn)(const Geom, const DetGrid, const Work, const PatchTab);
 typedef void (*BeamFn)(const Geom, const DetGrid, const Work, const BeamSrc);
+typedef void (*ListFn)(const Geom, const DetGrid, const Work, const FateList);
 struct Plan {
   Route route = ROUTE_FUSED;
   KernelFn fn = nullptr;        // the kernel (a pipeline's trace kernel)
@@ -665,7 +700,23 @@ struct Plan {
   uint64_t launch_max = 0;      // ROUTE_FUSED / ROUTE_ASSIST: rays per launch (0: kLaunchMax)
   BeamFn beam_fn = nullptr;     // isx_fluxmap_beam: the pipeline's trace kernel (it takes the source as a fourth argument: beam) instead of fn
   BeamSrc beam{};
+  ListFn list_fn = nullptr;     // ROUTE_FLUX_PIPE behind the fate scan: isx_fate_scan_kernel, then this kernel on the rays it left, instead of fn
+  FateConsts fate{};
+  bool fate_auto = false;       // "fate_scan" -1: the rule's ray count is looked at per chunk (launch_pair)
 };
+
+// "fate_scan" = -1: where the scan pays (measured on MI355X, docs/LOG.md section 16.3).  A small launch is bound by its longest
+// ray, and a second launch in front of it only adds to that: trace + binning of the default configuration with the scan against
+// without, 1.18 / 1.05 ms at 1e6 rays, 2.29 / 2.21 at 5e6, 3.70 / 3.79 at 1e7, 6.65 / 7.01 at 2e7 -- break-even near 7e6.  And
+// the scan walks every interaction of every ray to settle the share (1 - rho) / ((1 - rho) + port area fraction) of them -- what
+// the wall absorbs of what ends at all: at 1e7 rays it gains at shares 0.87 and 0.57 and loses at 0.40 and below.
+constexpr uint64_t kFateMinRays = 10000000ull;
+constexpr double kFateMinShare = 0.50;
+bool fate_scan_auto(const isx_config* c, uint64_t chunk_rays) {
+  const double absorb = 1.0 - c->reflectance;
+  const double port = 0.5 * (1.0 + std::cos(c->theta_max_deg * M_PI / 180.0));
+  return chunk_rays >= kFateMinRays && absorb > 0.0 && absorb / (absorb + port) >= kFateMinShare;
+}
 
 // workgroups of a launch of n rays: enough for p.rays_per_lane rays per tracer lane, no more than `per_cu` per CU
 int pick_grid(const Plan& p, uint64_t n, int per_cu) {
@@ -696,7 +747,8 @@ void trace_shape(Plan& p, Shape sh, bool assist, int per_cu) {
   p.assist = assist;
 }
 
-Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bool discs_in_aux, uint64_t n, bool beam = false) {
+Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bool discs_in_aux, uint64_t n, bool beam = false,
+                 const FateConsts* fate = nullptr) {
   enum { LAMBERT, LOBE, ROUGH } const border =
       c->surface_model == ISX_SURFACE_LOBE ? LOBE : c->lambertian ? LAMBERT : ROUGH;   // (ISX_SURFACE_ROBAST: Lambertian or rough-specular)
   const bool pencil = c->source_model == ISX_SOURCE_PENCIL;   // (else ISX_SOURCE_BRDF)
@@ -756,6 +808,14 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     p.compat_lines = compat && d.bin_mode != 2;
     p.binning = d.bin_mode != 2;
     p.overlap = S.overlap > 1 && d.bin_mode == 1 && n >= (uint64_t)S.overlap * 65536;
+    // the fate scan in front of the headline trace kernel (fate_consts: pencil, Lambertian border, explicit bounces, first strike
+    // on the mirror patch): scheduling only -- anything else takes the kernels above whatever the option says
+    if (!beam && fate && fate->ok && p.fn == isx_trace_assist_kernel && !p.overlap &&
+        (S.fate_scan == 1 || (S.fate_scan < 0 && fate_scan_auto(c, std::min(n, S.pipe_chunk))))) {
+      p.list_fn = isx_trace_assist_list_kernel;
+      p.fate = *fate;
+      p.fate_auto = S.fate_scan < 0;   // (the largest chunk passes the rule; a shorter last chunk is asked again)
+    }
     if (p.lds_bin <= S.lds_limit || beam) return p;   // (beam: enqueue refuses a binning kernel whose LDS does not fit)
     p = Plan();   // (a binning kernel whose LDS does not fit: the fused kernel below)
   }
@@ -958,16 +1018,26 @@ int ensure_regions(size_t regions, int buf) {
 }
 // ... for a chunk of `rays` rays traced by `waves` waves: every region but a wave's last is closed with more than kRegion - 64
 // lines in it, and a launch cannot have more lines than rays (isx_kernels.hpp: kRegion)
-int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles) {
+// list: ... and the fate scan's ray list, 4 B per ray of the largest chunk so far (grown, never shrunk)
+int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles, bool list = false) {
+  if (list && rays > S.cap_list) {
+    HIPCHK(hipStreamSynchronize(S.stream));
+    if (S.d_list) HIPCHK(hipFree(S.d_list));
+    S.d_list = nullptr; S.cap_list = 0;
+    HIPCHK(hipMalloc(&S.d_list, rays * sizeof(uint32_t)));
+    S.cap_list = rays;
+  }
   return ensure_regions((rays / (kRegion - 63) + waves + 1) * slot_doubles / 6 + 1, buf);   // (capacity is counted in 6-double slots)
 }
 
 // ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_FIELD_PIPE and ROUTE_DISC_PIPE: a trace launch and a binning launch per chunk of at most pipe_chunk rays
 int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
-  int rc = set_lds(p.beam_fn ? (const void*)p.beam_fn : (const void*)p.fn, p.lds);
+  int rc = set_lds(p.beam_fn ? (const void*)p.beam_fn : p.list_fn ? (const void*)p.list_fn : (const void*)p.fn, p.lds);
+  if (rc == ISX_OK && p.list_fn) rc = set_lds((const void*)p.fn, p.lds);   // (a chunk below the automatic rule's size takes it)
   if (rc == ISX_OK) rc = set_lds((const void*)p.bin, p.lds_bin);
   if (rc) return rc;
-  const int tres = p.beam_fn ? blocks_per_cu(p.beam_fn, p.block, p.lds, p.per_cu) : blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
+  const int tres = p.beam_fn ? blocks_per_cu(p.beam_fn, p.block, p.lds, p.per_cu) :
+                   p.list_fn ? blocks_per_cu(p.list_fn, p.block, p.lds, p.per_cu) : blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
   const int bres = blocks_per_cu(p.bin, p.bblock, p.lds_bin, p.bin_per_cu);
   // what the two kernels see: a flux map's trace kernel keeps no histogram; the disc sweep's kernels walk the discs in cluster order
   DetGrid dt = d, db = d;
@@ -993,6 +1063,21 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     dt.rec_counts = db.rec_counts = S.d_rec_counts[buf];
     const int tgrid = pick_grid(p, cnt, tres);
     if (p.beam_fn) hipLaunchKernelGGL(p.beam_fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w, p.beam);
+    else if (p.list_fn && (!p.fate_auto || cnt >= kFateMinRays)) {
+      // the scan settles what the wall absorbs and leaves the rest in S.d_list, their number in ctr[Q_LIST] (zeroed with the
+      // launch's other counters); the trace kernel's grid is sized from the chunk, an upper bound.  Same stream, no host round
+      // trip; both kernels lie in the trace span.
+      FateScan fs;
+      fs.f = p.fate; fs.seed = w.seed; fs.first = w.first; fs.n = (uint32_t)cnt; fs.pad = 0;
+      fs.list = S.d_list; fs.ctr = w.ctr; fs.stats = w.stats;
+      const uint64_t want = (cnt + 4ull * kScanBlock - 1) / (4ull * kScanBlock), full = (uint64_t)S.cu_count * 8ull;
+      const int sgrid = S.grid_blocks > 0 ? S.grid_blocks : (int)std::max<uint64_t>(1, std::min(want, full));
+      hipLaunchKernelGGL(isx_fate_scan_kernel, dim3(sgrid), dim3(kScanBlock), 0, st, fs);
+      HIPCHK(hipGetLastError());
+      ++S.fate_launches;
+      const FateList fl{S.d_list, w.ctr + Q_LIST};
+      hipLaunchKernelGGL(p.list_fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w, fl);
+    }
     else hipLaunchKernelGGL(p.fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w);
     HIPCHK(hipGetLastError());
     size_t traced;
@@ -1043,7 +1128,7 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     return ISX_OK;
   }
   const uint64_t chunk = std::min(n, S.pipe_chunk);
-  rc = ensure_pipeline((size_t)chunk, (size_t)pick_grid(p, chunk, tres) * (p.block / 64), 0, p.slot_doubles); if (rc) return rc;
+  rc = ensure_pipeline((size_t)chunk, (size_t)pick_grid(p, chunk, tres) * (p.block / 64), 0, p.slot_doubles, p.list_fn != nullptr); if (rc) return rc;
   size_t t;
   rc = mark(S.stream, &t);
   for (uint64_t off = 0; off < n && rc == ISX_OK; off += chunk)
@@ -1058,9 +1143,10 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
             const WallSink* wm = nullptr, const FieldSink* lf = nullptr, const OrderSink* oh = nullptr,
             const PatchSink* wp = nullptr, const isx_beam_spec* bs = nullptr) {
   Geom g;
+  FateConsts fate;
   isx_config cb;
   if (bs && config_abi_ok(c) && bs->struct_size == (uint32_t)sizeof(isx_beam_spec)) { cb = beam_config(*c, *bs); c = &cb; }
-  int rc = prepare_geom(c, &g);
+  int rc = prepare_geom(c, &g, &fate);
   if (rc) return rc;
   if (n > ISX_MAX_RAYS_PER_CALL) return ISX_ERR_TOO_LARGE;
   if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;   // first + n (the exclusive end of the index range) must be representable
@@ -1071,7 +1157,7 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
   Work wk;
   wk.seed = seed; wk.first = first; wk.n = n; wk.hist = d_hist; wk.stats = d_stats ? d_stats : S.d_stats;
   wk.ctr = nullptr; wk.sub = 0; wk.pad = 0;
-  Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n, bs != nullptr);
+  Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n, bs != nullptr, &fate);
   if (sink == SINK_PATCH) p.patch_tab = patch_table(*c, *wp->spec);
   if (bs) {
     if (p.lds_bin > S.lds_limit) return ISX_ERR_BAD_CONFIG;   // (isx.h: a grid whose tables do not fit the binning kernels' LDS)
@@ -1352,6 +1438,8 @@ void isx_shutdown(void) {
   }
   if (S.d_ctr) (void)hipFree(S.d_ctr);
   S.d_ctr = nullptr; S.ctr_next = 0;
+  if (S.d_list) (void)hipFree(S.d_list);
+  S.d_list = nullptr; S.cap_list = 0; S.fate_launches = 0;
   S.attr_lds.clear();
   S.d_table = S.d_rowtab = S.d_coltab = nullptr;
   S.d_hist = S.d_stats = nullptr;
@@ -1396,6 +1484,7 @@ int isx_set_option(const char* key, int64_t value) {
   if (!std::strcmp(key, "lf_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.lf_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "surface_pipeline")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.surface_pipeline = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "ray_sub")) { if (value < 0 || value > (1 << 20)) return ISX_ERR_BAD_ARG; S.ray_sub = (int)value; return ISX_OK; }
+  if (!std::strcmp(key, "fate_scan")) { if (value < -1 || value > 1) return ISX_ERR_BAD_ARG; S.fate_scan = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "pipeline")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.pipeline = (int)value; return ISX_OK; }
   // (a launch addresses its rays by 30-bit offsets -- bits 30 and 31 of Ray::ido are flags in the queue records -- and counts
   //  them in 32 bits: the documented maximum of a chunk is 2^26 rays, 3.4 GB of exit-line workspace)
@@ -1471,6 +1560,36 @@ int isx_trace_endstates(const isx_config* cfg, uint64_t n, uint64_t seed, uint64
   HIPCHK(hipMemcpyAsync(last_point, d_lp, n * 24, hipMemcpyDeviceToHost, S.stream));
   HIPCHK(hipMemcpyAsync(direction, d_dir, n * 24, hipMemcpyDeviceToHost, S.stream));
   HIPCHK(hipStreamSynchronize(S.stream));
+  return ISX_OK;
+}
+
+int isx_fate_scan(const isx_config* cfg, uint64_t n, uint64_t seed, uint64_t first, int32_t* fate, int32_t* order) {
+  if (!S.init) return ISX_ERR_NOT_INIT;
+  if (!cfg || !fate || !order) return ISX_ERR_BAD_ARG;
+  if (n == 0) return ISX_OK;
+  if (n > (1ull << 28)) return ISX_ERR_TOO_LARGE;
+  if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;
+  Geom g;
+  FateConsts f;
+  int rc = prepare_geom(cfg, &g, &f);
+  if (rc) return rc;
+  if (!f.ok) return ISX_ERR_BAD_CONFIG;   // (a configuration the scan does not serve has no fates to report)
+  DevBuf<int32_t> b_ft, b_or;
+  HIPCHK(b_ft.alloc(n)); HIPCHK(b_or.alloc(n));
+  const int blk = 256;
+  const unsigned grid = (unsigned)((n + blk - 1) / blk);
+  hipLaunchKernelGGL(isx_fate_diag_kernel, dim3(grid), dim3(blk), 0, S.stream, f, seed, first, n, b_ft.p, b_or.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(fate, b_ft.p, n * 4, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipMemcpyAsync(order, b_or.p, n * 4, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipStreamSynchronize(S.stream));
+  return ISX_OK;
+}
+
+int isx_fate_scan_launches(uint64_t* launches) {
+  if (!S.init) return ISX_ERR_NOT_INIT;
+  if (!launches) return ISX_ERR_BAD_ARG;
+  *launches = S.fate_launches;
   return ISX_OK;
 }
 

@@ -616,6 +616,46 @@ __device__ __forceinline__ bool interact(const Hot& h, const G& g, int kind, con
   return true;
 }
 
+// ---------------------------------------------------------------- fate scan
+// On the headline path (pencil source, Lambertian border, explicit bounces) the fate of a ray that the inner wall absorbs is a
+// function of its Philox words alone: interact<LEAN> tests `wb < rho_thr` on the raw word before anything is emitted, and rule
+// S1' lands the emitted direction r_in s - p at r_in s up to the drift of |p| from r_in, so `q.z >= zcut_in` is a threshold on
+// the word wa that made s.z = sphere_z(wa).  The scan walks a ray's words and SETTLES it as absorbed, or leaves it to the trace
+// kernel -- which starts it again at interaction 0 -- as soon as a word comes within a margin of a decision the arithmetic
+// could take differently.  All thresholds are integers the host prepares (isx_api.hip: prepare_geom).
+struct FateConsts {
+  unsigned long long rho_thr;   // Geom::rho_thr
+  uint32_t w_leave;             // wa above it: the landing point may lie in the port opening (W_leave - MARG, rounded down)
+  uint32_t sep;                 // |wa_j - wa_{j-1}| below it: the chord may be too short for the bound on |v| (SEP)
+  uint32_t w_q0;                // the word whose sphere_z is Geom::q0.z / r_in: "wa" of the first strike
+  uint32_t j_cap;               // interactions after which the scan gives up (J_CAP)
+  int limit;                    // Geom::limit
+  int ok;                       // 0: the configuration is not served (host only)
+};
+enum : int { FATE_GO = -1, FATE_TRACE = 0 };   // (ST_ABSORBED = 2 is the one fate that is ever settled)
+// interaction j of a ray that is known to have arrived on the mirror patch: its two words -> FATE_GO (on to j + 1), ST_ABSORBED
+// (final: n_points = j + 2) or FATE_TRACE (undecided at j)
+__device__ __forceinline__ int fate_step(const FateConsts& f, uint32_t j, uint32_t wa, uint32_t wb, uint32_t& wprev) {
+  if (j >= f.j_cap) return FATE_TRACE;
+  if (!((unsigned long long)wb < f.rho_thr)) return ST_ABSORBED;          // interact(): decided on the integer, before the emission
+  if ((int)j + 2 > f.limit) return FATE_TRACE;                            // ray_arrive(): the bounce limit ends it here
+  if (wa > f.w_leave) return FATE_TRACE;                                  // lands in, or within the margin of, the port opening
+  const uint32_t dz = wa > wprev ? wa - wprev : wprev - wa;
+  if (dz < f.sep) return FATE_TRACE;                                      // |v| not bounded from below
+  wprev = wa;
+  return FATE_GO;
+}
+// the two interactions of Philox block j/2 (j even): the rule, stated once for the scan kernel and the diagnostic kernel
+__device__ __forceinline__ int fate_block(const FateConsts& f, const uint32_t (&w)[4], uint32_t& j, uint32_t& wprev) {
+  int ft = fate_step(f, j, w[0], w[1], wprev);
+  if (ft != FATE_GO) return ft;
+  ++j;
+  ft = fate_step(f, j, w[2], w[3], wprev);
+  if (ft != FATE_GO) return ft;
+  ++j;
+  return FATE_GO;
+}
+
 // ---------------------------------------------------------------- BRDF re-scatter (nonLambertianFlux.C:147-208)
 template <class G>
 __device__ inline V3 brdf_sample(const G& g, const V3 normal, const V3 incident, uint64_t seed, uint64_t ray) {

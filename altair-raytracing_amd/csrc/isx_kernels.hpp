@@ -136,7 +136,9 @@ struct Work {
   uint32_t* ctr;
   uint32_t sub, pad;          // pad (binning kernels): work units are (quarter regions) >> pad -- 0, or 2 for small launches (64-line units)
 };
-enum : int { Q_RAYS = 0 /* 64-bit: words 0-1 (it keeps counting after the last ray) */, Q_REGIONS = 2, Q_BIN = 3, Q_WORDS = 4 };
+// ctr[Q_SCAN]: the ray queue of the fate scan (64-bit, as Q_RAYS), ctr[Q_LIST]: rays it left to the trace kernel (isx_fate_scan_kernel).
+enum : int { Q_RAYS = 0 /* 64-bit: words 0-1 (it keeps counting after the last ray) */, Q_REGIONS = 2, Q_BIN = 3,
+             Q_SCAN = 4 /* 64-bit: words 4-5 */, Q_LIST = 6, Q_WORDS = 8 };
 // SINK_REC: a wave appends its exit lines to a private REGION of kRegion slots of the workspace and reserves the next one
 // (one atomic on ctr[Q_REGIONS]) when a trip's lines no longer fit; rec_counts[region] = lines in it.  A region is closed with
 // at least kRegion - 63 lines unless it is a wave's last, so a launch of n rays on W waves needs at most
@@ -2912,14 +2914,20 @@ __device__ __forceinline__ void ray_unpack(const uint4& a, const uint4& b, const
 // PH_EVEN, anything else goes to the assist wave with K_NONE, as a pencil whose Geom::q0_ok is 0 does.  The workgroup's one-thread
 // evaluation of Geom::q0 is skipped; the source lies behind the rings.  Exit lines, chunks, workspace and the kernels that follow
 // are isx_trace_assist_kernel's.  Explicit Lambertian lean path only.
+// LIST (the flux pipeline behind the fate scan, isx_fate_scan_kernel): the launch traces the rays whose offsets the scan left in a
+// list in HBM, not an index range -- a refilling lane takes list[k] where it took k, and the launch's ray count is the word the
+// scan left (read once per wave: the grid is sized from the chunk, an upper bound).  A launch that finds no ray ends through the
+// "queue dry" path like any other.  Everything else is isx_trace_assist_kernel.
+struct FateList { const uint32_t* list; const uint32_t* count; };
 template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false, bool ORDER = false, bool PATCH = false,
-          bool BEAM = false>
+          bool BEAM = false, bool LIST = false>
 __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk, const PatchTab* tab_arg = nullptr,
-                                            const BeamSrc* beam_arg = nullptr) {
+                                            const BeamSrc* beam_arg = nullptr, const FateList* list_arg = nullptr) {
   constexpr bool LEAN = SURF == SURF_LAMBERT;
   static_assert(LEAN || (CH == 0 && !RESC), "the chord identity and the BRDF re-scatter pipeline are built for the Lambertian border");
   static_assert(!PATCH || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER), "wall patches: the explicit Lambertian lean path, no other sink");
   static_assert(!BEAM || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && !PATCH), "beam source: the explicit Lambertian lean path, no other sink");
+  static_assert(!LIST || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && !PATCH && !BEAM), "ray list: the explicit Lambertian lean path of the flux pipeline");
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned long long* sstat = reinterpret_cast<unsigned long long*>(smem);
   Geom* g_lds = reinterpret_cast<Geom*>(sstat + 8);
@@ -2992,6 +3000,9 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     uint32_t next = 0, end = 0, spins = 0, beat_seen = 0;
     uint32_t park_base = 0, park_end = 0;   // BEAM: the wave's parked fresh rays are [park_base, park_end) of the launch
     bool drained = false;
+    typedef __attribute__((address_space(1))) const uint32_t GlbU32;
+    uint32_t n_list = 0;                    // LIST: rays of this launch
+    if constexpr (LIST) n_list = (uint32_t)__builtin_amdgcn_readfirstlane((int)((GlbU32*)list_arg->count)[0]);
     Ray r;
     ray_start(g, r, 0);
     bool run = false, hand = false;    // hand: the lane's ray waits to be handed to the assist wave
@@ -3042,7 +3053,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       }
       if (dead) {
         if (next == end) {   // this wave's sub-range is used up: the next one off the launch's queue (persistent_body)
-          const uint32_t n32 = (uint32_t)wk.n;
+          const uint32_t n32 = LIST ? n_list : (uint32_t)wk.n;
           const uint32_t share = (n32 - end) / (2u * (uint32_t)n_tracers * gridDim.x);
           const uint32_t want = share >= wk.sub ? wk.sub : (share > 64u ? share : 64u);
           unsigned long long b64 = 0;
@@ -3091,7 +3102,11 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         } else if (next < end) {
           const uint32_t left = end - next;
           const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(dead >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dead, 0u));
+          if constexpr (LIST) {
+            if (!(run || hand) && rank < left) { ray_start(g, r, ((GlbU32*)list_arg->list)[next + rank]); run = true; }
+          } else {
           if (!(run || hand) && rank < left) { ray_start(g, r, next + rank); run = true; }
+          }
           const uint32_t want = (uint32_t)__popcll(dead);
           const uint32_t take = want < left ? want : left;
           next += take; n_taken += take;
@@ -3649,6 +3664,11 @@ isx_trace_assist_patch_kernel(const Geom g, const DetGrid d, const Work wk, cons
 extern "C" __global__ void ISX_ASSIST_ATTR
 isx_trace_assist_beam_kernel(const Geom g, const DetGrid d, const Work wk, const BeamSrc beam) {
   assist_body<0, false, false, 0, SURF_LAMBERT, false, false, false, true>(g, d, wk, nullptr, &beam);
+}
+// the flux pipeline behind the fate scan: isx_trace_assist_kernel on the rays of a list; the list is a fourth argument
+extern "C" __global__ void ISX_ASSIST_ATTR
+isx_trace_assist_list_kernel(const Geom g, const DetGrid d, const Work wk, const FateList fl) {
+  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, false, false, true>(g, d, wk, nullptr, nullptr, &fl);
 }
 // the other border models on the same pipeline (round 5; until then round 1's fused isx_trace_bin_full_kernel served them):
 // the cos^2 lobe of "nonLambertianFlux copy.C":31-70,188-221 and ROBAST's rough-specular border (EnableLambertian(false))
@@ -4374,6 +4394,132 @@ isx_bin_cols_kernel(const DetGrid d_arg, const Work wk) {
     if (c) { global_add_u64(&ghist[b], (unsigned long long)c); flushed += c; }
   }
   if (flushed) atomicAdd(&wk.stats[5], flushed);
+}
+
+// ------------------------------------------------------------------ fate scan
+// Runs ahead of isx_trace_assist_list_kernel on the same chunk: every ray of [first, first + n) is walked over its Philox words
+// (fate_block, isx_device.hpp) until it is settled as absorbed -- launched, absorbed and wall_hits of the census are all it adds
+// to the result -- or left to the trace kernel: its 32-bit offset is appended to the chunk's list, ctr[Q_LIST] counts them.
+// Persistent waves, lane = ray, integer arithmetic only.  A trip is kScanBlocks Philox blocks (two interactions each) per lane; a
+// lane whose ray is decided takes the next ray of the wave's sub-range -- off the launch's queue ctr[Q_SCAN] -- at the top of the
+// next trip, so no wave waits for its longest ray with idle lanes (a ray lives ~57 interactions, the longest of 64 ~ 250).
+// The rays for the list are batched per wave in LDS (kScanBatch offsets) and appended with ONE global atomic and coalesced stores
+// per batch: an atomic per trip -- every trip leaves ~4 rays -- is 5e6 returning atomics on one address per 5e7 rays, which the
+// L2 serialises (measured: 74 ms for the chunk, docs/LOG.md section 16).  One census flush per workgroup.
+#ifndef ISX_SCAN_BLOCKS
+#define ISX_SCAN_BLOCKS 4
+#endif
+constexpr int kScanBlocks = ISX_SCAN_BLOCKS;
+constexpr int kScanBlock = 256;        // threads per workgroup
+constexpr uint32_t kScanSub = 256;     // rays a wave takes off the queue at a time
+constexpr uint32_t kScanBatch = 256;   // offsets a wave collects before it appends them to the list (+ 64: a trip's worth of room)
+struct FateScan {
+  FateConsts f;
+  uint64_t seed, first;
+  uint32_t n, pad;               // rays of the chunk (< 2^31)
+  uint32_t* list;                // [n] at least
+  uint32_t* ctr;                 // the launch's counter block (Work::ctr)
+  unsigned long long* stats;     // Work::stats
+};
+extern "C" __global__ void __launch_bounds__(kScanBlock)
+isx_fate_scan_kernel(const FateScan a) {
+  __shared__ unsigned long long s_cen[2];   // settled rays, their wall hits
+  __shared__ uint32_t s_batch[kScanBlock / 64][kScanBatch + 64];
+  const int tid = threadIdx.x, lane = tid & 63;
+  if (tid < 2) s_cen[tid] = 0ull;
+  __syncthreads();
+  typedef __attribute__((address_space(3))) uint32_t LdsU32;
+  volatile LdsU32* batch = (volatile LdsU32*)s_batch[__builtin_amdgcn_readfirstlane(tid >> 6)];
+  uint32_t n_batch = 0;     // per wave: offsets in the batch
+  // append the wave's batch to the list: base + i < rays left over so far <= n, inside the list
+  auto flush_batch = [&]() {
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(a.ctr + Q_LIST, n_batch);
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    __builtin_amdgcn_wave_barrier();
+    for (uint32_t i = (uint32_t)lane; i < n_batch; i += 64u) a.list[base + i] = batch[i];
+    __builtin_amdgcn_wave_barrier();
+    n_batch = 0;
+  };
+  const FateConsts f = a.f;
+  const uint64_t seed = a.seed, first = a.first;
+  const uint32_t n32 = a.n;
+  uint32_t off = 0, j = 0, wprev = 0;
+  bool run = false;
+  uint32_t next = 0, end = 0;
+  bool dry = false;
+  uint32_t n_wall = 0;      // per lane
+  uint32_t n_settled = 0;   // per wave
+  for (;;) {
+    unsigned long long dead = __ballot(!run);
+    while (dead && !dry) {
+      if (next == end) {
+        unsigned long long b64 = 0;
+        if (lane == 0) b64 = atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + Q_SCAN), (unsigned long long)kScanSub);
+        const uint32_t bhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(b64 >> 32));
+        const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b64);
+        if (bhi == 0u && b < n32) { next = b; end = n32 - b > kScanSub ? b + kScanSub : n32; }
+        else { dry = true; break; }
+      }
+      const uint32_t left = end - next;
+      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(dead >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dead, 0u));
+      if (!run && rank < left) { off = next + rank; j = 0; wprev = f.w_q0; run = true; }
+      const uint32_t want = (uint32_t)__popcll(dead);
+      next += want < left ? want : left;
+      dead = __ballot(!run);
+    }
+    if (__ballot(run) == 0ull) break;
+    int ft = FATE_GO;
+#pragma unroll
+    for (int k = 0; k < kScanBlocks; ++k) {
+      if (run && ft == FATE_GO) {
+        uint32_t w[4];
+        draw_block(seed, first + (uint64_t)off, j >> 1, 0u, w);
+        ft = fate_block(f, w, j, wprev);
+      }
+    }
+    const bool settled = run && ft == ST_ABSORBED, left_over = run && ft == FATE_TRACE;
+    if (settled) {
+      n_wall += j + 1u;
+      if (n_wall > 0x7fffffffu) { atomicAdd(&s_cen[1], (unsigned long long)n_wall); n_wall = 0; }
+    }
+    n_settled += (uint32_t)__popcll(__ballot(settled));
+    const unsigned long long lm = __ballot(left_over);
+    if (lm) {
+      if (left_over) {   // (n_batch < kScanBatch here, rank < 64: inside the wave's block)
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(lm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lm, 0u));
+        batch[n_batch + rank] = off;
+      }
+      n_batch += (uint32_t)__popcll(lm);
+      if (n_batch >= kScanBatch) flush_batch();
+    }
+    if (settled || left_over) run = false;
+  }
+  if (n_batch) flush_batch();
+  atomicAdd(&s_cen[1], (unsigned long long)n_wall);
+  if (lane == 0) atomicAdd(&s_cen[0], (unsigned long long)n_settled);
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned long long c = s_cen[0], w = s_cen[1];
+    if (c) { global_add_u64(a.stats + 0, c); global_add_u64(a.stats + 3, c); }   // launched, absorbed
+    if (w) global_add_u64(a.stats + 6, w);                                        // wall_hits
+  }
+}
+// isx_fate_scan (diagnostic): the same rule per ray, in index order -- fate 2 (absorbed at interaction `order`) or 0 (left to the
+// trace kernel at interaction `order`)
+extern "C" __global__ void __launch_bounds__(256)
+isx_fate_diag_kernel(const FateConsts f, uint64_t seed, uint64_t first, uint64_t n, int32_t* __restrict__ fate, int32_t* __restrict__ order) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t j = 0, wprev = f.w_q0;
+  int ft;
+  do {
+    uint32_t w[4];
+    draw_block(seed, first + i, j >> 1, 0u, w);
+    ft = fate_block(f, w, j, wprev);
+  } while (ft == FATE_GO);
+  fate[i] = ft;
+  order[i] = (int32_t)j;
 }
 
 // ------------------------------------------------------------------ per-ray end states (parity tests)

@@ -197,6 +197,14 @@ int isx_last_kernel_ms(double* single_ms, double* trace_ms, double* bin_ms);
  *                  rough-specular kernels; "rays_per_lane" > 0 sizes every grid for that many rays per tracer lane, 0 = by launch
  *                  size: 1 below 1.5e5 rays, 2 below 3e5, else 4 -- a small launch is bound by its longest ray, not by throughput)
  *   "ray_sub"      rays a wave takes off a launch's ray queue at a time (0 = default: 128)
+ *   "fate_scan"    a SCHEDULING option, it changes no result: -1 (default) automatic, 1 on wherever eligible, 0 off.  On the headline
+ *                  path of isx_fluxmap / isx_fluxmap_device (pencil source whose first strike lies on the mirror patch, Lambertian
+ *                  border, explicit bounces, "assist" 1, no "overlap") isx_fate_scan_kernel first walks every ray of a chunk over
+ *                  its Philox words alone and settles the rays the inner wall absorbs -- launched, absorbed and wall_hits are all
+ *                  they add to a result; the trace kernel then runs on the list of the others, each from its first interaction
+ *                  (DESIGN.md 4.2d).  Automatic: chunks of at least 1e7 rays whose expected settled share
+ *                  (1 - rho) / ((1 - rho) + port area fraction) is at least 0.5.  Anything else takes the kernels it took before,
+ *                  also with 1.  WORKSPACE: 4 B per ray of the largest chunk, kept until isx_shutdown()
  *   "overlap", "overlap_trace_streams"  cut a flux-map call into k chunks, binning of chunk i on a second stream while chunk
  *                  i+1 is traced (measured slower on MI355X, default 0)
  *   "disc_pipeline"  1 (default): the shared-ray disc sweep as trace kernel + disc-binning kernel (discs clustered by eight on the
@@ -221,6 +229,16 @@ typedef enum isx_ray_status { ISX_RAY_EXITED = 1, ISX_RAY_ABSORBED = 2, ISX_RAY_
 int isx_trace_endstates(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
                         int32_t* status, int32_t* n_points, double* last_point /*[n][3]*/,
                         double* direction /*[n][3]*/);
+
+/*
+ * Diagnostic of the "fate_scan" option (tests): the scan's rule per ray, in index order.  fate[i] = ISX_RAY_ABSORBED (2) if the
+ * scan settles ray first_ray + i as absorbed at interaction order[i] (isx_trace_endstates then reports ISX_RAY_ABSORBED and
+ * n_points = order[i] + 2), or 0 if it leaves the ray to the trace kernel, undecided at interaction order[i].  Host buffers sized
+ * n_rays.  ISX_ERR_BAD_CONFIG for a configuration the scan does not serve.
+ */
+int isx_fate_scan(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t first_ray, int32_t* fate, int32_t* order);
+/* Chunks that took the scan since isx_init (one isx_fate_scan_kernel launch each): shows which path a call took (tests). */
+int isx_fate_scan_launches(uint64_t* launches);
 
 /*
  * Physical-disc sweep (integratingSphereDetectorSweep.C:31-105,145-172): n_disc
