@@ -143,7 +143,7 @@ RhoConsts reflectance_consts(double rho) {
 constexpr uint32_t kFateMarg = 1u << 16, kFateSep = 1u << 17, kFateJCap = 1024u;
 FateConsts fate_consts(const isx_config* c, const Geom& g) {
   FateConsts f{};
-  f.rho_thr = g.rho_thr; f.sep = kFateSep; f.j_cap = kFateJCap; f.limit = g.limit;
+  f.rho_thr = (uint32_t)g.rho_thr; f.never = g.rho_thr > 0xffffffffull ? 1u : 0u; f.sep = kFateSep; f.j_cap = kFateJCap; f.limit = g.limit;
   const double w_leave = (1.0 - 0x1.0p-32 - g.zcut_in / g.r_in) * 0x1.0p31 - (double)kFateMarg;
   const double px = g.src[0], py = g.src[1], pz = g.src[2], vx = g.dir0[0], vy = g.dir0[1], vz = g.dir0[2];
   const double b = px * vx + py * vy + pz * vz;

@@ -624,7 +624,8 @@ __device__ __forceinline__ bool interact(const Hot& h, const G& g, int kind, con
 // kernel -- which starts it again at interaction 0 -- as soon as a word comes within a margin of a decision the arithmetic
 // could take differently.  All thresholds are integers the host prepares (isx_api.hip: prepare_geom).
 struct FateConsts {
-  unsigned long long rho_thr;   // Geom::rho_thr
+  uint32_t rho_thr;             // wb at or above it: absorbed.  The low word of Geom::rho_thr, which is 2^32 only for rho = 1:
+  uint32_t never;               //   then no word absorbs, never = 1, and the compare's lane mask is cleared wave-uniformly
   uint32_t w_leave;             // wa above it: the landing point may lie in the port opening (W_leave - MARG, rounded down)
   uint32_t sep;                 // |wa_j - wa_{j-1}| below it: the chord may be too short for the bound on |v| (SEP)
   uint32_t w_q0;                // the word whose sphere_z is Geom::q0.z / r_in: "wa" of the first strike
@@ -632,28 +633,52 @@ struct FateConsts {
   int limit;                    // Geom::limit
   int ok;                       // 0: the configuration is not served (host only)
 };
-enum : int { FATE_GO = -1, FATE_TRACE = 0 };   // (ST_ABSORBED = 2 is the one fate that is ever settled)
-// interaction j of a ray that is known to have arrived on the mirror patch: its two words -> FATE_GO (on to j + 1), ST_ABSORBED
-// (final: n_points = j + 2) or FATE_TRACE (undecided at j)
-__device__ __forceinline__ int fate_step(const FateConsts& f, uint32_t j, uint32_t wa, uint32_t wb, uint32_t& wprev) {
-  if (j >= f.j_cap) return FATE_TRACE;
-  if (!((unsigned long long)wb < f.rho_thr)) return ST_ABSORBED;          // interact(): decided on the integer, before the emission
-  if ((int)j + 2 > f.limit) return FATE_TRACE;                            // ray_arrive(): the bounce limit ends it here
-  if (wa > f.w_leave) return FATE_TRACE;                                  // lands in, or within the margin of, the port opening
-  const uint32_t dz = wa > wprev ? wa - wprev : wprev - wa;
-  if (dz < f.sep) return FATE_TRACE;                                      // |v| not bounded from below
-  wprev = wa;
-  return FATE_GO;
+enum : int { FATE_TRACE = 0 };   // (ST_ABSORBED = 2 is the one fate that is ever settled)
+// a compare as the wave's 64-bit lane mask, where the compare instruction leaves it (__ballot takes an int: 0 / 1 in a VGPR first)
+__device__ __forceinline__ unsigned long long lane_mask(bool b) { return __builtin_amdgcn_ballot_w64(b); }
+// |a - b| of two 32-bit words, exactly (not the difference modulo 2^32), in one instruction: v_sad_u32 d, a, b, 0.  hipcc
+// writes v_max_u32 / v_min_u32 / v_sub_u32 for the C expression: 16 more of a trip's 191 vector instructions in the scan.
+// (A plain VALU instruction on VGPRs: no wait state of its own is needed around it.)
+__device__ __forceinline__ uint32_t abs_diff_u32(uint32_t a, uint32_t b) {
+  uint32_t d;
+  asm("v_sad_u32 %0, %1, %2, 0" : "=v"(d) : "v"(a), "v"(b));
+  return d;
 }
-// the two interactions of Philox block j/2 (j even): the rule, stated once for the scan kernel and the diagnostic kernel
-__device__ __forceinline__ int fate_block(const FateConsts& f, const uint32_t (&w)[4], uint32_t& j, uint32_t& wprev) {
-  int ft = fate_step(f, j, w[0], w[1], wprev);
-  if (ft != FATE_GO) return ft;
-  ++j;
-  ft = fate_step(f, j, w[2], w[3], wprev);
-  if (ft != FATE_GO) return ft;
-  ++j;
-  return FATE_GO;
+// The two interactions j = 2 jb and j + 1 of Philox block jb of a ray that is known to have arrived on the mirror patch -- the
+// rule, stated once for the scan kernel and the diagnostic kernel.  Per interaction, in this order:
+//   1  j >= J_CAP            -> left to the trace kernel          (BOUNDS)
+//   2  wb >= rho_thr         -> ABSORBED (final: n_points = j + 2; interact() decides it on the integer, before the emission)
+//   3  j + 2 > limit         -> left (ray_arrive(): the bounce limit ends it here)          (BOUNDS)
+//   4  wa > w_leave          -> left (lands in, or within the margin of, the port opening)
+//   5  |wa - wa_{j-1}| < sep -> left (|v| not bounded from below)
+// and interaction j before j + 1.  Both interactions are evaluated for every lane, each test one compare into a lane mask, and
+// the verdict is put together from the masks: no branch, and nothing per lane but jb, wprev and the words.
+//   go        in: the lanes whose ray is undecided; out: those still undecided after both interactions (their jb advanced)
+//   absorbed  gains the lanes whose ray was decided here by rule 2 (the others decided here: left to the trace kernel)
+//   odd       gains the lanes whose ray was decided at the block's second interaction: it stopped at j = 2 jb + odd
+// All three are wave masks in scalar registers.  wprev of a lane that stopped is not read again: it takes the block's last word
+// without a select.  BOUNDS = false leaves rules 1 and 3 out: the caller has checked that neither can fire up to interaction
+// 2 jb + 1 (isx_fate_scan_kernel: once per trip, for the whole wave).
+template <bool BOUNDS>
+__device__ __forceinline__ void fate_block(const FateConsts& f, const uint32_t (&w)[4], unsigned long long& go, uint32_t& jb,
+                                           uint32_t& wprev, unsigned long long& absorbed, unsigned long long& odd) {
+  const unsigned long long may = f.never ? 0ull : ~0ull;
+  const unsigned long long ab0 = lane_mask(w[1] >= f.rho_thr) & may, ab1 = lane_mask(w[3] >= f.rho_thr) & may;
+  unsigned long long tr0 = lane_mask(w[0] > f.w_leave) | lane_mask(abs_diff_u32(w[0], wprev) < f.sep);
+  unsigned long long tr1 = lane_mask(w[2] > f.w_leave) | lane_mask(abs_diff_u32(w[2], w[0]) < f.sep);
+  unsigned long long cap0 = 0ull, cap1 = 0ull;
+  if (BOUNDS) {
+    const uint32_t j = 2u * jb;
+    cap0 = lane_mask(j >= f.j_cap); cap1 = lane_mask(j + 1u >= f.j_cap);
+    tr0 |= lane_mask((int)j + 2 > f.limit); tr1 |= lane_mask((int)j + 3 > f.limit);
+  }
+  const unsigned long long on1 = go & ~(cap0 | ab0 | tr0);          // undecided after interaction j
+  absorbed |= (go & ~cap0 & ab0) | (on1 & ~cap1 & ab1);
+  const unsigned long long stop1 = cap1 | ab1 | tr1;
+  odd |= on1 & stop1;
+  go = on1 & ~stop1;
+  jb += __builtin_amdgcn_inverse_ballot_w64(go) ? 1u : 0u;
+  wprev = w[2];
 }
 
 // ---------------------------------------------------------------- BRDF re-scatter (nonLambertianFlux.C:147-208)

@@ -4400,9 +4400,12 @@ isx_bin_cols_kernel(const DetGrid d_arg, const Work wk) {
 // Runs ahead of isx_trace_assist_list_kernel on the same chunk: every ray of [first, first + n) is walked over its Philox words
 // (fate_block, isx_device.hpp) until it is settled as absorbed -- launched, absorbed and wall_hits of the census are all it adds
 // to the result -- or left to the trace kernel: its 32-bit offset is appended to the chunk's list, ctr[Q_LIST] counts them.
-// Persistent waves, lane = ray, integer arithmetic only.  A trip is kScanBlocks Philox blocks (two interactions each) per lane; a
-// lane whose ray is decided takes the next ray of the wave's sub-range -- off the launch's queue ctr[Q_SCAN] -- at the top of the
-// next trip, so no wave waits for its longest ray with idle lanes (a ray lives ~57 interactions, the longest of 64 ~ 250).
+// Persistent waves, lane = ray, integer arithmetic only.  A trip is kScanBlocks Philox blocks (two interactions each) per lane,
+// evaluated for every lane without a branch: fate_block states the rule on lane masks, and the wave decides once per trip whether
+// any of its rays can meet one of the two bounds on j within the trip (then fate_block<true>, else fate_block<false>).  A lane
+// whose ray is decided idles to the end of the trip and takes the next ray of the wave's portion -- off the launch's queue
+// ctr[Q_SCAN], sized as the trace kernel sizes its own: large in the body of the launch, down to 64 rays at its end -- at the top
+// of the next trip, so no wave waits for its longest ray with idle lanes (a ray lives ~57 interactions, the longest of 64 ~ 250).
 // The rays for the list are batched per wave in LDS (kScanBatch offsets) and appended with ONE global atomic and coalesced stores
 // per batch: an atomic per trip -- every trip leaves ~4 rays -- is 5e6 returning atomics on one address per 5e7 rays, which the
 // L2 serialises (measured: 74 ms for the chunk, docs/LOG.md section 16).  One census flush per workgroup.
@@ -4411,8 +4414,14 @@ isx_bin_cols_kernel(const DetGrid d_arg, const Work wk) {
 #endif
 constexpr int kScanBlocks = ISX_SCAN_BLOCKS;
 constexpr int kScanBlock = 256;        // threads per workgroup
-constexpr uint32_t kScanSub = 256;     // rays a wave takes off the queue at a time
-constexpr uint32_t kScanBatch = 256;   // offsets a wave collects before it appends them to the list (+ 64: a trip's worth of room)
+#ifndef ISX_SCAN_SUB
+#define ISX_SCAN_SUB 2048
+#endif
+#ifndef ISX_SCAN_BATCH
+#define ISX_SCAN_BATCH 512
+#endif
+constexpr uint32_t kScanSub = ISX_SCAN_SUB;     // most rays a wave takes off the queue at a time (the least: 64)
+constexpr uint32_t kScanBatch = ISX_SCAN_BATCH;   // offsets a wave collects before it appends them to the list (+ 64: a trip's worth of room)
 struct FateScan {
   FateConsts f;
   uint64_t seed, first;
@@ -4442,9 +4451,15 @@ isx_fate_scan_kernel(const FateScan a) {
     n_batch = 0;
   };
   const FateConsts f = a.f;
-  const uint64_t seed = a.seed, first = a.first;
+  const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
+  const uint64_t first = a.first;
   const uint32_t n32 = a.n;
-  uint32_t off = 0, j = 0, wprev = 0;
+  const uint32_t waves = (uint32_t)(kScanBlock / 64) * gridDim.x;
+  // the last block at which a whole trip needs neither bound on j (rules 1 and 3 of fate_block): its last interaction is
+  // 2 (jb + kScanBlocks) - 1, below J_CAP and with its j + 2 within the limit iff 2 (jb + kScanBlocks) <= min(J_CAP, limit - 1)
+  const int jbound = min((int)f.j_cap, f.limit < 1 ? 0 : f.limit - 1);
+  const int jb_fast = jbound >= 2 * kScanBlocks ? (jbound - 2 * kScanBlocks) >> 1 : -1;
+  uint32_t c0 = 0, c1 = 0, jb = 0, wprev = 0;   // per lane: the ray's index (Philox counter words 0 and 1), its block, wa_{j-1}
   bool run = false;
   uint32_t next = 0, end = 0;
   bool dry = false;
@@ -4453,47 +4468,65 @@ isx_fate_scan_kernel(const FateScan a) {
   for (;;) {
     unsigned long long dead = __ballot(!run);
     while (dead && !dry) {
-      if (next == end) {
+      if (next == end) {   // the wave's portion is used up: the next one off the launch's queue, sized as the trace kernel sizes its own
+        const uint32_t share = (n32 - end) / (2u * waves);   // (end: where the queue stood at the last visit)
+        const uint32_t want = share >= kScanSub ? kScanSub : (share > 64u ? share : 64u);
         unsigned long long b64 = 0;
-        if (lane == 0) b64 = atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + Q_SCAN), (unsigned long long)kScanSub);
+        if (lane == 0) b64 = atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + Q_SCAN), (unsigned long long)want);
         const uint32_t bhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(b64 >> 32));
         const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b64);
-        if (bhi == 0u && b < n32) { next = b; end = n32 - b > kScanSub ? b + kScanSub : n32; }
+        if (bhi == 0u && b < n32) { next = b; end = n32 - b > want ? b + want : n32; }
         else { dry = true; break; }
       }
       const uint32_t left = end - next;
       const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(dead >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dead, 0u));
-      if (!run && rank < left) { off = next + rank; j = 0; wprev = f.w_q0; run = true; }
+      if (!run && rank < left) {
+        const uint64_t ray = first + (uint64_t)(next + rank);
+        c0 = (uint32_t)ray; c1 = (uint32_t)(ray >> 32); jb = 0; wprev = f.w_q0; run = true;
+      }
       const uint32_t want = (uint32_t)__popcll(dead);
       next += want < left ? want : left;
       dead = __ballot(!run);
     }
-    if (__ballot(run) == 0ull) break;
-    int ft = FATE_GO;
+    const unsigned long long running = __ballot(run);
+    if (running == 0ull) break;
+    // a trip: kScanBlocks blocks for every lane, no branch inside; a ray decided early keeps its verdict (go is off) to the end
+    unsigned long long go = running, absorbed = 0ull, odd = 0ull;   // lane masks
+    if ((running & lane_mask((int)jb > jb_fast)) == 0ull) {
 #pragma unroll
-    for (int k = 0; k < kScanBlocks; ++k) {
-      if (run && ft == FATE_GO) {
+      for (int k = 0; k < kScanBlocks; ++k) {
         uint32_t w[4];
-        draw_block(seed, first + (uint64_t)off, j >> 1, 0u, w);
-        ft = fate_block(f, w, j, wprev);
+        philox4x32_10(c0, c1, jb, 0u, k0, k1, w);
+        fate_block<false>(f, w, go, jb, wprev, absorbed, odd);
+      }
+    } else {   // a ray of the wave may meet J_CAP or the bounce limit in this trip
+      // (jb made opaque on this side: hipcc otherwise hoists the first block of both bodies above the branch and carries its
+      //  compares across it as 0 / 1 in VGPRs)
+      asm volatile("" : "+v"(jb));
+#pragma unroll
+      for (int k = 0; k < kScanBlocks; ++k) {
+        uint32_t w[4];
+        philox4x32_10(c0, c1, jb, 0u, k0, k1, w);
+        fate_block<true>(f, w, go, jb, wprev, absorbed, odd);
       }
     }
-    const bool settled = run && ft == ST_ABSORBED, left_over = run && ft == FATE_TRACE;
-    if (settled) {
-      n_wall += j + 1u;
-      if (n_wall > 0x7fffffffu) { atomicAdd(&s_cen[1], (unsigned long long)n_wall); n_wall = 0; }
+    const unsigned long long sm = absorbed, lm = running & ~go & ~absorbed;   // settled, left to the trace kernel
+    if (sm) {
+      if (__builtin_amdgcn_inverse_ballot_w64(sm)) {   // stopped at interaction j = 2 jb + odd: j + 1 wall hits
+        n_wall += 2u * jb + (__builtin_amdgcn_inverse_ballot_w64(odd) ? 2u : 1u);
+        if (n_wall > 0x7fffffffu) { atomicAdd(&s_cen[1], (unsigned long long)n_wall); n_wall = 0; }
+      }
+      n_settled += (uint32_t)__popcll(sm);
     }
-    n_settled += (uint32_t)__popcll(__ballot(settled));
-    const unsigned long long lm = __ballot(left_over);
     if (lm) {
-      if (left_over) {   // (n_batch < kScanBatch here, rank < 64: inside the wave's block)
+      if (__builtin_amdgcn_inverse_ballot_w64(lm)) {   // (n_batch < kScanBatch here, rank < 64: inside the wave's block)
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(lm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lm, 0u));
-        batch[n_batch + rank] = off;
+        batch[n_batch + rank] = c0 - (uint32_t)first;   // the ray's offset in the chunk
       }
       n_batch += (uint32_t)__popcll(lm);
       if (n_batch >= kScanBatch) flush_batch();
     }
-    if (settled || left_over) run = false;
+    run = __builtin_amdgcn_inverse_ballot_w64(go);
   }
   if (n_batch) flush_batch();
   atomicAdd(&s_cen[1], (unsigned long long)n_wall);
@@ -4511,15 +4544,16 @@ extern "C" __global__ void __launch_bounds__(256)
 isx_fate_diag_kernel(const FateConsts f, uint64_t seed, uint64_t first, uint64_t n, int32_t* __restrict__ fate, int32_t* __restrict__ order) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  uint32_t j = 0, wprev = f.w_q0;
-  int ft;
-  do {
+  uint32_t jb = 0, wprev = f.w_q0;
+  unsigned long long go = __ballot(1), absorbed = 0ull, odd = 0ull;   // (the wave's lanes with a ray; the loop is wave-uniform:
+  do {                                                                 //  a decided lane keeps its jb and its bits)
     uint32_t w[4];
-    draw_block(seed, first + i, j >> 1, 0u, w);
-    ft = fate_block(f, w, j, wprev);
-  } while (ft == FATE_GO);
-  fate[i] = ft;
-  order[i] = (int32_t)j;
+    draw_block(seed, first + i, jb, 0u, w);
+    fate_block<true>(f, w, go, jb, wprev, absorbed, odd);
+  } while (go);
+  const unsigned long long bit = 1ull << (threadIdx.x & 63u);
+  fate[i] = (absorbed & bit) ? ST_ABSORBED : FATE_TRACE;
+  order[i] = (int32_t)(2u * jb + ((odd & bit) ? 1u : 0u));
 }
 
 // ------------------------------------------------------------------ per-ray end states (parity tests)
