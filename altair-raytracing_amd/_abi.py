@@ -30,6 +30,7 @@ LIGHT_FIELD_MAX_BINS, LIGHT_FIELD_MAX_AXIS = 1 << 22, 1024   # ISX_LIGHT_FIELD_M
 ORDER_HIST_MAX_ORDERS, ORDER_HIST_MAX_WORDS, ORDER_HIST_MAX_DZ = 2048, 8192, 64   # ISX_ORDER_HIST_MAX_ORDERS / _MAX_WORDS, n_dz <= 64
 MAX_WALL_PATCHES = 8   # ISX_MAX_WALL_PATCHES
 BEAM_UNIFORM, BEAM_LAMBERT = 0, 1   # ISX_BEAM_UNIFORM / ISX_BEAM_LAMBERT
+MAX_BAFFLES = 4   # ISX_MAX_BAFFLES
 INJECT_FLUX, INJECT_EXIT_MAPS, INJECT_LIGHT_FIELD = 0, 1, 2   # ISX_INJECT_*: the sink of isx_bin_injected_lines
 INJECT_UNIT_AUTO = -1                                          # ISX_INJECT_UNIT_AUTO (else 0: 256-line work units, 2: 64-line units)
 INJECT_MAX_LINES, INJECT_MAX_REGIONS = 1 << 20, 1024   # (the flux sink also wants |P| <= sqrt(3) cfg.box_half)
@@ -47,6 +48,7 @@ EXPORTS = [
     "isx_default_order_hist_spec", "isx_order_hist", "isx_order_hist_device", "isx_order_reweight",
     "isx_default_wall_patch_spec", "isx_wall_patch_cap", "isx_wall_patches", "isx_wall_patches_device",
     "isx_default_beam_spec", "isx_beam_cone", "isx_beam_endstates", "isx_fluxmap_beam", "isx_fluxmap_beam_device",
+    "isx_default_baffle_spec", "isx_baffle_disc", "isx_baffle_endstates", "isx_fluxmap_baffle", "isx_fluxmap_baffle_device",
 ]
 
 
@@ -199,6 +201,36 @@ class BeamSpec(C.Structure):
         return s
 
 
+class Baffle(C.Structure):
+    """isx_baffle (include/isx.h): a two-sided disc inside the cavity; the normal is used as given, side 0 is the side it points to."""
+
+    _fields_ = [("centre", C.c_double * 3), ("normal", C.c_double * 3), ("radius", C.c_double), ("reflectance", C.c_double)]
+
+
+class BaffleSpec(C.Structure):
+    """isx_baffle_spec (include/isx.h): up to MAX_BAFFLES discs."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("n_baffles", C.c_int32), ("reserved1", C.c_int32),
+                ("baffle", Baffle * MAX_BAFFLES)]
+
+    def copy(self):
+        s = BaffleSpec()
+        C.memmove(C.byref(s), C.byref(self), C.sizeof(BaffleSpec))
+        return s
+
+
+class BaffleCounts(C.Structure):
+    """isx_baffle_counts (include/isx.h): arrivals and absorbed rays per [baffle][side]."""
+
+    _fields_ = [("arrivals", (C.c_uint64 * 2) * MAX_BAFFLES), ("absorbed", (C.c_uint64 * 2) * MAX_BAFFLES)]
+
+    def arrays(self):
+        """-> (arrivals[MAX_BAFFLES, 2], absorbed[MAX_BAFFLES, 2]) uint64"""
+        a = np.array([[self.arrivals[k][s] for s in range(2)] for k in range(MAX_BAFFLES)], dtype=np.uint64)
+        b = np.array([[self.absorbed[k][s] for s in range(2)] for k in range(MAX_BAFFLES)], dtype=np.uint64)
+        return a, b
+
+
 _lib = None
 
 
@@ -268,6 +300,12 @@ def load():
     L.isx_beam_endstates.argtypes = [P(Config), P(BeamSpec), u64, u64, u64, P(i32), P(i32), P(dbl), P(dbl), P(dbl), P(dbl)]
     L.isx_fluxmap_beam.argtypes = [P(Config), P(BeamSpec), u64, u64, u64, P(u64), P(Stats)]
     L.isx_fluxmap_beam_device.argtypes = [P(Config), P(BeamSpec), u64, u64, u64, C.c_void_p]
+    L.isx_default_baffle_spec.argtypes = [P(Config), P(BaffleSpec)]
+    L.isx_default_baffle_spec.restype = None
+    L.isx_baffle_disc.argtypes = [P(Config), P(dbl), P(dbl), dbl, dbl, P(Baffle)]
+    L.isx_baffle_endstates.argtypes = [P(Config), P(BaffleSpec), u64, u64, u64, P(i32), P(i32), P(dbl), P(dbl), P(i32)]
+    L.isx_fluxmap_baffle.argtypes = [P(Config), P(BaffleSpec), u64, u64, u64, P(u64), P(BaffleCounts), P(Stats)]
+    L.isx_fluxmap_baffle_device.argtypes = [P(Config), P(BaffleSpec), u64, u64, u64, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -697,6 +735,67 @@ def fluxmap_beam_device(cfg, spec, n_rays, seed, first_ray, d_hits_ptr):
     """Enqueue on the library stream, accumulating into device memory at d_hits_ptr ([n_theta * n_phi] uint64)."""
     _chk(load().isx_fluxmap_beam_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
                                         C.c_void_p(int(d_hits_ptr or 0) or None)), "isx_fluxmap_beam_device")
+
+
+def default_baffle_spec(cfg):
+    """No baffle: n_baffles 0 (no GPU needed)."""
+    s = BaffleSpec()
+    load().isx_default_baffle_spec(C.byref(cfg), C.byref(s))
+    return s
+
+
+def baffle_disc(cfg, centre, direction, radius, reflectance):
+    """-> Baffle: the disc of `radius` about `centre` with normal direction / |direction| (include/isx.h: isx_baffle_disc; host only)."""
+    c = (C.c_double * 3)(*[float(x) for x in centre])
+    d = (C.c_double * 3)(*[float(x) for x in direction])
+    out = Baffle()
+    _chk(load().isx_baffle_disc(C.byref(cfg), c, d, float(radius), float(reflectance), C.byref(out)), "isx_baffle_disc")
+    return out
+
+
+def baffle_spec(cfg, baffles):
+    """-> BaffleSpec holding the given Baffle objects, in order."""
+    s = default_baffle_spec(cfg)
+    baffles = list(baffles)
+    if len(baffles) > MAX_BAFFLES:
+        raise ValueError("at most %d baffles" % MAX_BAFFLES)
+    for k, b in enumerate(baffles):
+        C.memmove(C.byref(s.baffle[k]), C.byref(b), C.sizeof(Baffle))
+    s.n_baffles = len(baffles)
+    return s
+
+
+def baffle_endstates(cfg, spec, n, seed, first_ray=0):
+    """-> (status, n_points, last_point, direction, last_baffle): trace_endstates with the baffles; last_baffle is -1 or
+    2 k + side of the ray's last baffle interaction."""
+    n = int(n)
+    status = np.zeros(n, dtype=np.int32)
+    npts = np.zeros(n, dtype=np.int32)
+    lb = np.zeros(n, dtype=np.int32)
+    lp, d = (np.zeros((n, 3), dtype=np.float64) for _ in range(2))
+    _chk(load().isx_baffle_endstates(C.byref(cfg), C.byref(spec), n, int(seed), int(first_ray), _p(status, C.c_int32),
+                                     _p(npts, C.c_int32), _p(lp, C.c_double), _p(d, C.c_double), _p(lb, C.c_int32)),
+         "isx_baffle_endstates")
+    return status, npts, lp, d, lb
+
+
+def fluxmap_baffle(cfg, spec, n_rays, seed, first_ray=0):
+    """-> (hits[n_theta, n_phi] uint64, BaffleCounts, Stats): the flux map with the baffles of `spec` in the cavity
+    (include/isx.h: isx_fluxmap_baffle)."""
+    hits = np.zeros(max(cfg.n_theta, 0) * max(cfg.n_phi, 0), dtype=np.uint64)
+    st = Stats()
+    cnt = BaffleCounts()
+    _chk(load().isx_fluxmap_baffle(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray), _p(hits, C.c_uint64),
+                                   C.byref(cnt), C.byref(st)), "isx_fluxmap_baffle")
+    return hits.reshape(cfg.n_theta, cfg.n_phi), cnt, st
+
+
+def fluxmap_baffle_device(cfg, spec, n_rays, seed, first_ray, d_hits_ptr, d_counts_ptr):
+    """Enqueue on the library stream, accumulating into device memory at d_hits_ptr ([n_theta * n_phi] uint64) and d_counts_ptr
+    ([16] uint64, BaffleCounts' layout)."""
+    _chk(load().isx_fluxmap_baffle_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
+                                          C.c_void_p(int(d_hits_ptr or 0) or None), C.c_void_p(int(d_counts_ptr or 0) or None)),
+         "isx_fluxmap_baffle_device")
 
 
 def fluxmap_series(cfgs, n_rays, seed, first_ray=0):

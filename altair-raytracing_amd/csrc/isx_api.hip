@@ -534,6 +534,59 @@ bool beam_frame(const double dir[3], double axis[3], double e1[3], double e2[3])
   return true;
 }
 
+// isx_fluxmap_baffle: the checked spec and the device counters of the call (isx_baffle_counts' layout)
+struct BaffleSink { const isx_baffle_spec* spec = nullptr; unsigned long long* counts = nullptr; };
+static_assert(ISX_MAX_BAFFLES == kMaxBaffles, "isx.h and BaffleTab");
+static_assert(sizeof(isx_baffle_counts) == 4 * kMaxBaffles * sizeof(uint64_t), "isx.h and the kernels' counters");
+// isx.h: the limits of a baffle spec and the scope of the call (the explicit Lambertian lean path, either hit line)
+int check_baffle_call(const isx_config* c, const isx_baffle_spec* s) {
+  if (!config_abi_ok(c) || s->struct_size != (uint32_t)sizeof(isx_baffle_spec)) return ISX_ERR_BAD_CONFIG;
+  if (c->source_model != ISX_SOURCE_PENCIL || c->surface_model != ISX_SURFACE_ROBAST || c->lambertian == 0 ||
+      c->trace_mode != ISX_TRACE_EXPLICIT)
+    return ISX_ERR_BAD_CONFIG;
+  if (s->n_baffles < 0 || s->n_baffles > ISX_MAX_BAFFLES) return ISX_ERR_BAD_CONFIG;
+  auto dot = [](const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+  for (int k = 0; k < s->n_baffles; ++k) {
+    const isx_baffle& b = s->baffle[k];
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(b.centre[i]) || !std::isfinite(b.normal[i])) return ISX_ERR_BAD_CONFIG;
+    if (!std::isfinite(b.radius) || !std::isfinite(b.reflectance)) return ISX_ERR_BAD_CONFIG;
+    if (!(b.radius > 0.0) || !(b.reflectance >= 0.0 && b.reflectance <= 1.0)) return ISX_ERR_BAD_CONFIG;
+    if (!(std::fabs(std::sqrt(dot(b.normal, b.normal)) - 1.0) <= 1e-12)) return ISX_ERR_BAD_CONFIG;
+    // (the disc lies strictly inside the cavity and never touches a wall)
+    if (!((std::sqrt(dot(b.centre, b.centre)) + b.radius) * (1.0 + 1e-12) < c->r_in)) return ISX_ERR_BAD_CONFIG;
+  }
+  return ISX_OK;
+}
+// isx.h: a detector grid whose tables do not fit the binning kernels' LDS is refused -- answered before a device is asked for.  The
+// tables are plan_launch's (histogram, row table, column table, DetGrid); the binning kernel that needs least next to them is
+// isx_bin_lines_kernel (128 words per wave), which plan_launch falls back to when the slot kernels do not fit.  The LDS a workgroup
+// may have is the device's once isx_init has asked it, and gfx950's 160 KiB -- the one target of this library -- before.
+constexpr size_t kGfx950Lds = 160 * 1024;
+size_t hist_lds(int nbins);
+int check_baffle_grid(const isx_config* c) {
+  const int rc = check_grid(c);
+  if (rc) return rc;
+  const size_t tables = hist_lds(c->n_theta * c->n_phi) + (size_t)(4 * c->n_theta) * 8 + (size_t)(2 * c->n_phi) * sizeof(ColX) + sizeof(DetGrid) + 16;
+  const size_t limit = S.init ? S.lds_limit : kGfx950Lds;
+  return tables + (size_t)(S.bin_block / 64) * 128 * 4 <= limit ? ISX_OK : ISX_ERR_BAD_CONFIG;
+}
+// the kernels' table of a checked spec (isx.h: the precomputations of the contract, done once here)
+BaffleTab baffle_table(const isx_config& c, const isx_baffle_spec& s, unsigned long long* d_counts) {
+  BaffleTab t;
+  std::memset(&t, 0, sizeof(t));
+  t.n = s.n_baffles;
+  t.counts = d_counts;
+  for (int k = 0; k < s.n_baffles; ++k) {
+    const isx_baffle& b = s.baffle[k];
+    const RhoConsts rc = reflectance_consts(b.reflectance);
+    t.rho_thr[k] = rc.rho_thr; t.psi_k1[k] = rc.psi_k1; t.psi_k0[k] = rc.psi_k0;
+    t.r2[k] = b.radius * b.radius;
+    for (int i = 0; i < 3; ++i) { t.centre[k][i] = b.centre[i]; t.normal[k][i] = b.normal[i]; t.rm[k][i] = c.r_in * b.normal[i]; }
+  }
+  return t;
+}
+
 // LDS of a workgroup's histogram: 4 B per bin, 16-byte aligned
 size_t hist_lds(int nbins) { return ((size_t)nbins * 4 + 15) & ~(size_t)15; }
 
@@ -678,6 +731,7 @@ typedef void (*BinFn)(const DetGrid, const Work);
 typedef void (*PatchFn)(const Geom, const DetGrid, const Work, const PatchTab);
 typedef void (*BeamFn)(const Geom, const DetGrid, const Work, const BeamSrc);
 typedef void (*ListFn)(const Geom, const DetGrid, const Work, const FateList);
+typedef void (*BaffleFn)(const Geom, const DetGrid, const Work, const BaffleTab);
 struct Plan {
   Route route = ROUTE_FUSED;
   KernelFn fn = nullptr;        // the kernel (a pipeline's trace kernel)
@@ -703,6 +757,8 @@ struct Plan {
   ListFn list_fn = nullptr;     // ROUTE_FLUX_PIPE behind the fate scan: isx_fate_scan_kernel, then this kernel on the rays it left, instead of fn
   FateConsts fate{};
   bool fate_auto = false;       // "fate_scan" -1: the rule's ray count is looked at per chunk (launch_pair)
+  BaffleFn baffle_fn = nullptr; // isx_fluxmap_baffle: the pipeline's trace kernel (it takes the baffles as a fourth argument: baffles) instead of fn
+  BaffleTab baffles{};
 };
 
 // "fate_scan" = -1: where the scan pays (measured on MI355X, docs/LOG.md section 16.3).  A small launch is bound by its longest
@@ -748,7 +804,7 @@ void trace_shape(Plan& p, Shape sh, bool assist, int per_cu) {
 }
 
 Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bool discs_in_aux, uint64_t n, bool beam = false,
-                 const FateConsts* fate = nullptr) {
+                 const FateConsts* fate = nullptr, bool baffle = false) {
   enum { LAMBERT, LOBE, ROUGH } const border =
       c->surface_model == ISX_SURFACE_LOBE ? LOBE : c->lambertian ? LAMBERT : ROUGH;   // (ISX_SURFACE_ROBAST: Lambertian or rough-specular)
   const bool pencil = c->source_model == ISX_SOURCE_PENCIL;   // (else ISX_SOURCE_BRDF)
@@ -784,12 +840,18 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
   // The beam source (isx_fluxmap_beam) has one route whatever the switches say: its assist-wave trace kernel (the call is refused
   // outside the explicit Lambertian lean path: check_beam_call), the source behind the rings, and isx_fluxmap's binning kernels
   // (bin_mode 0: the brute-force form of isx_bin_lines_kernel).
-  if (sink == SINK_FLUX && (beam || (flux_served && S.pipeline && S.bin_mode != 0))) {
+  // The baffles (isx_fluxmap_baffle) likewise: their assist-wave trace kernel (check_baffle_call), the table behind the rings.
+  if (sink == SINK_FLUX && (beam || baffle || (flux_served && S.pipeline && S.bin_mode != 0))) {
     if (beam) {
       p.route = ROUTE_FLUX_PIPE;
       p.beam_fn = isx_trace_assist_beam_kernel;
       trace_shape(p, small_shape(std::min(n, S.pipe_chunk), S.assist_block), true, resident_unless(S.trace_blocks_per_cu));
       p.lds += beam_lds(p.tracers);
+    } else if (baffle) {
+      p.route = ROUTE_FLUX_PIPE;
+      p.baffle_fn = isx_trace_assist_baffle_kernel;
+      trace_shape(p, small_shape(std::min(n, S.pipe_chunk), S.assist_block), true, resident_unless(S.trace_blocks_per_cu));
+      p.lds += kBaffleLds;
     } else
     pipe_trace(ROUTE_FLUX_PIPE);
     // The binning kernel keeps the histogram and the detector tables in LDS.  With slot queues (1024-thread workgroups: 61 KB of
@@ -816,7 +878,7 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
       p.fate = *fate;
       p.fate_auto = S.fate_scan < 0;   // (the largest chunk passes the rule; a shorter last chunk is asked again)
     }
-    if (p.lds_bin <= S.lds_limit || beam) return p;   // (beam: enqueue refuses a binning kernel whose LDS does not fit)
+    if (p.lds_bin <= S.lds_limit || beam || baffle) return p;   // (beam, baffles: enqueue refuses a binning kernel whose LDS does not fit)
     p = Plan();   // (a binning kernel whose LDS does not fit: the fused kernel below)
   }
 
@@ -1032,11 +1094,12 @@ int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles, boo
 
 // ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_FIELD_PIPE and ROUTE_DISC_PIPE: a trace launch and a binning launch per chunk of at most pipe_chunk rays
 int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
-  int rc = set_lds(p.beam_fn ? (const void*)p.beam_fn : p.list_fn ? (const void*)p.list_fn : (const void*)p.fn, p.lds);
+  int rc = set_lds(p.beam_fn ? (const void*)p.beam_fn : p.baffle_fn ? (const void*)p.baffle_fn : p.list_fn ? (const void*)p.list_fn : (const void*)p.fn, p.lds);
   if (rc == ISX_OK && p.list_fn) rc = set_lds((const void*)p.fn, p.lds);   // (a chunk below the automatic rule's size takes it)
   if (rc == ISX_OK) rc = set_lds((const void*)p.bin, p.lds_bin);
   if (rc) return rc;
   const int tres = p.beam_fn ? blocks_per_cu(p.beam_fn, p.block, p.lds, p.per_cu) :
+                   p.baffle_fn ? blocks_per_cu(p.baffle_fn, p.block, p.lds, p.per_cu) :
                    p.list_fn ? blocks_per_cu(p.list_fn, p.block, p.lds, p.per_cu) : blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
   const int bres = blocks_per_cu(p.bin, p.bblock, p.lds_bin, p.bin_per_cu);
   // what the two kernels see: a flux map's trace kernel keeps no histogram; the disc sweep's kernels walk the discs in cluster order
@@ -1063,6 +1126,7 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     dt.rec_counts = db.rec_counts = S.d_rec_counts[buf];
     const int tgrid = pick_grid(p, cnt, tres);
     if (p.beam_fn) hipLaunchKernelGGL(p.beam_fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w, p.beam);
+    else if (p.baffle_fn) hipLaunchKernelGGL(p.baffle_fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w, p.baffles);
     else if (p.list_fn && (!p.fate_auto || cnt >= kFateMinRays)) {
       // the scan settles what the wall absorbs and leaves the rest in S.d_list, their number in ctr[Q_LIST] (zeroed with the
       // launch's other counters); the trace kernel's grid is sized from the chunk, an upper bound.  Same stream, no host round
@@ -1141,7 +1205,7 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
             int nbins_override, const double* d_discs, double disc_r, double disc_h, const PerPos* pp = nullptr,
             const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr, const ExitSink* xm = nullptr,
             const WallSink* wm = nullptr, const FieldSink* lf = nullptr, const OrderSink* oh = nullptr,
-            const PatchSink* wp = nullptr, const isx_beam_spec* bs = nullptr) {
+            const PatchSink* wp = nullptr, const isx_beam_spec* bs = nullptr, const BaffleSink* bf = nullptr) {
   Geom g;
   FateConsts fate;
   isx_config cb;
@@ -1153,11 +1217,19 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
   DetGrid d;
   size_t lds = 0;
   rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, xm, wm, lf, oh, wp, bs, d, lds);
+  if (rc == ISX_OK && bf) {
+    rc = check_baffle_call(c, bf->spec);
+    if (S.bin_mode == 2) d.bin_mode = 1;   // (isx.h: the trace-only diagnostic does not apply to the baffles)
+  }
   if (rc || n == 0) return rc;
   Work wk;
   wk.seed = seed; wk.first = first; wk.n = n; wk.hist = d_hist; wk.stats = d_stats ? d_stats : S.d_stats;
   wk.ctr = nullptr; wk.sub = 0; wk.pad = 0;
-  Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n, bs != nullptr, &fate);
+  Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n, bs != nullptr, &fate, bf != nullptr);
+  if (bf) {
+    if (p.lds_bin > S.lds_limit) return ISX_ERR_BAD_CONFIG;   // (isx.h: a grid whose tables do not fit the binning kernels' LDS)
+    p.baffles = baffle_table(*c, *bf->spec, bf->counts);
+  }
   if (sink == SINK_PATCH) p.patch_tab = patch_table(*c, *wp->spec);
   if (bs) {
     if (p.lds_bin > S.lds_limit) return ISX_ERR_BAD_CONFIG;   // (isx.h: a grid whose tables do not fit the binning kernels' LDS)
@@ -2262,6 +2334,102 @@ int isx_fluxmap_beam(const isx_config* cfg, const isx_beam_spec* spec, uint64_t 
   if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
   rc = call_close(rc, stats);
   if (rc == ISX_OK) fetch_result(hits, bytes);
+  return rc;
+}
+
+void isx_default_baffle_spec(const isx_config* cfg, isx_baffle_spec* spec) {
+  (void)cfg;
+  if (!spec) return;
+  std::memset(spec, 0, sizeof(*spec));
+  spec->struct_size = (uint32_t)sizeof(isx_baffle_spec);
+}
+
+int isx_baffle_disc(const isx_config* cfg, const double centre[3], const double dir[3], double radius, double reflectance,
+                    isx_baffle* out) {
+  if (!cfg || !centre || !dir || !out) return ISX_ERR_BAD_ARG;
+  if (!config_abi_ok(cfg)) return ISX_ERR_BAD_CONFIG;
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(centre[k]) || !std::isfinite(dir[k])) return ISX_ERR_BAD_CONFIG;
+  if (!std::isfinite(radius) || !(radius > 0.0)) return ISX_ERR_BAD_CONFIG;
+  if (!(reflectance >= 0.0 && reflectance <= 1.0)) return ISX_ERR_BAD_CONFIG;
+  const double dx = dir[0], dy = dir[1], dz = dir[2];
+  const double mag = std::sqrt(dx * dx + dy * dy + dz * dz);   // (prepare_geom's expression for the pencil, as isx_beam_cone)
+  if (!(mag > 0) || !std::isfinite(mag)) return ISX_ERR_BAD_CONFIG;
+  isx_baffle b;
+  std::memset(&b, 0, sizeof(b));
+  for (int k = 0; k < 3; ++k) b.centre[k] = centre[k];
+  b.normal[0] = dx / mag; b.normal[1] = dy / mag; b.normal[2] = dz / mag;
+  b.radius = radius;
+  b.reflectance = reflectance;
+  *out = b;
+  return ISX_OK;
+}
+
+int isx_baffle_endstates(const isx_config* cfg, const isx_baffle_spec* spec, uint64_t n, uint64_t seed, uint64_t first,
+                         int32_t* status, int32_t* n_points, double* last_point, double* direction, int32_t* last_baffle) {
+  // (what needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one)
+  if (!cfg || !spec || !status || !n_points || !last_point || !direction) return ISX_ERR_BAD_ARG;
+  int rc = check_baffle_call(cfg, spec);
+  if (rc) return rc;
+  if (!S.init) return not_initialised();
+  if (n == 0) return ISX_OK;
+  if (n > (1ull << 28)) return ISX_ERR_TOO_LARGE;
+  if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;
+  Geom g;
+  rc = prepare_geom(cfg, &g);
+  if (rc) return rc;
+  const BaffleTab t = baffle_table(*cfg, *spec, nullptr);
+  DevBuf<int32_t> b_st, b_np, b_lb;
+  DevBuf<double> b_lp, b_dir;
+  HIPCHK(b_st.alloc(n)); HIPCHK(b_np.alloc(n)); HIPCHK(b_lp.alloc(n * 3)); HIPCHK(b_dir.alloc(n * 3));
+  if (last_baffle) HIPCHK(b_lb.alloc(n));
+  const int blk = 256;
+  const unsigned grid = (unsigned)((n + blk - 1) / blk);
+  hipLaunchKernelGGL(isx_baffle_endstates_kernel, dim3(grid), dim3(blk), 0, S.stream, g, t, seed, first, n, b_st.p, b_np.p, b_lp.p,
+                     b_dir.p, b_lb.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(status, b_st.p, n * 4, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipMemcpyAsync(n_points, b_np.p, n * 4, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipMemcpyAsync(last_point, b_lp.p, n * 24, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipMemcpyAsync(direction, b_dir.p, n * 24, hipMemcpyDeviceToHost, S.stream));
+  if (last_baffle) HIPCHK(hipMemcpyAsync(last_baffle, b_lb.p, n * 4, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipStreamSynchronize(S.stream));
+  return ISX_OK;
+}
+
+int isx_fluxmap_baffle_device(const isx_config* cfg, const isx_baffle_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                              uint64_t* d_hits, uint64_t* d_counts) {
+  if (!cfg || !spec || !d_hits || !d_counts) return ISX_ERR_BAD_ARG;
+  int bad = check_baffle_call(cfg, spec);
+  if (bad == ISX_OK) bad = check_baffle_grid(cfg);
+  if (bad) return bad;
+  if (!S.init) return not_initialised();
+  const BaffleSink bf{spec, (unsigned long long*)d_counts};
+  return enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, (unsigned long long*)d_hits, 0, nullptr, 0, 0, nullptr, nullptr, nullptr,
+                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &bf);
+}
+
+int isx_fluxmap_baffle(const isx_config* cfg, const isx_baffle_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                       uint64_t* hits, isx_baffle_counts* counts, isx_stats* stats) {
+  if (!cfg || !spec || !hits) return ISX_ERR_BAD_ARG;
+  int rc = check_baffle_call(cfg, spec);
+  if (rc == ISX_OK) rc = check_baffle_grid(cfg);
+  if (rc) return rc;
+  if (!S.init) return not_initialised();
+  // the histogram and, behind it, the 16 counters: one device block, one staged result
+  const size_t nb = (size_t)cfg->n_theta * cfg->n_phi, nc = 4 * kMaxBaffles, bytes = (nb + nc) * sizeof(unsigned long long);
+  rc = call_open(nb + nc);
+  if (rc) return rc;
+  rc = zero_hist(nb + nc);
+  const BaffleSink bf{spec, S.d_hist + nb};
+  if (rc == ISX_OK) rc = enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, S.d_hist, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, &bf);
+  if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK) {
+    fetch_result(hits, nb * sizeof(unsigned long long));
+    if (counts) std::memcpy(counts, reinterpret_cast<const unsigned long long*>(S.h_pin + 64) + nb, nc * sizeof(unsigned long long));
+  }
   return rc;
 }
 

@@ -2297,6 +2297,85 @@ __device__ __forceinline__ void beam_start(const B& b, Ray& r, uint64_t seed, ui
   r.v.x = dx / mag; r.v.y = dy / mag; r.v.z = dz / mag;
 }
 
+// ------------------------------------------------------------------ baffles (isx.h: isx_fluxmap_baffle, isx_baffle_endstates)
+// The baffles of a call as the kernels get them (a kernel argument of its own; the trace kernel copies it into the workgroup's LDS
+// behind the rings): per disc the checked centre and normal, r2 = radius^2, rm = r_in * normal and the three constants of its
+// reflectance that the interaction needs (isx_api.hip: reflectance_consts, as the wall's own); the device counters of the call
+// (isx_baffle_counts' layout: arrivals [k][side], then absorbed [k][side]; NULL: not counted) and the count.
+constexpr int kMaxBaffles = 4;
+struct BaffleTab {
+  double centre[kMaxBaffles][3], normal[kMaxBaffles][3], rm[kMaxBaffles][3];
+  double r2[kMaxBaffles], psi_k1[kMaxBaffles], psi_k0[kMaxBaffles];
+  unsigned long long rho_thr[kMaxBaffles];
+  unsigned long long* counts;
+  int n, pad;
+};
+// LDS of the baffle kernel's block behind the rings: the table and its 4 kMaxBaffles u32 counters
+constexpr size_t kBaffleLds = ((sizeof(BaffleTab) + 4 * kMaxBaffles * sizeof(uint32_t)) + 15) & ~(size_t)15;
+// The segment test of isx.h's contract, operation for operation (IEEE double, left to right, no fma: -ffp-contract=off; / is the
+// correctly rounded one): the baffle that the segment p -> q strikes first -- the smallest f, on equal f the lowest index -- as
+// 2 k + side (side 0: the side the normal points to), or -1.  `skip` is the baffle of the ray's previous interaction (-1: none).
+// bf is the struck baffle's f: the struck point is baffle_point(p, q, bf) -- the expression the hit test looked at, formed again
+// by the one caller that needs it instead of being carried through the loop (six registers).  `t` is the kernel argument
+// (isx_baffle_endstates_kernel) or the workgroup's LDS copy (assist_body<.., BAFFLE>); both kernels call this and nothing else
+// states the test.
+__device__ __forceinline__ V3 baffle_point(const V3& p, const V3& q, double f) {
+  V3 c;
+  c.x = p.x + f * (q.x - p.x); c.y = p.y + f * (q.y - p.y); c.z = p.z + f * (q.z - p.z);
+  return c;
+}
+template <class B>
+__device__ __forceinline__ int baffle_segment(const B& t, int n, const V3& p, const V3& q, int skip, double& bf) {
+  int best = -1;
+  bf = 0.0;
+#pragma unroll 1
+  for (int k = 0; k < n; ++k) {
+    if (k == skip) continue;
+    const double cx = t.centre[k][0], cy = t.centre[k][1], cz = t.centre[k][2];
+    const double mx = t.normal[k][0], my = t.normal[k][1], mz = t.normal[k][2];
+    const double sp = ((p.x - cx) * mx + (p.y - cy) * my) + (p.z - cz) * mz;
+    const double sq = ((q.x - cx) * mx + (q.y - cy) * my) + (q.z - cz) * mz;
+    if ((sp > 0.0 && sq < 0.0) || (sp < 0.0 && sq > 0.0)) {   // (a NaN compares false: no crossing)
+      const double f = sp / (sp - sq);
+      const V3 c = baffle_point(p, q, f);
+      const double dx = c.x - cx, dy = c.y - cy, dz = c.z - cz;
+      if ((dx * dx + dy * dy) + dz * dz <= t.r2[k] && (best < 0 || f < bf)) {
+        best = 2 * k + (sp > 0.0 ? 0 : 1); bf = f;
+      }
+    }
+  }
+  return best;
+}
+// The interaction of a ray with side `side` of baffle k at x, with the words of its interaction j (isx.h's contract): the absorb
+// test on the raw word, then the cosine-law emission about the struck side's normal -- the library's own sphere point S (what
+// interact() forms for the inner sphere at q = 0), w = +-rm + S, v = w / |w| -- then the bounce limit.  The ray goes on from x on
+// no surface (the caller has moved it there): Ray::on becomes -(k + 1) -- on no boundary (baffle_on: K_NONE for the search), with
+// baffle k to be skipped by the next segment's test (baffle_skip) -- one register for both, in the lane and in a queue record.
+// Returns 0 while the ray runs, else its end status; the direction of an absorbed ray is left as it arrived.
+__device__ __forceinline__ int baffle_on(int on) { return on < 0 ? (int)K_NONE : on; }
+__device__ __forceinline__ int baffle_skip(int on) { return on < 0 ? -on - 1 : -1; }
+template <class B>
+__device__ __forceinline__ int baffle_arrive(const B& t, const Hot& h, Ray& r, uint64_t seed, uint64_t id_base, int k, int side) {
+  r.on = -(k + 1);
+  uint32_t wa, wb;
+  bounce_words<PH_DIRECT>(seed, id_base + (uint64_t)r.offset(), r.j, r.stream(), r.cw, wa, wb);
+  r.j++;
+  if (!((unsigned long long)wb < t.rho_thr[k])) return ST_ABSORBED;
+  const double zs = sphere_z(wa);
+  const double rs = sqrt_unit(fma(-zs, zs, 1.0));
+  double sf, cf;
+  circle_point_psi(fma((double)wb, t.psi_k1[k], t.psi_k0[k]), cf, sf);
+  const double Rrs = h.r_in * rs;
+  const double sx = Rrs * cf, sy = Rrs * sf, sz = h.r_in * zs;
+  double mx = t.rm[k][0], my = t.rm[k][1], mz = t.rm[k][2];
+  if (side != 0) { mx = -mx; my = -my; mz = -mz; }
+  const double wx = mx + sx, wy = my + sy, wz = mz + sz;
+  const double mag = sqrt((wx * wx + wy * wy) + wz * wz);
+  r.v.x = wx / mag; r.v.y = wy / mag; r.v.z = wz / mag;
+  if ((int)r.j + 1 > h.limit) return ST_SUSPENDED;
+  return 0;
+}
+
 // ------------------------------------------------------------------ persistent trace kernel, one per sink
 //   SINK_FLUX: 180x90 detector flux map (the headline path)
 //   SINK_DZ  : histogram of the exit direction's z component (distributionSphereDetectorSweep.C:54,91)
@@ -2918,16 +2997,26 @@ __device__ __forceinline__ void ray_unpack(const uint4& a, const uint4& b, const
 // list in HBM, not an index range -- a refilling lane takes list[k] where it took k, and the launch's ray count is the word the
 // scan left (read once per wave: the grid is sized from the chunk, an upper bound).  A launch that finds no ray ends through the
 // "queue dry" path like any other.  Everything else is isx_trace_assist_kernel.
+// BAFFLE (isx_fluxmap_baffle): discs inside the cavity that every segment is tested against (baffle_segment).  The tracer waves only
+// ask whether the segment rule S1' found is clear; a lane whose segment strikes a disc stays where it is and is handed over like a
+// lane whose rule failed.  The workgroup's shared first segment src -> Geom::q0 is tested by the thread that evaluates q0: a disc in
+// its way clears q0_ok.  The assist wave does what happens on a baffle: it searches as the end-state kernel does (next_hit: the ray
+// it was handed still obeys rule S1', a ray that leaves a baffle is a fresh ray at an interior point), tests the segment, and runs
+// baffle_arrive or the boundary's ray_arrive; Ray::on = -(k + 1) is "on baffle k" in the lane and in the pending ring's record.  The
+// table and the workgroup's 16 u32 counters lie behind the rings.  Exit lines, chunks, workspace and the kernels that follow are
+// isx_trace_assist_kernel's.  Explicit Lambertian lean path only.
 struct FateList { const uint32_t* list; const uint32_t* count; };
 template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false, bool ORDER = false, bool PATCH = false,
-          bool BEAM = false, bool LIST = false>
+          bool BEAM = false, bool LIST = false, bool BAFFLE = false>
 __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk, const PatchTab* tab_arg = nullptr,
-                                            const BeamSrc* beam_arg = nullptr, const FateList* list_arg = nullptr) {
+                                            const BeamSrc* beam_arg = nullptr, const FateList* list_arg = nullptr,
+                                            const BaffleTab* baf_arg = nullptr) {
   constexpr bool LEAN = SURF == SURF_LAMBERT;
   static_assert(LEAN || (CH == 0 && !RESC), "the chord identity and the BRDF re-scatter pipeline are built for the Lambertian border");
   static_assert(!PATCH || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER), "wall patches: the explicit Lambertian lean path, no other sink");
   static_assert(!BEAM || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && !PATCH), "beam source: the explicit Lambertian lean path, no other sink");
   static_assert(!LIST || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && !PATCH && !BEAM), "ray list: the explicit Lambertian lean path of the flux pipeline");
+  static_assert(!BAFFLE || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && !PATCH && !BEAM && !LIST), "baffles: the explicit Lambertian lean path of the flux pipeline");
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned long long* sstat = reinterpret_cast<unsigned long long*>(smem);
   Geom* g_lds = reinterpret_cast<Geom*>(sstat + 8);
@@ -2964,6 +3053,16 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   const uint32_t beam_wave = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform: a scalar register)
   volatile LdsDouble* park = (volatile LdsDouble*)(reinterpret_cast<unsigned char*>(hist) + kBeamSrcBytes) +
                               (size_t)beam_wave * (6 * 64);
+  // BAFFLE: the table | u32[arrivals [k][side] | absorbed [k][side]]
+  typedef __attribute__((address_space(3))) BaffleTab LdsBaffle;
+  uint32_t* bcnt = reinterpret_cast<uint32_t*>(reinterpret_cast<BaffleTab*>(hist) + 1);
+  int n_baf = 0;
+  if constexpr (BAFFLE) {
+    n_baf = baf_arg->n;   // (a kernel argument: wave-uniform, a scalar register)
+    if (tid == 65) *reinterpret_cast<BaffleTab*>(hist) = *baf_arg;
+    if (tid < 4 * kMaxBaffles) bcnt[tid] = 0u;
+  }
+  const volatile LdsBaffle& baf = *(const volatile LdsBaffle*)hist;
   if (tid < 8) sstat[tid] = 0ull;
   if (tid == 64) {
     *g_lds = g_arg;
@@ -2976,7 +3075,11 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       s0.x = g_arg.src[0]; s0.y = g_arg.src[1]; s0.z = g_arg.src[2];
       d0.x = g_arg.dir0[0]; d0.y = g_arg.dir0[1]; d0.z = g_arg.dir0[2];
       q0 = s0;
-      const bool ok = next_hit_s1<true>(h0, g_arg, s0, d0, K_NONE, q0);
+      bool ok = next_hit_s1<true>(h0, g_arg, s0, d0, K_NONE, q0);
+      if constexpr (BAFFLE) {   // the launch's shared first segment: a baffle in its way sends every fresh ray to the assist wave
+        double f0;
+        if (ok && baffle_segment(*baf_arg, n_baf, s0, q0, -1, f0) >= 0) ok = false;
+      }
       g_lds->q0[0] = q0.x; g_lds->q0[1] = q0.y; g_lds->q0[2] = q0.z;
       g_lds->q0_ok = ok ? 1 : 0;
     }
@@ -3199,6 +3302,11 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       };
       auto hot_search = [&](V3& q) -> bool {
         if (CH != 0 && r.tgt) return chord_arrive<true>(h, r, q);
+        if constexpr (BAFFLE) {   // a segment that strikes a baffle is the assist wave's: the ray stays where it is
+          if (!next_hit_s1<false>(h, g, r.p, r.v, K_INNER, q)) return false;
+          double f;
+          return baffle_segment(baf, n_baf, r.p, q, -1, f) < 0;
+        }
         return next_hit_s1<false>(h, g, r.p, r.v, K_INNER, q);
       };
       if (next == kDry) { ISX_TD_ADD(14, 1); ISX_TD_ADD(15, __popcll(__ballot(run))); }   // (-DISX_DIAG: trips after the launch's queue ran dry)
@@ -3402,6 +3510,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         const uint4 a = src[0], b = src[1], c = src[2], e = src[3];
         ray_unpack(a, b, c, e, r);
         r.on = (int)e.z;
+        if constexpr (BAFFLE) r.tgt = false;   // (explicit bounces only: the flag's bit is never set, and need not be carried)
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");          // (the slots are free once they have been read)
       if (lane == 0) add(&Q->pend_head, take);
@@ -3411,12 +3520,21 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       // need one.  (No room there: it takes its steps here.)
       int st = 0;
       bool go = have;
+      bool given = false;   // BAFFLE: the ray went back to the tracers from inside the step loop
+      (void)given;
       for (;;) {
         if (go) {
+          V3 q;
+          int kind;
+          if constexpr (BAFFLE) {
+            // (a tracer hands over a ray whose segment strikes a baffle with rule S1' intact, and a ray that leaves a baffle is a
+            //  fresh ray at an interior point: the whole search of the end-state kernel, rule S1 first)
+            kind = next_hit(h, g, r.p, r.v, baffle_on(r.on), q);
+          } else {
           if (CH != 0 && r.tgt) chord_leave(r);
           else if (r.on == K_INNER) unit_dir(r.v);   // handed over by a tracer whose rule S1' failed: unit direction from here on
-          V3 q;
-          const int kind = next_hit_generic(g, r.p, r.v, r.on, q);
+          kind = next_hit_generic(g, r.p, r.v, r.on, q);
+          }
           if (WALL && kind != K_BOX) wall_record(wspec, hist, wall_nmap, kind, r.j, q, 1u);
           if constexpr (PATCH) {
             Hot hp = h;
@@ -3424,6 +3542,17 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
             if (kind != K_BOX) cls = patch_arrive<false>(ptab, n_patch, pcnt, kind, q, hp);
             st = ray_arrive<false, LEAN, CH, PH_DIRECT, true, SURF>(hp, g, r, seed, first, kind, q);
             if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
+          } else if constexpr (BAFFLE) {
+            double bf;
+            const int ks = baffle_segment(baf, n_baf, r.p, q, baffle_skip(r.on), bf);
+            if (ks >= 0) {   // the segment ends on the baffle: its interaction instead of the boundary's
+              r.p = baffle_point(r.p, q, bf);
+              atomicAdd(&bcnt[ks], 1u);
+              st = baffle_arrive(baf, h, r, seed, first, ks >> 1, ks & 1);
+              if (st == ST_ABSORBED) atomicAdd(&bcnt[2 * kMaxBaffles + ks], 1u);
+            } else {
+              st = ray_arrive<false, LEAN, CH, PH_DIRECT, true, SURF>(h, g, r, seed, first, kind, q);
+            }
           } else
           st = ray_arrive<DISC || PP == 2, LEAN, CH, PH_DIRECT, true, SURF>(h, g, r, seed, first, kind, q);   // (DISC: r.prev = start of this segment)
           if (RESC && st != 0 && h.source_model == 1 && !r.scattered()) {   // nonLambertianFlux.C:253-268
@@ -3431,7 +3560,47 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
             ray_rescatter(g, r, seed, first);
             st = 0;
           }
-          if (st != 0 || r.on == K_INNER) go = false;
+          if (st != 0 || (!BAFFLE && r.on == K_INNER)) go = false;
+        }
+        if constexpr (BAFFLE) {
+          // This wave never WAITS for room in the resume ring.  With baffles most rays it is handed come back alive, so that ring
+          // fills; the tracer lanes take from it only when they are free, and a lane whose segment strikes a baffle is not free
+          // until this wave has taken its ray off the pending ring: with both rings full and every lane holding such a ray a wait
+          // here would never end (the tracers' trips keep the beat going, so it would not be given up either -- seen as a hang
+          // of the 5e7-ray call, docs/LOG.md section 18).  A ray on the inner sphere goes back if there is room NOW; else it goes
+          // to the pending ring below like a ray on the rim, or, with no room there either, takes its next step here.
+          const bool wb = go && r.on == K_INNER;
+          const unsigned long long bm = __ballot(wb);
+          if (bm) {
+            const uint32_t cnt = (uint32_t)__popcll(bm);
+            uint32_t pubr = 0, ok = 0;
+            if (lane == 0) {
+              for (;;) {
+                const uint32_t rs = ld(&Q->resume_res);
+                if (rs + cnt - ld(&Q->resume_head) > kResumeCap) break;
+                uint32_t expect = rs;
+                if (__hip_atomic_compare_exchange_strong(&Q->resume_res, &expect, rs + cnt, __ATOMIC_ACQ_REL, __ATOMIC_RELAXED,
+                                                         __HIP_MEMORY_SCOPE_WORKGROUP)) { pubr = rs; ok = 1u; break; }
+              }
+            }
+            ok = (uint32_t)__builtin_amdgcn_readfirstlane((int)ok);
+            pubr = (uint32_t)__builtin_amdgcn_readfirstlane((int)pubr);
+            if (ok) {
+              if (wb) {   // (the record of the "back to the tracers" block below, which this build never reaches)
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u));
+                uint32_t cw2 = 0u, cw3 = 0u;
+                if (r.j & 1u) {   // the tracer's next step finds words (2,3) of block j/2 in the lane (bounce_words, PH_EVEN)
+                  uint32_t wv[4];
+                  draw_block(seed, first + (uint64_t)r.offset(), r.j >> 1, r.stream(), wv);
+                  cw2 = wv[2]; cw3 = wv[3];
+                }
+                ray_pack(resume_q + 4 * ((pubr + rank) & (kResumeCap - 1)), r, cw2, cw3);
+                go = false; given = true;
+              }
+              __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+              if (lane == 0) add(&Q->resume_pub, cnt);
+            }
+          }
         }
         const unsigned long long gm = __ballot(go);
         if (gm == 0ull) break;
@@ -3530,7 +3699,10 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         reg_slot += cnt; reg_left -= cnt;
       }
       // ---- the rays that go on: back to the tracers
-      const bool back = have && st == 0 && !requeued;
+      // (BAFFLE: every ray that goes on was given back or requeued inside the step loop -- `back` is false in every lane, this
+      //  block is dead in that build, and its wait is the one that build must not have.  The other builds' expression is left
+      //  exactly as it was: one more operand changed the code of every older kernel.)
+      const bool back = BAFFLE ? false : (have && st == 0 && !requeued);
       const unsigned long long bm = __ballot(back);
       if (bm) {
         const uint32_t cnt = (uint32_t)__popcll(bm);
@@ -3594,7 +3766,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   // (BEAM: the thread index rebuilt from the wave's number -- a scalar -- and the lane's rank in the wave: kept from the kernel's
   //  entry for these last lines it is the one register more than the parking of the fresh rays leaves, and went to scratch)
   uint32_t tid_end = (uint32_t)tid;
-  if constexpr (BEAM) tid_end = beam_wave * 64u + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  if constexpr (BEAM || BAFFLE) tid_end = beam_wave * 64u + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   if (tid_end == 0u && Q->failed) atomicAdd(&wk.stats[7], (unsigned long long)Q->failed);
   if (WALL) {   // one flush of the workgroup's map; binned = its increments
     const unsigned long long flushed = wall_flush(d_arg, hist, tid, nthr);
@@ -3611,9 +3783,17 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     if (flushed) atomicAdd(&sstat[5], flushed);
     __syncthreads();
   }
+  if constexpr (BAFFLE) {   // one flush of the workgroup's counters (the thread index rebuilt, as the beam kernel's)
+    uint32_t t3 = tid_end;
+    asm volatile("" : "+v"(t3));
+    if (t3 < (uint32_t)(4 * kMaxBaffles)) {
+      const uint32_t c = bcnt[t3];
+      if (c) global_add_u64(baf_arg->counts + t3, (unsigned long long)c);
+    }
+  }
   {
     uint32_t t2 = threadIdx.x;
-    if constexpr (BEAM) t2 = tid_end;
+    if constexpr (BEAM || BAFFLE) t2 = tid_end;
     asm volatile("" : "+v"(t2));
     if (t2 < 7u) {
       const unsigned long long c = sstat[t2];
@@ -3664,6 +3844,11 @@ isx_trace_assist_patch_kernel(const Geom g, const DetGrid d, const Work wk, cons
 extern "C" __global__ void ISX_ASSIST_ATTR
 isx_trace_assist_beam_kernel(const Geom g, const DetGrid d, const Work wk, const BeamSrc beam) {
   assist_body<0, false, false, 0, SURF_LAMBERT, false, false, false, true>(g, d, wk, nullptr, &beam);
+}
+// baffles (isx_fluxmap_baffle): isx_trace_assist_kernel with every segment tested against the discs; the table is a fourth argument
+extern "C" __global__ void ISX_ASSIST_ATTR
+isx_trace_assist_baffle_kernel(const Geom g, const DetGrid d, const Work wk, const BaffleTab baf) {
+  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, false, false, false, true>(g, d, wk, nullptr, nullptr, nullptr, &baf);
 }
 // the flux pipeline behind the fate scan: isx_trace_assist_kernel on the rays of a list; the list is a fourth argument
 extern "C" __global__ void ISX_ASSIST_ATTR
@@ -4598,6 +4783,38 @@ isx_beam_endstates_kernel(const Geom g, const BeamSrc beam, uint64_t seed, uint6
   npts[i] = (int)r.j + 1 + (st == ST_EXITED ? 1 : 0);
   lp[3 * i] = r.p.x; lp[3 * i + 1] = r.p.y; lp[3 * i + 2] = r.p.z;
   dir[3 * i] = r.v.x; dir[3 * i + 1] = r.v.y; dir[3 * i + 2] = r.v.z;
+}
+
+// isx_baffle_endstates: the same with every segment tested against the baffles (baffle_segment / baffle_arrive); last_baffle
+// (may be NULL) is -1 or 2 k + side of the ray's last baffle interaction
+extern "C" __global__ void __launch_bounds__(256)
+isx_baffle_endstates_kernel(const Geom g, const BaffleTab baf, uint64_t seed, uint64_t first, uint64_t n, int32_t* __restrict__ status,
+                            int32_t* __restrict__ npts, double* __restrict__ lp, double* __restrict__ dir, int32_t* __restrict__ last) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Hot h = make_hot(g);
+  Ray r;
+  ray_start(g, r, (uint32_t)i);
+  int st, lb = -1;
+  for (;;) {
+    V3 q;
+    double bf;
+    const int kind = next_hit(h, g, r.p, r.v, baffle_on(r.on), q);
+    const int ks = baffle_segment(baf, baf.n, r.p, q, baffle_skip(r.on), bf);
+    if (ks >= 0) {
+      r.p = baffle_point(r.p, q, bf);
+      st = baffle_arrive(baf, h, r, seed, first, ks >> 1, ks & 1);
+      lb = ks;
+    } else {
+      st = ray_arrive<false, false, 2>(h, g, r, seed, first, kind, q);
+    }
+    if (st != 0) break;
+  }
+  status[i] = st;
+  npts[i] = (int)r.j + 1 + (st == ST_EXITED ? 1 : 0);
+  lp[3 * i] = r.p.x; lp[3 * i + 1] = r.p.y; lp[3 * i + 2] = r.p.z;
+  dir[3 * i] = r.v.x; dir[3 * i + 1] = r.v.y; dir[3 * i + 2] = r.v.z;
+  if (last) last[i] = lb;
 }
 
 // ------------------------------------------------------------------ device-side self test of the numeric contract

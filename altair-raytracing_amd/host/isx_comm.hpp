@@ -89,6 +89,10 @@ int wall_patches_all(const isx_config* cfg, const isx_wall_patch_spec* spec, uin
 // the beam-source flux map (isx_fluxmap_beam): contiguous ray ranges, histogram plus census in the one collective of the call
 int fluxmap_beam_all(const isx_config* cfg, const isx_beam_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
                      uint64_t* hits, isx_stats* st);
+// the flux map with baffles (isx_fluxmap_baffle): contiguous ray ranges; histogram, the 16 baffle counters and the census in the
+// one collective of the call
+int fluxmap_baffle_all(const isx_config* cfg, const isx_baffle_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                       uint64_t* hits, isx_baffle_counts* counts, isx_stats* st);
 // the wall map (isx_wall_map): the map and the four counters travel in the one collective of the call
 int wall_map_all(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
                  uint64_t* wall_map, isx_wall_map_counts* counts, isx_stats* st);

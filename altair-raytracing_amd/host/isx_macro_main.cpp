@@ -52,6 +52,8 @@ int main(int argc, char** argv) {
                  "  orderHist [--rays <n>] [--seed <s>] [--orders <n>] [--dz <n>] [--reflectances <a,b,...>] |\n"
                  "  wallPatches [--rays <n>] [--seed <s>] [--patch <ax,ay,az,half_angle_deg,rho>]... |\n"
                  "  beamFlux [--rays <n>] [--seed <s>] [--origin <x,y,z>] [--axis <x,y,z>] [--radius <r>] [--half-angle <deg>] [--law uniform|lambert] |\n"
+                 "  baffleFlux [--rays <n>] [--seed <s>] [--centre <x,y,z> --normal <x,y,z> --radius <r> --reflectance <rho>]... |\n"
+                 "    (--radius is beamFlux's and baffleFlux's: every one given is a baffle's radius, the last one the beam's) |\n"
                  "  distributionSphereDetectorSweep | --selftest-writer <file> | --unique <path> | --shard <n> | --analyze <csv>... | --analyze <folder> [average]\n";
     return 2;
   }
@@ -113,7 +115,21 @@ int main(int argc, char** argv) {
         const double v = std::strtod(argv[i + 1], &rest);
         if (rest == argv[i + 1] || *rest != '\0') { std::cerr << "bad number for --" << key << ": " << argv[i + 1] << "\n"; return 2; }
         (key == "radius" ? options().beam_radius : options().beam_half_angle) = v;
+        if (key == "radius") options().baffle_radii.push_back(v);   // (baffleFlux: one per baffle)
       } else options().beam_law = argv[i + 1];
+      ++i;
+      continue;
+    }
+    if ((!std::strcmp(argv[i], "--centre") || !std::strcmp(argv[i], "--normal") || !std::strcmp(argv[i], "--reflectance")) && i + 1 < argc) {   // baffleFlux (repeatable)
+      const std::string key = argv[i] + 2;
+      if (key == "centre") options().baffle_centres.push_back(argv[i + 1]);
+      else if (key == "normal") options().baffle_normals.push_back(argv[i + 1]);
+      else {   // a number, the whole token
+        char* rest = nullptr;
+        const double v = std::strtod(argv[i + 1], &rest);
+        if (rest == argv[i + 1] || *rest != '\0') { std::cerr << "bad number for --" << key << ": " << argv[i + 1] << "\n"; return 2; }
+        options().baffle_reflectances.push_back(v);
+      }
       ++i;
       continue;
     }
@@ -143,6 +159,7 @@ int main(int argc, char** argv) {
   else if (entry == "orderHist") rootMacros::orderHist();
   else if (entry == "wallPatches") rootMacros::wallPatches();
   else if (entry == "beamFlux") rootMacros::beamFlux();
+  else if (entry == "baffleFlux") rootMacros::baffleFlux();
   else { std::cerr << "unknown entry point " << entry << "\n"; return 2; }
   const bool ok = ensure_device();  // false: the entry point printed its error and returned early
   comm().finalize();

@@ -1534,6 +1534,103 @@ void beamFlux() {
   f << "# Detector hits: " << st.bin_increments << std::endl;
 }
 
+// Flux map of the library's default sphere with baffles in the cavity (isx.h: isx_fluxmap_baffle).
+void baffleFlux() {
+  if (!ready_everywhere()) return;
+  isx_config c;
+  isx_default_config(&c);
+  const long n = pick_n(1000000);
+  // exactly three numbers, each the whole of its token
+  auto triple = [](const std::string& arg, double v[3]) {
+    int got = 0;
+    std::stringstream ss(arg);
+    std::string tok;
+    while (std::getline(ss, tok, ',')) {
+      char* rest = nullptr;
+      const double x = std::strtod(tok.c_str(), &rest);
+      if (got == 3 || rest == tok.c_str() || *rest != '\0') return false;
+      v[got++] = x;
+    }
+    return got == 3 && !arg.empty() && arg.back() != ',';
+  };
+  const RunOptions& o = options();
+  const size_t nb = o.baffle_centres.size();
+  if (nb > (size_t)ISX_MAX_BAFFLES || o.baffle_normals.size() != nb || o.baffle_radii.size() != nb || o.baffle_reflectances.size() != nb) {
+    err() << "Error: a baffle wants --centre, --normal, --radius and --reflectance, one of each, " << ISX_MAX_BAFFLES << " baffles at most" << std::endl;
+    return;
+  }
+  isx_baffle_spec sp;
+  isx_default_baffle_spec(&c, &sp);
+  for (size_t k = 0; k < nb; ++k) {
+    double centre[3], normal[3];
+    if (!triple(o.baffle_centres[k], centre) || !triple(o.baffle_normals[k], normal)) {
+      err() << "Error: --centre and --normal want x,y,z" << std::endl;
+      return;
+    }
+    const int rc = isx_baffle_disc(&c, centre, normal, o.baffle_radii[k], o.baffle_reflectances[k], &sp.baffle[k]);
+    if (rc != ISX_OK) {
+      err() << "Error: isx_baffle_disc: " << isx_strerror(rc) << std::endl;
+      return;
+    }
+  }
+  sp.n_baffles = (int32_t)nb;
+  std::vector<uint64_t> hits((size_t)c.n_theta * c.n_phi);
+  isx_stats st;
+  isx_baffle_counts bc{};
+  const uint64_t first = take_rays((uint64_t)n);
+  const int rc = fluxmap_baffle_all(&c, &sp, (uint64_t)n, options().seed, first, hits.data(), &bc, &st);
+  if (rc != ISX_OK) {
+    err() << "Error: isx_fluxmap_baffle: " << isx_strerror(rc) << std::endl;
+    return;
+  }
+  std::cout << "Total rays exiting port: " << st.counted_below_z << " out of " << n << std::endl;
+  FluxMapMeta mm;
+  mm.title = "Flux Map Data (Baffles)";
+  mm.n_label = "Number of rays";
+  mm.method_line = "Trace-Once (single trace, multiple detector positions)";
+  mm.n = n; mm.det_w = mm.det_h = c.det_diameter; mm.r_in = c.r_in; mm.r_out = c.r_out; mm.thetaMax = c.theta_max_deg;
+  mm.nTheta = c.n_theta; mm.nPhi = c.n_phi; mm.reflectance = c.reflectance; mm.roughness = c.roughness_rad; mm.maxReflections = c.max_points;
+  for (int k = 0; k < 3; ++k) { mm.src[k] = c.src[k]; mm.dir[k] = c.dir[k]; }
+  // the flux maps' header with the baffles' lines ahead of the column line
+  std::string head = fluxmap_header(mm, currentTimeString());
+  const std::string cols = "theta,phi,fraction\n";
+  if (head.size() < cols.size() || head.compare(head.size() - cols.size(), cols.size(), cols) != 0) {
+    err() << "Error: the flux-map header does not end with its column line" << std::endl;
+    return;
+  }
+  head.erase(head.size() - cols.size());
+  std::ofstream f(outputPath("baffle_flux.csv"));
+  f << head;
+  {
+    std::ostringstream os;
+    os << std::setprecision(17);
+    os << "# Seed: " << options().seed << std::endl;
+    os << "# First ray: " << first << std::endl;
+    os << "# Baffles: " << sp.n_baffles << std::endl;
+    for (int k = 0; k < sp.n_baffles; ++k) {
+      const isx_baffle& b = sp.baffle[k];
+      os << "# Baffle " << k << " centre (x,y,z): " << b.centre[0] << "cm, " << b.centre[1] << "cm, " << b.centre[2] << "cm" << std::endl;
+      os << "# Baffle " << k << " normal (x,y,z): " << b.normal[0] << ", " << b.normal[1] << ", " << b.normal[2] << std::endl;
+      os << "# Baffle " << k << " radius: " << b.radius << "cm" << std::endl;
+      os << "# Baffle " << k << " reflectance: " << b.reflectance << std::endl;
+    }
+    f << os.str();
+  }
+  f << cols;
+  f << fluxmap_rows(hits.data(), n, c.n_theta, c.n_phi, 1);
+  for (int k = 0; k < sp.n_baffles; ++k) {
+    f << "# Baffle " << k << " arrivals (side 0, side 1): " << bc.arrivals[k][0] << ", " << bc.arrivals[k][1] << std::endl;
+    f << "# Baffle " << k << " absorbed (side 0, side 1): " << bc.absorbed[k][0] << ", " << bc.absorbed[k][1] << std::endl;
+  }
+  f << "# Launched: " << st.launched << std::endl;
+  f << "# Exited: " << st.exited << std::endl;
+  f << "# Total rays exiting port: " << st.counted_below_z << " out of " << n << std::endl;
+  f << "# Absorbed: " << st.absorbed << std::endl;
+  f << "# Suspended: " << st.suspended << std::endl;
+  f << "# Wall hits: " << st.wall_hits << std::endl;
+  f << "# Detector hits: " << st.bin_increments << std::endl;
+}
+
 }  // namespace rootMacros
 
 }  // namespace isxhost

@@ -60,6 +60,9 @@ struct RunOptions {
   // beamFlux --origin x,y,z --axis x,y,z --radius r --half-angle deg --law uniform|lambert (defaults: the pencil of the default config)
   std::string beam_origin, beam_axis, beam_law = "uniform";
   double beam_radius = 0.0, beam_half_angle = 0.0;
+  // baffleFlux --centre x,y,z --normal x,y,z --radius r --reflectance rho, repeatable: the k-th of each makes baffle k
+  std::vector<std::string> baffle_centres, baffle_normals;
+  std::vector<double> baffle_radii, baffle_reflectances;
   bool quiet = false;              // env ISX_QUIET
   int flush_rows = 0;              // env ISX_FLUSH_ROWS: theta rows per launch of the per-position sweep, written and flushed
                                    // before the next launch starts (0 = as many as hold ~4e9 rays: one launch for the reference's n)
@@ -197,6 +200,10 @@ void wallPatches();
 // the flux map of the default sphere lit by a beam source (--origin, --axis, --radius, --half-angle, --law; isx_beam_cone makes
 // the spec) through isx_fluxmap_beam: beam_flux.csv in the flux maps' format (theta,phi,fraction), the beam in the # metadata
 void beamFlux();
+// the flux map of the default sphere with up to four baffles in the cavity (--centre, --normal, --radius, --reflectance, each
+// repeatable: isx_baffle_disc makes baffle k from the k-th of each) through isx_fluxmap_baffle: baffle_flux.csv in the flux maps'
+// format (theta,phi,fraction), the baffles and their counters in the # metadata
+void baffleFlux();
 }  // namespace rootMacros
 
 }  // namespace isxhost

@@ -229,3 +229,34 @@ def fluxmap_beam_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, fi
     `trace(cfg, spec, count, seed, first) -> (hits, stats)`, then the flux map's ONE SUM all-reduce of histogram plus census.
     Returns (hits[n_theta, n_phi] uint64, census dict) -- identical on every rank."""
     return fluxmap_sharded(lambda c, count, s, first: trace(c, spec, count, s, first), cfg, n_total, seed, first_ray, device)
+
+
+def fluxmap_baffle_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, first_ray: int = 0, device=None):
+    """The flux map with baffles (altair_raytracing_amd.fluxmap_baffle) ray-sharded: this rank's contiguous shard through
+    `trace(cfg, spec, count, seed, first) -> (hits, counts, stats)`, then ONE SUM all-reduce that carries the histogram, the 16
+    baffle counters and the census.  Returns (hits[n_theta, n_phi] uint64, arrivals[4, 2] uint64, absorbed[4, 2] uint64, census
+    dict) -- identical on every rank."""
+    import torch
+    import torch.distributed as dist
+
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(), dist.get_world_size()
+    else:
+        rank, world = 0, 1
+    first, count = shard(n_total, rank, world)
+    hits, cnt, st = trace(cfg, spec, count, seed, first_ray + first)
+    arr, ab = cnt.arrays()
+    census = np.array([getattr(st, k) for k in CENSUS_FIELDS], dtype=np.int64)
+    if world > 1:
+        buf = torch.from_numpy(np.concatenate([hits.reshape(-1).astype(np.int64), arr.reshape(-1).astype(np.int64),
+                                               ab.reshape(-1).astype(np.int64), census]))
+        if device is not None:
+            buf = buf.to(device)
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+        buf = buf.cpu().numpy()
+        nh, na = hits.size, arr.size
+        hits = buf[:nh].astype(np.uint64).reshape(hits.shape)
+        arr = buf[nh:nh + na].astype(np.uint64).reshape(arr.shape)
+        ab = buf[nh + na:nh + 2 * na].astype(np.uint64).reshape(ab.shape)
+        census = buf[nh + 2 * na:]
+    return hits, arr, ab, dict(zip(CENSUS_FIELDS, (int(x) for x in census)))

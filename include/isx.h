@@ -734,6 +734,98 @@ int isx_fluxmap_beam_device(const isx_config* cfg, const isx_beam_spec* spec, ui
                             uint64_t* d_hits);
 
 /*
+ * Baffles: up to ISX_MAX_BAFFLES flat two-sided discs inside the cavity that block and scatter rays -- what keeps the first-strike
+ * spot, or a lamp, from being seen directly by the port or a detector.  The ray is traced exactly as isx_fluxmap /
+ * isx_trace_endstates trace it -- Philox stream 0, the words of interaction j, the bounce limit and the census are unchanged --
+ * except that every segment is tested against the baffles before the ray is taken to its next boundary point.
+ *
+ * A segment runs from the ray's current point p to q, the next boundary point the library finds from p (of any kind, the world
+ * box included).  Once per call, on the host: r2 = radius * radius; rm[i] = cfg->r_in * normal[i]; rho_thr, psi_k1, psi_k0 of the
+ * baffle's reflectance exactly as the library derives them from cfg->reflectance.  Per segment, in IEEE double, every expression
+ * evaluated left to right as written, no fma; / and sqrt are the correctly rounded ones (c = centre, m = normal):
+ *
+ *       for each baffle k except the one the ray's previous interaction was with:
+ *           s_p = ((p.x - c.x) * m.x + (p.y - c.y) * m.y) + (p.z - c.z) * m.z;   s_q = the same with q
+ *           crossing iff (s_p > 0 and s_q < 0) or (s_p < 0 and s_q > 0)                     (a NaN: no crossing)
+ *           f = s_p / (s_p - s_q);   x.i = p.i + f * (q.i - p.i);   d = x - c
+ *           hit iff (d.x * d.x + d.y * d.y) + d.z * d.z <= r2
+ *       the baffle with the smallest f is struck; on equal f the lowest k.  No hit: the ray goes to q as always.
+ *
+ * On a hit the interaction of the ray's index j runs on the baffle, with the words (wa, wb) a wall interaction of that j has:
+ *   - side = s_p > 0 ? 0 : 1 (side 0 is the side the normal points to); arrivals[k][side] += 1; the ray's point becomes x;
+ *     n_points += 1; j += 1.
+ *   - The ray survives iff wb < rho_thr(baffle k).  Otherwise absorbed[k][side] += 1 and the ray ends ISX_RAY_ABSORBED with last
+ *     point x; its direction is that of the segment it arrived on, as for a ray the wall absorbs.
+ *   - Re-emission by the cosine law about the struck side's normal, from the library's own sphere point:
+ *       zs = fma(-2^-31, wa, 1 - 2^-32);  rs = sqrt(fma(-zs, zs, 1));  (cf, sf) = circle_point_psi(fma(wb, psi_k1, psi_k0))
+ *       Rrs = r_in * rs;  S = (Rrs * cf, Rrs * sf, r_in * zs)
+ *     (bit for bit what the inner sphere's emission gives for q = (0, 0, 0): the oracle's isxo_cosine_emission of kind 1 there,
+ *     with the baffle's reflectance in cfg);  w.i = rm[i] + S.i on side 0, (-rm[i]) + S.i on side 1;
+ *       mag = sqrt((w.x * w.x + w.y * w.y) + w.z * w.z);  v = (w.x / mag, w.y / mag, w.z / mag)
+ *   - The bounce limit is then applied as after a wall interaction.  The ray goes on from x along v on no surface: its next
+ *     boundary is searched as for the first segment of a pencil placed at x, with baffle k skipped for that one segment.
+ *
+ * stats.wall_hits counts baffle interactions too, stats.absorbed the rays a baffle absorbs, stats.bin_increments is the
+ * histogram's sum: sum(arrivals) + (wall interactions) == wall_hits and sum(absorbed[k][s]) <= stats.absorbed for every call.
+ * With n_baffles == 0 every result is bit for bit that of isx_fluxmap / isx_trace_endstates (through the baffle kernels all the
+ * same: one route whatever the switches say, as for the beam; the fate scan does not apply).  No result depends on any
+ * isx_set_option switch nor on how a job is cut into calls.
+ *
+ * Scope: ISX_SOURCE_PENCIL, ISX_SURFACE_ROBAST with `lambertian` set, ISX_TRACE_EXPLICIT, both hit-line modes.  Refused with
+ * ISX_ERR_BAD_CONFIG, whether or not a device is present: anything outside that scope; struct_size != sizeof(isx_baffle_spec) (or
+ * a cfg of the wrong size); n_baffles outside 0 .. ISX_MAX_BAFFLES; a field of a baffle that is not finite; radius <= 0; a
+ * reflectance outside [0, 1]; | sqrt(m . m) - 1 | > 1e-12; a baffle that does not satisfy
+ * (sqrt(c . c) + radius) * (1 + 1e-12) < cfg->r_in (plain products summed left to right) -- the disc lies strictly inside the
+ * cavity and never touches a wall; and, for the two flux-map calls, a detector grid that isx_fluxmap refuses or whose tables --
+ * 4 B per bin, 32 B per row, 64 B per column -- do not fit the binning kernels' LDS (the device's once isx_init() has asked it,
+ * 160 KiB before; the default 180 x 90 grid fits).  ISX_ERR_BAD_ARG: a NULL pointer (last_baffle, counts and
+ * stats excepted).  Without a HIP device: ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT.
+ * Out of scope: the beam source combined with baffles, baffles for the other sinks (exit maps, wall map, light field, order
+ * histograms, wall patches, disc sweeps), and the chord mode.
+ */
+#define ISX_MAX_BAFFLES 4
+typedef struct isx_baffle {
+  double centre[3];
+  double normal[3];     /* USED AS GIVEN; side 0 is the side the normal points to */
+  double radius;        /* > 0 */
+  double reflectance;   /* in [0, 1], both sides */
+} isx_baffle;
+typedef struct isx_baffle_spec {
+  uint32_t struct_size;      /* sizeof(isx_baffle_spec), set by isx_default_baffle_spec() */
+  uint32_t reserved0;        /* 0 */
+  int32_t n_baffles;         /* 0 .. ISX_MAX_BAFFLES */
+  int32_t reserved1;         /* 0 */
+  isx_baffle baffle[ISX_MAX_BAFFLES];
+} isx_baffle_spec;
+typedef struct isx_baffle_counts {
+  uint64_t arrivals[ISX_MAX_BAFFLES][2];   /* [baffle][side] */
+  uint64_t absorbed[ISX_MAX_BAFFLES][2];
+} isx_baffle_counts;
+
+/* No baffle: n_baffles 0, everything else zero.  Host only, no GPU needed (cfg is not looked at). */
+void isx_default_baffle_spec(const isx_config* cfg, isx_baffle_spec* spec);
+/* Host only, no GPU needed: the disc of `radius` about `centre` with normal = dir / |dir| (as isx_beam_cone normalises its axis:
+ * mag = sqrt(dx*dx + dy*dy + dz*dz), three divisions).  ISX_ERR_BAD_ARG: a NULL argument; ISX_ERR_BAD_CONFIG: a cfg of the wrong
+ * size, centre or dir not finite, dir of zero length, radius not finite or <= 0, reflectance outside [0, 1].  Whether the disc
+ * lies inside the cavity is checked by the calls that trace it. */
+int isx_baffle_disc(const isx_config* cfg, const double centre[3], const double dir[3], double radius, double reflectance,
+                    isx_baffle* out);
+/* isx_trace_endstates with the baffles; last_baffle[i] (may be NULL) is -1 if ray i never touched a baffle, else 2 k + side of
+ * its last baffle interaction. */
+int isx_baffle_endstates(const isx_config* cfg, const isx_baffle_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                         int32_t* status, int32_t* n_points, double* last_point /*[n][3]*/, double* direction /*[n][3]*/,
+                         int32_t* last_baffle /*[n]*/);
+/* isx_fluxmap / isx_fluxmap_device with the baffles: hits [n_theta * n_phi] and counts, zeroed by the callee (counts and stats
+ * may be NULL).  The device form ACCUMULATES into d_hits and d_counts (16 words, isx_baffle_counts' layout; neither may be NULL)
+ * and returns after enqueueing; isx_sync() / isx_take_stats() as for isx_fluxmap_device.  The trace kernel is
+ * isx_trace_assist_baffle_kernel, the binning kernels are isx_fluxmap's ("pipeline" 0, "assist" 0, "fate_scan" and "bin_mode" 2
+ * do not apply; "bin_mode" 0 bins by brute force). */
+int isx_fluxmap_baffle(const isx_config* cfg, const isx_baffle_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                       uint64_t* hits, isx_baffle_counts* counts, isx_stats* stats);
+int isx_fluxmap_baffle_device(const isx_config* cfg, const isx_baffle_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                              uint64_t* d_hits, uint64_t* d_counts /*[16]*/);
+
+/*
  * Series driver (sweepSeries, fluxAtObserverOptimize.C:892-921 / fluxAtObserverFast.C:1641-1673):
  * n_cfg configurations sharing one detector grid, traced back to back on the device with ONE
  * host synchronisation; hits[n_cfg][n_theta*n_phi], stats[n_cfg] (t_kernel_ms = whole series).
