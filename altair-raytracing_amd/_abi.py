@@ -49,6 +49,7 @@ EXPORTS = [
     "isx_default_wall_patch_spec", "isx_wall_patch_cap", "isx_wall_patches", "isx_wall_patches_device",
     "isx_default_beam_spec", "isx_beam_cone", "isx_beam_endstates", "isx_fluxmap_beam", "isx_fluxmap_beam_device",
     "isx_default_baffle_spec", "isx_baffle_disc", "isx_baffle_endstates", "isx_fluxmap_baffle", "isx_fluxmap_baffle_device",
+    "isx_default_scene_spec", "isx_scene_endstates", "isx_fluxmap_scene", "isx_fluxmap_scene_device",
 ]
 
 
@@ -231,6 +232,37 @@ class BaffleCounts(C.Structure):
         return a, b
 
 
+class SceneSpec(C.Structure):
+    """isx_scene_spec (include/isx.h): the beam source, the baffles and the wall patches of one trace."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("beam", BeamSpec), ("baffles", BaffleSpec),
+                ("patches", WallPatchSpec)]
+
+    def copy(self):
+        s = SceneSpec()
+        C.memmove(C.byref(s), C.byref(self), C.sizeof(SceneSpec))
+        return s
+
+
+class SceneCounts(C.Structure):
+    """isx_scene_counts (include/isx.h): arrivals and absorbed rays per wall class and per [baffle][side]; 36 words."""
+
+    _fields_ = [("patch_arrivals", C.c_uint64 * (MAX_WALL_PATCHES + 2)), ("patch_absorbed", C.c_uint64 * (MAX_WALL_PATCHES + 2)),
+                ("baffle", BaffleCounts)]
+
+    def arrays(self):
+        """-> (patch_arrivals[MAX_WALL_PATCHES + 2], patch_absorbed[...], baffle arrivals[MAX_BAFFLES, 2], baffle absorbed[...]) uint64"""
+        pa = np.array(list(self.patch_arrivals), dtype=np.uint64)
+        pb = np.array(list(self.patch_absorbed), dtype=np.uint64)
+        return (pa, pb) + self.baffle.arrays()
+
+    def words(self):
+        """-> the 36 words in the struct's order (the device form's layout)"""
+        return np.frombuffer(bytes(self), dtype=np.uint64).copy()
+
+
+SCENE_COUNT_WORDS = 2 * (MAX_WALL_PATCHES + 2) + 4 * MAX_BAFFLES   # sizeof(isx_scene_counts) / 8
+
 _lib = None
 
 
@@ -306,6 +338,12 @@ def load():
     L.isx_baffle_endstates.argtypes = [P(Config), P(BaffleSpec), u64, u64, u64, P(i32), P(i32), P(dbl), P(dbl), P(i32)]
     L.isx_fluxmap_baffle.argtypes = [P(Config), P(BaffleSpec), u64, u64, u64, P(u64), P(BaffleCounts), P(Stats)]
     L.isx_fluxmap_baffle_device.argtypes = [P(Config), P(BaffleSpec), u64, u64, u64, C.c_void_p, C.c_void_p]
+    L.isx_default_scene_spec.argtypes = [P(Config), P(SceneSpec)]
+    L.isx_default_scene_spec.restype = None
+    L.isx_scene_endstates.argtypes = [P(Config), P(SceneSpec), u64, u64, u64, P(i32), P(i32), P(dbl), P(dbl), P(dbl), P(dbl), P(i32),
+                                      P(i32)]
+    L.isx_fluxmap_scene.argtypes = [P(Config), P(SceneSpec), u64, u64, u64, P(u64), P(SceneCounts), P(Stats)]
+    L.isx_fluxmap_scene_device.argtypes = [P(Config), P(SceneSpec), u64, u64, u64, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -796,6 +834,58 @@ def fluxmap_baffle_device(cfg, spec, n_rays, seed, first_ray, d_hits_ptr, d_coun
     _chk(load().isx_fluxmap_baffle_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
                                           C.c_void_p(int(d_hits_ptr or 0) or None), C.c_void_p(int(d_counts_ptr or 0) or None)),
          "isx_fluxmap_baffle_device")
+
+
+def default_scene_spec(cfg):
+    """The empty scene: the pencil of `cfg` as a beam, no baffle, no patch (no GPU needed)."""
+    s = SceneSpec()
+    load().isx_default_scene_spec(C.byref(cfg), C.byref(s))
+    return s
+
+
+def scene_spec(cfg, beam=None, baffles=(), patches=()):
+    """-> SceneSpec: the BeamSpec `beam` (None: the pencil of `cfg`), the Baffle objects and the WallPatch objects, in order."""
+    s = default_scene_spec(cfg)
+    if beam is not None:
+        C.memmove(C.byref(s.beam), C.byref(beam), C.sizeof(BeamSpec))
+    bs, ps = baffle_spec(cfg, baffles), wall_patch_spec(cfg, patches)
+    C.memmove(C.byref(s.baffles), C.byref(bs), C.sizeof(BaffleSpec))
+    C.memmove(C.byref(s.patches), C.byref(ps), C.sizeof(WallPatchSpec))
+    return s
+
+
+def scene_endstates(cfg, spec, n, seed, first_ray=0):
+    """-> (status, n_points, last_point, direction, start_point, start_dir, last_baffle, last_class): trace_endstates of the
+    scene; last_baffle is -1 or 2 k + side of the ray's last baffle interaction, last_class -1 or the class of its last mirror
+    interaction."""
+    n = int(n)
+    status = np.zeros(n, dtype=np.int32)
+    npts = np.zeros(n, dtype=np.int32)
+    lb = np.zeros(n, dtype=np.int32)
+    lc = np.zeros(n, dtype=np.int32)
+    lp, d, sp, sd = (np.zeros((n, 3), dtype=np.float64) for _ in range(4))
+    _chk(load().isx_scene_endstates(C.byref(cfg), C.byref(spec), n, int(seed), int(first_ray), _p(status, C.c_int32),
+                                    _p(npts, C.c_int32), _p(lp, C.c_double), _p(d, C.c_double), _p(sp, C.c_double),
+                                    _p(sd, C.c_double), _p(lb, C.c_int32), _p(lc, C.c_int32)), "isx_scene_endstates")
+    return status, npts, lp, d, sp, sd, lb, lc
+
+
+def fluxmap_scene(cfg, spec, n_rays, seed, first_ray=0):
+    """-> (hits[n_theta, n_phi] uint64, SceneCounts, Stats): the flux map of the scene `spec` (include/isx.h: isx_fluxmap_scene)."""
+    hits = np.zeros(max(cfg.n_theta, 0) * max(cfg.n_phi, 0), dtype=np.uint64)
+    st = Stats()
+    cnt = SceneCounts()
+    _chk(load().isx_fluxmap_scene(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray), _p(hits, C.c_uint64),
+                                  C.byref(cnt), C.byref(st)), "isx_fluxmap_scene")
+    return hits.reshape(cfg.n_theta, cfg.n_phi), cnt, st
+
+
+def fluxmap_scene_device(cfg, spec, n_rays, seed, first_ray, d_hits_ptr, d_counts_ptr):
+    """Enqueue on the library stream, accumulating into device memory at d_hits_ptr ([n_theta * n_phi] uint64) and d_counts_ptr
+    ([36] uint64, SceneCounts' layout)."""
+    _chk(load().isx_fluxmap_scene_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
+                                         C.c_void_p(int(d_hits_ptr or 0) or None), C.c_void_p(int(d_counts_ptr or 0) or None)),
+         "isx_fluxmap_scene_device")
 
 
 def fluxmap_series(cfgs, n_rays, seed, first_ray=0):

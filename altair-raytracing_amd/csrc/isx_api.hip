@@ -587,6 +587,23 @@ BaffleTab baffle_table(const isx_config& c, const isx_baffle_spec& s, unsigned l
   return t;
 }
 
+// isx_fluxmap_scene: the checked spec and the device counters of the call (isx_scene_counts' layout: 36 words)
+constexpr int kSceneBlock = 640;
+struct SceneSink { const isx_scene_spec* spec = nullptr; unsigned long long* counts = nullptr; };
+constexpr size_t kSceneWords = sizeof(isx_scene_counts) / sizeof(uint64_t);
+static_assert(kSceneWords == 2 * (kMaxPatches + 2) + 4 * kMaxBaffles, "isx.h and the kernels' counters");
+static_assert(kPatchLds == (sizeof(PatchTab) + 2 * (kMaxPatches + 2) * sizeof(uint32_t) + 15) / 16 * 16, "SceneLds and patch_lds()");
+// isx.h: what the three component calls refuse (the nested struct_size fields are theirs to check), in the order beam, baffles,
+// patches; `grid`: the two flux-map calls, whose detector grid has to fit the binning kernels' LDS
+int check_scene_call(const isx_config* c, const isx_scene_spec* s, bool grid) {
+  if (!config_abi_ok(c) || s->struct_size != (uint32_t)sizeof(isx_scene_spec)) return ISX_ERR_BAD_CONFIG;
+  int rc = check_beam_call(c, &s->beam);
+  if (rc == ISX_OK) rc = check_baffle_call(c, &s->baffles);
+  if (rc == ISX_OK) rc = check_patch_call(c, &s->patches);
+  if (rc == ISX_OK && grid) rc = check_baffle_grid(c);
+  return rc;
+}
+
 // LDS of a workgroup's histogram: 4 B per bin, 16-byte aligned
 size_t hist_lds(int nbins) { return ((size_t)nbins * 4 + 15) & ~(size_t)15; }
 
@@ -732,6 +749,7 @@ typedef void (*PatchFn)(const Geom, const DetGrid, const Work, const PatchTab);
 typedef void (*BeamFn)(const Geom, const DetGrid, const Work, const BeamSrc);
 typedef void (*ListFn)(const Geom, const DetGrid, const Work, const FateList);
 typedef void (*BaffleFn)(const Geom, const DetGrid, const Work, const BaffleTab);
+typedef void (*SceneFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab);
 struct Plan {
   Route route = ROUTE_FUSED;
   KernelFn fn = nullptr;        // the kernel (a pipeline's trace kernel)
@@ -759,6 +777,7 @@ struct Plan {
   bool fate_auto = false;       // "fate_scan" -1: the rule's ray count is looked at per chunk (launch_pair)
   BaffleFn baffle_fn = nullptr; // isx_fluxmap_baffle: the pipeline's trace kernel (it takes the baffles as a fourth argument: baffles) instead of fn
   BaffleTab baffles{};
+  SceneFn scene_fn = nullptr;   // isx_fluxmap_scene: the pipeline's trace kernel (patch_tab, beam and baffles are its fourth to sixth arguments) instead of fn
 };
 
 // "fate_scan" = -1: where the scan pays (measured on MI355X, docs/LOG.md section 16.3).  A small launch is bound by its longest
@@ -804,7 +823,7 @@ void trace_shape(Plan& p, Shape sh, bool assist, int per_cu) {
 }
 
 Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bool discs_in_aux, uint64_t n, bool beam = false,
-                 const FateConsts* fate = nullptr, bool baffle = false) {
+                 const FateConsts* fate = nullptr, bool baffle = false, bool scene = false) {
   enum { LAMBERT, LOBE, ROUGH } const border =
       c->surface_model == ISX_SURFACE_LOBE ? LOBE : c->lambertian ? LAMBERT : ROUGH;   // (ISX_SURFACE_ROBAST: Lambertian or rough-specular)
   const bool pencil = c->source_model == ISX_SOURCE_PENCIL;   // (else ISX_SOURCE_BRDF)
@@ -841,8 +860,17 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
   // outside the explicit Lambertian lean path: check_beam_call), the source behind the rings, and isx_fluxmap's binning kernels
   // (bin_mode 0: the brute-force form of isx_bin_lines_kernel).
   // The baffles (isx_fluxmap_baffle) likewise: their assist-wave trace kernel (check_baffle_call), the table behind the rings.
+  // The scene (isx_fluxmap_scene) likewise: its assist-wave trace kernel (check_scene_call), the three blocks behind the rings.
   if (sink == SINK_FLUX && (beam || baffle || (flux_served && S.pipeline && S.bin_mode != 0))) {
-    if (beam) {
+    if (scene) {
+      p.route = ROUTE_FLUX_PIPE;
+      p.scene_fn = isx_trace_assist_scene_kernel;
+      // (the kernel is built for five waves per SIMD: 640 threads -- nine tracer waves and the assist wave -- are what two
+      //  workgroups of a CU may have, unless assist_block was set)
+      trace_shape(p, small_shape(std::min(n, S.pipe_chunk), S.assist_block_set ? S.assist_block : kSceneBlock), true,
+                  resident_unless(S.trace_blocks_per_cu));
+      p.lds += SceneLds::bytes(p.tracers);
+    } else if (beam) {
       p.route = ROUTE_FLUX_PIPE;
       p.beam_fn = isx_trace_assist_beam_kernel;
       trace_shape(p, small_shape(std::min(n, S.pipe_chunk), S.assist_block), true, resident_unless(S.trace_blocks_per_cu));
@@ -1094,11 +1122,12 @@ int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles, boo
 
 // ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_FIELD_PIPE and ROUTE_DISC_PIPE: a trace launch and a binning launch per chunk of at most pipe_chunk rays
 int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
-  int rc = set_lds(p.beam_fn ? (const void*)p.beam_fn : p.baffle_fn ? (const void*)p.baffle_fn : p.list_fn ? (const void*)p.list_fn : (const void*)p.fn, p.lds);
+  int rc = set_lds(p.scene_fn ? (const void*)p.scene_fn : p.beam_fn ? (const void*)p.beam_fn : p.baffle_fn ? (const void*)p.baffle_fn : p.list_fn ? (const void*)p.list_fn : (const void*)p.fn, p.lds);
   if (rc == ISX_OK && p.list_fn) rc = set_lds((const void*)p.fn, p.lds);   // (a chunk below the automatic rule's size takes it)
   if (rc == ISX_OK) rc = set_lds((const void*)p.bin, p.lds_bin);
   if (rc) return rc;
-  const int tres = p.beam_fn ? blocks_per_cu(p.beam_fn, p.block, p.lds, p.per_cu) :
+  const int tres = p.scene_fn ? blocks_per_cu(p.scene_fn, p.block, p.lds, p.per_cu) :
+                   p.beam_fn ? blocks_per_cu(p.beam_fn, p.block, p.lds, p.per_cu) :
                    p.baffle_fn ? blocks_per_cu(p.baffle_fn, p.block, p.lds, p.per_cu) :
                    p.list_fn ? blocks_per_cu(p.list_fn, p.block, p.lds, p.per_cu) : blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
   const int bres = blocks_per_cu(p.bin, p.bblock, p.lds_bin, p.bin_per_cu);
@@ -1125,7 +1154,8 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     dt.rec_lines = db.rec_lines = S.d_rec[buf];
     dt.rec_counts = db.rec_counts = S.d_rec_counts[buf];
     const int tgrid = pick_grid(p, cnt, tres);
-    if (p.beam_fn) hipLaunchKernelGGL(p.beam_fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w, p.beam);
+    if (p.scene_fn) hipLaunchKernelGGL(p.scene_fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w, p.patch_tab, p.beam, p.baffles);
+    else if (p.beam_fn) hipLaunchKernelGGL(p.beam_fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w, p.beam);
     else if (p.baffle_fn) hipLaunchKernelGGL(p.baffle_fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w, p.baffles);
     else if (p.list_fn && (!p.fate_auto || cnt >= kFateMinRays)) {
       // the scan settles what the wall absorbs and leaves the rest in S.d_list, their number in ctr[Q_LIST] (zeroed with the
@@ -1205,10 +1235,14 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
             int nbins_override, const double* d_discs, double disc_r, double disc_h, const PerPos* pp = nullptr,
             const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr, const ExitSink* xm = nullptr,
             const WallSink* wm = nullptr, const FieldSink* lf = nullptr, const OrderSink* oh = nullptr,
-            const PatchSink* wp = nullptr, const isx_beam_spec* bs = nullptr, const BaffleSink* bf = nullptr) {
+            const PatchSink* wp = nullptr, const isx_beam_spec* bs = nullptr, const BaffleSink* bf = nullptr,
+            const SceneSink* sc = nullptr) {
   Geom g;
   FateConsts fate;
   isx_config cb;
+  // (a scene is its beam, its baffles -- whose counters are the last 16 of the scene's 36 -- and its patches)
+  BaffleSink sc_bf;
+  if (sc) { bs = &sc->spec->beam; sc_bf.spec = &sc->spec->baffles; sc_bf.counts = sc->counts + 2 * (kMaxPatches + 2); bf = &sc_bf; }
   if (bs && config_abi_ok(c) && bs->struct_size == (uint32_t)sizeof(isx_beam_spec)) { cb = beam_config(*c, *bs); c = &cb; }
   int rc = prepare_geom(c, &g, &fate);
   if (rc) return rc;
@@ -1221,16 +1255,23 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
     rc = check_baffle_call(c, bf->spec);
     if (S.bin_mode == 2) d.bin_mode = 1;   // (isx.h: the trace-only diagnostic does not apply to the baffles)
   }
+  if (rc == ISX_OK && sc) {
+    rc = check_patch_call(c, &sc->spec->patches);
+    // (the patches travel in the exit maps' words of DetGrid, as SINK_PATCH's do: a flux map's trace kernel has no other use for them)
+    d.xm_nx = sc->spec->patches.n_patches;
+    d.xm_dir = sc->counts; d.xm_pos = sc->counts + (kMaxPatches + 2);
+  }
   if (rc || n == 0) return rc;
   Work wk;
   wk.seed = seed; wk.first = first; wk.n = n; wk.hist = d_hist; wk.stats = d_stats ? d_stats : S.d_stats;
   wk.ctr = nullptr; wk.sub = 0; wk.pad = 0;
-  Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n, bs != nullptr, &fate, bf != nullptr);
+  Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n, bs != nullptr, &fate, bf != nullptr, sc != nullptr);
   if (bf) {
     if (p.lds_bin > S.lds_limit) return ISX_ERR_BAD_CONFIG;   // (isx.h: a grid whose tables do not fit the binning kernels' LDS)
     p.baffles = baffle_table(*c, *bf->spec, bf->counts);
   }
   if (sink == SINK_PATCH) p.patch_tab = patch_table(*c, *wp->spec);
+  if (sc) p.patch_tab = patch_table(*c, sc->spec->patches);
   if (bs) {
     if (p.lds_bin > S.lds_limit) return ISX_ERR_BAD_CONFIG;   // (isx.h: a grid whose tables do not fit the binning kernels' LDS)
     p.beam = beam_source(*bs);
@@ -2424,6 +2465,91 @@ int isx_fluxmap_baffle(const isx_config* cfg, const isx_baffle_spec* spec, uint6
   const BaffleSink bf{spec, S.d_hist + nb};
   if (rc == ISX_OK) rc = enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, S.d_hist, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
                                  nullptr, nullptr, nullptr, nullptr, nullptr, &bf);
+  if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK) {
+    fetch_result(hits, nb * sizeof(unsigned long long));
+    if (counts) std::memcpy(counts, reinterpret_cast<const unsigned long long*>(S.h_pin + 64) + nb, nc * sizeof(unsigned long long));
+  }
+  return rc;
+}
+
+void isx_default_scene_spec(const isx_config* cfg, isx_scene_spec* spec) {
+  if (!spec) return;
+  std::memset(spec, 0, sizeof(*spec));
+  spec->struct_size = (uint32_t)sizeof(isx_scene_spec);
+  isx_default_beam_spec(cfg, &spec->beam);
+  isx_default_baffle_spec(cfg, &spec->baffles);
+  isx_default_wall_patch_spec(cfg, &spec->patches);
+}
+
+int isx_scene_endstates(const isx_config* cfg, const isx_scene_spec* spec, uint64_t n, uint64_t seed, uint64_t first, int32_t* status,
+                        int32_t* n_points, double* last_point, double* direction, double* start_point, double* start_dir,
+                        int32_t* last_baffle, int32_t* last_class) {
+  // (what needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one)
+  if (!cfg || !spec || !status || !n_points || !last_point || !direction) return ISX_ERR_BAD_ARG;
+  int rc = check_scene_call(cfg, spec, false);
+  if (rc) return rc;
+  if (!S.init) return not_initialised();
+  if (n == 0) return ISX_OK;
+  if (n > (1ull << 28)) return ISX_ERR_TOO_LARGE;
+  if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;
+  Geom g;
+  const isx_config cb = beam_config(*cfg, spec->beam);
+  rc = prepare_geom(&cb, &g);
+  if (rc) return rc;
+  const BeamSrc b = beam_source(spec->beam);
+  const BaffleTab t = baffle_table(cb, spec->baffles, nullptr);
+  const PatchTab pt = patch_table(cb, spec->patches);
+  DevBuf<int32_t> b_st, b_np, b_lb, b_lc;
+  DevBuf<double> b_lp, b_dir, b_sp, b_sd;
+  HIPCHK(b_st.alloc(n)); HIPCHK(b_np.alloc(n)); HIPCHK(b_lp.alloc(n * 3)); HIPCHK(b_dir.alloc(n * 3));
+  if (start_point) HIPCHK(b_sp.alloc(n * 3));
+  if (start_dir) HIPCHK(b_sd.alloc(n * 3));
+  if (last_baffle) HIPCHK(b_lb.alloc(n));
+  if (last_class) HIPCHK(b_lc.alloc(n));
+  const int blk = 256;
+  const unsigned grid = (unsigned)((n + blk - 1) / blk);
+  hipLaunchKernelGGL(isx_scene_endstates_kernel, dim3(grid), dim3(blk), 0, S.stream, g, pt, b, t, seed, first, n, b_st.p, b_np.p,
+                     b_lp.p, b_dir.p, b_sp.p, b_sd.p, b_lb.p, b_lc.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(status, b_st.p, n * 4, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipMemcpyAsync(n_points, b_np.p, n * 4, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipMemcpyAsync(last_point, b_lp.p, n * 24, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipMemcpyAsync(direction, b_dir.p, n * 24, hipMemcpyDeviceToHost, S.stream));
+  if (start_point) HIPCHK(hipMemcpyAsync(start_point, b_sp.p, n * 24, hipMemcpyDeviceToHost, S.stream));
+  if (start_dir) HIPCHK(hipMemcpyAsync(start_dir, b_sd.p, n * 24, hipMemcpyDeviceToHost, S.stream));
+  if (last_baffle) HIPCHK(hipMemcpyAsync(last_baffle, b_lb.p, n * 4, hipMemcpyDeviceToHost, S.stream));
+  if (last_class) HIPCHK(hipMemcpyAsync(last_class, b_lc.p, n * 4, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipStreamSynchronize(S.stream));
+  return ISX_OK;
+}
+
+int isx_fluxmap_scene_device(const isx_config* cfg, const isx_scene_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                             uint64_t* d_hits, uint64_t* d_counts) {
+  if (!cfg || !spec || !d_hits || !d_counts) return ISX_ERR_BAD_ARG;
+  const int bad = check_scene_call(cfg, spec, true);
+  if (bad) return bad;
+  if (!S.init) return not_initialised();
+  const SceneSink sc{spec, (unsigned long long*)d_counts};
+  return enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, (unsigned long long*)d_hits, 0, nullptr, 0, 0, nullptr, nullptr, nullptr,
+                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sc);
+}
+
+int isx_fluxmap_scene(const isx_config* cfg, const isx_scene_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                      uint64_t* hits, isx_scene_counts* counts, isx_stats* stats) {
+  if (!cfg || !spec || !hits) return ISX_ERR_BAD_ARG;
+  int rc = check_scene_call(cfg, spec, true);
+  if (rc) return rc;
+  if (!S.init) return not_initialised();
+  // the histogram and, behind it, the 36 counters: one device block, one staged result
+  const size_t nb = (size_t)cfg->n_theta * cfg->n_phi, nc = kSceneWords, bytes = (nb + nc) * sizeof(unsigned long long);
+  rc = call_open(nb + nc);
+  if (rc) return rc;
+  rc = zero_hist(nb + nc);
+  const SceneSink sc{spec, S.d_hist + nb};
+  if (rc == ISX_OK) rc = enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, S.d_hist, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sc);
   if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
   rc = call_close(rc, stats);
   if (rc == ISX_OK) {

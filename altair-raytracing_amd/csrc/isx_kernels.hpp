@@ -2312,6 +2312,14 @@ struct BaffleTab {
 };
 // LDS of the baffle kernel's block behind the rings: the table and its 4 kMaxBaffles u32 counters
 constexpr size_t kBaffleLds = ((sizeof(BaffleTab) + 4 * kMaxBaffles * sizeof(uint32_t)) + 15) & ~(size_t)15;
+// LDS of the scene kernel's block behind the rings (isx_fluxmap_scene: patches, beam and baffles in one launch): the three blocks
+// of the three kernels, each 16-byte aligned -- the patch table and its 2 (P + 2) u32 counters, the source, the baffle table and
+// its counters -- and last, because its size is the launch's, the tracer waves' parked starts
+constexpr size_t kPatchLds = (sizeof(PatchTab) + 2 * (kMaxPatches + 2) * sizeof(uint32_t) + 15) & ~(size_t)15;
+struct SceneLds {
+  static constexpr size_t beam = kPatchLds, baffle = beam + kBeamSrcBytes, park = baffle + kBaffleLds;
+  static constexpr size_t bytes(int tracers) { return park + (size_t)tracers * kBeamParkBytes; }
+};
 // The segment test of isx.h's contract, operation for operation (IEEE double, left to right, no fma: -ffp-contract=off; / is the
 // correctly rounded one): the baffle that the segment p -> q strikes first -- the smallest f, on equal f the lowest index -- as
 // 2 k + side (side 0: the side the normal points to), or -1.  `skip` is the baffle of the ray's previous interaction (-1: none).
@@ -3005,6 +3013,13 @@ __device__ __forceinline__ void ray_unpack(const uint4& a, const uint4& b, const
 // baffle_arrive or the boundary's ray_arrive; Ray::on = -(k + 1) is "on baffle k" in the lane and in the pending ring's record.  The
 // table and the workgroup's 16 u32 counters lie behind the rings.  Exit lines, chunks, workspace and the kernels that follow are
 // isx_trace_assist_kernel's.  Explicit Lambertian lean path only.
+// PATCH && BEAM && BAFFLE (isx_fluxmap_scene): the three in one trace, and the only combination of them -- nothing is stated for
+// it.  Each part is its own build's code; where they meet: the parked first segment of a fresh ray is tested against the discs
+// before it counts as an arrival (a struck one is parked as its start and handed over with K_NONE, like a failed rule S1); the
+// tracers' arrival is PATCH's, their search BAFFLE's; the assist wave runs baffle_arrive, or patch_arrive<false> and then the
+// boundary's ray_arrive with the class's constants.  The three blocks lie one behind the other behind the rings (SceneLds).  Exit
+// lines are written as in the BEAM and BAFFLE builds; patch_flush adds nothing to bin_increments (the binning kernel's count).
+// The assist wave never waits for the resume ring, as in every BAFFLE build (docs/LOG.md sections 18.4, 19.2).
 struct FateList { const uint32_t* list; const uint32_t* count; };
 template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false, bool ORDER = false, bool PATCH = false,
           bool BEAM = false, bool LIST = false, bool BAFFLE = false>
@@ -3014,9 +3029,10 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   constexpr bool LEAN = SURF == SURF_LAMBERT;
   static_assert(LEAN || (CH == 0 && !RESC), "the chord identity and the BRDF re-scatter pipeline are built for the Lambertian border");
   static_assert(!PATCH || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER), "wall patches: the explicit Lambertian lean path, no other sink");
-  static_assert(!BEAM || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && !PATCH), "beam source: the explicit Lambertian lean path, no other sink");
+  constexpr bool SCENE = PATCH && BEAM && BAFFLE;   // isx_fluxmap_scene: the three together, and no two of them without the third
+  static_assert(!BEAM || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && (!PATCH || SCENE)), "beam source: the explicit Lambertian lean path, no other sink");
   static_assert(!LIST || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && !PATCH && !BEAM), "ray list: the explicit Lambertian lean path of the flux pipeline");
-  static_assert(!BAFFLE || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && !PATCH && !BEAM && !LIST), "baffles: the explicit Lambertian lean path of the flux pipeline");
+  static_assert(!BAFFLE || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && (!PATCH || SCENE) && (!BEAM || SCENE) && !LIST), "baffles: the explicit Lambertian lean path of the flux pipeline");
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned long long* sstat = reinterpret_cast<unsigned long long*>(smem);
   Geom* g_lds = reinterpret_cast<Geom*>(sstat + 8);
@@ -3034,6 +3050,9 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   static_assert(!(WALL && ORDER), "one LDS block behind the rings");
   const OrderSpec ospec = order_spec<ORDER>(d_arg);
   if (ORDER) for (int b = tid; b < d_arg.nbins; b += nthr) hist[b] = 0u;
+  // SCENE: the three blocks one behind the other (SceneLds), where each of the three kernels has its one block at `hist`
+  constexpr size_t off_beam = SCENE ? SceneLds::beam : 0, off_baf = SCENE ? SceneLds::baffle : 0;
+  constexpr size_t off_park = SCENE ? SceneLds::park : kBeamSrcBytes;
   // PATCH: the table | u32[arrivals (n_patch + 2) | absorbed (n_patch + 2)]
   PatchTab* ptab = reinterpret_cast<PatchTab*>(hist);
   uint32_t* pcnt = reinterpret_cast<uint32_t*>(ptab + 1);
@@ -3045,24 +3064,24 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   // BEAM: the source
   typedef __attribute__((address_space(3))) BeamSrc LdsBeam;
   if constexpr (BEAM) {
-    if (tid == 65) *reinterpret_cast<BeamSrc*>(hist) = *beam_arg;
+    if (tid == (SCENE ? 66 : 65)) *reinterpret_cast<BeamSrc*>(reinterpret_cast<unsigned char*>(hist) + off_beam) = *beam_arg;
   }
-  const volatile LdsBeam& beam = *(const volatile LdsBeam*)hist;
+  const volatile LdsBeam& beam = *(const volatile LdsBeam*)(reinterpret_cast<unsigned char*>(hist) + off_beam);
   // ... and behind it, per tracer wave, the parked starts of 64 fresh rays: double[6][64] (kBeamParkBytes)
   typedef __attribute__((address_space(3))) double LdsDouble;
   const uint32_t beam_wave = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform: a scalar register)
-  volatile LdsDouble* park = (volatile LdsDouble*)(reinterpret_cast<unsigned char*>(hist) + kBeamSrcBytes) +
+  volatile LdsDouble* park = (volatile LdsDouble*)(reinterpret_cast<unsigned char*>(hist) + off_park) +
                               (size_t)beam_wave * (6 * 64);
   // BAFFLE: the table | u32[arrivals [k][side] | absorbed [k][side]]
   typedef __attribute__((address_space(3))) BaffleTab LdsBaffle;
-  uint32_t* bcnt = reinterpret_cast<uint32_t*>(reinterpret_cast<BaffleTab*>(hist) + 1);
+  uint32_t* bcnt = reinterpret_cast<uint32_t*>(reinterpret_cast<BaffleTab*>(reinterpret_cast<unsigned char*>(hist) + off_baf) + 1);
   int n_baf = 0;
   if constexpr (BAFFLE) {
     n_baf = baf_arg->n;   // (a kernel argument: wave-uniform, a scalar register)
-    if (tid == 65) *reinterpret_cast<BaffleTab*>(hist) = *baf_arg;
+    if (tid == (SCENE ? 67 : 65)) *reinterpret_cast<BaffleTab*>(reinterpret_cast<unsigned char*>(hist) + off_baf) = *baf_arg;
     if (tid < 4 * kMaxBaffles) bcnt[tid] = 0u;
   }
-  const volatile LdsBaffle& baf = *(const volatile LdsBaffle*)hist;
+  const volatile LdsBaffle& baf = *(const volatile LdsBaffle*)(reinterpret_cast<unsigned char*>(hist) + off_baf);
   if (tid < 8) sstat[tid] = 0ull;
   if (tid == 64) {
     *g_lds = g_arg;
@@ -3181,6 +3200,12 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
                 Ray t;
                 beam_start(beam, t, seed, first, park_base + (uint32_t)lane);
                 V3 q;
+                if constexpr (SCENE) {   // a baffle in the way of the ray's own first segment: parked as its start, the assist wave's
+                  double f0;
+                  if (next_hit_s1<true>(h, g, t.p, t.v, K_NONE, q) && baffle_segment(baf, n_baf, t.p, q, -1, f0) < 0) {
+                    t.p = q; t.v.x = __builtin_nan("");
+                  }
+                } else
                 if (next_hit_s1<true>(h, g, t.p, t.v, K_NONE, q)) { t.p = q; t.v.x = __builtin_nan(""); }
                 park[0 * 64 + lane] = t.p.x; park[1 * 64 + lane] = t.p.y; park[2 * 64 + lane] = t.p.z;
                 park[3 * 64 + lane] = t.v.x; park[4 * 64 + lane] = t.v.y; park[5 * 64 + lane] = t.v.z;
@@ -3536,7 +3561,22 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           kind = next_hit_generic(g, r.p, r.v, r.on, q);
           }
           if (WALL && kind != K_BOX) wall_record(wspec, hist, wall_nmap, kind, r.j, q, 1u);
-          if constexpr (PATCH) {
+          if constexpr (SCENE) {   // the baffle's interaction, or the class of the wall's arrival and then the wall's interaction
+            double bf;
+            const int ks = baffle_segment(baf, n_baf, r.p, q, baffle_skip(r.on), bf);
+            if (ks >= 0) {
+              r.p = baffle_point(r.p, q, bf);
+              atomicAdd(&bcnt[ks], 1u);
+              st = baffle_arrive(baf, h, r, seed, first, ks >> 1, ks & 1);
+              if (st == ST_ABSORBED) atomicAdd(&bcnt[2 * kMaxBaffles + ks], 1u);
+            } else {
+              Hot hp = h;
+              int cls = 0;
+              if (kind != K_BOX) cls = patch_arrive<false>(ptab, n_patch, pcnt, kind, q, hp);
+              st = ray_arrive<false, LEAN, CH, PH_DIRECT, true, SURF>(hp, g, r, seed, first, kind, q);
+              if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
+            }
+          } else if constexpr (PATCH) {
             Hot hp = h;
             int cls = 0;
             if (kind != K_BOX) cls = patch_arrive<false>(ptab, n_patch, pcnt, kind, q, hp);
@@ -3671,7 +3711,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         if (hit1) atomicAdd(&wk.hist[b1], 1ull);
         n_inc += (unsigned long long)__popcll(__ballot(hit0)) + (unsigned long long)__popcll(__ballot(hit1));
       }
-      const unsigned long long m = (PP != 0 || WALL || ORDER || PATCH) ? 0ull : __ballot(keep);
+      const unsigned long long m = (PP != 0 || WALL || ORDER || (PATCH && !SCENE)) ? 0ull : __ballot(keep);
       if (m) {
         const uint32_t cnt = (uint32_t)__popcll(m);
         if (cnt > reg_left) {   // close the open region, reserve the next one (kRegion)
@@ -3778,6 +3818,9 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     if (flushed) atomicAdd(&sstat[5], flushed);
     __syncthreads();
   }
+  if constexpr (SCENE) {   // one flush of the workgroup's counters (bin_increments is the binning kernel's: the histogram's sum)
+    (void)patch_flush(d_arg, pcnt);
+  } else
   if constexpr (PATCH) {   // one flush of the workgroup's counters; bin_increments = the arrivals on the patches
     const unsigned long long flushed = patch_flush(d_arg, pcnt);
     if (flushed) atomicAdd(&sstat[5], flushed);
@@ -3849,6 +3892,17 @@ isx_trace_assist_beam_kernel(const Geom g, const DetGrid d, const Work wk, const
 extern "C" __global__ void ISX_ASSIST_ATTR
 isx_trace_assist_baffle_kernel(const Geom g, const DetGrid d, const Work wk, const BaffleTab baf) {
   assist_body<0, false, false, 0, SURF_LAMBERT, false, false, false, false, false, true>(g, d, wk, nullptr, nullptr, nullptr, &baf);
+}
+// the scene (isx_fluxmap_scene): beam source, baffles and wall patches in one trace -- the three kernels above in one; the three
+// tables are its fourth to sixth arguments
+// (the three kernels sit at 80 VGPRs each; the three in one kept 12 B of scratch there: five waves per SIMD, and 640-thread
+//  workgroups by default so that two still fit a CU -- isx_api.hip: plan_launch, docs/LOG.md section 19.1)
+#ifndef ISX_SCENE_WAVES
+#define ISX_SCENE_WAVES 5
+#endif
+extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_SCENE_WAVES, ISX_SCENE_WAVES)))
+isx_trace_assist_scene_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab, const BeamSrc beam, const BaffleTab baf) {
+  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true>(g, d, wk, &tab, &beam, nullptr, &baf);
 }
 // the flux pipeline behind the fate scan: isx_trace_assist_kernel on the rays of a list; the list is a fourth argument
 extern "C" __global__ void ISX_ASSIST_ATTR
@@ -4815,6 +4869,47 @@ isx_baffle_endstates_kernel(const Geom g, const BaffleTab baf, uint64_t seed, ui
   lp[3 * i] = r.p.x; lp[3 * i + 1] = r.p.y; lp[3 * i + 2] = r.p.z;
   dir[3 * i] = r.v.x; dir[3 * i + 1] = r.v.y; dir[3 * i + 2] = r.v.z;
   if (last) last[i] = lb;
+}
+
+// isx_scene_endstates: the beam's start (beam_start), then isx_baffle_endstates_kernel's loop with the class of every wall arrival
+// (patch_arrive) in front of the wall's interaction; last_class (may be NULL, as sp, sd and last) is the class of the ray's last
+// mirror interaction, or -1.  The arrivals are not counted here (cnt: a block of LDS that nothing reads).
+extern "C" __global__ void __launch_bounds__(256)
+isx_scene_endstates_kernel(const Geom g, const PatchTab tab, const BeamSrc beam, const BaffleTab baf, uint64_t seed, uint64_t first,
+                           uint64_t n, int32_t* __restrict__ status, int32_t* __restrict__ npts, double* __restrict__ lp,
+                           double* __restrict__ dir, double* __restrict__ sp, double* __restrict__ sd, int32_t* __restrict__ last,
+                           int32_t* __restrict__ lcls) {
+  __shared__ uint32_t cnt[kMaxPatches + 2];
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Hot h = make_hot(g);
+  Ray r;
+  beam_start(beam, r, seed, first, (uint32_t)i);
+  if (sp) { sp[3 * i] = r.p.x; sp[3 * i + 1] = r.p.y; sp[3 * i + 2] = r.p.z; }
+  if (sd) { sd[3 * i] = r.v.x; sd[3 * i + 1] = r.v.y; sd[3 * i + 2] = r.v.z; }
+  int st, lb = -1, lc = -1;
+  for (;;) {
+    V3 q;
+    double bf;
+    const int kind = next_hit(h, g, r.p, r.v, baffle_on(r.on), q);
+    const int ks = baffle_segment(baf, baf.n, r.p, q, baffle_skip(r.on), bf);
+    if (ks >= 0) {
+      r.p = baffle_point(r.p, q, bf);
+      st = baffle_arrive(baf, h, r, seed, first, ks >> 1, ks & 1);
+      lb = ks;
+    } else {
+      Hot hp = h;
+      if (kind != K_BOX) lc = patch_arrive<false>(&tab, tab.n, cnt, kind, q, hp);
+      st = ray_arrive<false, false, 2>(hp, g, r, seed, first, kind, q);
+    }
+    if (st != 0) break;
+  }
+  status[i] = st;
+  npts[i] = (int)r.j + 1 + (st == ST_EXITED ? 1 : 0);
+  lp[3 * i] = r.p.x; lp[3 * i + 1] = r.p.y; lp[3 * i + 2] = r.p.z;
+  dir[3 * i] = r.v.x; dir[3 * i + 1] = r.v.y; dir[3 * i + 2] = r.v.z;
+  if (last) last[i] = lb;
+  if (lcls) lcls[i] = lc;
 }
 
 // ------------------------------------------------------------------ device-side self test of the numeric contract

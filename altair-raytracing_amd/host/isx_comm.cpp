@@ -797,4 +797,24 @@ int fluxmap_baffle_all(const isx_config* cfg, const isx_baffle_spec* spec, uint6
   return rc;
 }
 
+int fluxmap_scene_all(const isx_config* cfg, const isx_scene_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                      uint64_t* hits, isx_scene_counts* counts, isx_stats* st) {
+  Comm& c = comm();
+  if (!c.active()) return isx_fluxmap_scene(cfg, spec, n_rays, seed, first_ray, hits, counts, st);
+  uint64_t f, cnt;
+  c.shard(n_rays, f, cnt);
+  isx_stats local{};
+  const size_t nb = grid_bins(cfg), nc = sizeof(isx_scene_counts) / sizeof(uint64_t);
+  std::vector<uint64_t> buf(nb + nc, 0);   // histogram | counters: ONE sum
+  isx_scene_counts lc{};
+  int rc = hits ? isx_fluxmap_scene(cfg, spec, cnt, seed, first_ray + f, buf.data(), &lc, &local) : ISX_ERR_BAD_ARG;
+  std::memcpy(buf.data() + nb, &lc, sizeof(lc));
+  rc = c.reduce(rc, buf.data(), nb + nc, &local);
+  if (rc != ISX_OK) return rc;
+  std::memcpy(hits, buf.data(), nb * sizeof(uint64_t));
+  if (counts) std::memcpy(counts, buf.data() + nb, sizeof(*counts));
+  if (st) *st = local;
+  return rc;
+}
+
 }  // namespace isxhost

@@ -93,6 +93,10 @@ int fluxmap_beam_all(const isx_config* cfg, const isx_beam_spec* spec, uint64_t 
 // one collective of the call
 int fluxmap_baffle_all(const isx_config* cfg, const isx_baffle_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
                        uint64_t* hits, isx_baffle_counts* counts, isx_stats* st);
+// the flux map of a scene (isx_fluxmap_scene): contiguous ray ranges; histogram, the 36 scene counters and the census in the one
+// collective of the call
+int fluxmap_scene_all(const isx_config* cfg, const isx_scene_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                      uint64_t* hits, isx_scene_counts* counts, isx_stats* st);
 // the wall map (isx_wall_map): the map and the four counters travel in the one collective of the call
 int wall_map_all(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
                  uint64_t* wall_map, isx_wall_map_counts* counts, isx_stats* st);

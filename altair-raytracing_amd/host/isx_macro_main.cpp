@@ -54,6 +54,9 @@ int main(int argc, char** argv) {
                  "  beamFlux [--rays <n>] [--seed <s>] [--origin <x,y,z>] [--axis <x,y,z>] [--radius <r>] [--half-angle <deg>] [--law uniform|lambert] |\n"
                  "  baffleFlux [--rays <n>] [--seed <s>] [--centre <x,y,z> --normal <x,y,z> --radius <r> --reflectance <rho>]... |\n"
                  "    (--radius is beamFlux's and baffleFlux's: every one given is a baffle's radius, the last one the beam's) |\n"
+                 "  sceneFlux [--rays <n>] [--seed <s>] [beamFlux's options] [baffleFlux's options]\n"
+                 "    [--patch-dir <x,y,z> --patch-half-angle <deg> --patch-reflectance <rho>]... |\n"
+                 "    (--radius: one per baffle, and one more, if given, for the beam) |\n"
                  "  distributionSphereDetectorSweep | --selftest-writer <file> | --unique <path> | --shard <n> | --analyze <csv>... | --analyze <folder> [average]\n";
     return 2;
   }
@@ -133,6 +136,19 @@ int main(int argc, char** argv) {
       ++i;
       continue;
     }
+    if ((!std::strcmp(argv[i], "--patch-dir") || !std::strcmp(argv[i], "--patch-half-angle") || !std::strcmp(argv[i], "--patch-reflectance")) &&
+        i + 1 < argc) {   // sceneFlux (repeatable)
+      const std::string key = argv[i] + 2;
+      if (key == "patch-dir") options().patch_dirs.push_back(argv[i + 1]);
+      else {   // a number, the whole token
+        char* rest = nullptr;
+        const double v = std::strtod(argv[i + 1], &rest);
+        if (rest == argv[i + 1] || *rest != '\0') { std::cerr << "bad number for --" << key << ": " << argv[i + 1] << "\n"; return 2; }
+        (key == "patch-half-angle" ? options().patch_half_angles : options().patch_reflectances).push_back(v);
+      }
+      ++i;
+      continue;
+    }
     const char* eq = std::strchr(argv[i], '=');
     if (!eq) { std::cerr << "bad argument " << argv[i] << " (want key=value)\n"; return 2; }
     kv[std::string(argv[i], eq - argv[i])] = eq + 1;
@@ -160,6 +176,7 @@ int main(int argc, char** argv) {
   else if (entry == "wallPatches") rootMacros::wallPatches();
   else if (entry == "beamFlux") rootMacros::beamFlux();
   else if (entry == "baffleFlux") rootMacros::baffleFlux();
+  else if (entry == "sceneFlux") rootMacros::sceneFlux();
   else { std::cerr << "unknown entry point " << entry << "\n"; return 2; }
   const bool ok = ensure_device();  // false: the entry point printed its error and returned early
   comm().finalize();

@@ -1631,6 +1631,163 @@ void baffleFlux() {
   f << "# Detector hits: " << st.bin_increments << std::endl;
 }
 
+// Flux map of a scene in the library's default sphere: a beam source, baffles and wall patches in one trace (isx.h: isx_fluxmap_scene).
+void sceneFlux() {
+  if (!ready_everywhere()) return;
+  isx_config c;
+  isx_default_config(&c);
+  const long n = pick_n(1000000);
+  // exactly three numbers, each the whole of its token
+  auto triple = [](const std::string& arg, double v[3]) {
+    int got = 0;
+    std::stringstream ss(arg);
+    std::string tok;
+    while (std::getline(ss, tok, ',')) {
+      char* rest = nullptr;
+      const double x = std::strtod(tok.c_str(), &rest);
+      if (got == 3 || rest == tok.c_str() || *rest != '\0') return false;
+      v[got++] = x;
+    }
+    return got == 3 && !arg.empty() && arg.back() != ',';
+  };
+  const RunOptions& o = options();
+  isx_scene_spec sp;
+  isx_default_scene_spec(&c, &sp);
+  // the baffles: baffleFlux's options; of the --radius values the first ones are theirs, one more, if given, is the beam's
+  const size_t nb = o.baffle_centres.size();
+  if (nb > (size_t)ISX_MAX_BAFFLES || o.baffle_normals.size() != nb || (o.baffle_radii.size() != nb && o.baffle_radii.size() != nb + 1) ||
+      o.baffle_reflectances.size() != nb) {
+    err() << "Error: a baffle wants --centre, --normal, --radius and --reflectance, one of each, " << ISX_MAX_BAFFLES << " baffles at most" << std::endl;
+    return;
+  }
+  for (size_t k = 0; k < nb; ++k) {
+    double centre[3], normal[3];
+    if (!triple(o.baffle_centres[k], centre) || !triple(o.baffle_normals[k], normal)) {
+      err() << "Error: --centre and --normal want x,y,z" << std::endl;
+      return;
+    }
+    const int rc = isx_baffle_disc(&c, centre, normal, o.baffle_radii[k], o.baffle_reflectances[k], &sp.baffles.baffle[k]);
+    if (rc != ISX_OK) {
+      err() << "Error: isx_baffle_disc: " << isx_strerror(rc) << std::endl;
+      return;
+    }
+  }
+  sp.baffles.n_baffles = (int32_t)nb;
+  // the source: beamFlux's options
+  double origin[3] = {c.src[0], c.src[1], c.src[2]}, axis[3] = {c.dir[0], c.dir[1], c.dir[2]};
+  if ((!o.beam_origin.empty() && !triple(o.beam_origin, origin)) || (!o.beam_axis.empty() && !triple(o.beam_axis, axis))) {
+    err() << "Error: --origin and --axis want x,y,z" << std::endl;
+    return;
+  }
+  const std::string& law = o.beam_law;
+  if (law != "uniform" && law != "lambert") {
+    err() << "Error: --law wants uniform or lambert: " << law << std::endl;
+    return;
+  }
+  const double beam_radius = o.baffle_radii.size() == nb + 1 ? o.baffle_radii[nb] : 0.0;
+  int rc = isx_beam_cone(&c, origin, axis, beam_radius, o.beam_half_angle, law == "lambert" ? ISX_BEAM_LAMBERT : ISX_BEAM_UNIFORM, &sp.beam);
+  if (rc != ISX_OK) {
+    err() << "Error: isx_beam_cone: " << isx_strerror(rc) << std::endl;
+    return;
+  }
+  // the wall patches
+  const size_t np = o.patch_dirs.size();
+  if (np > (size_t)ISX_MAX_WALL_PATCHES || o.patch_half_angles.size() != np || o.patch_reflectances.size() != np) {
+    err() << "Error: a patch wants --patch-dir, --patch-half-angle and --patch-reflectance, one of each, " << ISX_MAX_WALL_PATCHES
+          << " patches at most" << std::endl;
+    return;
+  }
+  for (size_t k = 0; k < np; ++k) {
+    double dir[3];
+    if (!triple(o.patch_dirs[k], dir)) {
+      err() << "Error: --patch-dir wants x,y,z" << std::endl;
+      return;
+    }
+    rc = isx_wall_patch_cap(&c, dir, o.patch_half_angles[k], o.patch_reflectances[k], &sp.patches.patch[k]);
+    if (rc != ISX_OK) {
+      err() << "Error: isx_wall_patch_cap: " << isx_strerror(rc) << std::endl;
+      return;
+    }
+  }
+  sp.patches.n_patches = (int32_t)np;
+  std::vector<uint64_t> hits((size_t)c.n_theta * c.n_phi);
+  isx_stats st;
+  isx_scene_counts sc{};
+  const uint64_t first = take_rays((uint64_t)n);
+  rc = fluxmap_scene_all(&c, &sp, (uint64_t)n, options().seed, first, hits.data(), &sc, &st);
+  if (rc != ISX_OK) {
+    err() << "Error: isx_fluxmap_scene: " << isx_strerror(rc) << std::endl;
+    return;
+  }
+  std::cout << "Total rays exiting port: " << st.counted_below_z << " out of " << n << std::endl;
+  FluxMapMeta mm;
+  mm.title = "Flux Map Data (Scene)";
+  mm.n_label = "Number of rays";
+  mm.method_line = "Trace-Once (single trace, multiple detector positions)";
+  mm.n = n; mm.det_w = mm.det_h = c.det_diameter; mm.r_in = c.r_in; mm.r_out = c.r_out; mm.thetaMax = c.theta_max_deg;
+  mm.nTheta = c.n_theta; mm.nPhi = c.n_phi; mm.reflectance = c.reflectance; mm.roughness = c.roughness_rad; mm.maxReflections = c.max_points;
+  for (int k = 0; k < 3; ++k) { mm.src[k] = sp.beam.origin[k]; mm.dir[k] = sp.beam.axis[k]; }
+  // the flux maps' header with the scene's lines ahead of the column line
+  std::string head = fluxmap_header(mm, currentTimeString());
+  const std::string cols = "theta,phi,fraction\n";
+  if (head.size() < cols.size() || head.compare(head.size() - cols.size(), cols.size(), cols) != 0) {
+    err() << "Error: the flux-map header does not end with its column line" << std::endl;
+    return;
+  }
+  head.erase(head.size() - cols.size());
+  std::ofstream f(outputPath("scene_flux.csv"));
+  f << head;
+  {
+    std::ostringstream os;
+    os << std::setprecision(17);
+    os << "# Seed: " << options().seed << std::endl;
+    os << "# First ray: " << first << std::endl;
+    const isx_beam_spec& b = sp.beam;
+    os << "# Beam origin (x,y,z): " << b.origin[0] << "cm, " << b.origin[1] << "cm, " << b.origin[2] << "cm" << std::endl;
+    os << "# Beam axis (x,y,z): " << b.axis[0] << ", " << b.axis[1] << ", " << b.axis[2] << std::endl;
+    os << "# Beam e1 (x,y,z): " << b.e1[0] << ", " << b.e1[1] << ", " << b.e1[2] << std::endl;
+    os << "# Beam e2 (x,y,z): " << b.e2[0] << ", " << b.e2[1] << ", " << b.e2[2] << std::endl;
+    os << "# Beam radius: " << b.radius << "cm" << std::endl;
+    os << "# Beam half angle: " << o.beam_half_angle << " degrees, cos_min " << b.cos_min << std::endl;
+    os << "# Beam angular law: " << law << std::endl;
+    os << "# Baffles: " << sp.baffles.n_baffles << std::endl;
+    for (int k = 0; k < sp.baffles.n_baffles; ++k) {
+      const isx_baffle& d = sp.baffles.baffle[k];
+      os << "# Baffle " << k << " centre (x,y,z): " << d.centre[0] << "cm, " << d.centre[1] << "cm, " << d.centre[2] << "cm" << std::endl;
+      os << "# Baffle " << k << " normal (x,y,z): " << d.normal[0] << ", " << d.normal[1] << ", " << d.normal[2] << std::endl;
+      os << "# Baffle " << k << " radius: " << d.radius << "cm" << std::endl;
+      os << "# Baffle " << k << " reflectance: " << d.reflectance << std::endl;
+    }
+    os << "# Wall patches: " << sp.patches.n_patches << std::endl;
+    for (int k = 0; k < sp.patches.n_patches; ++k) {
+      const isx_wall_patch& p = sp.patches.patch[k];
+      os << "# Patch " << k << " axis (x,y,z): " << p.axis[0] << ", " << p.axis[1] << ", " << p.axis[2] << std::endl;
+      os << "# Patch " << k << " half angle: " << o.patch_half_angles[(size_t)k] << " degrees, min_dot " << p.min_dot << std::endl;
+      os << "# Patch " << k << " reflectance: " << p.reflectance << std::endl;
+    }
+    f << os.str();
+  }
+  f << cols;
+  f << fluxmap_rows(hits.data(), n, c.n_theta, c.n_phi, 1);
+  for (int k = 0; k < sp.baffles.n_baffles; ++k) {
+    f << "# Baffle " << k << " arrivals (side 0, side 1): " << sc.baffle.arrivals[k][0] << ", " << sc.baffle.arrivals[k][1] << std::endl;
+    f << "# Baffle " << k << " absorbed (side 0, side 1): " << sc.baffle.absorbed[k][0] << ", " << sc.baffle.absorbed[k][1] << std::endl;
+  }
+  // per class: the patches, the rest of the inner sphere, rim and outer sphere
+  f << "# Class arrivals:";
+  for (int k = 0; k < sp.patches.n_patches + 2; ++k) f << (k ? ", " : " ") << sc.patch_arrivals[k];
+  f << std::endl << "# Class absorbed:";
+  for (int k = 0; k < sp.patches.n_patches + 2; ++k) f << (k ? ", " : " ") << sc.patch_absorbed[k];
+  f << std::endl;
+  f << "# Launched: " << st.launched << std::endl;
+  f << "# Exited: " << st.exited << std::endl;
+  f << "# Total rays exiting port: " << st.counted_below_z << " out of " << n << std::endl;
+  f << "# Absorbed: " << st.absorbed << std::endl;
+  f << "# Suspended: " << st.suspended << std::endl;
+  f << "# Wall hits: " << st.wall_hits << std::endl;
+  f << "# Detector hits: " << st.bin_increments << std::endl;
+}
+
 }  // namespace rootMacros
 
 }  // namespace isxhost

@@ -63,6 +63,9 @@ struct RunOptions {
   // baffleFlux --centre x,y,z --normal x,y,z --radius r --reflectance rho, repeatable: the k-th of each makes baffle k
   std::vector<std::string> baffle_centres, baffle_normals;
   std::vector<double> baffle_radii, baffle_reflectances;
+  // sceneFlux --patch-dir x,y,z --patch-half-angle deg --patch-reflectance rho, repeatable: the k-th of each makes patch k
+  std::vector<std::string> patch_dirs;
+  std::vector<double> patch_half_angles, patch_reflectances;
   bool quiet = false;              // env ISX_QUIET
   int flush_rows = 0;              // env ISX_FLUSH_ROWS: theta rows per launch of the per-position sweep, written and flushed
                                    // before the next launch starts (0 = as many as hold ~4e9 rays: one launch for the reference's n)
@@ -204,6 +207,11 @@ void beamFlux();
 // repeatable: isx_baffle_disc makes baffle k from the k-th of each) through isx_fluxmap_baffle: baffle_flux.csv in the flux maps'
 // format (theta,phi,fraction), the baffles and their counters in the # metadata
 void baffleFlux();
+// the flux map of a scene -- beamFlux's source (--origin, --axis, --half-angle, --law), baffleFlux's baffles (--centre, --normal,
+// --radius, --reflectance) and wall patches (--patch-dir, --patch-half-angle, --patch-reflectance, each repeatable:
+// isx_wall_patch_cap makes patch k from the k-th of each) -- through isx_fluxmap_scene: scene_flux.csv in the flux maps' format,
+// the scene and all counters in the # metadata.  --radius: the first ones are the baffles', one more, if given, is the beam's.
+void sceneFlux();
 }  // namespace rootMacros
 
 }  // namespace isxhost

@@ -260,3 +260,35 @@ def fluxmap_baffle_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, 
         ab = buf[nh + na:nh + 2 * na].astype(np.uint64).reshape(ab.shape)
         census = buf[nh + 2 * na:]
     return hits, arr, ab, dict(zip(CENSUS_FIELDS, (int(x) for x in census)))
+
+
+def fluxmap_scene_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, first_ray: int = 0, device=None):
+    """The flux map of a scene (altair_raytracing_amd.fluxmap_scene) ray-sharded: this rank's contiguous shard through
+    `trace(cfg, spec, count, seed, first) -> (hits, counts, stats)`, then ONE SUM all-reduce that carries the histogram, the 36
+    scene counters and the census.  Returns (hits[n_theta, n_phi] uint64, patch_arrivals[10] uint64, patch_absorbed[10] uint64,
+    baffle arrivals[4, 2] uint64, baffle absorbed[4, 2] uint64, census dict) -- identical on every rank."""
+    import torch
+    import torch.distributed as dist
+
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(), dist.get_world_size()
+    else:
+        rank, world = 0, 1
+    first, count = shard(n_total, rank, world)
+    hits, cnt, st = trace(cfg, spec, count, seed, first_ray + first)
+    parts = list(cnt.arrays())
+    census = np.array([getattr(st, k) for k in CENSUS_FIELDS], dtype=np.int64)
+    if world > 1:
+        buf = torch.from_numpy(np.concatenate([hits.reshape(-1).astype(np.int64)] + [a.reshape(-1).astype(np.int64) for a in parts] +
+                                              [census]))
+        if device is not None:
+            buf = buf.to(device)
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+        buf = buf.cpu().numpy()
+        at = hits.size
+        hits = buf[:at].astype(np.uint64).reshape(hits.shape)
+        for k, a in enumerate(parts):
+            parts[k] = buf[at:at + a.size].astype(np.uint64).reshape(a.shape)
+            at += a.size
+        census = buf[at:]
+    return (hits, *parts, dict(zip(CENSUS_FIELDS, (int(x) for x in census))))

@@ -780,8 +780,8 @@ int isx_fluxmap_beam_device(const isx_config* cfg, const isx_beam_spec* spec, ui
  * 4 B per bin, 32 B per row, 64 B per column -- do not fit the binning kernels' LDS (the device's once isx_init() has asked it,
  * 160 KiB before; the default 180 x 90 grid fits).  ISX_ERR_BAD_ARG: a NULL pointer (last_baffle, counts and
  * stats excepted).  Without a HIP device: ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT.
- * Out of scope: the beam source combined with baffles, baffles for the other sinks (exit maps, wall map, light field, order
- * histograms, wall patches, disc sweeps), and the chord mode.
+ * Out of scope: baffles for the other sinks (exit maps, wall map, light field, order histograms, disc sweeps), and the chord mode.
+ * The beam source and the wall patches combine with baffles in the scene calls below (isx_fluxmap_scene).
  */
 #define ISX_MAX_BAFFLES 4
 typedef struct isx_baffle {
@@ -824,6 +824,66 @@ int isx_fluxmap_baffle(const isx_config* cfg, const isx_baffle_spec* spec, uint6
                        uint64_t* hits, isx_baffle_counts* counts, isx_stats* stats);
 int isx_fluxmap_baffle_device(const isx_config* cfg, const isx_baffle_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
                               uint64_t* d_hits, uint64_t* d_counts /*[16]*/);
+
+/*
+ * Scene: the beam source, the baffles and the wall patches in ONE trace -- a lamp inside the sphere, a screen between lamp and
+ * detector, a detector on the wall, a shield over the port.  No rule of its own: per ray the three contracts above, operation for
+ * operation as they are stated there.
+ *   1. Start: (p, v) by the beam contract (isx_fluxmap_beam: Philox stream 3, block 0); the ray starts on no surface.
+ *   2. Segment: q, the next boundary point, as always; the segment p -> q is tested against every baffle except the one of the
+ *      ray's previous interaction, by the baffle contract's rule (isx_fluxmap_baffle: smallest f, lowest k on a tie, a NaN or
+ *      s_p == 0 is no crossing -- which also covers a start point in a baffle's plane).
+ *   3. Baffle struck: the baffle takes the interaction with the ray's index j exactly as in isx_fluxmap_baffle -- counted by side,
+ *      absorbed against the baffle's own threshold, re-emitted by the cosine law about the struck side, bounce limit, that baffle
+ *      skipped for one segment.
+ *   4. Wall arrival (no hit, q on a mirror): classified by the wall-patch rule (isx_wall_patches): the class is the lowest k with
+ *      q . axis >= min_dot, else P, and P + 1 off the inner sphere; patch_arrivals[class] += 1; the absorb test and the re-emission
+ *      use rho_eff of the class, the azimuth's uniform being (b + 1/2) / rho_thr(rho_eff); an absorbed ray adds to
+ *      patch_absorbed[class].
+ *   5. Box (no hit, q on the world box): the ray is ISX_RAY_EXITED, as always.
+ *   6. last_baffle[i] is as in isx_baffle_endstates; last_class[i] is the class of the ray's last mirror interaction, -1 if none.
+ * For every call: sum(patch_arrivals) + sum(baffle.arrivals) == stats.wall_hits; sum(patch_absorbed) + sum(baffle.absorbed) ==
+ * stats.absorbed; stats.bin_increments is the histogram's sum.  No result depends on any isx_set_option switch nor on how a job is
+ * cut into calls.  One route whatever the switches say, as for the beam and the baffles: the trace kernel is
+ * isx_trace_assist_scene_kernel, the binning kernels are isx_fluxmap's ("pipeline" 0, "assist" 0, "fate_scan" and "bin_mode" 2 do
+ * not apply; "bin_mode" 0 bins by brute force); a scene never takes one of the specialised kernels, and the specialised calls
+ * stay the faster choice for their own cases.  With the default spec (the pencil as the degenerate beam, no baffle, no patch)
+ * every result is bit for bit isx_fluxmap's / isx_trace_endstates'.
+ *
+ * Scope: ISX_SOURCE_PENCIL, ISX_SURFACE_ROBAST with `lambertian` set, ISX_TRACE_EXPLICIT, both hit-line modes.  Refused, with the
+ * same codes and whether or not a device is present: everything isx_fluxmap_beam refuses of `beam`, isx_fluxmap_baffle of `baffles`
+ * (the detector grid included, for the two flux-map calls) and isx_wall_patches of `patches` -- each nested struct_size must be
+ * right as well as the outer one.  ISX_ERR_BAD_ARG: a NULL pointer (start_point, start_dir, last_baffle, last_class, counts and
+ * stats excepted).  Out of scope: a scene for the other sinks (exit maps, wall map, light field, order histograms, disc sweeps),
+ * the chord mode, the other borders and the BRDF source.
+ */
+typedef struct isx_scene_spec {
+  uint32_t struct_size;        /* sizeof(isx_scene_spec), set by isx_default_scene_spec() */
+  uint32_t reserved0;          /* 0 */
+  isx_beam_spec beam;          /* the source (the pencil is the degenerate beam) */
+  isx_baffle_spec baffles;     /* n_baffles 0: none */
+  isx_wall_patch_spec patches; /* n_patches 0: none */
+} isx_scene_spec;
+typedef struct isx_scene_counts {
+  uint64_t patch_arrivals[ISX_MAX_WALL_PATCHES + 2];  /* class k < P patch k, P the rest of the inner sphere, P + 1 rim and outer sphere; entries above P + 1 stay 0 */
+  uint64_t patch_absorbed[ISX_MAX_WALL_PATCHES + 2];
+  isx_baffle_counts baffle;                            /* arrivals[k][side], absorbed[k][side] */
+} isx_scene_counts;                                    /* 36 words */
+
+/* isx_default_beam_spec, isx_default_baffle_spec and isx_default_wall_patch_spec into the three parts.  Host only, no GPU needed. */
+void isx_default_scene_spec(const isx_config* cfg, isx_scene_spec* spec);
+/* isx_trace_endstates of the scene; start_point, start_dir, last_baffle and last_class may be NULL. */
+int isx_scene_endstates(const isx_config* cfg, const isx_scene_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                        int32_t* status, int32_t* n_points, double* last_point /*[n][3]*/, double* direction /*[n][3]*/,
+                        double* start_point /*[n][3]*/, double* start_dir /*[n][3]*/, int32_t* last_baffle /*[n]*/,
+                        int32_t* last_class /*[n]*/);
+/* isx_fluxmap / isx_fluxmap_device of the scene: hits [n_theta * n_phi] and counts, zeroed by the callee (counts and stats may be
+ * NULL).  The device form ACCUMULATES into d_hits and d_counts (36 words, isx_scene_counts' layout; neither may be NULL) and
+ * returns after enqueueing; isx_sync() / isx_take_stats() as for isx_fluxmap_device. */
+int isx_fluxmap_scene(const isx_config* cfg, const isx_scene_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                      uint64_t* hits, isx_scene_counts* counts, isx_stats* stats);
+int isx_fluxmap_scene_device(const isx_config* cfg, const isx_scene_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                             uint64_t* d_hits, uint64_t* d_counts /*[36]*/);
 
 /*
  * Series driver (sweepSeries, fluxAtObserverOptimize.C:892-921 / fluxAtObserverFast.C:1641-1673):
