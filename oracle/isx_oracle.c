@@ -1188,3 +1188,215 @@ int isxo_exit_directions(const isxo_config* c, uint64_t n, uint64_t seed, uint64
   *count = k;
   return 0;
 }
+
+/* ------------------------------------------------------------------------- */
+/* scene walk: the composed contract of include/isx.h (scene section, steps   */
+/* 1-6) -- beam start, baffle segment test, wall-patch classes -- on the      */
+/* statics above.  The segment test, the beam sampling and the cap test are   */
+/* plain products summed left to right as the header writes them (NOT dot3,   */
+/* which is an fma chain); contraction is off for this file.                  */
+/* ------------------------------------------------------------------------- */
+typedef struct {
+  isxo_scene_counts cnt;
+  isxo_stats st;
+  uint64_t after_baffle, after_patch, baffle_to_baffle;
+} walk_totals;
+
+static void walk_totals_add(walk_totals* a, const walk_totals* b) {
+  uint64_t* wa = (uint64_t*)&a->cnt;
+  const uint64_t* wb = (const uint64_t*)&b->cnt;
+  for (size_t k = 0; k < sizeof(isxo_scene_counts) / sizeof(uint64_t); k++) wa[k] += wb[k];
+  stats_add(&a->st, &b->st);
+  a->after_baffle += b->after_baffle;
+  a->after_patch += b->after_patch;
+  a->baffle_to_baffle += b->baffle_to_baffle;
+}
+
+/* the start of a ray by the beam contract: block 0 of Philox stream 3 */
+static void beam_start(const isxo_beam_spec* b, uint64_t seed, uint64_t ray, v3* p_out, v3* v_out) {
+  uint32_t w[4];
+  draw_block(seed, ray, 0u, 3u, w);
+  const double u0 = isxo_u01(w[0]), u1 = isxo_u01(w[1]), u2 = isxo_u01(w[2]), u3 = isxo_u01(w[3]);
+  const double rr = b->radius * sqrt(u0);
+  double s1, c1, s3, c3;
+  isxo_sincos2pi(u1, &s1, &c1);
+  const double a = rr * c1;
+  const double bb = rr * s1;
+  p_out->x = (b->origin[0] + a * b->e1[0]) + bb * b->e2[0];
+  p_out->y = (b->origin[1] + a * b->e1[1]) + bb * b->e2[1];
+  p_out->z = (b->origin[2] + a * b->e1[2]) + bb * b->e2[2];
+  double ct, st;
+  if (b->angular_law == 1) {
+    const double s2 = u2 * (1.0 - b->cos_min * b->cos_min);
+    st = sqrt(s2);
+    ct = sqrt(1.0 - s2);
+  } else {
+    ct = 1.0 - u2 * (1.0 - b->cos_min);
+    st = sqrt(1.0 - ct * ct);
+  }
+  isxo_sincos2pi(u3, &s3, &c3);
+  const double k1 = st * c3;
+  const double k2 = st * s3;
+  const double dx = (ct * b->axis[0] + k1 * b->e1[0]) + k2 * b->e2[0];
+  const double dy = (ct * b->axis[1] + k1 * b->e1[1]) + k2 * b->e2[1];
+  const double dz = (ct * b->axis[2] + k1 * b->e1[2]) + k2 * b->e2[2];
+  const double mag = sqrt((dx * dx + dy * dy) + dz * dz);
+  v_out->x = dx / mag; v_out->y = dy / mag; v_out->z = dz / mag;
+}
+
+/* the baffle contract's segment test p -> q: the struck baffle (or -1), its side and the point x */
+static int baffle_segment(const isxo_baffle* bf, int nb, const double* r2, v3 p, v3 q, int skip, int* side_out, v3* x_out) {
+  int best = -1;
+  double bf_f = 0.0;
+  for (int k = 0; k < nb; k++) {
+    if (k == skip) continue;
+    const double cx = bf[k].centre[0], cy = bf[k].centre[1], cz = bf[k].centre[2];
+    const double mx = bf[k].normal[0], my = bf[k].normal[1], mz = bf[k].normal[2];
+    const double sp = ((p.x - cx) * mx + (p.y - cy) * my) + (p.z - cz) * mz;
+    const double sq = ((q.x - cx) * mx + (q.y - cy) * my) + (q.z - cz) * mz;
+    if (!((sp > 0.0 && sq < 0.0) || (sp < 0.0 && sq > 0.0))) continue;
+    const double f = sp / (sp - sq);
+    v3 x = { p.x + f * (q.x - p.x), p.y + f * (q.y - p.y), p.z + f * (q.z - p.z) };
+    const double dx = x.x - cx, dy = x.y - cy, dz = x.z - cz;
+    if ((dx * dx + dy * dy) + dz * dz <= r2[k] && (best < 0 || f < bf_f)) {
+      best = k; bf_f = f; *x_out = x; *side_out = sp > 0.0 ? 0 : 1;
+    }
+  }
+  return best;
+}
+
+int isxo_scene_walk(const isxo_config* c, const isxo_beam_spec* beam, const isxo_baffle_spec* baffles,
+                    const isxo_wall_patch_spec* patches, uint64_t n, uint64_t seed, uint64_t first,
+                    const isxo_scene_rays* rays, isxo_scene_totals* totals, int nthreads) {
+  geom g;
+  if (!c) return -3;
+  int rc = prepare(c, &g);
+  if (rc) return rc;
+  /* the replays' scope: the pencil's source model, the Lambertian ROBAST border, explicit bounces */
+  if (c->lambertian != 1 || c->surface_model != 0 || c->source_model != 0 || c->trace_mode != 0) return -2;
+  const int nb = baffles ? baffles->n_baffles : 0;
+  const int P = patches ? patches->n_patches : 0;
+  if (nb < 0 || nb > ISXO_MAX_BAFFLES || P < 0 || P > ISXO_MAX_WALL_PATCHES) return -2;
+  if (beam && beam->angular_law != 0 && beam->angular_law != 1) return -2;
+  /* per class and per baffle: the configuration with that reflectance through prepare(), so that the threshold and
+   * psi_k1 / psi_k0 come from the one place that makes the wall's */
+  geom cg[ISXO_MAX_WALL_PATCHES + 2], bg[ISXO_MAX_BAFFLES];
+  double r2[ISXO_MAX_BAFFLES];
+  v3 rm[ISXO_MAX_BAFFLES];
+  for (int k = 0; k < P + 2; k++) {
+    isxo_config ck = *c;
+    if (k < P) ck.reflectance = patches->patch[k].reflectance;
+    if ((rc = prepare(&ck, &cg[k]))) return rc;
+  }
+  for (int k = 0; k < nb; k++) {
+    isxo_config ck = *c;
+    ck.reflectance = baffles->baffle[k].reflectance;
+    if ((rc = prepare(&ck, &bg[k]))) return rc;
+    r2[k] = baffles->baffle[k].radius * baffles->baffle[k].radius;
+    rm[k].x = c->r_in * baffles->baffle[k].normal[0];
+    rm[k].y = c->r_in * baffles->baffle[k].normal[1];
+    rm[k].z = c->r_in * baffles->baffle[k].normal[2];
+  }
+  const isxo_scene_rays none = { 0 };
+  const isxo_scene_rays R = rays ? *rays : none;
+  walk_totals tot;
+  memset(&tot, 0, sizeof(tot));
+  double t0 = now_ms();
+#ifdef _OPENMP
+  if (nthreads > 0) omp_set_num_threads(nthreads);
+  else omp_set_num_threads(omp_get_num_procs());
+#endif
+#pragma omp parallel
+  {
+    walk_totals my;
+    memset(&my, 0, sizeof(my));
+#pragma omp for schedule(dynamic, 256)
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+      const uint64_t ray = first + (uint64_t)i;
+      v3 p, v;
+      if (beam) beam_start(beam, seed, ray, &p, &v);
+      else { p = g.src; v = g.dir0; }
+      const v3 p0 = p, v0 = v;
+      int on = K_NONE, npts = 1, status, skip = -1, lb = -1, lc = -1, fc = -1, fk = -1, b2b = 0;
+      uint32_t j = 0;
+      for (;;) {
+        v3 q, x;
+        int side = 0;
+        const int kind = next_hit(&g, p, &v, on, &q);
+        const int k = nb ? baffle_segment(baffles->baffle, nb, r2, p, q, skip, &side, &x) : -1;
+        if (npts == 1) fk = k >= 0 ? -2 : kind;
+        npts++;
+        uint32_t wl[4];
+        draw_block(seed, ray, j >> 1, 0u, wl);
+        const uint32_t wa = wl[2u * (j & 1u)], wb = wl[2u * (j & 1u) + 1u];
+        if (k >= 0) {
+          p = x;
+          my.cnt.baffle.arrivals[k][side]++;
+          if (lb >= 0 && skip >= 0 && skip != k) b2b = 1;   /* straight from another baffle */
+          lb = 2 * k + side;
+          if (j == 0) fc = -2;
+          on = K_NONE; skip = k;
+          j++;
+          if (!((uint64_t)wb < bg[k].rho_thr)) { my.cnt.baffle.absorbed[k][side]++; status = ISXO_ABSORBED; break; }
+          const v3 zero = { 0.0, 0.0, 0.0 };
+          const v3 S = cosine_emission(&bg[k], K_INNER, zero, wa, wb);
+          v3 w;
+          if (side == 0) { w.x = rm[k].x + S.x; w.y = rm[k].y + S.y; w.z = rm[k].z + S.z; }
+          else { w.x = (-rm[k].x) + S.x; w.y = (-rm[k].y) + S.y; w.z = (-rm[k].z) + S.z; }
+          const double mag = sqrt((w.x * w.x + w.y * w.y) + w.z * w.z);
+          v.x = w.x / mag; v.y = w.y / mag; v.z = w.z / mag;
+          if (npts > g.limit) { status = ISXO_SUSPENDED; my.after_baffle++; break; }
+          continue;
+        }
+        skip = -1;
+        p = q;
+        if (kind == K_BOX) { status = ISXO_EXITED; break; }
+        on = kind;
+        int cls = P + 1;
+        if (kind == K_INNER) {
+          cls = P;
+          for (int m = 0; m < P; m++) {
+            const isxo_wall_patch* wp = &patches->patch[m];
+            if ((p.x * wp->axis[0] + p.y * wp->axis[1]) + p.z * wp->axis[2] >= wp->min_dot) { cls = m; break; }
+          }
+        }
+        my.cnt.patch_arrivals[cls]++;
+        lc = cls;
+        if (j == 0) fc = cls;
+        j++;
+        if (!((uint64_t)wb < cg[cls].rho_thr)) { my.cnt.patch_absorbed[cls]++; status = ISXO_ABSORBED; break; }
+        v = cosine_emission(&cg[cls], kind, p, wa, wb);
+        if (npts > g.limit) { status = ISXO_SUSPENDED; if (cls < P) my.after_patch++; break; }
+      }
+      my.st.launched++;
+      my.st.wall_hits += j;
+      if (status == ISXO_EXITED) {
+        my.st.exited++;
+        if (p.z < c->exit_port_z) my.st.counted_below_z++;
+      } else if (status == ISXO_ABSORBED) my.st.absorbed++;
+      else my.st.suspended++;
+      my.baffle_to_baffle += (uint64_t)b2b;
+      if (R.status) R.status[i] = status;
+      if (R.n_points) R.n_points[i] = npts;
+      if (R.last_point) { R.last_point[3 * i] = p.x; R.last_point[3 * i + 1] = p.y; R.last_point[3 * i + 2] = p.z; }
+      if (R.direction) { R.direction[3 * i] = v.x; R.direction[3 * i + 1] = v.y; R.direction[3 * i + 2] = v.z; }
+      if (R.start_point) { R.start_point[3 * i] = p0.x; R.start_point[3 * i + 1] = p0.y; R.start_point[3 * i + 2] = p0.z; }
+      if (R.start_dir) { R.start_dir[3 * i] = v0.x; R.start_dir[3 * i + 1] = v0.y; R.start_dir[3 * i + 2] = v0.z; }
+      if (R.last_baffle) R.last_baffle[i] = lb;
+      if (R.last_class) R.last_class[i] = lc;
+      if (R.first_class) R.first_class[i] = fc;
+      if (R.first_kind) R.first_kind[i] = fk;
+    }
+#pragma omp critical
+    walk_totals_add(&tot, &my);
+  }
+  tot.st.t_kernel_ms = now_ms() - t0;
+  if (totals) {
+    totals->counts = tot.cnt;
+    totals->census = tot.st;
+    totals->suspended_after_baffle = tot.after_baffle;
+    totals->suspended_after_patch = tot.after_patch;
+    totals->rays_baffle_to_baffle = tot.baffle_to_baffle;
+  }
+  return 0;
+}

@@ -107,6 +107,58 @@ int isxo_next_boundary(const isxo_config* cfg, const double p[3], const double v
 int isxo_surface_normal(const isxo_config* cfg, int kind, const double q[3], double n_out[3]);
 int isxo_cosine_emission(const isxo_config* cfg, int kind, const double q[3], uint32_t wa, uint32_t wb, double w_out[3]);
 
+/* The scene of include/isx.h (isx_fluxmap_scene, steps 1-6: beam start, baffle segment test, wall-patch classes) walked
+ * natively, ray by ray, on this file's own trace loop.  The four structs are layout twins of isx_beam_spec, isx_baffle_spec,
+ * isx_wall_patch_spec and isx_scene_counts; their struct_size / reserved fields are not interpreted. */
+#define ISXO_MAX_WALL_PATCHES 8
+#define ISXO_MAX_BAFFLES 4
+typedef struct isxo_beam_spec {
+  uint32_t struct_size, reserved0;
+  double origin[3], axis[3], e1[3], e2[3];   /* used as given */
+  double radius, cos_min;
+  int32_t angular_law, reserved1;            /* 0: uniform in solid angle, 1: cosine-weighted */
+} isxo_beam_spec;
+typedef struct isxo_baffle { double centre[3], normal[3], radius, reflectance; } isxo_baffle;
+typedef struct isxo_baffle_spec {
+  uint32_t struct_size, reserved0;
+  int32_t n_baffles, reserved1;
+  isxo_baffle baffle[ISXO_MAX_BAFFLES];
+} isxo_baffle_spec;
+typedef struct isxo_wall_patch { double axis[3], min_dot, reflectance; } isxo_wall_patch;
+typedef struct isxo_wall_patch_spec {
+  uint32_t struct_size, reserved0;
+  int32_t n_patches, reserved1;
+  isxo_wall_patch patch[ISXO_MAX_WALL_PATCHES];
+} isxo_wall_patch_spec;
+typedef struct isxo_baffle_counts {
+  uint64_t arrivals[ISXO_MAX_BAFFLES][2], absorbed[ISXO_MAX_BAFFLES][2];   /* [baffle][side] */
+} isxo_baffle_counts;
+typedef struct isxo_scene_counts {
+  uint64_t patch_arrivals[ISXO_MAX_WALL_PATCHES + 2], patch_absorbed[ISXO_MAX_WALL_PATCHES + 2];
+  isxo_baffle_counts baffle;
+} isxo_scene_counts;   /* 36 words */
+/* per-ray outputs, [n] or [n][3]; every pointer may be NULL.  first_class: the class of the ray's FIRST interaction if that was a
+ * wall's, -2 if a baffle's, -1 if it had none; first_kind: the boundary its first segment ends on, -2: on a baffle. */
+typedef struct isxo_scene_rays {
+  int32_t *status, *n_points;
+  double *last_point, *direction, *start_point, *start_dir;
+  int32_t *last_baffle, *last_class, *first_class, *first_kind;
+} isxo_scene_rays;
+typedef struct isxo_scene_totals {
+  isxo_scene_counts counts;
+  isxo_stats census;                 /* bin_increments stays 0: the walk bins nothing */
+  uint64_t suspended_after_baffle;   /* rays the bounce limit stopped right after a baffle interaction */
+  uint64_t suspended_after_patch;    /* ... right after an interaction on a patch (class < P) */
+  uint64_t rays_baffle_to_baffle;    /* rays with a baffle interaction that directly follows one on another baffle */
+} isxo_scene_totals;
+/* beam NULL: the pencil of cfg (src, dir / |dir|); baffles / patches NULL: none; rays / totals may be NULL.  OpenMP over rays
+ * (nthreads <= 0: all cores); the totals are summed per thread, then added: no result depends on the thread count.  Scope: the
+ * Lambertian ROBAST border, the pencil's source model, explicit bounces; -2 for anything else, for a part count out of range or
+ * an unknown angular law.  The refusals of the library's scene calls are NOT restated: what is handed over is walked. */
+int isxo_scene_walk(const isxo_config* cfg, const isxo_beam_spec* beam, const isxo_baffle_spec* baffles,
+                    const isxo_wall_patch_spec* patches, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
+                    const isxo_scene_rays* rays, isxo_scene_totals* totals, int nthreads);
+
 int isxo_max_threads(void);
 
 #ifdef __cplusplus

@@ -47,6 +47,46 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class BeamSpec(C.Structure):
+    """Layout twins of isx_beam_spec, isx_baffle_spec, isx_wall_patch_spec and isx_scene_counts (isxo_* in oracle/isx_oracle.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("origin", C.c_double * 3), ("axis", C.c_double * 3),
+                ("e1", C.c_double * 3), ("e2", C.c_double * 3), ("radius", C.c_double), ("cos_min", C.c_double),
+                ("angular_law", C.c_int32), ("reserved1", C.c_int32)]
+
+
+class Baffle(C.Structure):
+    _fields_ = [("centre", C.c_double * 3), ("normal", C.c_double * 3), ("radius", C.c_double), ("reflectance", C.c_double)]
+
+
+class BaffleSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("n_baffles", C.c_int32), ("reserved1", C.c_int32),
+                ("baffle", Baffle * 4)]
+
+
+class WallPatch(C.Structure):
+    _fields_ = [("axis", C.c_double * 3), ("min_dot", C.c_double), ("reflectance", C.c_double)]
+
+
+class WallPatchSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("n_patches", C.c_int32), ("reserved1", C.c_int32),
+                ("patch", WallPatch * 8)]
+
+
+class SceneRays(C.Structure):
+    _fields_ = [("status", C.POINTER(C.c_int32)), ("n_points", C.POINTER(C.c_int32)),
+                ("last_point", C.POINTER(C.c_double)), ("direction", C.POINTER(C.c_double)),
+                ("start_point", C.POINTER(C.c_double)), ("start_dir", C.POINTER(C.c_double)),
+                ("last_baffle", C.POINTER(C.c_int32)), ("last_class", C.POINTER(C.c_int32)),
+                ("first_class", C.POINTER(C.c_int32)), ("first_kind", C.POINTER(C.c_int32))]
+
+
+class SceneTotals(C.Structure):
+    _fields_ = [("patch_arrivals", C.c_uint64 * 10), ("patch_absorbed", C.c_uint64 * 10),
+                ("baffle_arrivals", (C.c_uint64 * 2) * 4), ("baffle_absorbed", (C.c_uint64 * 2) * 4),
+                ("census", Stats), ("suspended_after_baffle", C.c_uint64), ("suspended_after_patch", C.c_uint64),
+                ("rays_baffle_to_baffle", C.c_uint64)]
+
+
 _lib = None
 
 
@@ -93,6 +133,8 @@ def lib():
         L.isxo_next_boundary.argtypes = [P(Config), P(dbl), P(dbl), C.c_int, P(dbl), P(dbl)]
         L.isxo_surface_normal.argtypes = [P(Config), C.c_int, P(dbl), P(dbl)]
         L.isxo_cosine_emission.argtypes = [P(Config), C.c_int, P(dbl), C.c_uint32, C.c_uint32, P(dbl)]
+        L.isxo_scene_walk.argtypes = [P(Config), P(BeamSpec), P(BaffleSpec), P(WallPatchSpec), u64, u64, u64, P(SceneRays),
+                                      P(SceneTotals), C.c_int]
         _lib = L
     return _lib
 
@@ -258,3 +300,54 @@ def exit_directions(cfg, n, seed, first=0, capacity=None):
     assert rc == 0, rc
     k = min(int(cnt.value), cap)
     return ids[:k], d[:k], int(cnt.value)
+
+
+WALK_THREADS = 16      # (the walk's default: a fixed number, not the machine's core count)
+
+
+def scene_walk(cfg, scene, n, seed, first=0, nthreads=None):
+    """The scene of scene_np.spec_of() -- {"beam": a beam_np spec or None (the pencil of cfg), "baffles": [(centre, normal,
+    radius, reflectance)], "patches": [(axis, min_dot, reflectance)]} -- walked natively by isxo_scene_walk.  -> the dict of
+    scene_np.replay(): the per-ray arrays, patch_arrivals / patch_absorbed [P + 2], baffle_arrivals / baffle_absorbed [K, 2]
+    (K = max(len(baffles), 1)), the census dict, suspended_after_baffle / suspended_after_patch; and one key more,
+    rays_baffle_to_baffle: the rays with a baffle interaction that directly follows one on ANOTHER baffle."""
+    beam, baffles, patches = scene.get("beam"), list(scene.get("baffles") or ()), list(scene.get("patches") or ())
+    assert len(baffles) <= 4 and len(patches) <= 8
+    bs = None
+    if beam is not None:
+        bs = BeamSpec()
+        bs.struct_size = C.sizeof(BeamSpec)
+        for k in ("origin", "axis", "e1", "e2"):
+            setattr(bs, k, (C.c_double * 3)(*[float(x) for x in beam[k]]))
+        bs.radius, bs.cos_min, bs.angular_law = float(beam["radius"]), float(beam["cos_min"]), int(beam["law"])
+    fs = BaffleSpec()
+    fs.struct_size, fs.n_baffles = C.sizeof(BaffleSpec), len(baffles)
+    for k, (centre, normal, radius, rho) in enumerate(baffles):
+        fs.baffle[k].centre = (C.c_double * 3)(*[float(x) for x in centre])
+        fs.baffle[k].normal = (C.c_double * 3)(*[float(x) for x in normal])
+        fs.baffle[k].radius, fs.baffle[k].reflectance = float(radius), float(rho)
+    ws = WallPatchSpec()
+    ws.struct_size, ws.n_patches = C.sizeof(WallPatchSpec), len(patches)
+    for k, (axis, min_dot, rho) in enumerate(patches):
+        ws.patch[k].axis = (C.c_double * 3)(*[float(x) for x in axis])
+        ws.patch[k].min_dot, ws.patch[k].reflectance = float(min_dot), float(rho)
+    out = {k: np.zeros(n, dtype=np.int32) for k in ("status", "n_points", "last_baffle", "last_class", "first_class", "first_kind")}
+    out.update({k: np.zeros((n, 3), dtype=np.float64) for k in ("last_point", "direction", "start_point", "start_dir")})
+    rays = SceneRays()
+    for k, a in out.items():
+        setattr(rays, k, _p(a, C.c_double if a.dtype == np.float64 else C.c_int32))
+    tot = SceneTotals()
+    rc = lib().isxo_scene_walk(C.byref(cfg), None if bs is None else C.byref(bs), C.byref(fs), C.byref(ws), n, seed, first,
+                               C.byref(rays), C.byref(tot), WALK_THREADS if nthreads is None else nthreads)
+    assert rc == 0, rc
+    P, K = len(patches), max(len(baffles), 1)
+    out["patch_arrivals"] = np.array(tot.patch_arrivals[:P + 2], dtype=np.uint64)
+    out["patch_absorbed"] = np.array(tot.patch_absorbed[:P + 2], dtype=np.uint64)
+    out["baffle_arrivals"] = np.array([list(r) for r in tot.baffle_arrivals], dtype=np.uint64)[:K]
+    out["baffle_absorbed"] = np.array([list(r) for r in tot.baffle_absorbed], dtype=np.uint64)[:K]
+    out["census"] = {k: int(getattr(tot.census, k)) for k in ("launched", "exited", "counted_below_z", "absorbed", "suspended",
+                                                              "wall_hits")}
+    out["suspended_after_baffle"] = int(tot.suspended_after_baffle)
+    out["suspended_after_patch"] = int(tot.suspended_after_patch)
+    out["rays_baffle_to_baffle"] = int(tot.rays_baffle_to_baffle)
+    return out

@@ -133,7 +133,13 @@ def test_surface_series_and_chunks(isx, orc):
 def test_bounded_wait_failure_is_reported_not_silent():
     """libisx_giveup.so is libisx.so built with -DISX_TEST_GIVEUP -- the assist wave of workgroup 0 finds "no
     room on the resume ring and no progress" at its first batch.  The wave must leave its rays unwritten (the ring stays consistent),
-    every wave of the workgroup must leave promptly, and the host must report ISX_ERR_HIP instead of a short histogram."""
+    every wave of the workgroup must leave promptly, and the host must report ISX_ERR_HIP instead of a short histogram.
+
+    The failing launch runs on 8 workgroups (`grid_blocks`).  On the default grid the rays come off one queue shared by the default grid
+    (a workgroup for every two rays per tracer lane), and a workgroup 0 that started late found it dry: its assist wave never came to a hand-back, nothing gave up, and
+    the test failed with NO-ERROR now and then (docs/LOG.md 17.4).  With 8 workgroups resident from the start and 25 000 rays for
+    each, workgroup 0 cannot miss its share, while seven others still run to their end beside the one that gives up.  The call
+    after the failure is on the default grid again."""
     lib = os.path.join(ROOT, "altair-raytracing_amd", "csrc", "libisx_giveup.so")
     assert os.path.exists(lib), "libisx_giveup.so not built (make -C altair-raytracing_amd/csrc libisx_giveup.so)"
     code = r"""
@@ -141,12 +147,14 @@ import sys, time
 sys.path.insert(0, %r)
 import altair_raytracing_amd as isx
 isx.load(); isx.init(0)
+isx.set_option("grid_blocks", 8)
 t0 = time.time()
 try:
     isx.fluxmap(isx.default_config(), 200000, 1)
     print("NO-ERROR")
 except isx.IsxError as e:
     print("STATUS", e.status, "HIP", isx.load().isx_last_hip_error(), "T", round(time.time() - t0, 3))
+isx.set_option("grid_blocks", 0)
 # the library is usable afterwards (the failed launch left no wave behind): an option that avoids the assist wave gives a map
 isx.set_option("assist", 0)
 h, st = isx.fluxmap(isx.default_config(), 20000, 1)
