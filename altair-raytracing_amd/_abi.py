@@ -50,6 +50,7 @@ EXPORTS = [
     "isx_default_beam_spec", "isx_beam_cone", "isx_beam_endstates", "isx_fluxmap_beam", "isx_fluxmap_beam_device",
     "isx_default_baffle_spec", "isx_baffle_disc", "isx_baffle_endstates", "isx_fluxmap_baffle", "isx_fluxmap_baffle_device",
     "isx_default_scene_spec", "isx_scene_endstates", "isx_fluxmap_scene", "isx_fluxmap_scene_device",
+    "isx_default_response_spec", "isx_scene_response", "isx_scene_response_device", "isx_response_reweight",
 ]
 
 
@@ -263,6 +264,22 @@ class SceneCounts(C.Structure):
 
 SCENE_COUNT_WORDS = 2 * (MAX_WALL_PATCHES + 2) + 4 * MAX_BAFFLES   # sizeof(isx_scene_counts) / 8
 
+RESPONSE_FATES, RESPONSE_MAX_AXIS, RESPONSE_MAX_BINS = 21, 1024, 4096
+# the fate slots of isx_scene_response: wall classes 0 .. P + 1 first, then ...
+RESPONSE_BAFFLE0, RESPONSE_PORT, RESPONSE_EXITED_OTHER, RESPONSE_SUSPENDED = 10, 18, 19, 20
+
+
+class ResponseSpec(C.Structure):
+    """isx_response_spec (include/isx.h): bins per axis of the source's sample space -- disc ring, disc azimuth, polar band,
+    direction azimuth."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("n", C.c_int32 * 4)]
+
+    @property
+    def bins(self):
+        return int(self.n[0]) * int(self.n[1]) * int(self.n[2]) * int(self.n[3])
+
+
 _lib = None
 
 
@@ -344,6 +361,11 @@ def load():
                                       P(i32)]
     L.isx_fluxmap_scene.argtypes = [P(Config), P(SceneSpec), u64, u64, u64, P(u64), P(SceneCounts), P(Stats)]
     L.isx_fluxmap_scene_device.argtypes = [P(Config), P(SceneSpec), u64, u64, u64, C.c_void_p, C.c_void_p]
+    L.isx_default_response_spec.argtypes = [P(Config), P(ResponseSpec)]
+    L.isx_default_response_spec.restype = None
+    L.isx_scene_response.argtypes = [P(Config), P(SceneSpec), P(ResponseSpec), u64, u64, u64, P(u64), P(SceneCounts), P(Stats)]
+    L.isx_scene_response_device.argtypes = [P(Config), P(SceneSpec), P(ResponseSpec), u64, u64, u64, C.c_void_p, C.c_void_p]
+    L.isx_response_reweight.argtypes = [P(ResponseSpec), P(u64), P(dbl), P(dbl), P(dbl)]
     _lib = L
     return L
 
@@ -886,6 +908,62 @@ def fluxmap_scene_device(cfg, spec, n_rays, seed, first_ray, d_hits_ptr, d_count
     _chk(load().isx_fluxmap_scene_device(C.byref(cfg), C.byref(spec), int(n_rays), int(seed), int(first_ray),
                                          C.c_void_p(int(d_hits_ptr or 0) or None), C.c_void_p(int(d_counts_ptr or 0) or None)),
          "isx_fluxmap_scene_device")
+
+
+def default_response_spec(cfg):
+    """n = (1, 1, 6, 12): a point lamp's directions in 6 polar bands x 12 azimuths (no GPU needed)."""
+    s = ResponseSpec()
+    load().isx_default_response_spec(C.byref(cfg), C.byref(s))
+    return s
+
+
+def response_spec(n0, n1, n2, n3):
+    """-> ResponseSpec with n0 disc rings x n1 disc azimuths x n2 polar bands x n3 direction azimuths (checked by the calls)."""
+    s = ResponseSpec()
+    s.struct_size = C.sizeof(ResponseSpec)
+    s.n[0], s.n[1], s.n[2], s.n[3] = int(n0), int(n1), int(n2), int(n3)
+    return s
+
+
+def _response_bins(rspec):
+    """B of the arrays a call may touch; 1 for a spec the library refuses (it says so itself)."""
+    ok = all(1 <= int(v) <= RESPONSE_MAX_AXIS for v in rspec.n) and rspec.bins <= RESPONSE_MAX_BINS
+    return rspec.bins if ok else 1
+
+
+def scene_response(cfg, scene, rspec, n_rays, seed, first_ray=0):
+    """-> (response[21, B] uint64, SceneCounts, Stats): the fate of every ray of the scene -- absorbed by wall class 0 .. P + 1,
+    by side s of baffle k (10 + 2 k + s), through the port (18), exited otherwise (19), suspended (20) -- binned over the
+    source's sample space (include/isx.h: isx_scene_response)."""
+    B = _response_bins(rspec)
+    resp = np.zeros(RESPONSE_FATES * B, dtype=np.uint64)
+    st = Stats()
+    cnt = SceneCounts()
+    _chk(load().isx_scene_response(C.byref(cfg), C.byref(scene), C.byref(rspec), int(n_rays), int(seed), int(first_ray),
+                                   _p(resp, C.c_uint64), C.byref(cnt), C.byref(st)), "isx_scene_response")
+    return resp.reshape(RESPONSE_FATES, B), cnt, st
+
+
+def scene_response_device(cfg, scene, rspec, n_rays, seed, first_ray, d_response_ptr, d_counts_ptr):
+    """Enqueue on the library stream, accumulating into device memory at d_response_ptr ([21 * B] uint64) and d_counts_ptr
+    ([36] uint64, SceneCounts' layout)."""
+    _chk(load().isx_scene_response_device(C.byref(cfg), C.byref(scene), C.byref(rspec), int(n_rays), int(seed), int(first_ray),
+                                          C.c_void_p(int(d_response_ptr or 0) or None), C.c_void_p(int(d_counts_ptr or 0) or None)),
+         "isx_scene_response_device")
+
+
+def response_reweight(rspec, response, weight):
+    """-> (fraction[21], sigma[21]): the fate fractions of a lamp whose intensity relative to the traced source is weight[b] in
+    bin b, from one scene_response result (include/isx.h: isx_response_reweight; host only, no GPU needed)."""
+    B = _response_bins(rspec)
+    h = np.ascontiguousarray(np.asarray(response, dtype=np.uint64).reshape(-1))
+    w = np.ascontiguousarray(np.asarray(weight, dtype=np.float64).reshape(-1))
+    if h.size < RESPONSE_FATES * B or w.size < B:
+        raise ValueError("response has %d words and weight %d, the spec wants %d and %d" % (h.size, w.size, RESPONSE_FATES * B, B))
+    frac, sig = np.zeros(RESPONSE_FATES), np.zeros(RESPONSE_FATES)
+    _chk(load().isx_response_reweight(C.byref(rspec), _p(h, C.c_uint64), _p(w, C.c_double), _p(frac, C.c_double),
+                                      _p(sig, C.c_double)), "isx_response_reweight")
+    return frac, sig
 
 
 def fluxmap_series(cfgs, n_rays, seed, first_ray=0):

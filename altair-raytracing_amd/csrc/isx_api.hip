@@ -72,6 +72,7 @@ struct State {
   int bin_cols = 1;                             // 1 (2: the same): isx_bin_cols_kernel ((line, column) slots) where bin_slots applies; 0: row slots
   int bin_slots = 1;                            // 1: isx_bin_slots_kernel (slot queues by window length) where the grid allows it
   int lf_global = 0;                            // 1: isx_bin_lightfield_kernel's global form for a field that fits the LDS as well (diagnostic)
+  int resp_global = 0;                          // 1: isx_trace_assist_scene_response_kernel's global form for a response that fits the LDS as well (diagnostic)
   int surface_pipeline = 1;                     // 1 (default): the lobe / rough-specular borders and the origin-compat hit line on the assist-wave
                                                 // pipeline (round 5); 0: round 1's fused isx_trace_bin_full_kernel
   // options
@@ -604,6 +605,22 @@ int check_scene_call(const isx_config* c, const isx_scene_spec* s, bool grid) {
   return rc;
 }
 
+// isx_scene_response: the checked spec and the device array of the call ([ISX_RESPONSE_FATES][B]); the scene travels as SceneSink
+struct ResponseSink { const isx_response_spec* spec = nullptr; unsigned long long* out = nullptr; };
+static_assert(ISX_RESPONSE_FATES == kRespFates && kRespBaffle0 == ISX_MAX_WALL_PATCHES + 2 &&
+              kRespPort == kRespBaffle0 + 2 * ISX_MAX_BAFFLES && kRespSuspended == kRespPort + 2, "isx.h and resp_record's slots");
+// isx.h: the limits of a response spec
+int check_response_spec(const isx_response_spec* s) {
+  if (s->struct_size != (uint32_t)sizeof(isx_response_spec) || s->reserved0 != 0u) return ISX_ERR_BAD_CONFIG;
+  long long bins = 1;
+  for (int a = 0; a < 4; ++a) {
+    if (s->n[a] < 1 || s->n[a] > ISX_RESPONSE_MAX_AXIS) return ISX_ERR_BAD_CONFIG;
+    bins *= s->n[a];   // (at most 2^40)
+  }
+  return bins <= ISX_RESPONSE_MAX_BINS ? ISX_OK : ISX_ERR_BAD_CONFIG;
+}
+size_t response_bins(const isx_response_spec& s) { return (size_t)s.n[0] * s.n[1] * s.n[2] * s.n[3]; }
+
 // LDS of a workgroup's histogram: 4 B per bin, 16-byte aligned
 size_t hist_lds(int nbins) { return ((size_t)nbins * 4 + 15) & ~(size_t)15; }
 
@@ -716,6 +733,12 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
     d.xm_dir = wp->arrivals; d.xm_pos = wp->absorbed;
     d.nbins = 2 * (wp->spec->n_patches + 2);
     lds = patch_lds() + 64 + sizeof(Geom) + sizeof(DetGrid);
+  } else if (sink == SINK_RESPONSE) {
+    // (isx.h: hit_line_mode and the detector grid are ignored -- no exit line is written, no grid is looked at; the scene and the
+    //  response spec were checked by the entry, the patches' words are enqueue's)
+    d.hit_line_mode = ISX_HITLINE_LAST_SEGMENT;
+    d.nbins = 1;
+    lds = 16 + 64 + sizeof(Geom) + sizeof(DetGrid);
   } else {
     if (nbins_override < 1 || nbins_override > 36000) return ISX_ERR_BAD_ARG;
     d.nbins = nbins_override;
@@ -750,6 +773,7 @@ typedef void (*BeamFn)(const Geom, const DetGrid, const Work, const BeamSrc);
 typedef void (*ListFn)(const Geom, const DetGrid, const Work, const FateList);
 typedef void (*BaffleFn)(const Geom, const DetGrid, const Work, const BaffleTab);
 typedef void (*SceneFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab);
+typedef void (*ResponseFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab, const RespSink);
 struct Plan {
   Route route = ROUTE_FUSED;
   KernelFn fn = nullptr;        // the kernel (a pipeline's trace kernel)
@@ -778,6 +802,8 @@ struct Plan {
   BaffleFn baffle_fn = nullptr; // isx_fluxmap_baffle: the pipeline's trace kernel (it takes the baffles as a fourth argument: baffles) instead of fn
   BaffleTab baffles{};
   SceneFn scene_fn = nullptr;   // isx_fluxmap_scene: the pipeline's trace kernel (patch_tab, beam and baffles are its fourth to sixth arguments) instead of fn
+  ResponseFn resp_fn = nullptr; // isx_scene_response: ROUTE_ASSIST's one kernel (the scene's three arguments, and resp the seventh) instead of fn
+  RespSink resp{};              // (resp.lds_words: plan_launch's choice of the form; the rest is enqueue's)
 };
 
 // "fate_scan" = -1: where the scan pays (measured on MI355X, docs/LOG.md section 16.3).  A small launch is bound by its longest
@@ -823,7 +849,7 @@ void trace_shape(Plan& p, Shape sh, bool assist, int per_cu) {
 }
 
 Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bool discs_in_aux, uint64_t n, bool beam = false,
-                 const FateConsts* fate = nullptr, bool baffle = false, bool scene = false) {
+                 const FateConsts* fate = nullptr, bool baffle = false, bool scene = false, size_t resp_words = 0) {
   enum { LAMBERT, LOBE, ROUGH } const border =
       c->surface_model == ISX_SURFACE_LOBE ? LOBE : c->lambertian ? LAMBERT : ROUGH;   // (ISX_SURFACE_ROBAST: Lambertian or rough-specular)
   const bool pencil = c->source_model == ISX_SOURCE_PENCIL;   // (else ISX_SOURCE_BRDF)
@@ -838,6 +864,31 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
   // was set (measured 47.1 against 48.3 ms and 33.4 against 34.0 ms for 5e7 rays, profiles/r05_surface_shapes.json)
   const int ablock = (border != LAMBERT && !S.assist_block_set) ? 512 : S.assist_block;
   Plan p;
+
+  // The scene response (isx_scene_response) has one route whatever the switches say, as the scene has: the scene's trace kernel with
+  // the response as its one sink (check_scene_call: the explicit Lambertian lean path), in the scene's shape, the scene's three
+  // blocks behind the rings; no exit lines, no second kernel.  Launches are cut at pipeline_chunk as the scene's are.  The
+  // kernel has two forms (isx_kernels.hpp: resp_record): `resp_words` u32 words -- the scene's compact slots times the bins --
+  // behind the parks, flushed once per workgroup, where that block costs no resident workgroup (as many workgroups as the
+  // occupancy query of the grid finds without it still fit the LDS with it); else, or with resp_global = 1, one global u64 add
+  // per ended ray.  The form is RespSink::lds_words, nothing else.
+  if (sink == SINK_RESPONSE) {
+    p.route = ROUTE_ASSIST;
+    p.resp_fn = isx_trace_assist_scene_response_kernel;
+    p.launch_max = std::min(kLaunchMax, S.pipe_chunk);
+    trace_shape(p, small_shape(std::min(n, p.launch_max), S.assist_block_set ? S.assist_block : kSceneBlock), true,
+                resident_unless(S.trace_blocks_per_cu));
+    p.lds += SceneLds::bytes(p.tracers);
+    // (two 640-thread workgroups: 68.8 KiB each without the block, 80 KiB to be had -- 2864 words; the sum is taken over
+    //  2 KiB steps so that the device's allocation granule cannot turn "fits" into one workgroup fewer)
+    const size_t with = p.lds + hist_lds((int)resp_words);
+    const size_t resident = (size_t)blocks_per_cu(p.resp_fn, p.block, p.lds, kResident);
+    if (!S.resp_global && ((with + 2047) & ~(size_t)2047) * resident <= S.lds_limit) {
+      p.resp.lds_words = (uint32_t)resp_words;
+      p.lds = with;
+    }
+    return p;
+  }
 
   // The flux pipeline's trace kernels without an assist wave serve the lean cases (pencil source, either trace mode; BRDF source,
   // explicit trace).  Those with one serve, unless surface_pipeline = 0, the origin-compat hit line as well (the assist wave writes
@@ -1076,16 +1127,18 @@ int span(int kind, size_t* from) {
 
 // ROUTE_FUSED and ROUTE_ASSIST: launches of at most kLaunchMax rays, one span
 int run_single(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
-  const void* fn = p.patch_fn ? (const void*)p.patch_fn : (const void*)p.fn;
+  const void* fn = p.resp_fn ? (const void*)p.resp_fn : p.patch_fn ? (const void*)p.patch_fn : (const void*)p.fn;
   int rc = set_lds(fn, p.lds); if (rc) return rc;
-  const int per_cu = p.patch_fn ? blocks_per_cu(p.patch_fn, p.block, p.lds, p.per_cu) : blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
+  const int per_cu = p.resp_fn ? blocks_per_cu(p.resp_fn, p.block, p.lds, p.per_cu) :
+                     p.patch_fn ? blocks_per_cu(p.patch_fn, p.block, p.lds, p.per_cu) : blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
   const uint64_t launch_max = p.launch_max ? p.launch_max : kLaunchMax;
   size_t t;
   rc = mark(S.stream, &t); if (rc) return rc;
   for (uint64_t off = 0; off < wk.n; off += launch_max) {
     Work w;
     rc = launch_work(wk, off, std::min(wk.n - off, launch_max), 0, S.stream, &w); if (rc) return rc;
-    if (p.patch_fn) hipLaunchKernelGGL(p.patch_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab);
+    if (p.resp_fn) hipLaunchKernelGGL(p.resp_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.resp);
+    else if (p.patch_fn) hipLaunchKernelGGL(p.patch_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab);
     else hipLaunchKernelGGL(p.fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w);
     HIPCHK(hipGetLastError());
   }
@@ -1236,7 +1289,7 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
             const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr, const ExitSink* xm = nullptr,
             const WallSink* wm = nullptr, const FieldSink* lf = nullptr, const OrderSink* oh = nullptr,
             const PatchSink* wp = nullptr, const isx_beam_spec* bs = nullptr, const BaffleSink* bf = nullptr,
-            const SceneSink* sc = nullptr) {
+            const SceneSink* sc = nullptr, const ResponseSink* rs = nullptr) {
   Geom g;
   FateConsts fate;
   isx_config cb;
@@ -1265,7 +1318,15 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
   Work wk;
   wk.seed = seed; wk.first = first; wk.n = n; wk.hist = d_hist; wk.stats = d_stats ? d_stats : S.d_stats;
   wk.ctr = nullptr; wk.sub = 0; wk.pad = 0;
-  Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n, bs != nullptr, &fate, bf != nullptr, sc != nullptr);
+  // (a response keeps the scene's compact slots per bin: P + 2 wall classes, two sides per baffle, port / other exits / suspended)
+  const size_t resp_bins = rs ? response_bins(*rs->spec) : 0;
+  const size_t resp_words = rs ? (size_t)((sc->spec->patches.n_patches + 2) + 2 * sc->spec->baffles.n_baffles + 3) * resp_bins : 0;
+  Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n, bs != nullptr, &fate, bf != nullptr, sc != nullptr, resp_words);
+  if (rs) {
+    p.resp.out = rs->out;
+    for (int a = 0; a < 4; ++a) p.resp.n[a] = (uint32_t)rs->spec->n[a];
+    p.resp.B = (uint32_t)resp_bins;
+  }
   if (bf) {
     if (p.lds_bin > S.lds_limit) return ISX_ERR_BAD_CONFIG;   // (isx.h: a grid whose tables do not fit the binning kernels' LDS)
     p.baffles = baffle_table(*c, *bf->spec, bf->counts);
@@ -1595,6 +1656,7 @@ int isx_set_option(const char* key, int64_t value) {
   if (!std::strcmp(key, "bin_cols")) { if (value < 0 || value > 2) return ISX_ERR_BAD_ARG; S.bin_cols = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "bin_slots")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.bin_slots = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "lf_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.lf_global = (int)value; return ISX_OK; }
+  if (!std::strcmp(key, "resp_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.resp_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "surface_pipeline")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.surface_pipeline = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "ray_sub")) { if (value < 0 || value > (1 << 20)) return ISX_ERR_BAD_ARG; S.ray_sub = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "fate_scan")) { if (value < -1 || value > 1) return ISX_ERR_BAD_ARG; S.fate_scan = (int)value; return ISX_OK; }
@@ -2557,6 +2619,88 @@ int isx_fluxmap_scene(const isx_config* cfg, const isx_scene_spec* spec, uint64_
     if (counts) std::memcpy(counts, reinterpret_cast<const unsigned long long*>(S.h_pin + 64) + nb, nc * sizeof(unsigned long long));
   }
   return rc;
+}
+
+void isx_default_response_spec(const isx_config* cfg, isx_response_spec* spec) {
+  (void)cfg;   // (the default does not depend on the configuration: the axes are the source's sample space)
+  if (!spec) return;
+  std::memset(spec, 0, sizeof(*spec));
+  spec->struct_size = (uint32_t)sizeof(isx_response_spec);
+  spec->n[0] = 1; spec->n[1] = 1; spec->n[2] = 6; spec->n[3] = 12;
+}
+
+int isx_scene_response_device(const isx_config* cfg, const isx_scene_spec* scene, const isx_response_spec* rspec, uint64_t n_rays,
+                              uint64_t seed, uint64_t first_ray, uint64_t* d_response, uint64_t* d_counts) {
+  // (what needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one)
+  if (!cfg || !scene || !rspec || !d_response || !d_counts) return ISX_ERR_BAD_ARG;
+  int bad = check_scene_call(cfg, scene, false);   // (isx.h: the detector grid is ignored -- isx_scene_endstates' refusals)
+  if (bad == ISX_OK) bad = check_response_spec(rspec);
+  if (bad) return bad;
+  if (!S.init) return not_initialised();
+  const SceneSink sc{scene, (unsigned long long*)d_counts};
+  const ResponseSink rs{rspec, (unsigned long long*)d_response};
+  return enqueue(SINK_RESPONSE, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                 nullptr, nullptr, nullptr, nullptr, nullptr, &sc, &rs);
+}
+
+int isx_scene_response(const isx_config* cfg, const isx_scene_spec* scene, const isx_response_spec* rspec, uint64_t n_rays,
+                       uint64_t seed, uint64_t first_ray, uint64_t* response, isx_scene_counts* counts, isx_stats* stats) {
+  if (!cfg || !scene || !rspec || !response) return ISX_ERR_BAD_ARG;
+  int rc = check_scene_call(cfg, scene, false);
+  if (rc == ISX_OK) rc = check_response_spec(rspec);
+  if (rc) return rc;
+  if (!S.init) return not_initialised();
+  // the response and, behind it, the 36 counters: one device block, one staged result
+  const size_t nb = (size_t)ISX_RESPONSE_FATES * response_bins(*rspec), nc = kSceneWords, bytes = (nb + nc) * sizeof(unsigned long long);
+  rc = call_open(nb + nc);
+  if (rc) return rc;
+  rc = zero_hist(nb + nc);
+  const SceneSink sc{scene, S.d_hist + nb};
+  const ResponseSink rs{rspec, S.d_hist};
+  if (rc == ISX_OK) rc = enqueue(SINK_RESPONSE, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sc, &rs);
+  if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK) {
+    fetch_result(response, nb * sizeof(unsigned long long));
+    if (counts) std::memcpy(counts, reinterpret_cast<const unsigned long long*>(S.h_pin + 64) + nb, nc * sizeof(unsigned long long));
+  }
+  return rc;
+}
+
+int isx_response_reweight(const isx_response_spec* rspec, const uint64_t* response, const double* weight, double* fraction,
+                          double* sigma) {
+  if (!rspec || !response || !weight || !fraction) return ISX_ERR_BAD_ARG;
+  const int rc = check_response_spec(rspec);
+  if (rc) return rc;
+  const size_t B = response_bins(*rspec);
+  for (size_t b = 0; b < B; ++b)
+    if (!(std::isfinite(weight[b]) && weight[b] >= 0)) return ISX_ERR_BAD_ARG;
+  std::vector<double> nb(B);
+  double L = 0;
+  for (size_t b = 0; b < B; ++b) {
+    uint64_t col = 0;
+    for (int f = 0; f < ISX_RESPONSE_FATES; ++f) col += response[(size_t)f * B + b];
+    nb[b] = (double)col;
+    L += weight[b] * nb[b];
+  }
+  if (!(L > 0)) return ISX_ERR_BAD_CONFIG;
+  for (int f = 0; f < ISX_RESPONSE_FATES; ++f) {
+    const uint64_t* row = response + (size_t)f * B;
+    double s = 0;
+    for (size_t b = 0; b < B; ++b) s += weight[b] * (double)row[b];
+    const double F = s / L;
+    fraction[f] = F;
+    if (sigma) {
+      double v = 0;
+      for (size_t b = 0; b < B; ++b) {
+        const double h = (double)row[b];
+        v += weight[b] * weight[b] * (h * (1.0 - F) * (1.0 - F) + (nb[b] - h) * F * F);
+      }
+      sigma[f] = std::sqrt(v) / L;
+    }
+  }
+  return ISX_OK;
 }
 
 #ifdef ISX_DIAG

@@ -121,7 +121,8 @@ __device__ unsigned long long g_diag[48];   // [32..47]: the assist wave of assi
 #endif
 
 enum : int { SINK_FLUX = 0, SINK_DZ = 1, SINK_DISC = 2, SINK_PERPOS = 3, SINK_LOG = 4, SINK_DISCPOS = 5, SINK_REC = 6, SINK_EXITMAP = 7, SINK_WALL = 8,
-              SINK_LIGHTFIELD = 9, SINK_ORDER = 10, SINK_PATCH = 11 };
+              SINK_LIGHTFIELD = 9, SINK_ORDER = 10, SINK_PATCH = 11,
+              SINK_RESPONSE = 12 };   // (isx_scene_response: no kernel is built on it -- the host's name for the scene's second sink)
 
 struct Work {
   uint64_t seed, first, n;    // one launch traces rays [first, first + n), n < 2^31 (a lane keeps a 31-bit offset from `first`)
@@ -2320,6 +2321,45 @@ struct SceneLds {
   static constexpr size_t beam = kPatchLds, baffle = beam + kBeamSrcBytes, park = baffle + kBaffleLds;
   static constexpr size_t bytes(int tracers) { return park + (size_t)tracers * kBeamParkBytes; }
 };
+// ------------------------------------------------------------------ scene response (isx.h: isx_scene_response)
+// The response sink of a call as the kernel gets it (a kernel argument of its own, read where it is used): the device array
+// [kRespFates][B] (+=), the four axes, B, and the size of the workgroup's u32 block behind the parks -- the compact slots
+// (P + 2 wall classes | 2 per baffle | port, other exits, suspended) times B; 0: the global form, one u64 add per ended ray.
+constexpr int kRespFates = 21, kRespBaffle0 = 10, kRespPort = 18, kRespSuspended = 20;
+struct RespSink {
+  unsigned long long* out;
+  uint32_t n[4];
+  uint32_t B, lds_words;
+};
+// A ray's end: its bin by isx.h's rule on the words of block 0 of Philox stream 3 of the ray -- i_a = (w[a] * n[a]) >> 32, in
+// integers -- and one add to slot `fate` of that bin.  Every census point of the RESP build calls this and nothing else states
+// the rule.  `out` stays a kernel argument's field: a global_atomic, not a flat one.
+__device__ __forceinline__ void resp_record(const RespSink& s, uint32_t* blk, int n_patch, int n_baf, int fate, uint64_t seed,
+                                            uint64_t ray) {
+  uint32_t w[4];
+  draw_block(seed, ray, 0u, 3u, w);
+  const uint32_t i0 = __umulhi(w[0], s.n[0]), i1 = __umulhi(w[1], s.n[1]), i2 = __umulhi(w[2], s.n[2]), i3 = __umulhi(w[3], s.n[3]);
+  const uint32_t b = ((i0 * s.n[1] + i1) * s.n[2] + i2) * s.n[3] + i3;
+  if (s.lds_words != 0u) {
+    const int c = fate < kRespBaffle0 ? fate : fate < kRespPort ? fate - kRespBaffle0 + (n_patch + 2) : fate - kRespPort + (n_patch + 2) + 2 * n_baf;
+    atomicAdd(&blk[(uint32_t)c * s.B + b], 1u);
+  } else {
+    global_add_u64(s.out + ((uint32_t)fate * s.B + b), 1ull);
+  }
+}
+// one flush of the workgroup's block: compact slot -> fate slot
+__device__ __forceinline__ void resp_flush(const RespSink& s, const uint32_t* blk, int n_patch, int n_baf, uint32_t tid, uint32_t nthr) {
+  const uint32_t nw = (uint32_t)(n_patch + 2), nb = nw + 2u * (uint32_t)n_baf;
+  for (uint32_t i = tid; i < s.lds_words; i += nthr) {
+    const uint32_t c = blk[i];
+    if (c) {
+      const uint32_t cs = i / s.B, b = i - cs * s.B;
+      const uint32_t fate = cs < nw ? cs : cs < nb ? cs - nw + (uint32_t)kRespBaffle0 : cs - nb + (uint32_t)kRespPort;
+      global_add_u64(s.out + (fate * s.B + b), (unsigned long long)c);
+    }
+  }
+}
+
 // The segment test of isx.h's contract, operation for operation (IEEE double, left to right, no fma: -ffp-contract=off; / is the
 // correctly rounded one): the baffle that the segment p -> q strikes first -- the smallest f, on equal f the lowest index -- as
 // 2 k + side (side 0: the side the normal points to), or -1.  `skip` is the baffle of the ray's previous interaction (-1: none).
@@ -3020,12 +3060,18 @@ __device__ __forceinline__ void ray_unpack(const uint4& a, const uint4& b, const
 // boundary's ray_arrive with the class's constants.  The three blocks lie one behind the other behind the rings (SceneLds).  Exit
 // lines are written as in the BEAM and BAFFLE builds; patch_flush adds nothing to bin_increments (the binning kernel's count).
 // The assist wave never waits for the resume ring, as in every BAFFLE build (docs/LOG.md sections 18.4, 19.2).
+// RESP (isx_scene_response; SCENE only): every ray is binned once, where it ends, by the wave that takes its census, as ORDER's
+// are -- resp_record with the fate slot the wave has in hand: the tracers with the class of the arrival that absorbed the ray
+// (kept from the bounce step to the per-trip block of the ended lanes) or "suspended", the assist wave with the baffle's side, the
+// wall class, or the exit with the census's own counted-below-z test.  The bin is recomputed from the ray's index there; nothing
+// is carried through the steps or the queue records.  The workgroup's u32 block, if the launch has one, lies behind the parks.
+// No exit lines, no second kernel; the step loop, the rings and the parks are the SCENE build's, unchanged.
 struct FateList { const uint32_t* list; const uint32_t* count; };
 template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false, bool ORDER = false, bool PATCH = false,
-          bool BEAM = false, bool LIST = false, bool BAFFLE = false>
+          bool BEAM = false, bool LIST = false, bool BAFFLE = false, bool RESP = false>
 __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk, const PatchTab* tab_arg = nullptr,
                                             const BeamSrc* beam_arg = nullptr, const FateList* list_arg = nullptr,
-                                            const BaffleTab* baf_arg = nullptr) {
+                                            const BaffleTab* baf_arg = nullptr, const RespSink* resp_arg = nullptr) {
   constexpr bool LEAN = SURF == SURF_LAMBERT;
   static_assert(LEAN || (CH == 0 && !RESC), "the chord identity and the BRDF re-scatter pipeline are built for the Lambertian border");
   static_assert(!PATCH || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER), "wall patches: the explicit Lambertian lean path, no other sink");
@@ -3033,6 +3079,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   static_assert(!BEAM || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && (!PATCH || SCENE)), "beam source: the explicit Lambertian lean path, no other sink");
   static_assert(!LIST || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && !PATCH && !BEAM), "ray list: the explicit Lambertian lean path of the flux pipeline");
   static_assert(!BAFFLE || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && (!PATCH || SCENE) && (!BEAM || SCENE) && !LIST), "baffles: the explicit Lambertian lean path of the flux pipeline");
+  static_assert(!RESP || SCENE, "scene response: the scene's trace, nothing else");
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned long long* sstat = reinterpret_cast<unsigned long long*>(smem);
   Geom* g_lds = reinterpret_cast<Geom*>(sstat + 8);
@@ -3082,6 +3129,11 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     if (tid < 4 * kMaxBaffles) bcnt[tid] = 0u;
   }
   const volatile LdsBaffle& baf = *(const volatile LdsBaffle*)(reinterpret_cast<unsigned char*>(hist) + off_baf);
+  // RESP: the workgroup's u32 block behind the parks (RespSink::lds_words of it; none in the global form)
+  uint32_t* rblk = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(hist) + SceneLds::bytes(n_tracers));
+  if constexpr (RESP) {
+    for (uint32_t b = (uint32_t)tid; b < resp_arg->lds_words; b += (uint32_t)nthr) rblk[b] = 0u;
+  }
   if (tid < 8) sstat[tid] = 0ull;
   if (tid == 64) {
     *g_lds = g_arg;
@@ -3269,6 +3321,8 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       // (the end of a ray as two flags -- lane masks in scalar registers -- instead of a status word per lane; a tracer lane's ray
       //  sits on the inner sphere unless it is fresh, so Ray::on is neither read nor written in the steps)
       bool ended = false, susp = false;
+      int eslot = 0;   // RESP: the class of the arrival that absorbed the lane's ray
+      (void)eslot;
       auto arrive = [&](const V3& q, auto ph, bool record = true) {
         if (WALL && record) wall_record(wspec, hist, wall_nmap, K_INNER, r.j, q, 1u);
         int st;
@@ -3277,6 +3331,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           const int cls = patch_arrive<true>(ptab, n_patch, pcnt, K_INNER, q, hp);
           st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(hp, g, r, seed, first, K_INNER, q);
           if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
+          if constexpr (RESP) { if (st == ST_ABSORBED) eslot = cls; }
         } else st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(h, g, r, seed, first, K_INNER, q);
         if (st != 0) { run = false; ended = true; susp = st == ST_SUSPENDED; }
       };
@@ -3393,6 +3448,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           n_wall += r.j;
           if (n_wall > 0x7fffffffu) { atomicAdd(&sstat[6], (unsigned long long)n_wall); n_wall = 0; }
           if (ORDER) order_record(ospec, hist, false, false, susp, r.j, 0.0);
+          if constexpr (RESP) resp_record(*resp_arg, rblk, n_patch, n_baf, susp ? kRespSuspended : eslot, seed, first + (uint64_t)r.offset());
         }
         const unsigned long long me = __ballot(ended);
         if (me) {
@@ -3547,6 +3603,8 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       bool go = have;
       bool given = false;   // BAFFLE: the ray went back to the tracers from inside the step loop
       (void)given;
+      int eslot = 0;        // RESP: the slot of the interaction that absorbed the lane's ray (a wall class, or a baffle's side)
+      (void)eslot;
       for (;;) {
         if (go) {
           V3 q;
@@ -3569,12 +3627,14 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
               atomicAdd(&bcnt[ks], 1u);
               st = baffle_arrive(baf, h, r, seed, first, ks >> 1, ks & 1);
               if (st == ST_ABSORBED) atomicAdd(&bcnt[2 * kMaxBaffles + ks], 1u);
+              if constexpr (RESP) eslot = kRespBaffle0 + ks;
             } else {
               Hot hp = h;
               int cls = 0;
               if (kind != K_BOX) cls = patch_arrive<false>(ptab, n_patch, pcnt, kind, q, hp);
               st = ray_arrive<false, LEAN, CH, PH_DIRECT, true, SURF>(hp, g, r, seed, first, kind, q);
               if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
+              if constexpr (RESP) eslot = cls;
             }
           } else if constexpr (PATCH) {
             Hot hp = h;
@@ -3673,6 +3733,11 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       if (ended) n_wall += r.j;
       if (n_wall > 0x7fffffffu) { atomicAdd(&sstat[6], (unsigned long long)n_wall); n_wall = 0; }
       if (ORDER && ended) order_record(ospec, hist, exited, below, st == ST_SUSPENDED, r.j, r.v.z);
+      if constexpr (RESP) {
+        if (ended) resp_record(*resp_arg, rblk, n_patch, n_baf,
+                               exited ? (below ? kRespPort : kRespPort + 1) : st == ST_SUSPENDED ? kRespSuspended : eslot, seed,
+                               first + (uint64_t)r.offset());
+      }
       const uint32_t c_ended = (uint32_t)__popcll(__ballot(ended));
       n_ended += c_ended;
       n_exited += (uint32_t)__popcll(__ballot(exited));
@@ -3712,7 +3777,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         n_inc += (unsigned long long)__popcll(__ballot(hit0)) + (unsigned long long)__popcll(__ballot(hit1));
       }
       const unsigned long long m = (PP != 0 || WALL || ORDER || (PATCH && !SCENE)) ? 0ull : __ballot(keep);
-      if (m) {
+      if (!RESP && m) {   // (RESP: no exit lines -- the response is the build's one sink, no kernel follows)
         const uint32_t cnt = (uint32_t)__popcll(m);
         if (cnt > reg_left) {   // close the open region, reserve the next one (kRegion)
           if (lane == 0 && reg_id != 0xffffffffu) d_arg.rec_counts[reg_id] = kRegion - reg_left;
@@ -3801,6 +3866,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     atomicAdd(&sstat[3], (unsigned long long)(n_ended - n_exited - n_susp));  // absorbed
     atomicAdd(&sstat[4], (unsigned long long)n_susp);
     atomicAdd(&sstat[0], (unsigned long long)n_taken);
+    if constexpr (RESP) atomicAdd(&sstat[5], (unsigned long long)n_ended);   // bin_increments: one per ended ray
   }
   __syncthreads();
   // (BEAM: the thread index rebuilt from the wave's number -- a scalar -- and the lane's rank in the wave: kept from the kernel's
@@ -3826,6 +3892,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     if (flushed) atomicAdd(&sstat[5], flushed);
     __syncthreads();
   }
+  if constexpr (RESP) resp_flush(*resp_arg, rblk, n_patch, n_baf, tid_end, (uint32_t)blockDim.x);   // (the global form: nothing to flush)
   if constexpr (BAFFLE) {   // one flush of the workgroup's counters (the thread index rebuilt, as the beam kernel's)
     uint32_t t3 = tid_end;
     asm volatile("" : "+v"(t3));
@@ -3903,6 +3970,13 @@ isx_trace_assist_baffle_kernel(const Geom g, const DetGrid d, const Work wk, con
 extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_SCENE_WAVES, ISX_SCENE_WAVES)))
 isx_trace_assist_scene_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab, const BeamSrc beam, const BaffleTab baf) {
   assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true>(g, d, wk, &tab, &beam, nullptr, &baf);
+}
+// the scene response (isx_scene_response): the scene kernel with one add per ended ray -- its fate, binned over the source's sample
+// space (resp_record) -- and no exit lines; the sink is a seventh argument
+extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_SCENE_WAVES, ISX_SCENE_WAVES)))
+isx_trace_assist_scene_response_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab, const BeamSrc beam, const BaffleTab baf,
+                                       const RespSink resp) {
+  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true, true>(g, d, wk, &tab, &beam, nullptr, &baf, &resp);
 }
 // the flux pipeline behind the fate scan: isx_trace_assist_kernel on the rays of a list; the list is a fourth argument
 extern "C" __global__ void ISX_ASSIST_ATTR

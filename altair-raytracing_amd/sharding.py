@@ -292,3 +292,13 @@ def fluxmap_scene_sharded(trace: Callable, cfg, spec, n_total: int, seed: int, f
             at += a.size
         census = buf[at:]
     return (hits, *parts, dict(zip(CENSUS_FIELDS, (int(x) for x in census))))
+
+
+def scene_response_sharded(trace: Callable, cfg, scene, rspec, n_total: int, seed: int, first_ray: int = 0, device=None):
+    """The response of a scene (altair_raytracing_amd.scene_response) ray-sharded: this rank's contiguous shard through
+    `trace(cfg, scene, rspec, count, seed, first) -> (response, counts, stats)`, then ONE SUM all-reduce that carries the response,
+    the 36 scene counters and the census -- fluxmap_scene_sharded with the response in the histogram's place.  Returns
+    (response[21, B] uint64, patch_arrivals[10] uint64, patch_absorbed[10] uint64, baffle arrivals[4, 2] uint64, baffle
+    absorbed[4, 2] uint64, census dict) -- identical on every rank."""
+    return fluxmap_scene_sharded(lambda c, sp, count, sd, first: trace(c, sp, rspec, count, sd, first), cfg, scene, n_total, seed,
+                                 first_ray, device)

@@ -192,6 +192,8 @@ int isx_last_kernel_ms(double* single_ms, double* trace_ms, double* bin_ms);
  *                  isx_trace_bin_full_kernel
  *   "lf_global"    0 (default): isx_light_field bins a field of at most 32 768 words in the workgroup's LDS and a larger one with
  *                  one global atomic add per ray; 1: the global form for every field (a diagnostic)
+ *   "resp_global"  0 (default): isx_scene_response keeps a response that fits in the workgroup's LDS there and takes one global
+ *                  atomic add per ended ray for a larger one; 1: the global form for every spec (a diagnostic)
  *   "bin_block", "bin_blocks_per_cu"  shape of round 2's binning kernel (0 workgroups per CU = what is resident)
  *                  (round 5: "assist_block" 0 = the default again -- 768 threads, 256 for launches below 1e6 rays, 512 for the lobe /
  *                  rough-specular kernels; "rays_per_lane" > 0 sizes every grid for that many rays per tracer lane, 0 = by launch
@@ -884,6 +886,87 @@ int isx_fluxmap_scene(const isx_config* cfg, const isx_scene_spec* spec, uint64_
                       uint64_t* hits, isx_scene_counts* counts, isx_stats* stats);
 int isx_fluxmap_scene_device(const isx_config* cfg, const isx_scene_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
                              uint64_t* d_hits, uint64_t* d_counts /*[36]*/);
+
+/*
+ * Scene response: the fates of a scene's rays binned over the source's sample space -- how a detector's signal (or any other
+ * fate) depends on where the lamp sends its light: the sphere's spatial response.  One trace of a wide source (the isotropic lamp:
+ * radius 0, cos_min -1) answers for every lamp whose intensity relative to it is a function of the source sample:
+ * isx_response_reweight, a host-side reweighting, as isx_order_reweight answers for every wall reflectance.
+ *
+ * The ray histories are those of isx_fluxmap_scene / isx_scene_endstates for the same (cfg, scene, seed, ray index): nothing of a
+ * history changes.  Every traced ray adds exactly 1 to response[f * B + b], B = n[0] * n[1] * n[2] * n[3]:
+ *
+ *   b, the bin, from the words w[0..3] of the beam contract (block 0 of Philox4x32-10 stream 3 of the ray: counter (ray lo, ray hi,
+ *   0, 3), key (seed lo, seed hi)), in INTEGER arithmetic -- the rule is stated on the words, not on u01(w): for an n that is no
+ *   power of two floor(u01(w) * n) differs from it at some words:
+ *
+ *       i_a = (uint32_t)(((uint64_t)w[a] * (uint64_t)n[a]) >> 32)            a = 0 .. 3
+ *       b   = ((i_0 * n[1] + i_1) * n[2] + i_2) * n[3] + i_3
+ *
+ *   axis 0: equal-area rings of the emitting disc (u_0 = (rr / radius)^2);  axis 1: the disc's azimuth;  axis 2: equal-probability
+ *   polar bands of the cone, counted from the axis outward (ISX_BEAM_UNIFORM: bands of equal solid angle, ct = 1 - u_2 (1 - cos_min));
+ *   axis 3: the direction's azimuth about the axis in the (e1, e2) frame.  Every bin has the same expected number of launches.
+ *
+ *   f, the fate slot, from status, last point, last class and last baffle as isx_scene_endstates defines them:
+ *
+ *       ISX_RAY_SUSPENDED                                                                  20
+ *       ISX_RAY_EXITED with last_point.z < cfg->exit_port_z (the census's counted_below_z) 18
+ *       ISX_RAY_EXITED otherwise                                                           19
+ *       ISX_RAY_ABSORBED by side s of baffle k                                             10 + 2 k + s
+ *       ISX_RAY_ABSORBED on a wall: the class of that interaction                          0 .. P + 1, as in isx_scene_counts
+ *
+ *   Slots the scene cannot fill stay 0.
+ *
+ * For every call: the slots of a column (bin) sum to the rays launched into that bin; the rows (slots) sum to -- rows 0..9
+ * counts.patch_absorbed, rows 10..17 counts.baffle.absorbed, row 18 counted_below_z, rows 18 + 19 exited, row 20 suspended; the whole
+ * sums to stats.launched == stats.bin_increments.  `counts` and every other field of stats except t_kernel_ms are
+ * isx_fluxmap_scene's for the same arguments.  No result depends on any isx_set_option switch nor on how a job is cut into calls.
+ * cfg->hit_line_mode and the detector-grid fields of cfg are ignored and never a reason for refusal (the grid's LDS check of
+ * isx_fluxmap_scene does not apply).  One route whatever the switches say: isx_trace_assist_scene_response_kernel -- the scene's
+ * trace kernel with one add per ended ray, where the census is taken; it writes no exit lines and no kernel follows it.  A response
+ * small enough is kept as u32 words in the workgroup's LDS and flushed once, a larger one (or any, with "resp_global" 1) takes one
+ * global u64 add per ended ray.
+ *
+ * Refused, whether or not a device is present: everything isx_scene_endstates refuses of cfg and scene, with its codes;
+ * ISX_ERR_BAD_CONFIG: struct_size != sizeof(isx_response_spec), reserved0 != 0, an axis outside 1..ISX_RESPONSE_MAX_AXIS,
+ * B > ISX_RESPONSE_MAX_BINS; ISX_ERR_BAD_ARG: a NULL cfg, scene, rspec or response (device form: d_response, d_counts).  Without a
+ * HIP device: ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT (as isx_fluxmap_scene).
+ * Out of scope: the isx_macro command line, a binning over the first-strike point on the wall, a response of the other sinks.
+ */
+#define ISX_RESPONSE_FATES 21
+#define ISX_RESPONSE_MAX_AXIS 1024
+#define ISX_RESPONSE_MAX_BINS 4096
+typedef struct isx_response_spec {
+  uint32_t struct_size;      /* sizeof(isx_response_spec), set by isx_default_response_spec(); a spec of another size is refused */
+  uint32_t reserved0;        /* 0 */
+  int32_t n[4];              /* bins per axis: disc ring, disc azimuth, polar band, direction azimuth; each 1..ISX_RESPONSE_MAX_AXIS */
+} isx_response_spec;         /* 24 bytes */
+
+/* n = {1, 1, 6, 12}: a point lamp's directions in 6 polar bands x 12 azimuths.  Host only, no GPU needed. */
+void isx_default_response_spec(const isx_config* cfg, isx_response_spec* spec);
+/* Blocking: response[ISX_RESPONSE_FATES * B] and counts (host, zeroed by the callee; counts and stats may be NULL). */
+int isx_scene_response(const isx_config* cfg, const isx_scene_spec* scene, const isx_response_spec* rspec, uint64_t n_rays,
+                       uint64_t seed, uint64_t first_ray, uint64_t* response, isx_scene_counts* counts, isx_stats* stats);
+/* ACCUMULATES (+=) into d_response [ISX_RESPONSE_FATES * B] and d_counts (36 words, isx_scene_counts' layout; neither may be
+ * NULL) on the library's stream and returns after enqueueing; isx_sync() / isx_take_stats() as for isx_fluxmap_scene_device. */
+int isx_scene_response_device(const isx_config* cfg, const isx_scene_spec* scene, const isx_response_spec* rspec, uint64_t n_rays,
+                              uint64_t seed, uint64_t first_ray, uint64_t* d_response, uint64_t* d_counts /*[36]*/);
+/*
+ * The fate fractions of another lamp from one isx_scene_response result.  Host only, no GPU needed.  weight[b] is the lamp's
+ * intensity in bin b relative to the traced source; with n_b = the column sum of bin b (the rays launched into it), the sums taken
+ * in increasing b:
+ *
+ *       L = sum over b of weight[b] * n_b ;  S_f = sum over b of weight[b] * response[f][b]
+ *       fraction[f] = S_f / L
+ *       sigma[f]    = sqrt(sum over b of weight[b]^2 * (response[f][b] * (1 - F)^2 + (n_b - response[f][b]) * F^2)) / L ,  F = fraction[f]
+ *
+ * -- the self-normalised estimator.  With every weight 1, fraction[f] is the row's sum / launched exactly as the division gives
+ * it, and sigma[f] the binomial sqrt(F (1 - F) / launched) up to the rounding of the sum.  fraction and sigma have
+ * ISX_RESPONSE_FATES entries; sigma may be NULL.  ISX_ERR_BAD_ARG: a NULL rspec, response, weight or fraction, a weight that is
+ * negative or not finite; ISX_ERR_BAD_CONFIG: a spec isx_scene_response refuses, L == 0.
+ */
+int isx_response_reweight(const isx_response_spec* rspec, const uint64_t* response, const double* weight /*[B]*/,
+                          double* fraction /*[21]*/, double* sigma /*[21]*/);
 
 /*
  * Series driver (sweepSeries, fluxAtObserverOptimize.C:892-921 / fluxAtObserverFast.C:1641-1673):
