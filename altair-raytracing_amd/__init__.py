@@ -18,7 +18,7 @@ from ._abi import (  # noqa: F401
     ExitMapSpec, ExitMapCounts, default_exit_map_spec, exit_maps, exit_maps_device,
     WallMapSpec, WallMapCounts, default_wall_map_spec, wall_map, wall_map_device,
     LightFieldCounts, default_light_field_spec, light_field, light_field_device,
-    bin_injected_lines, INJECT_FLUX, INJECT_EXIT_MAPS, INJECT_LIGHT_FIELD, INJECT_UNIT_AUTO,
+    bin_injected_lines, bin_injected_segments, INJECT_FLUX, INJECT_EXIT_MAPS, INJECT_LIGHT_FIELD, INJECT_UNIT_AUTO,
     OrderHistSpec, OrderHistCounts, default_order_hist_spec, order_hist, order_hist_device, order_reweight,
     WallPatch, WallPatchSpec, default_wall_patch_spec, wall_patch_cap, wall_patch_spec, wall_patches, wall_patches_device,
     BeamSpec, default_beam_spec, beam_cone, beam_endstates, fluxmap_beam, fluxmap_beam_device, BEAM_UNIFORM, BEAM_LAMBERT,
@@ -35,7 +35,7 @@ __all__ = ["abi", "sharding", "shard", "step_slice", "fluxmap_sharded", "disc_sw
            "ExitMapSpec", "ExitMapCounts", "default_exit_map_spec", "exit_maps", "exit_maps_device",
            "WallMapSpec", "WallMapCounts", "default_wall_map_spec", "wall_map", "wall_map_device",
            "LightFieldCounts", "default_light_field_spec", "light_field", "light_field_device",
-           "bin_injected_lines", "INJECT_FLUX", "INJECT_EXIT_MAPS", "INJECT_LIGHT_FIELD", "INJECT_UNIT_AUTO",
+           "bin_injected_lines", "bin_injected_segments", "INJECT_FLUX", "INJECT_EXIT_MAPS", "INJECT_LIGHT_FIELD", "INJECT_UNIT_AUTO",
            "OrderHistSpec", "OrderHistCounts", "default_order_hist_spec", "order_hist", "order_hist_device", "order_reweight",
            "WallPatch", "WallPatchSpec", "default_wall_patch_spec", "wall_patch_cap", "wall_patch_spec", "wall_patches", "wall_patches_device",
            "wall_patches_sharded",

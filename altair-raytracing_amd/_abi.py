@@ -45,6 +45,7 @@ EXPORTS = [
     "isx_default_exit_map_spec", "isx_exit_maps", "isx_exit_maps_device",
     "isx_default_wall_map_spec", "isx_wall_map", "isx_wall_map_device",
     "isx_default_light_field_spec", "isx_light_field", "isx_light_field_device", "isx_bin_injected_lines",
+    "isx_bin_injected_segments",
     "isx_default_order_hist_spec", "isx_order_hist", "isx_order_hist_device", "isx_order_reweight",
     "isx_default_wall_patch_spec", "isx_wall_patch_cap", "isx_wall_patches", "isx_wall_patches_device",
     "isx_default_beam_spec", "isx_beam_cone", "isx_beam_endstates", "isx_fluxmap_beam", "isx_fluxmap_beam_device",
@@ -332,6 +333,7 @@ def load():
     L.isx_light_field_device.argtypes = [P(Config), P(ExitMapSpec), u64, u64, u64, C.c_void_p, C.c_void_p]
     L.isx_bin_injected_lines.argtypes = [P(Config), i32, P(ExitMapSpec), P(dbl), u64, P(C.c_uint32), i32, i32, P(u64), P(u64), P(u64),
                                          P(u64)]
+    L.isx_bin_injected_segments.argtypes = [P(Config), P(dbl), i32, dbl, dbl, P(dbl), u64, P(C.c_uint32), i32, i32, P(u64), P(u64)]
     L.isx_default_order_hist_spec.argtypes = [P(Config), P(OrderHistSpec)]
     L.isx_default_order_hist_spec.restype = None
     L.isx_order_hist.argtypes = [P(Config), P(OrderHistSpec), u64, u64, u64, P(u64), P(u64), P(OrderHistCounts), P(Stats)]
@@ -644,6 +646,24 @@ def bin_injected_lines(cfg, sink, P, V, spec=None, region_counts=None, unit=INJE
                                        0 if rc_arr is None else rc_arr.size, int(unit), ptr(a), ptr(b), ptr(k), C.byref(inc)),
          "isx_bin_injected_lines")
     return a, b, k, int(inc.value)
+
+
+def bin_injected_segments(cfg, centers_axes, radius, half_thick, segments, region_counts=None, unit=INJECT_UNIT_AUTO, into=None):
+    """The disc sweep's binning kernel alone on the caller's exit segments[n, 7] (start, direction, tmax) (include/isx.h:
+    isx_bin_injected_segments; parity tests).  -> (hits[n_disc], bin_increments).  region_counts: segments per 1024-slot region of
+    the workspace (None: full regions); into: the hits of an earlier call to accumulate into."""
+    ca = np.ascontiguousarray(centers_axes, dtype=np.float64).reshape(-1, 6)
+    seg = np.ascontiguousarray(segments, dtype=np.float64).reshape(-1, 7)
+    n = seg.shape[0]
+    hits = into if into is not None else np.zeros(ca.shape[0], dtype=np.uint64)
+    rc_arr = None if region_counts is None else np.ascontiguousarray(region_counts, dtype=np.uint32)
+    inc = C.c_uint64(0)
+    _chk(load().isx_bin_injected_segments(C.byref(cfg), _p(ca, C.c_double), ca.shape[0], float(radius), float(half_thick),
+                                          _p(seg, C.c_double) if n else None, n,
+                                          _p(rc_arr, C.c_uint32) if rc_arr is not None else None,
+                                          0 if rc_arr is None else rc_arr.size, int(unit), _p(hits, C.c_uint64), C.byref(inc)),
+         "isx_bin_injected_segments")
+    return hits, int(inc.value)
 
 
 def default_order_hist_spec(cfg):

@@ -1173,6 +1173,14 @@ int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles, boo
   return ensure_regions((rays / (kRegion - 63) + waves + 1) * slot_doubles / 6 + 1, buf);   // (capacity is counted in 6-double slots)
 }
 
+// what the disc sweep's two kernels see of the list upload_discs_clustered left in the aux buffer: the discs in cluster order
+void clustered_discs(DetGrid& d) {
+  d.discs = S.d_aux + g_disc_clusters.off_ordered;
+  d.clusters = reinterpret_cast<const float*>(S.d_aux + g_disc_clusters.off_clusters);
+  d.disc_perm = reinterpret_cast<const int*>(S.d_aux + g_disc_clusters.off_perm);
+  d.n_clusters = g_disc_clusters.n_clusters;
+}
+
 // ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_FIELD_PIPE and ROUTE_DISC_PIPE: a trace launch and a binning launch per chunk of at most pipe_chunk rays
 int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
   int rc = set_lds(p.scene_fn ? (const void*)p.scene_fn : p.beam_fn ? (const void*)p.beam_fn : p.baffle_fn ? (const void*)p.baffle_fn : p.list_fn ? (const void*)p.list_fn : (const void*)p.fn, p.lds);
@@ -1190,10 +1198,7 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     dt.nbins = 1; dt.n_theta = 0; dt.n_phi = 0;
     if (p.route == ROUTE_FIELD_PIPE) db.nbins = p.bin_words;
   } else {
-    db.discs = S.d_aux + g_disc_clusters.off_ordered;
-    db.clusters = reinterpret_cast<const float*>(S.d_aux + g_disc_clusters.off_clusters);
-    db.disc_perm = reinterpret_cast<const int*>(S.d_aux + g_disc_clusters.off_perm);
-    db.n_clusters = g_disc_clusters.n_clusters;
+    clustered_discs(db);
     dt = db;
   }
   // one trace launch on `st` and the binning of its `cnt` rays from `off` on `sb`, through workspace `buf`.  t: one stream, each
@@ -1475,20 +1480,28 @@ int call_open(size_t bins) {
 int zero_hist(size_t bins) { return hip_rc(hipMemsetAsync(S.d_hist, 0, bins * sizeof(unsigned long long), S.stream)); }
 int call_close(int rc, isx_stats* stats) { const int rc2 = collect_stats(stats); return rc ? rc : rc2; }
 
-// isx_bin_injected_lines: the binning kernel of plan `p` on `n` caller-supplied lines laid out as `counts` says (one entry per
-// region), through the pipeline's own workspace, queue words and launch helpers -- what run_pipeline's launch_pair does after its
-// trace kernel, with the host in the trace kernel's place.  The slots of a region that hold no line carry `loud`.
+// isx_bin_injected_lines / isx_bin_injected_segments: the binning kernel of plan `p` on `n` caller-supplied records laid out as
+// `counts` says (one entry per region), through the pipeline's own workspace, queue words and launch helpers -- what
+// run_pipeline's launch_pair does after its trace kernel, with the host in the trace kernel's place.  `slot`: doubles per slot of
+// the workspace -- 6: exit lines, the caller's rows as they are; 8: exit segments (isx_trace_assist_disc_kernel), the caller's rows
+// of 7 doubles and a zero.  The slots of a region that hold no record carry `loud` (a whole slot).
 int run_injected(const Plan& p, const DetGrid& d, const double* lines, uint64_t n, const std::vector<uint32_t>& counts,
-                 uint32_t pad, const double loud[6], unsigned long long* d_hist) {
+                 uint32_t pad, const double* loud, unsigned long long* d_hist, size_t slot = 6) {
   const size_t regions = counts.size();
+  const size_t row = slot == 8 ? 7 : slot;   // doubles per record of the caller
   int rc = set_lds((const void*)p.bin, p.lds_bin); if (rc) return rc;
   const int bres = blocks_per_cu(p.bin, p.bblock, p.lds_bin, p.bin_per_cu);
-  rc = ensure_regions(regions + 1, 0); if (rc) return rc;
-  std::vector<double> rec(regions * (size_t)kRegion * 6);
-  for (size_t s = 0; s < rec.size(); s += 6) std::memcpy(&rec[s], loud, 6 * sizeof(double));
+  rc = ensure_regions(slot == 6 ? regions + 1 : (regions + 1) * slot / 6 + 1, 0); if (rc) return rc;   // (capacity is counted in 6-double slots)
+  std::vector<double> rec(regions * (size_t)kRegion * slot);
+  for (size_t s = 0; s < rec.size(); s += slot) std::memcpy(&rec[s], loud, slot * sizeof(double));
   uint64_t at = 0;
   for (size_t r = 0; r < regions; ++r) {
-    if (counts[r]) std::memcpy(&rec[r * (size_t)kRegion * 6], lines + 6 * at, (size_t)counts[r] * 6 * sizeof(double));
+    double* dst = &rec[r * (size_t)kRegion * slot];
+    if (counts[r] && row == slot) std::memcpy(dst, lines + row * at, (size_t)counts[r] * row * sizeof(double));
+    else for (uint32_t i = 0; i < counts[r]; ++i) {
+      std::memcpy(dst + slot * i, lines + row * (at + i), row * sizeof(double));
+      for (size_t k = row; k < slot; ++k) dst[slot * i + k] = 0.0;
+    }
     at += counts[r];
   }
   if (at != n) return ISX_ERR_BAD_ARG;
@@ -2096,16 +2109,8 @@ int isx_light_field(const isx_config* cfg, const isx_exit_map_spec* spec, uint64
   return rc;
 }
 
-static int bin_injected_lines(const isx_config* cfg, int32_t sink, const isx_exit_map_spec* spec, const double* lines, uint64_t n,
-                           const uint32_t* region_counts, int32_t n_regions, int32_t unit, uint64_t* out_a, uint64_t* out_b,
-                           uint64_t* counts, uint64_t* bin_increments) {
-  // ---- what needs no device (isx.h: the refusals)
-  if (!cfg || (n && !lines)) return ISX_ERR_BAD_ARG;
-  if (sink != ISX_INJECT_FLUX && sink != ISX_INJECT_EXIT_MAPS && sink != ISX_INJECT_LIGHT_FIELD) return ISX_ERR_BAD_ARG;
-  if (unit != ISX_INJECT_UNIT_AUTO && unit != 0 && unit != 2) return ISX_ERR_BAD_ARG;
-  if (n > ISX_INJECT_MAX_LINES) return ISX_ERR_TOO_LARGE;
-  if (!config_abi_ok(cfg)) return ISX_ERR_BAD_CONFIG;
-  std::vector<uint32_t> layout;
+// the region layout of an injected call, checked (isx.h): the caller's counts, or full regions with the rest in the last
+static int inject_layout(uint64_t n, const uint32_t* region_counts, int32_t n_regions, std::vector<uint32_t>& layout) {
   if (region_counts) {
     if (n_regions < 1 || n_regions > ISX_INJECT_MAX_REGIONS) return ISX_ERR_BAD_ARG;
     uint64_t sum = 0;
@@ -2119,8 +2124,22 @@ static int bin_injected_lines(const isx_config* cfg, int32_t sink, const isx_exi
     if (n_regions != 0) return ISX_ERR_BAD_ARG;
     for (uint64_t left = n; left > 0; left -= layout.back()) layout.push_back((uint32_t)std::min<uint64_t>(left, kRegion));
   }
+  return ISX_OK;
+}
+
+static int bin_injected_lines(const isx_config* cfg, int32_t sink, const isx_exit_map_spec* spec, const double* lines, uint64_t n,
+                           const uint32_t* region_counts, int32_t n_regions, int32_t unit, uint64_t* out_a, uint64_t* out_b,
+                           uint64_t* counts, uint64_t* bin_increments) {
+  // ---- what needs no device (isx.h: the refusals)
+  if (!cfg || (n && !lines)) return ISX_ERR_BAD_ARG;
+  if (sink != ISX_INJECT_FLUX && sink != ISX_INJECT_EXIT_MAPS && sink != ISX_INJECT_LIGHT_FIELD) return ISX_ERR_BAD_ARG;
+  if (unit != ISX_INJECT_UNIT_AUTO && unit != 0 && unit != 2) return ISX_ERR_BAD_ARG;
+  if (n > ISX_INJECT_MAX_LINES) return ISX_ERR_TOO_LARGE;
+  if (!config_abi_ok(cfg)) return ISX_ERR_BAD_CONFIG;
+  std::vector<uint32_t> layout;
+  int rc = inject_layout(n, region_counts, n_regions, layout);
+  if (rc) return rc;
   size_t na = 0, nb = 0, nc = 0;   // words of out_a, out_b, counts
-  int rc;
   {
     Geom g;
     rc = prepare_geom(cfg, &g);   // (the geometry is not used, but a config the public calls refuse is refused here too)
@@ -2199,6 +2218,88 @@ int isx_bin_injected_lines(const isx_config* cfg, int32_t sink, const isx_exit_m
   // (the staging copies are std::vectors: no exception crosses the ABI)
   try {
     return bin_injected_lines(cfg, sink, spec, lines, n, region_counts, n_regions, unit, out_a, out_b, counts, bin_increments);
+  } catch (const std::bad_alloc&) {
+    return ISX_ERR_TOO_LARGE;
+  }
+}
+
+static int bin_injected_segments(const isx_config* cfg, const double* centers_axes, int32_t n_disc, double radius, double half_thick,
+                                 const double* segments, uint64_t n, const uint32_t* region_counts, int32_t n_regions, int32_t unit,
+                                 uint64_t* hits, uint64_t* bin_increments) {
+  // ---- what needs no device (isx.h: the refusals)
+  if (!cfg || !centers_axes || !hits || (n && !segments)) return ISX_ERR_BAD_ARG;
+  if (n_disc < 1 || n_disc > 36000) return ISX_ERR_BAD_ARG;   // (sink_grid's limit for a disc list)
+  if (!(radius > 0) || !(half_thick > 0) || !std::isfinite(radius) || !std::isfinite(half_thick)) return ISX_ERR_BAD_ARG;
+  if (unit != ISX_INJECT_UNIT_AUTO && unit != 0 && unit != 2) return ISX_ERR_BAD_ARG;
+  if (n > ISX_INJECT_MAX_LINES) return ISX_ERR_TOO_LARGE;
+  if (!config_abi_ok(cfg)) return ISX_ERR_BAD_CONFIG;
+  std::vector<uint32_t> layout;
+  int rc = inject_layout(n, region_counts, n_regions, layout);
+  if (rc) return rc;
+  {
+    Geom g;
+    rc = prepare_geom(cfg, &g);   // (the geometry is not used, but a config isx_disc_sweep refuses is refused here too)
+    if (rc) return rc;
+    if (cfg->source_model != ISX_SOURCE_PENCIL) return ISX_ERR_BAD_CONFIG;
+  }
+  // the domain: what isx_trace_assist_disc_kernel can leave behind, and what the binary32 margins of the cluster test are written for
+  const double reach2 = 3.0 * cfg->box_half * cfg->box_half, tmax_max = 2.0 * std::sqrt(3.0) * cfg->box_half;
+  auto unit_vec = [](const double* v) { return std::fabs(std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) - 1.0) <= 1e-12; };
+  auto in_reach = [&](const double* x) { return x[0] * x[0] + x[1] * x[1] + x[2] * x[2] <= reach2; };
+  for (int32_t k = 0; k < n_disc; ++k) {
+    const double* ca = centers_axes + 6 * (size_t)k;
+    for (int q = 0; q < 6; ++q) if (!std::isfinite(ca[q])) return ISX_ERR_BAD_ARG;
+    if (!in_reach(ca) || !unit_vec(ca + 3)) return ISX_ERR_BAD_ARG;
+  }
+  for (uint64_t i = 0; i < n; ++i) {
+    const double* s = segments + 7 * i;
+    for (int q = 0; q < 7; ++q) if (!std::isfinite(s[q])) return ISX_ERR_BAD_ARG;
+    if (!in_reach(s) || !unit_vec(s + 3) || !(s[6] >= 0.0) || !(s[6] <= tmax_max)) return ISX_ERR_BAD_ARG;
+  }
+  if (!S.init) return not_initialised();
+  if (bin_increments) *bin_increments = 0;
+  if (n == 0) return ISX_OK;
+  // ---- the call as isx_disc_sweep opens it: its histogram, the clustered disc list, its DetGrid and its plan
+  rc = call_open((size_t)n_disc);
+  if (rc) return rc;
+  std::vector<unsigned long long> host((size_t)n_disc);
+  isx_stats st;
+  std::memset(&st, 0, sizeof(st));
+  g_disc_clusters = DiscClusters();
+  rc = S.disc_pipeline ? upload_discs_clustered(centers_axes, (size_t)n_disc, radius, half_thick) : ISX_ERR_BAD_CONFIG;
+  if (rc == ISX_OK) rc = zero_hist((size_t)n_disc);
+  if (rc == ISX_OK) {
+    DetGrid d;
+    size_t lds = 0;
+    rc = sink_grid(SINK_DISC, cfg, n_disc, S.d_aux, radius, half_thick, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d, lds);
+    if (rc == ISX_OK) {
+      const Plan p = plan_launch(SINK_DISC, cfg, d, lds, true, n);
+      if (p.route != ROUTE_DISC_PIPE || p.bin != isx_bin_discs_kernel || p.slot_doubles != 8) rc = ISX_ERR_BAD_CONFIG;   // (the fused kernel answers isx_disc_sweep)
+      else {
+        clustered_discs(d);
+        // through the centre of disc 0 along its axis, from one unit before the centre to one unit behind
+        const double* c0 = centers_axes;
+        const double loud[8] = {c0[0] - c0[3], c0[1] - c0[4], c0[2] - c0[5], c0[3], c0[4], c0[5], 2.0, 0.0};
+        const uint32_t pad = unit == ISX_INJECT_UNIT_AUTO ? (n < 1000000ull ? 2u : 0u) : (uint32_t)unit;
+        rc = run_injected(p, d, segments, n, layout, pad, loud, S.d_hist, 8);
+      }
+    }
+  }
+  if (rc == ISX_OK) rc = copy_out(host.data(), S.d_hist, (size_t)n_disc * sizeof(unsigned long long));
+  rc = call_close(rc, &st);
+  if (rc) return rc;
+  for (int32_t k = 0; k < n_disc; ++k) hits[k] += host[(size_t)k];
+  if (bin_increments) *bin_increments = st.bin_increments;
+  return ISX_OK;
+}
+
+int isx_bin_injected_segments(const isx_config* cfg, const double* centers_axes, int32_t n_disc, double radius, double half_thick,
+                              const double* segments, uint64_t n, const uint32_t* region_counts, int32_t n_regions, int32_t unit,
+                              uint64_t* hits, uint64_t* bin_increments) {
+  // (the staging copies are std::vectors: no exception crosses the ABI)
+  try {
+    return bin_injected_segments(cfg, centers_axes, n_disc, radius, half_thick, segments, n, region_counts, n_regions, unit, hits,
+                                 bin_increments);
   } catch (const std::bad_alloc&) {
     return ISX_ERR_TOO_LARGE;
   }

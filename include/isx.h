@@ -497,7 +497,8 @@ int isx_light_field_device(const isx_config* cfg, const isx_exit_map_spec* spec,
  * refuses.  The exit-map and light-field sinks take any doubles: their contract defines NaN and inf as "outside".
  * With a device, ISX_ERR_BAD_CONFIG as well where the plan has no binning kernel for the call: a flux grid whose histogram and
  * tables do not fit the binning kernels' LDS (isx_fluxmap then runs the fused kernel), "pipeline" 0, "bin_mode" 0 or 2, a border /
- * source combination that the pipeline does not serve.  The disc sweep's binning kernel (8-double segments) is not reachable here.
+ * source combination that the pipeline does not serve.  The disc sweep's binning kernel (8-double segments) is not reachable here:
+ * isx_bin_injected_segments below.
  */
 #define ISX_INJECT_FLUX 0
 #define ISX_INJECT_EXIT_MAPS 1
@@ -509,6 +510,39 @@ int isx_light_field_device(const isx_config* cfg, const isx_exit_map_spec* spec,
 int isx_bin_injected_lines(const isx_config* cfg, int32_t sink, const isx_exit_map_spec* spec, const double* lines /*[n][6]*/,
                            uint64_t n, const uint32_t* region_counts, int32_t n_regions, int32_t unit, uint64_t* out_a,
                            uint64_t* out_b, uint64_t* counts, uint64_t* bin_increments);
+
+/*
+ * The same for the shared-ray disc sweep (isx_disc_sweep on its two-kernel route): the sweep's binning kernel alone, on exit
+ * SEGMENTS the caller supplies (parity tests: segments that graze a disc's rim, that end at the tube, that sit on the ties of the
+ * exact test, that lie at the edge of a cluster's ball -- where the kernel's two culls could drop a hit).  No ray is traced: the
+ * segments are laid into the pipeline's workspace exactly as the sweep's trace kernel leaves them -- 8 doubles per slot, the
+ * eighth 0, regions of 1024 slots, a count per region -- and the binning kernel runs on them with the plan's workgroup size, LDS
+ * and grid ("grid_blocks" keeps its meaning).  The disc list goes the way isx_disc_sweep sends it: into cluster order, with the
+ * cluster table.
+ *
+ *   centers_axes[n_disc][6], radius, half_thick   the discs of isx_disc_sweep
+ *   segments[n][7]  start point, direction, length tmax: the forward segment { start + t direction, 0 <= t <= tmax }
+ *   region_counts[n_regions], unit   as for isx_bin_injected_lines.  The slots of a region that hold no segment are filled with
+ *         one segment through the centre of disc 0 along its axis, from one unit before the centre to one unit behind it: a kernel
+ *         that reads past a region's count shows up as extra counts in hits[0]
+ *
+ * hits[n_disc] is a HOST array and ACCUMULATES (+=); *bin_increments (may be NULL) is set to what this call added.  Blocking.
+ * The result does not depend on the layout, the unit, the order of the segments or "grid_blocks".
+ *
+ * Domain: what the sweep's trace kernel can produce, which is what the binary32 margins of the cluster test are written for --
+ * every coordinate finite, directions and disc axes with | |V| - 1 | <= 1e-12, start points and disc centres with
+ * |x|^2 <= 3 cfg->box_half^2, 0 <= tmax <= 2 sqrt(3) cfg->box_half.  Refused with ISX_ERR_BAD_ARG, before any device is asked
+ * for: a NULL cfg, centers_axes, hits or segments (with n > 0); n_disc < 1 (or above the 36 000 of isx_disc_sweep); radius or
+ * half_thick not > 0; anything outside the domain; a unit that is none of the above; n_regions or a region count out of range,
+ * counts that do not sum to n; n above ISX_INJECT_MAX_LINES (ISX_ERR_TOO_LARGE, as is host memory that cannot be had for the
+ * staging copy).  ISX_ERR_BAD_CONFIG, likewise before the device: a config that isx_disc_sweep refuses.  With a device,
+ * ISX_ERR_BAD_CONFIG as well where the plan does not choose the two-kernel route for the sweep: "disc_pipeline", "pipeline" or
+ * "assist" 0, a border, source or hit line that the route does not serve, a disc list whose tables do not fit the binning
+ * kernel's LDS (isx_disc_sweep then runs the fused kernel).
+ */
+int isx_bin_injected_segments(const isx_config* cfg, const double* centers_axes /*[n_disc][6]*/, int32_t n_disc, double radius,
+                              double half_thick, const double* segments /*[n][7]*/, uint64_t n, const uint32_t* region_counts,
+                              int32_t n_regions, int32_t unit, uint64_t* hits /*[n_disc]*/, uint64_t* bin_increments);
 
 /*
  * Bounce-order histograms: how long the light stayed in the sphere before it ended.  A ray that ends after k mirror

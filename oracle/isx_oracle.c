@@ -1079,6 +1079,66 @@ int isxo_disc_sweep(const isxo_config* c, const double* ca, int32_t nd, double r
   return 0;
 }
 
+/* The disc test alone: every segment[7] (start, direction, tmax) against every disc, brute force, with the loop of
+ * isxo_disc_sweep and its segment_hits_tube -- no cull, no cluster (tests: segments on a disc's rim, at the tube's ends, on the
+ * ties of the test). */
+int isxo_bin_segments(const double* ca, int32_t nd, double radius, double half_thick, const double* seg, uint64_t n,
+                      uint64_t* hits, int nthreads) {
+  if (!hits || !ca || nd < 1 || (n && !seg)) return -3;
+  memset(hits, 0, (size_t)nd * sizeof(uint64_t));
+  int failed = 0;
+#ifdef _OPENMP
+  if (nthreads > 0) omp_set_num_threads(nthreads);
+  else omp_set_num_threads(omp_get_num_procs());
+#endif
+#pragma omp parallel
+  {
+    uint64_t* h = (uint64_t*)calloc((size_t)nd, sizeof(uint64_t));
+    if (!h) {
+#pragma omp atomic write
+      failed = 1;
+    }
+#pragma omp for schedule(dynamic, 64)
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+      if (!h) continue;
+      const double* s = seg + 7 * i;
+      const v3 p = { s[0], s[1], s[2] }, v = { s[3], s[4], s[5] };
+      for (int k = 0; k < nd; k++)
+        if (segment_hits_tube(p, v, s[6], ca + 6 * k, radius, half_thick)) h[k]++;
+    }
+#pragma omp critical
+    {
+      if (h) for (int k = 0; k < nd; k++) hits[k] += h[k];
+    }
+    free(h);
+  }
+  return failed ? -3 : 0;
+}
+
+/* The exit segments isxo_disc_sweep tests, per ray: status[n] and, for an EXITED ray, seg[n][7] = the start of the last segment
+ * (the last mirror point), the final direction and tmax = (p - start).v; zeros for every other ray. */
+int isxo_exit_segments(const isxo_config* c, uint64_t n, uint64_t seed, uint64_t first, int32_t* status, double* seg) {
+  geom g;
+  if (!c || !status || !seg) return -3;
+  int rc = prepare(c, &g);
+  if (rc) return rc;
+#pragma omp parallel for schedule(dynamic, 256)
+  for (int64_t i = 0; i < (int64_t)n; i++) {
+    endstate es;
+    trace_one(&g, seed, first + (uint64_t)i, 0u, g.src, g.dir0, K_NONE, &es);
+    double* s = seg + 7 * i;
+    status[i] = es.status;
+    memset(s, 0, 7 * sizeof(double));
+    if (es.status == ISXO_EXITED) {
+      const v3 seg_start = es.prev, p = es.p, v = es.v;
+      v3 dlt = { p.x - seg_start.x, p.y - seg_start.y, p.z - seg_start.z };
+      s[0] = seg_start.x; s[1] = seg_start.y; s[2] = seg_start.z; s[3] = v.x; s[4] = v.y; s[5] = v.z;
+      s[6] = dot3(dlt, v);
+    }
+  }
+  return 0;
+}
+
 /* the sweep as the reference writes it (integratingSphereDetectorSweep.C:54-77): disc k sees only its own rays
  * [first + k*rpp, +rpp) */
 int isxo_disc_sweep_per_position(const isxo_config* c, const double* ca, int32_t nd, double radius, double half_thick,

@@ -84,6 +84,14 @@ int isxo_trace_rays_detector(const isxo_config* cfg, const double* detector, dou
 int isxo_disc_sweep(const isxo_config* cfg, const double* centers_axes, int32_t n_disc, double radius,
                     double half_thick, uint64_t n_rays, uint64_t seed, uint64_t first_ray, uint64_t* hits,
                     isxo_stats* stats, int nthreads);
+/* The disc test alone on caller-supplied segments[n][7] (start, direction, tmax): every segment against every disc with the
+ * sweep's own test, brute force. hits[n_disc] zeroed then filled. nthreads<=0: all cores. */
+int isxo_bin_segments(const double* centers_axes, int32_t n_disc, double radius, double half_thick, const double* segments,
+                      uint64_t n, uint64_t* hits, int nthreads);
+/* The segments isxo_disc_sweep tests: status[n]; segments[n][7] = last mirror point, final direction, (p - start).v for an
+ * EXITED ray, zeros otherwise. */
+int isxo_exit_segments(const isxo_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t first_ray, int32_t* status,
+                       double* segments);
 /* The same with every disc position seeing only its own rays [first_ray + k*rays_per_position, +rays_per_position)
  * (the loop integratingSphereDetectorSweep.C:54-77 as written). */
 int isxo_disc_sweep_per_position(const isxo_config* cfg, const double* centers_axes, int32_t n_disc, double radius,

@@ -124,6 +124,8 @@ def lib():
         L.isxo_fluxmap.argtypes = [P(Config), u64, u64, u64, P(u64), P(Stats), C.c_int]
         L.isxo_bin_lines.argtypes = [P(Config), P(dbl), u64, P(u64), C.c_int]
         L.isxo_disc_sweep.argtypes = [P(Config), P(dbl), i32, dbl, dbl, u64, u64, u64, P(u64), P(Stats), C.c_int]
+        L.isxo_bin_segments.argtypes = [P(dbl), i32, dbl, dbl, P(dbl), u64, P(u64), C.c_int]
+        L.isxo_exit_segments.argtypes = [P(Config), u64, u64, u64, P(i32), P(dbl)]
         L.isxo_disc_sweep_per_position.argtypes = [P(Config), P(dbl), i32, dbl, dbl, u64, u64, u64, P(u64), P(Stats), C.c_int]
         L.isxo_exit_dz_hist.argtypes = [P(Config), u64, u64, u64, i32, P(u64), P(Stats), C.c_int]
         L.isxo_fluxmap_per_position.argtypes = [P(Config), u64, i32, u64, u64, u64, u64, P(u64), P(Stats), C.c_int]
@@ -249,6 +251,28 @@ def disc_sweep(cfg, centers_axes, radius, half_thick, n, seed, first=0, nthreads
                                _p(hits, C.c_uint64), C.byref(st), nthreads)
     assert rc == 0, rc
     return hits, st
+
+
+def bin_segments(centers_axes, radius, half_thick, segments, nthreads=0):
+    """-> hits[n_disc]: the sweep's own segment_hits_tube of every segment[7] (start, direction, tmax) against every disc."""
+    ca = np.ascontiguousarray(centers_axes, dtype=np.float64).reshape(-1, 6)
+    seg = np.ascontiguousarray(segments, dtype=np.float64).reshape(-1, 7)
+    hits = np.zeros(ca.shape[0], dtype=np.uint64)
+    if nthreads <= 0 and seg.shape[0] * ca.shape[0] <= 1 << 16:
+        nthreads = 1                                            # (a handful of tests: not worth a team of threads)
+    rc = lib().isxo_bin_segments(_p(ca, C.c_double), ca.shape[0], radius, half_thick, _p(seg, C.c_double), seg.shape[0],
+                                 _p(hits, C.c_uint64), nthreads)
+    assert rc == 0, rc
+    return hits
+
+
+def exit_segments(cfg, n, seed, first=0):
+    """-> (status[n], segments[n, 7]): what isxo_disc_sweep tests of every ray (zeros where the ray did not exit)"""
+    status = np.zeros(n, dtype=np.int32)
+    seg = np.zeros((n, 7), dtype=np.float64)
+    rc = lib().isxo_exit_segments(C.byref(cfg), n, seed, first, _p(status, C.c_int32), _p(seg, C.c_double))
+    assert rc == 0, rc
+    return status, seg
 
 
 def disc_sweep_per_position(cfg, centers_axes, radius, half_thick, rpp, seed, first=0, nthreads=0):
