@@ -52,6 +52,7 @@ EXPORTS = [
     "isx_default_baffle_spec", "isx_baffle_disc", "isx_baffle_endstates", "isx_fluxmap_baffle", "isx_fluxmap_baffle_device",
     "isx_default_scene_spec", "isx_scene_endstates", "isx_fluxmap_scene", "isx_fluxmap_scene_device",
     "isx_default_response_spec", "isx_scene_response", "isx_scene_response_device", "isx_response_reweight",
+    "isx_view_frame", "isx_scene_view", "isx_scene_view_device", "isx_view_reweight", "isx_view_weight_fov",
 ]
 
 
@@ -281,6 +282,37 @@ class ResponseSpec(C.Structure):
         return int(self.n[0]) * int(self.n[1]) * int(self.n[2]) * int(self.n[3])
 
 
+VIEW_MAX_AXIS, VIEW_MAX_BINS = 1024, 65536
+
+
+class ViewSpec(C.Structure):
+    """isx_view_spec (include/isx.h): the selected wall class (the detector), the map's size, the detector's frame -- used as
+    given -- and the half extent of the map in direction cosines."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("patch", C.c_int32), ("n_u", C.c_int32), ("n_v", C.c_int32),
+                ("reserved1", C.c_int32), ("axis", C.c_double * 3), ("e1", C.c_double * 3), ("e2", C.c_double * 3),
+                ("half_extent", C.c_double)]
+
+    @property
+    def bins(self):
+        return int(self.n_u) * int(self.n_v)
+
+    def copy(self):
+        s = ViewSpec()
+        C.memmove(C.byref(s), C.byref(self), C.sizeof(ViewSpec))
+        return s
+
+
+class ViewCounts(C.Structure):
+    """isx_view_counts (include/isx.h): the selected rays by what became of them."""
+
+    _fields_ = [("binned", C.c_uint64), ("outside", C.c_uint64), ("behind", C.c_uint64), ("direct", C.c_uint64)]
+
+    def words(self):
+        """-> the 4 words in the struct's order (the device form's layout)"""
+        return np.frombuffer(bytes(self), dtype=np.uint64).copy()
+
+
 _lib = None
 
 
@@ -368,6 +400,11 @@ def load():
     L.isx_scene_response.argtypes = [P(Config), P(SceneSpec), P(ResponseSpec), u64, u64, u64, P(u64), P(SceneCounts), P(Stats)]
     L.isx_scene_response_device.argtypes = [P(Config), P(SceneSpec), P(ResponseSpec), u64, u64, u64, C.c_void_p, C.c_void_p]
     L.isx_response_reweight.argtypes = [P(ResponseSpec), P(u64), P(dbl), P(dbl), P(dbl)]
+    L.isx_view_frame.argtypes = [P(Config), P(SceneSpec), i32, i32, i32, dbl, P(ViewSpec)]
+    L.isx_scene_view.argtypes = [P(Config), P(SceneSpec), P(ViewSpec), u64, u64, u64, P(u64), P(ViewCounts), P(SceneCounts), P(Stats)]
+    L.isx_scene_view_device.argtypes = [P(Config), P(SceneSpec), P(ViewSpec), u64, u64, u64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.isx_view_reweight.argtypes = [P(ViewSpec), P(u64), P(ViewCounts), u64, P(dbl), dbl, P(dbl), P(dbl)]
+    L.isx_view_weight_fov.argtypes = [P(ViewSpec), dbl, P(dbl)]
     _lib = L
     return L
 
@@ -984,6 +1021,66 @@ def response_reweight(rspec, response, weight):
     _chk(load().isx_response_reweight(C.byref(rspec), _p(h, C.c_uint64), _p(w, C.c_double), _p(frac, C.c_double),
                                       _p(sig, C.c_double)), "isx_response_reweight")
     return frac, sig
+
+
+def view_frame(cfg, scene, patch, n_u, n_v, half_extent=1.0):
+    """-> ViewSpec for patch `patch` of the scene: its axis as given, e1 and e2 by beam_cone's frame rule about it, an n_u x n_v
+    map over [-half_extent, half_extent]^2 of the direction cosines (include/isx.h: isx_view_frame; no GPU needed)."""
+    s = ViewSpec()
+    _chk(load().isx_view_frame(C.byref(cfg), C.byref(scene), int(patch), int(n_u), int(n_v), float(half_extent), C.byref(s)),
+         "isx_view_frame")
+    return s
+
+
+def _view_bins(vspec):
+    """the words of the arrays a call may touch; 1 for a spec the library refuses (it says so itself)"""
+    ok = 1 <= int(vspec.n_u) <= VIEW_MAX_AXIS and 1 <= int(vspec.n_v) <= VIEW_MAX_AXIS and vspec.bins <= VIEW_MAX_BINS
+    return (int(vspec.n_v), int(vspec.n_u)) if ok else (1, 1)
+
+
+def scene_view(cfg, scene, vspec, n_rays, seed, first_ray=0):
+    """-> (view[n_v, n_u] uint64, ViewCounts, SceneCounts, Stats): the rays wall class vspec.patch of the scene absorbs, binned
+    over the direction they arrive from in the frame of vspec (include/isx.h: isx_scene_view)."""
+    nv, nu = _view_bins(vspec)
+    view = np.zeros(nv * nu, dtype=np.uint64)
+    st = Stats()
+    vc = ViewCounts()
+    cnt = SceneCounts()
+    _chk(load().isx_scene_view(C.byref(cfg), C.byref(scene), C.byref(vspec), int(n_rays), int(seed), int(first_ray),
+                               _p(view, C.c_uint64), C.byref(vc), C.byref(cnt), C.byref(st)), "isx_scene_view")
+    return view.reshape(nv, nu), vc, cnt, st
+
+
+def scene_view_device(cfg, scene, vspec, n_rays, seed, first_ray, d_view_ptr, d_view_counts_ptr, d_scene_counts_ptr):
+    """Enqueue on the library stream, accumulating into device memory at d_view_ptr ([n_v * n_u] uint64), d_view_counts_ptr
+    ([4] uint64, ViewCounts' layout) and d_scene_counts_ptr ([36] uint64, SceneCounts' layout)."""
+    _chk(load().isx_scene_view_device(C.byref(cfg), C.byref(scene), C.byref(vspec), int(n_rays), int(seed), int(first_ray),
+                                      C.c_void_p(int(d_view_ptr or 0) or None), C.c_void_p(int(d_view_counts_ptr or 0) or None),
+                                      C.c_void_p(int(d_scene_counts_ptr or 0) or None)), "isx_scene_view_device")
+
+
+def view_reweight(vspec, view, view_counts, launched, weight, direct_weight=0.0):
+    """-> (signal, sigma): the reading per launched ray of a detector whose angular response is weight[iv, iu] over the map and
+    direct_weight for the rays straight from the source, from one scene_view result (include/isx.h: isx_view_reweight; host
+    only, no GPU needed)."""
+    nv, nu = _view_bins(vspec)
+    h = np.ascontiguousarray(np.asarray(view, dtype=np.uint64).reshape(-1))
+    w = np.ascontiguousarray(np.asarray(weight, dtype=np.float64).reshape(-1))
+    if h.size < nv * nu or w.size < nv * nu:
+        raise ValueError("view has %d words and weight %d, the spec wants %d" % (h.size, w.size, nv * nu))
+    sig, sd = C.c_double(0.0), C.c_double(0.0)
+    _chk(load().isx_view_reweight(C.byref(vspec), _p(h, C.c_uint64), C.byref(view_counts), int(launched), _p(w, C.c_double),
+                                  float(direct_weight), C.byref(sig), C.byref(sd)), "isx_view_reweight")
+    return sig.value, sd.value
+
+
+def view_weight_fov(vspec, half_angle_deg):
+    """-> weight[n_v, n_u]: 1.0 for the bins whose centre lies within half_angle_deg of the detector's normal, else 0.0 -- a
+    field-of-view stop (include/isx.h: isx_view_weight_fov; host only, no GPU needed)."""
+    nv, nu = _view_bins(vspec)
+    w = np.zeros(nv * nu, dtype=np.float64)
+    _chk(load().isx_view_weight_fov(C.byref(vspec), float(half_angle_deg), _p(w, C.c_double)), "isx_view_weight_fov")
+    return w.reshape(nv, nu)
 
 
 def fluxmap_series(cfgs, n_rays, seed, first_ray=0):

@@ -73,6 +73,7 @@ struct State {
   int bin_slots = 1;                            // 1: isx_bin_slots_kernel (slot queues by window length) where the grid allows it
   int lf_global = 0;                            // 1: isx_bin_lightfield_kernel's global form for a field that fits the LDS as well (diagnostic)
   int resp_global = 0;                          // 1: isx_trace_assist_scene_response_kernel's global form for a response that fits the LDS as well (diagnostic)
+  int view_global = 0;                          // 1: isx_trace_assist_scene_view_kernel's global form for a map that fits the LDS as well (diagnostic)
   int surface_pipeline = 1;                     // 1 (default): the lobe / rough-specular borders and the origin-compat hit line on the assist-wave
                                                 // pipeline (round 5); 0: round 1's fused isx_trace_bin_full_kernel
   // options
@@ -621,6 +622,34 @@ int check_response_spec(const isx_response_spec* s) {
 }
 size_t response_bins(const isx_response_spec& s) { return (size_t)s.n[0] * s.n[1] * s.n[2] * s.n[3]; }
 
+// isx_scene_view: the checked spec and the device arrays of the call (the map [n_v][n_u], the four words of isx_view_counts); the
+// scene travels as SceneSink
+struct ViewCall { const isx_view_spec* spec = nullptr; unsigned long long* out = nullptr; unsigned long long* counts = nullptr; };
+static_assert(sizeof(isx_view_counts) == kViewCounters * sizeof(uint64_t) && offsetof(isx_view_counts, binned) == 8 * kViewBinned &&
+              offsetof(isx_view_counts, outside) == 8 * kViewOutside && offsetof(isx_view_counts, behind) == 8 * kViewBehind &&
+              offsetof(isx_view_counts, direct) == 8 * kViewDirect, "isx.h and view_record's counters");
+static_assert(sizeof(isx_view_spec) == 104, "isx.h: isx_view_spec");
+// isx.h: the limits of a view spec; n_patches < 0: no scene is at hand (the host-side helpers), the patch index is not looked at
+int check_view_spec(const isx_view_spec* s, int n_patches) {
+  if (s->struct_size != (uint32_t)sizeof(isx_view_spec) || s->reserved0 != 0u || s->reserved1 != 0) return ISX_ERR_BAD_CONFIG;
+  if (n_patches >= 0 && (s->patch < 0 || s->patch >= n_patches)) return ISX_ERR_BAD_CONFIG;
+  if (s->n_u < 1 || s->n_u > ISX_VIEW_MAX_AXIS || s->n_v < 1 || s->n_v > ISX_VIEW_MAX_AXIS) return ISX_ERR_BAD_CONFIG;
+  if ((long long)s->n_u * s->n_v > ISX_VIEW_MAX_BINS) return ISX_ERR_BAD_CONFIG;
+  if (!std::isfinite(s->half_extent) || !(s->half_extent > 0.0 && s->half_extent <= 1.0)) return ISX_ERR_BAD_CONFIG;
+  const double* vec[3] = {s->axis, s->e1, s->e2};
+  for (int k = 0; k < 3; ++k)
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(vec[k][i])) return ISX_ERR_BAD_CONFIG;
+  // (check_beam_call's test of a frame)
+  auto dot = [](const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+  for (int k = 0; k < 3; ++k) {
+    if (!(std::fabs(std::sqrt(dot(vec[k], vec[k])) - 1.0) <= 1e-12)) return ISX_ERR_BAD_CONFIG;
+    if (!(std::fabs(dot(vec[k], vec[(k + 1) % 3])) <= 1e-12)) return ISX_ERR_BAD_CONFIG;
+  }
+  return ISX_OK;
+}
+size_t view_bins(const isx_view_spec& s) { return (size_t)s.n_u * (size_t)s.n_v; }
+
 // LDS of a workgroup's histogram: 4 B per bin, 16-byte aligned
 size_t hist_lds(int nbins) { return ((size_t)nbins * 4 + 15) & ~(size_t)15; }
 
@@ -733,7 +762,7 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
     d.xm_dir = wp->arrivals; d.xm_pos = wp->absorbed;
     d.nbins = 2 * (wp->spec->n_patches + 2);
     lds = patch_lds() + 64 + sizeof(Geom) + sizeof(DetGrid);
-  } else if (sink == SINK_RESPONSE) {
+  } else if (sink == SINK_RESPONSE || sink == SINK_VIEW) {
     // (isx.h: hit_line_mode and the detector grid are ignored -- no exit line is written, no grid is looked at; the scene and the
     //  response spec were checked by the entry, the patches' words are enqueue's)
     d.hit_line_mode = ISX_HITLINE_LAST_SEGMENT;
@@ -774,6 +803,7 @@ typedef void (*ListFn)(const Geom, const DetGrid, const Work, const FateList);
 typedef void (*BaffleFn)(const Geom, const DetGrid, const Work, const BaffleTab);
 typedef void (*SceneFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab);
 typedef void (*ResponseFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab, const RespSink);
+typedef void (*ViewFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab, const ViewSink);
 struct Plan {
   Route route = ROUTE_FUSED;
   KernelFn fn = nullptr;        // the kernel (a pipeline's trace kernel)
@@ -804,6 +834,8 @@ struct Plan {
   SceneFn scene_fn = nullptr;   // isx_fluxmap_scene: the pipeline's trace kernel (patch_tab, beam and baffles are its fourth to sixth arguments) instead of fn
   ResponseFn resp_fn = nullptr; // isx_scene_response: ROUTE_ASSIST's one kernel (the scene's three arguments, and resp the seventh) instead of fn
   RespSink resp{};              // (resp.lds_words: plan_launch's choice of the form; the rest is enqueue's)
+  ViewFn view_fn = nullptr;     // isx_scene_view: ROUTE_ASSIST's one kernel (the scene's three arguments, and view the seventh) instead of fn
+  ViewSink view{};              // (view.lds_words: plan_launch's choice of the form; the rest is enqueue's)
 };
 
 // "fate_scan" = -1: where the scan pays (measured on MI355X, docs/LOG.md section 16.3).  A small launch is bound by its longest
@@ -885,6 +917,25 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     const size_t resident = (size_t)blocks_per_cu(p.resp_fn, p.block, p.lds, kResident);
     if (!S.resp_global && ((with + 2047) & ~(size_t)2047) * resident <= S.lds_limit) {
       p.resp.lds_words = (uint32_t)resp_words;
+      p.lds = with;
+    }
+    return p;
+  }
+  // The scene view (isx_scene_view): the same route, shape and rule -- the scene's trace kernel with the view as its one sink.
+  // Behind the parks lie the four counters (both forms) and, where that costs no resident workgroup, `resp_words` = n_u * n_v u32
+  // words of the map, flushed once per workgroup; else, or with view_global = 1, one global u64 add per binned ray
+  // (isx_kernels.hpp: view_record).  The form is ViewSink::lds_words, nothing else.
+  if (sink == SINK_VIEW) {
+    p.route = ROUTE_ASSIST;
+    p.view_fn = isx_trace_assist_scene_view_kernel;
+    p.launch_max = std::min(kLaunchMax, S.pipe_chunk);
+    trace_shape(p, small_shape(std::min(n, p.launch_max), S.assist_block_set ? S.assist_block : kSceneBlock), true,
+                resident_unless(S.trace_blocks_per_cu));
+    p.lds += SceneLds::bytes(p.tracers) + kViewCounters * sizeof(uint32_t);
+    const size_t with = p.lds + hist_lds((int)resp_words);
+    const size_t resident = (size_t)blocks_per_cu(p.view_fn, p.block, p.lds, kResident);
+    if (!S.view_global && ((with + 2047) & ~(size_t)2047) * resident <= S.lds_limit) {
+      p.view.lds_words = (uint32_t)resp_words;
       p.lds = with;
     }
     return p;
@@ -1127,9 +1178,10 @@ int span(int kind, size_t* from) {
 
 // ROUTE_FUSED and ROUTE_ASSIST: launches of at most kLaunchMax rays, one span
 int run_single(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
-  const void* fn = p.resp_fn ? (const void*)p.resp_fn : p.patch_fn ? (const void*)p.patch_fn : (const void*)p.fn;
+  const void* fn = p.view_fn ? (const void*)p.view_fn : p.resp_fn ? (const void*)p.resp_fn : p.patch_fn ? (const void*)p.patch_fn : (const void*)p.fn;
   int rc = set_lds(fn, p.lds); if (rc) return rc;
-  const int per_cu = p.resp_fn ? blocks_per_cu(p.resp_fn, p.block, p.lds, p.per_cu) :
+  const int per_cu = p.view_fn ? blocks_per_cu(p.view_fn, p.block, p.lds, p.per_cu) :
+                     p.resp_fn ? blocks_per_cu(p.resp_fn, p.block, p.lds, p.per_cu) :
                      p.patch_fn ? blocks_per_cu(p.patch_fn, p.block, p.lds, p.per_cu) : blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
   const uint64_t launch_max = p.launch_max ? p.launch_max : kLaunchMax;
   size_t t;
@@ -1137,7 +1189,8 @@ int run_single(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
   for (uint64_t off = 0; off < wk.n; off += launch_max) {
     Work w;
     rc = launch_work(wk, off, std::min(wk.n - off, launch_max), 0, S.stream, &w); if (rc) return rc;
-    if (p.resp_fn) hipLaunchKernelGGL(p.resp_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.resp);
+    if (p.view_fn) hipLaunchKernelGGL(p.view_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.view);
+    else if (p.resp_fn) hipLaunchKernelGGL(p.resp_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.resp);
     else if (p.patch_fn) hipLaunchKernelGGL(p.patch_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab);
     else hipLaunchKernelGGL(p.fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w);
     HIPCHK(hipGetLastError());
@@ -1294,7 +1347,7 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
             const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr, const ExitSink* xm = nullptr,
             const WallSink* wm = nullptr, const FieldSink* lf = nullptr, const OrderSink* oh = nullptr,
             const PatchSink* wp = nullptr, const isx_beam_spec* bs = nullptr, const BaffleSink* bf = nullptr,
-            const SceneSink* sc = nullptr, const ResponseSink* rs = nullptr) {
+            const SceneSink* sc = nullptr, const ResponseSink* rs = nullptr, const ViewCall* vw = nullptr) {
   Geom g;
   FateConsts fate;
   isx_config cb;
@@ -1326,7 +1379,15 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
   // (a response keeps the scene's compact slots per bin: P + 2 wall classes, two sides per baffle, port / other exits / suspended)
   const size_t resp_bins = rs ? response_bins(*rs->spec) : 0;
   const size_t resp_words = rs ? (size_t)((sc->spec->patches.n_patches + 2) + 2 * sc->spec->baffles.n_baffles + 3) * resp_bins : 0;
-  Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n, bs != nullptr, &fate, bf != nullptr, sc != nullptr, resp_words);
+  Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n, bs != nullptr, &fate, bf != nullptr, sc != nullptr,
+                       vw ? view_bins(*vw->spec) : resp_words);
+  if (vw) {
+    const isx_view_spec& v = *vw->spec;
+    p.view.out = vw->out; p.view.counts = vw->counts;
+    for (int i = 0; i < 3; ++i) { p.view.axis[i] = v.axis[i]; p.view.e1[i] = v.e1[i]; p.view.e2[i] = v.e2[i]; }
+    p.view.h = v.half_extent; p.view.fnu = (double)v.n_u; p.view.fnv = (double)v.n_v;
+    p.view.patch = v.patch; p.view.n_u = v.n_u;
+  }
   if (rs) {
     p.resp.out = rs->out;
     for (int a = 0; a < 4; ++a) p.resp.n[a] = (uint32_t)rs->spec->n[a];
@@ -1669,6 +1730,7 @@ int isx_set_option(const char* key, int64_t value) {
   if (!std::strcmp(key, "bin_cols")) { if (value < 0 || value > 2) return ISX_ERR_BAD_ARG; S.bin_cols = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "bin_slots")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.bin_slots = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "lf_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.lf_global = (int)value; return ISX_OK; }
+  if (!std::strcmp(key, "view_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.view_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "resp_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.resp_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "surface_pipeline")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.surface_pipeline = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "ray_sub")) { if (value < 0 || value > (1 << 20)) return ISX_ERR_BAD_ARG; S.ray_sub = (int)value; return ISX_OK; }
@@ -2799,6 +2861,111 @@ int isx_response_reweight(const isx_response_spec* rspec, const uint64_t* respon
         v += weight[b] * weight[b] * (h * (1.0 - F) * (1.0 - F) + (nb[b] - h) * F * F);
       }
       sigma[f] = std::sqrt(v) / L;
+    }
+  }
+  return ISX_OK;
+}
+
+int isx_view_frame(const isx_config* cfg, const isx_scene_spec* scene, int32_t patch, int32_t n_u, int32_t n_v, double half_extent,
+                   isx_view_spec* out) {
+  if (!cfg || !scene || !out) return ISX_ERR_BAD_ARG;
+  int rc = check_scene_call(cfg, scene, false);
+  if (rc) return rc;
+  if (patch < 0 || patch >= scene->patches.n_patches) return ISX_ERR_BAD_CONFIG;
+  isx_view_spec s;
+  std::memset(&s, 0, sizeof(s));
+  s.struct_size = (uint32_t)sizeof(isx_view_spec);
+  s.patch = patch; s.n_u = n_u; s.n_v = n_v; s.half_extent = half_extent;
+  const double* a = scene->patches.patch[patch].axis;
+  double unit[3];   // (the frame rule normalises its axis; the spec's axis is the patch's, bit for bit)
+  if (!beam_frame(a, unit, s.e1, s.e2)) return ISX_ERR_BAD_CONFIG;
+  for (int i = 0; i < 3; ++i) s.axis[i] = a[i];
+  rc = check_view_spec(&s, scene->patches.n_patches);
+  if (rc) return rc;
+  *out = s;
+  return ISX_OK;
+}
+
+int isx_scene_view_device(const isx_config* cfg, const isx_scene_spec* scene, const isx_view_spec* vspec, uint64_t n_rays,
+                          uint64_t seed, uint64_t first_ray, uint64_t* d_view, uint64_t* d_view_counts, uint64_t* d_scene_counts) {
+  // (what needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one)
+  if (!cfg || !scene || !vspec || !d_view || !d_view_counts || !d_scene_counts) return ISX_ERR_BAD_ARG;
+  int bad = check_scene_call(cfg, scene, false);   // (isx.h: the detector grid is ignored -- isx_scene_endstates' refusals)
+  if (bad == ISX_OK) bad = check_view_spec(vspec, scene->patches.n_patches);
+  if (bad) return bad;
+  if (!S.init) return not_initialised();
+  const SceneSink sc{scene, (unsigned long long*)d_scene_counts};
+  const ViewCall vw{vspec, (unsigned long long*)d_view, (unsigned long long*)d_view_counts};
+  return enqueue(SINK_VIEW, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                 nullptr, nullptr, nullptr, nullptr, nullptr, &sc, nullptr, &vw);
+}
+
+int isx_scene_view(const isx_config* cfg, const isx_scene_spec* scene, const isx_view_spec* vspec, uint64_t n_rays, uint64_t seed,
+                   uint64_t first_ray, uint64_t* view, isx_view_counts* view_counts, isx_scene_counts* scene_counts, isx_stats* stats) {
+  if (!cfg || !scene || !vspec || !view) return ISX_ERR_BAD_ARG;
+  int rc = check_scene_call(cfg, scene, false);
+  if (rc == ISX_OK) rc = check_view_spec(vspec, scene->patches.n_patches);
+  if (rc) return rc;
+  if (!S.init) return not_initialised();
+  // the map and, behind it, the four view counters and the 36 scene counters: one device block, one staged result
+  const size_t nb = view_bins(*vspec), nv = kViewCounters, nc = kSceneWords, bytes = (nb + nv + nc) * sizeof(unsigned long long);
+  rc = call_open(nb + nv + nc);
+  if (rc) return rc;
+  rc = zero_hist(nb + nv + nc);
+  const SceneSink sc{scene, S.d_hist + nb + nv};
+  const ViewCall vw{vspec, S.d_hist, S.d_hist + nb};
+  if (rc == ISX_OK) rc = enqueue(SINK_VIEW, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sc, nullptr, &vw);
+  if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK) {
+    fetch_result(view, nb * sizeof(unsigned long long));
+    const unsigned long long* tail = reinterpret_cast<const unsigned long long*>(S.h_pin + 64) + nb;
+    if (view_counts) std::memcpy(view_counts, tail, nv * sizeof(unsigned long long));
+    if (scene_counts) std::memcpy(scene_counts, tail + nv, nc * sizeof(unsigned long long));
+  }
+  return rc;
+}
+
+int isx_view_reweight(const isx_view_spec* vspec, const uint64_t* view, const isx_view_counts* view_counts, uint64_t launched,
+                      const double* weight, double direct_weight, double* signal, double* sigma) {
+  if (!vspec || !view || !view_counts || !weight || !signal) return ISX_ERR_BAD_ARG;
+  const int rc = check_view_spec(vspec, -1);
+  if (rc) return rc;
+  if (launched == 0) return ISX_ERR_BAD_CONFIG;
+  const size_t B = view_bins(*vspec);
+  for (size_t b = 0; b < B; ++b)
+    if (!(std::isfinite(weight[b]) && weight[b] >= 0)) return ISX_ERR_BAD_ARG;
+  if (!(std::isfinite(direct_weight) && direct_weight >= 0)) return ISX_ERR_BAD_ARG;
+  double s1 = 0, s2 = 0;
+  for (size_t b = 0; b < B; ++b) {
+    const double w = weight[b], c = (double)view[b];
+    s1 += w * c;
+    s2 += w * w * c;
+  }
+  const double nd = (double)view_counts->direct, nl = (double)launched;
+  s1 += direct_weight * nd;
+  s2 += direct_weight * direct_weight * nd;
+  *signal = s1 / nl;
+  if (sigma) {
+    const double var = s2 - s1 * s1 / nl;
+    *sigma = std::sqrt(var > 0 ? var : 0.0) / nl;
+  }
+  return ISX_OK;
+}
+
+int isx_view_weight_fov(const isx_view_spec* vspec, double half_angle_deg, double* weight) {
+  if (!vspec || !weight) return ISX_ERR_BAD_ARG;
+  const int rc = check_view_spec(vspec, -1);
+  if (rc) return rc;
+  if (!std::isfinite(half_angle_deg) || half_angle_deg < 0.0 || half_angle_deg > 90.0) return ISX_ERR_BAD_CONFIG;
+  const double s = half_angle_deg == 90.0 ? 1.0 : std::sin(half_angle_deg * 3.14159265358979323846 / 180.0);
+  const double h = vspec->half_extent, du = 2.0 * h / (double)vspec->n_u, dv = 2.0 * h / (double)vspec->n_v;
+  for (int iv = 0; iv < vspec->n_v; ++iv) {
+    const double vc = -h + ((double)iv + 0.5) * dv;
+    for (int iu = 0; iu < vspec->n_u; ++iu) {
+      const double uc = -h + ((double)iu + 0.5) * du;
+      weight[(size_t)iv * vspec->n_u + iu] = uc * uc + vc * vc <= s * s ? 1.0 : 0.0;
     }
   }
   return ISX_OK;

@@ -122,7 +122,8 @@ __device__ unsigned long long g_diag[48];   // [32..47]: the assist wave of assi
 
 enum : int { SINK_FLUX = 0, SINK_DZ = 1, SINK_DISC = 2, SINK_PERPOS = 3, SINK_LOG = 4, SINK_DISCPOS = 5, SINK_REC = 6, SINK_EXITMAP = 7, SINK_WALL = 8,
               SINK_LIGHTFIELD = 9, SINK_ORDER = 10, SINK_PATCH = 11,
-              SINK_RESPONSE = 12 };   // (isx_scene_response: no kernel is built on it -- the host's name for the scene's second sink)
+              SINK_RESPONSE = 12,     // (isx_scene_response: no kernel is built on it -- the host's name for the scene's second sink)
+              SINK_VIEW = 13 };       // (isx_scene_view: likewise, the scene's third sink)
 
 struct Work {
   uint64_t seed, first, n;    // one launch traces rays [first, first + n), n < 2^31 (a lane keeps a 31-bit offset from `first`)
@@ -2360,6 +2361,52 @@ __device__ __forceinline__ void resp_flush(const RespSink& s, const uint32_t* bl
   }
 }
 
+// ------------------------------------------------------------------ scene view (isx.h: isx_scene_view)
+// The view sink of a call as the kernel gets it (a kernel argument of its own, read where it is used -- wave-uniform words in
+// scalar registers, never a register per lane): the device map [n_v][n_u] and the four counters of isx_view_counts (+=), the
+// detector's frame, h, the two axis sizes as doubles (converted by the host: no VALU conversion whose result would stay in
+// vector registers), the selected class, n_u, and the size of the workgroup's u32 map in the LDS -- n_u * n_v, or 0: the global
+// form, one u64 add per binned ray.  The workgroup's block behind the parks is u32[4 counters | map] in both forms.
+constexpr int kViewCounters = 4, kViewBinned = 0, kViewOutside = 1, kViewBehind = 2, kViewDirect = 3;
+struct ViewSink {
+  unsigned long long* out;
+  unsigned long long* counts;
+  double axis[3], e1[3], e2[3];
+  double h, fnu, fnv;
+  int32_t patch, n_u;
+  uint32_t lds_words, pad;
+};
+// A selected ray's end -- absorbed at a wall arrival of the selected class, j its interaction count with that arrival, d the
+// direction of the segment it arrived on (Ray::v, which ray_arrive leaves as it is for an absorbed ray) -- by isx.h's rule,
+// operation for operation: IEEE double, left to right, no fma (-ffp-contract=off), the correctly rounded division and square
+// root.  The in-range test is made on the value floor() would see, as wall_bin's is: NaN and inf compare false.  Both census
+// points of the VIEW build call this and nothing else states the rule.  `out` stays a kernel argument's field: a global_atomic.
+__device__ __forceinline__ void view_record(const ViewSink& s, uint32_t* blk, uint32_t j, const V3& d) {
+  if (j == 1u) { atomicAdd(&blk[kViewDirect], 1u); return; }   // absorbed at its first interaction: straight from the source
+  const double c = (d.x * s.axis[0] + d.y * s.axis[1]) + d.z * s.axis[2];
+  if (!(c > 0.0)) { atomicAdd(&blk[kViewBehind], 1u); return; }
+  const double mag = sqrt((d.x * d.x + d.y * d.y) + d.z * d.z);
+  const double a = (d.x * s.e1[0] + d.y * s.e1[1]) + d.z * s.e1[2];
+  const double b = (d.x * s.e2[0] + d.y * s.e2[1]) + d.z * s.e2[2];
+  const double U = -(a / mag), V = -(b / mag);
+  const double fu = (U + s.h) / (2.0 * s.h) * s.fnu;
+  const double fv = (V + s.h) / (2.0 * s.h) * s.fnv;
+  if (fu >= 0.0 && fu < s.fnu && fv >= 0.0 && fv < s.fnv) {
+    const uint32_t bin = (uint32_t)(int)fv * (uint32_t)s.n_u + (uint32_t)(int)fu;
+    if (s.lds_words != 0u) atomicAdd(&blk[kViewCounters + bin], 1u);   // (binned: the sum of the map, view_flush)
+    else { global_add_u64(s.out + bin, 1ull); atomicAdd(&blk[kViewBinned], 1u); }
+  } else atomicAdd(&blk[kViewOutside], 1u);
+}
+// one flush of the workgroup's map (the LDS form; the global form has none): returns this thread's share of `binned`
+__device__ __forceinline__ uint32_t view_flush(const ViewSink& s, const uint32_t* blk, uint32_t tid, uint32_t nthr) {
+  uint32_t flushed = 0u;
+  for (uint32_t i = tid; i < s.lds_words; i += nthr) {
+    const uint32_t c = blk[kViewCounters + i];
+    if (c) { global_add_u64(s.out + i, (unsigned long long)c); flushed += c; }
+  }
+  return flushed;
+}
+
 // The segment test of isx.h's contract, operation for operation (IEEE double, left to right, no fma: -ffp-contract=off; / is the
 // correctly rounded one): the baffle that the segment p -> q strikes first -- the smallest f, on equal f the lowest index -- as
 // 2 k + side (side 0: the side the normal points to), or -1.  `skip` is the baffle of the ray's previous interaction (-1: none).
@@ -3066,12 +3113,17 @@ __device__ __forceinline__ void ray_unpack(const uint4& a, const uint4& b, const
 // wall class, or the exit with the census's own counted-below-z test.  The bin is recomputed from the ray's index there; nothing
 // is carried through the steps or the queue records.  The workgroup's u32 block, if the launch has one, lies behind the parks.
 // No exit lines, no second kernel; the step loop, the rings and the parks are the SCENE build's, unchanged.
+// VIEW (isx_scene_view; SCENE only, never with RESP): a ray absorbed at a wall arrival of the selected class is binned once, where
+// it ends, by the direction of the segment it arrived on -- view_record at RESP's two census points, with the class kept as RESP
+// keeps it.  The workgroup's u32 block -- four counters, and the map if the launch has one -- lies behind the parks.  No exit
+// lines, no second kernel, no per-ray state.
 struct FateList { const uint32_t* list; const uint32_t* count; };
 template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false, bool ORDER = false, bool PATCH = false,
-          bool BEAM = false, bool LIST = false, bool BAFFLE = false, bool RESP = false>
+          bool BEAM = false, bool LIST = false, bool BAFFLE = false, bool RESP = false, bool VIEW = false>
 __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk, const PatchTab* tab_arg = nullptr,
                                             const BeamSrc* beam_arg = nullptr, const FateList* list_arg = nullptr,
-                                            const BaffleTab* baf_arg = nullptr, const RespSink* resp_arg = nullptr) {
+                                            const BaffleTab* baf_arg = nullptr, const RespSink* resp_arg = nullptr,
+                                            const ViewSink* view_arg = nullptr) {
   constexpr bool LEAN = SURF == SURF_LAMBERT;
   static_assert(LEAN || (CH == 0 && !RESC), "the chord identity and the BRDF re-scatter pipeline are built for the Lambertian border");
   static_assert(!PATCH || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER), "wall patches: the explicit Lambertian lean path, no other sink");
@@ -3080,6 +3132,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   static_assert(!LIST || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && !PATCH && !BEAM), "ray list: the explicit Lambertian lean path of the flux pipeline");
   static_assert(!BAFFLE || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && (!PATCH || SCENE) && (!BEAM || SCENE) && !LIST), "baffles: the explicit Lambertian lean path of the flux pipeline");
   static_assert(!RESP || SCENE, "scene response: the scene's trace, nothing else");
+  static_assert(!VIEW || (SCENE && !RESP), "scene view: the scene's trace, nothing else");
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned long long* sstat = reinterpret_cast<unsigned long long*>(smem);
   Geom* g_lds = reinterpret_cast<Geom*>(sstat + 8);
@@ -3133,6 +3186,10 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   uint32_t* rblk = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(hist) + SceneLds::bytes(n_tracers));
   if constexpr (RESP) {
     for (uint32_t b = (uint32_t)tid; b < resp_arg->lds_words; b += (uint32_t)nthr) rblk[b] = 0u;
+  }
+  // VIEW: the workgroup's u32 block behind the parks -- four counters | ViewSink::lds_words of the map (none in the global form)
+  if constexpr (VIEW) {
+    for (uint32_t b = (uint32_t)tid; b < (uint32_t)kViewCounters + view_arg->lds_words; b += (uint32_t)nthr) rblk[b] = 0u;
   }
   if (tid < 8) sstat[tid] = 0ull;
   if (tid == 64) {
@@ -3321,7 +3378,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       // (the end of a ray as two flags -- lane masks in scalar registers -- instead of a status word per lane; a tracer lane's ray
       //  sits on the inner sphere unless it is fresh, so Ray::on is neither read nor written in the steps)
       bool ended = false, susp = false;
-      int eslot = 0;   // RESP: the class of the arrival that absorbed the lane's ray
+      int eslot = 0;   // RESP, VIEW: the class of the arrival that absorbed the lane's ray
       (void)eslot;
       auto arrive = [&](const V3& q, auto ph, bool record = true) {
         if (WALL && record) wall_record(wspec, hist, wall_nmap, K_INNER, r.j, q, 1u);
@@ -3331,7 +3388,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           const int cls = patch_arrive<true>(ptab, n_patch, pcnt, K_INNER, q, hp);
           st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(hp, g, r, seed, first, K_INNER, q);
           if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
-          if constexpr (RESP) { if (st == ST_ABSORBED) eslot = cls; }
+          if constexpr (RESP || VIEW) { if (st == ST_ABSORBED) eslot = cls; }
         } else st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(h, g, r, seed, first, K_INNER, q);
         if (st != 0) { run = false; ended = true; susp = st == ST_SUSPENDED; }
       };
@@ -3449,6 +3506,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           if (n_wall > 0x7fffffffu) { atomicAdd(&sstat[6], (unsigned long long)n_wall); n_wall = 0; }
           if (ORDER) order_record(ospec, hist, false, false, susp, r.j, 0.0);
           if constexpr (RESP) resp_record(*resp_arg, rblk, n_patch, n_baf, susp ? kRespSuspended : eslot, seed, first + (uint64_t)r.offset());
+          if constexpr (VIEW) { if (!susp && eslot == view_arg->patch) view_record(*view_arg, rblk, r.j, r.v); }
         }
         const unsigned long long me = __ballot(ended);
         if (me) {
@@ -3603,7 +3661,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       bool go = have;
       bool given = false;   // BAFFLE: the ray went back to the tracers from inside the step loop
       (void)given;
-      int eslot = 0;        // RESP: the slot of the interaction that absorbed the lane's ray (a wall class, or a baffle's side)
+      int eslot = 0;        // RESP, VIEW: the slot of the interaction that absorbed the lane's ray (a wall class, or a baffle's side)
       (void)eslot;
       for (;;) {
         if (go) {
@@ -3627,14 +3685,14 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
               atomicAdd(&bcnt[ks], 1u);
               st = baffle_arrive(baf, h, r, seed, first, ks >> 1, ks & 1);
               if (st == ST_ABSORBED) atomicAdd(&bcnt[2 * kMaxBaffles + ks], 1u);
-              if constexpr (RESP) eslot = kRespBaffle0 + ks;
+              if constexpr (RESP || VIEW) eslot = kRespBaffle0 + ks;
             } else {
               Hot hp = h;
               int cls = 0;
               if (kind != K_BOX) cls = patch_arrive<false>(ptab, n_patch, pcnt, kind, q, hp);
               st = ray_arrive<false, LEAN, CH, PH_DIRECT, true, SURF>(hp, g, r, seed, first, kind, q);
               if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
-              if constexpr (RESP) eslot = cls;
+              if constexpr (RESP || VIEW) eslot = cls;
             }
           } else if constexpr (PATCH) {
             Hot hp = h;
@@ -3738,6 +3796,9 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
                                exited ? (below ? kRespPort : kRespPort + 1) : st == ST_SUSPENDED ? kRespSuspended : eslot, seed,
                                first + (uint64_t)r.offset());
       }
+      if constexpr (VIEW) {   // (a baffle's side is a slot above every wall class: never the selected one)
+        if (ended && st == ST_ABSORBED && eslot == view_arg->patch) view_record(*view_arg, rblk, r.j, r.v);
+      }
       const uint32_t c_ended = (uint32_t)__popcll(__ballot(ended));
       n_ended += c_ended;
       n_exited += (uint32_t)__popcll(__ballot(exited));
@@ -3777,7 +3838,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         n_inc += (unsigned long long)__popcll(__ballot(hit0)) + (unsigned long long)__popcll(__ballot(hit1));
       }
       const unsigned long long m = (PP != 0 || WALL || ORDER || (PATCH && !SCENE)) ? 0ull : __ballot(keep);
-      if (!RESP && m) {   // (RESP: no exit lines -- the response is the build's one sink, no kernel follows)
+      if (!RESP && !VIEW && m) {   // (RESP, VIEW: no exit lines -- the response / the view is the build's one sink, no kernel follows)
         const uint32_t cnt = (uint32_t)__popcll(m);
         if (cnt > reg_left) {   // close the open region, reserve the next one (kRegion)
           if (lane == 0 && reg_id != 0xffffffffu) d_arg.rec_counts[reg_id] = kRegion - reg_left;
@@ -3893,6 +3954,17 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     __syncthreads();
   }
   if constexpr (RESP) resp_flush(*resp_arg, rblk, n_patch, n_baf, tid_end, (uint32_t)blockDim.x);   // (the global form: nothing to flush)
+  if constexpr (VIEW) {   // one flush of the workgroup's map, then of its four counters; bin_increments = binned
+    const uint32_t flushed = view_flush(*view_arg, rblk, tid_end, (uint32_t)blockDim.x);
+    if (flushed) atomicAdd(&rblk[kViewBinned], flushed);
+    __syncthreads();
+    if (tid_end < (uint32_t)kViewCounters) {
+      const uint32_t c = rblk[tid_end];
+      if (c) global_add_u64(view_arg->counts + tid_end, (unsigned long long)c);
+      if (tid_end == (uint32_t)kViewBinned && c) atomicAdd(&sstat[5], (unsigned long long)c);
+    }
+    __syncthreads();
+  }
   if constexpr (BAFFLE) {   // one flush of the workgroup's counters (the thread index rebuilt, as the beam kernel's)
     uint32_t t3 = tid_end;
     asm volatile("" : "+v"(t3));
@@ -3977,6 +4049,14 @@ extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((am
 isx_trace_assist_scene_response_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab, const BeamSrc beam, const BaffleTab baf,
                                        const RespSink resp) {
   assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true, true>(g, d, wk, &tab, &beam, nullptr, &baf, &resp);
+}
+// the scene view (isx_scene_view): the scene kernel with one add per ray absorbed on the selected wall class -- the direction it
+// arrived from, binned in the detector's frame (view_record) -- and no exit lines; the sink is a seventh argument
+extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_SCENE_WAVES, ISX_SCENE_WAVES)))
+isx_trace_assist_scene_view_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab, const BeamSrc beam, const BaffleTab baf,
+                                   const ViewSink view) {
+  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true, false, true>(g, d, wk, &tab, &beam, nullptr, &baf, nullptr,
+                                                                                                   &view);
 }
 // the flux pipeline behind the fate scan: isx_trace_assist_kernel on the rays of a list; the list is a fourth argument
 extern "C" __global__ void ISX_ASSIST_ATTR

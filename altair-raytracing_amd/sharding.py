@@ -302,3 +302,21 @@ def scene_response_sharded(trace: Callable, cfg, scene, rspec, n_total: int, see
     absorbed[4, 2] uint64, census dict) -- identical on every rank."""
     return fluxmap_scene_sharded(lambda c, sp, count, sd, first: trace(c, sp, rspec, count, sd, first), cfg, scene, n_total, seed,
                                  first_ray, device)
+
+
+def scene_view_sharded(trace: Callable, cfg, scene, vspec, n_total: int, seed: int, first_ray: int = 0, device=None):
+    """The view of a wall detector of a scene (altair_raytracing_amd.scene_view) ray-sharded: this rank's contiguous shard through
+    `trace(cfg, scene, vspec, count, seed, first) -> (view, view_counts, scene_counts, stats)`, then ONE SUM all-reduce that
+    carries the map, the 4 view counters, the 36 scene counters and the census -- fluxmap_scene_sharded with the map and its four
+    counters in the histogram's place.  Returns (view[n_v, n_u] uint64, view_counts[4] uint64 (binned, outside, behind, direct),
+    patch_arrivals[10] uint64, patch_absorbed[10] uint64, baffle arrivals[4, 2] uint64, baffle absorbed[4, 2] uint64, census
+    dict) -- identical on every rank."""
+    shape = []
+
+    def one(c, sp, count, sd, first):
+        view, vc, cnt, st = trace(c, sp, vspec, count, sd, first)
+        shape.append(view.shape)
+        return np.concatenate([np.asarray(view, dtype=np.uint64).reshape(-1), vc.words()]), cnt, st
+
+    out = fluxmap_scene_sharded(one, cfg, scene, n_total, seed, first_ray, device)
+    return (out[0][:-4].reshape(shape[0]), out[0][-4:]) + tuple(out[1:])

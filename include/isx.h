@@ -194,6 +194,8 @@ int isx_last_kernel_ms(double* single_ms, double* trace_ms, double* bin_ms);
  *                  one global atomic add per ray; 1: the global form for every field (a diagnostic)
  *   "resp_global"  0 (default): isx_scene_response keeps a response that fits in the workgroup's LDS there and takes one global
  *                  atomic add per ended ray for a larger one; 1: the global form for every spec (a diagnostic)
+ *   "view_global"  0 (default): isx_scene_view keeps a map that fits in the workgroup's LDS there and takes one global atomic
+ *                  add per binned ray for a larger one; 1: the global form for every spec (a diagnostic)
  *   "bin_block", "bin_blocks_per_cu"  shape of round 2's binning kernel (0 workgroups per CU = what is resident)
  *                  (round 5: "assist_block" 0 = the default again -- 768 threads, 256 for launches below 1e6 rays, 512 for the lobe /
  *                  rough-specular kernels; "rays_per_lane" > 0 sizes every grid for that many rays per tracer lane, 0 = by launch
@@ -890,8 +892,9 @@ int isx_fluxmap_baffle_device(const isx_config* cfg, const isx_baffle_spec* spec
  * same codes and whether or not a device is present: everything isx_fluxmap_beam refuses of `beam`, isx_fluxmap_baffle of `baffles`
  * (the detector grid included, for the two flux-map calls) and isx_wall_patches of `patches` -- each nested struct_size must be
  * right as well as the outer one.  ISX_ERR_BAD_ARG: a NULL pointer (start_point, start_dir, last_baffle, last_class, counts and
- * stats excepted).  Out of scope: a scene for the other sinks (exit maps, wall map, light field, order histograms, disc sweeps),
- * the chord mode, the other borders and the BRDF source.
+ * stats excepted).  Out of scope: a scene for the other sinks (exit maps, wall map, light field, order histograms, disc sweeps;
+ * the fates over the source's sample space are isx_scene_response, the directions a wall detector sees isx_scene_view), the chord
+ * mode, the other borders and the BRDF source.
  */
 typedef struct isx_scene_spec {
   uint32_t struct_size;        /* sizeof(isx_scene_spec), set by isx_default_scene_spec() */
@@ -1001,6 +1004,107 @@ int isx_scene_response_device(const isx_config* cfg, const isx_scene_spec* scene
  */
 int isx_response_reweight(const isx_response_spec* rspec, const uint64_t* response, const double* weight /*[B]*/,
                           double* fraction /*[21]*/, double* sigma /*[21]*/);
+
+/*
+ * Scene view: what a wall detector sees -- the rays a wall class of a scene absorbs, binned over the direction they arrive from,
+ * in the detector's own frame.  Baffles are placed by this quantity (the detector must not see the lamp nor the first-strike spot,
+ * and should see evenly lit wall everywhere else), and the reading of a hooded photodiode or of a detector behind a field-of-view
+ * stop is this map weighted by angle of incidence: isx_view_reweight, a host-side reweighting.
+ *
+ * The ray histories are those of isx_fluxmap_scene / isx_scene_endstates for the same (cfg, scene, seed, ray index): nothing of a
+ * history changes.  A ray is SELECTED if and only if its fate slot, as isx_scene_response defines it, equals vspec->patch: it is
+ * ISX_RAY_ABSORBED at a wall arrival of that class.  For every selected ray, with n_points and d = direction as
+ * isx_scene_endstates reports them (d is NOT a unit vector: the tracers report the un-normalised last chord), h = half_extent,
+ * in this order, in IEEE double, every expression left to right as written, no fma, / and sqrt correctly rounded:
+ *
+ *       n_points == 2                      : direct += 1, nothing else
+ *       c = (d.x*axis[0] + d.y*axis[1]) + d.z*axis[2]
+ *       c > 0.0 is false                   : behind += 1, nothing else            (NaN included)
+ *       mag = sqrt((d.x*d.x + d.y*d.y) + d.z*d.z)
+ *       a = (d.x*e1[0] + d.y*e1[1]) + d.z*e1[2] ;  b likewise with e2
+ *       U = -(a / mag) ;  V = -(b / mag)           (the direction the light CAME from, seen from the detector)
+ *       fu = (U + h) / (2.0 * h) * n_u ; iu = (int)floor(fu)                     (same with V, n_v -> iv)
+ *       0 <= iu < n_u and 0 <= iv < n_v    : view[iv * n_u + iu] += 1, binned += 1
+ *       else (NaN / inf included)          : outside += 1
+ *
+ * `direct` is counted and not binned: a ray absorbed at its first interaction came straight from the source, its direction is the
+ * source's own sample, known analytically -- and the scene's kernel keeps none for it (a fresh ray parked at its first wall point
+ * carries a marker where its direction was; recomputing the start could differ in the last bit where the boundary search
+ * re-normalises).  `behind`: a ray that arrives from behind the plane the frame's axis is the normal of (a wide cap, or a frame
+ * that is not the patch's own).
+ *
+ * In direction-cosine space the cos(theta) of the flux and the solid angle cancel, as for the exit maps: an evenly lit Lambertian
+ * interior gives a flat map inside the unit disc, and the radiance the detector sees is proportional to
+ * count / (N * du * dv), du = 2 h / n_u, dv = 2 h / n_v.
+ *
+ * For every call: binned + outside + behind + direct == counts.patch_absorbed[patch]; view sums to binned;
+ * stats.bin_increments == binned; the 36 scene counters and every other field of stats except t_kernel_ms are isx_fluxmap_scene's
+ * for the same arguments.  No result depends on any isx_set_option switch nor on how a job is cut into calls.  cfg->hit_line_mode
+ * and the detector-grid fields of cfg are ignored and never a reason for refusal.  One route whatever the switches say:
+ * isx_trace_assist_scene_view_kernel -- the scene's trace kernel with one add per binned ray, where the census is taken; it writes
+ * no exit lines and no kernel follows it.  A map small enough is kept as u32 words in the workgroup's LDS and flushed once, a larger
+ * one (or any, with "view_global" 1) takes one global u64 add per binned ray.
+ *
+ * Refused, whether or not a device is present: everything isx_scene_endstates refuses of cfg and scene, with its codes;
+ * ISX_ERR_BAD_CONFIG: struct_size != sizeof(isx_view_spec), a non-zero reserved field, patch outside 0 .. n_patches - 1 (so a scene
+ * without patches), n_u or n_v outside 1..ISX_VIEW_MAX_AXIS, n_u * n_v > ISX_VIEW_MAX_BINS, half_extent not finite or outside
+ * (0, 1], a non-finite frame component, (axis, e1, e2) not orthonormal to 1e-12 by the beam contract's test;
+ * ISX_ERR_BAD_ARG: a NULL cfg, scene, vspec or view (device form: d_view, d_view_counts, d_scene_counts).  Without a HIP device:
+ * ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT (as isx_fluxmap_scene).
+ * Out of scope: more than one patch per call, the position on the patch, views from baffle sides, the isx_macro command line, scenes
+ * for the remaining sinks.
+ */
+#define ISX_VIEW_MAX_AXIS 1024
+#define ISX_VIEW_MAX_BINS 65536
+typedef struct isx_view_spec {
+  uint32_t struct_size;      /* sizeof(isx_view_spec), set by isx_view_frame(); a spec of another size is refused */
+  uint32_t reserved0;        /* 0 */
+  int32_t patch;             /* 0 .. scene->patches.n_patches - 1: the detector */
+  int32_t n_u, n_v;          /* 1 .. ISX_VIEW_MAX_AXIS, n_u * n_v <= ISX_VIEW_MAX_BINS */
+  int32_t reserved1;         /* 0 */
+  double axis[3], e1[3], e2[3];  /* the detector's outward normal and its two in-plane axes: USED AS GIVEN */
+  double half_extent;        /* h in (0, 1]: the map covers [-h, h]^2 of the direction cosines */
+} isx_view_spec;             /* 104 bytes */
+typedef struct isx_view_counts { uint64_t binned, outside, behind, direct; } isx_view_counts;
+
+/* The spec for a patch of a scene: axis = scene->patches.patch[patch].axis as given, e1 and e2 by isx_beam_cone's frame rule about
+ * that axis.  Host only, no GPU needed.  Refuses what isx_scene_view refuses (ISX_ERR_BAD_ARG: a NULL cfg, scene or out). */
+int isx_view_frame(const isx_config* cfg, const isx_scene_spec* scene, int32_t patch, int32_t n_u, int32_t n_v, double half_extent,
+                   isx_view_spec* out);
+/* Blocking: view[n_v * n_u], view_counts and scene_counts (host, zeroed by the callee; view_counts, scene_counts and stats may be
+ * NULL). */
+int isx_scene_view(const isx_config* cfg, const isx_scene_spec* scene, const isx_view_spec* vspec, uint64_t n_rays, uint64_t seed,
+                   uint64_t first_ray, uint64_t* view, isx_view_counts* view_counts, isx_scene_counts* scene_counts, isx_stats* stats);
+/* ACCUMULATES (+=) into d_view [n_v * n_u], d_view_counts (4 words, isx_view_counts' layout) and d_scene_counts (36 words,
+ * isx_scene_counts' layout; none may be NULL) on the library's stream and returns after enqueueing; isx_sync() / isx_take_stats()
+ * as for isx_fluxmap_scene_device. */
+int isx_scene_view_device(const isx_config* cfg, const isx_scene_spec* scene, const isx_view_spec* vspec, uint64_t n_rays,
+                          uint64_t seed, uint64_t first_ray, uint64_t* d_view, uint64_t* d_view_counts /*[4]*/,
+                          uint64_t* d_scene_counts /*[36]*/);
+/*
+ * The reading of a detector whose angular response is weight[b] in bin b of the map (and direct_weight for the rays that came
+ * straight from the source), from one isx_scene_view result of `launched` rays.  Host only, no GPU needed.  The sums in
+ * increasing b:
+ *
+ *       S1 = sum over b of weight[b] * view[b]   + direct_weight * direct
+ *       S2 = sum over b of weight[b]^2 * view[b] + direct_weight^2 * direct
+ *       signal = S1 / launched
+ *       sigma  = sqrt(S2 - S1^2 / launched) / launched
+ *
+ * -- isx_order_reweight's estimator (a negative rounding residue under the root counts as 0).  With every weight 1, signal is
+ * (binned + direct) / launched exactly as the division gives it.  sigma may be NULL; view_counts gives `direct` (its other fields are not read).  ISX_ERR_BAD_ARG: a NULL vspec, view,
+ * view_counts, weight or signal, a weight (direct_weight included) that is negative or not finite; ISX_ERR_BAD_CONFIG: a spec
+ * isx_scene_view refuses (the patch index is not looked at: no scene is given), launched == 0.
+ */
+int isx_view_reweight(const isx_view_spec* vspec, const uint64_t* view, const isx_view_counts* view_counts, uint64_t launched,
+                      const double* weight /*[n_v * n_u]*/, double direct_weight, double* signal, double* sigma);
+/*
+ * A field-of-view stop as a weight for isx_view_reweight: weight[iv * n_u + iu] = 1.0 if the bin's centre (Uc, Vc) has
+ * Uc^2 + Vc^2 <= s^2, else 0.0; Uc = -h + (iu + 0.5) * (2 h / n_u), Vc = -h + (iv + 0.5) * (2 h / n_v),
+ * s = sin(half_angle_deg * pi / 180), with 90 degrees mapped to exactly 1.  Host only, no GPU needed.  ISX_ERR_BAD_ARG: a NULL
+ * vspec or weight; ISX_ERR_BAD_CONFIG: a spec isx_scene_view refuses (as above), a half angle outside [0, 90] or not finite.
+ */
+int isx_view_weight_fov(const isx_view_spec* vspec, double half_angle_deg, double* weight /*[n_v * n_u]*/);
 
 /*
  * Series driver (sweepSeries, fluxAtObserverOptimize.C:892-921 / fluxAtObserverFast.C:1641-1673):
