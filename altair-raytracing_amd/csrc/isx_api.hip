@@ -46,8 +46,9 @@ struct State {
   uint32_t* d_rec_counts[kRecBufs] = {nullptr, nullptr, nullptr};
   size_t cap_regions[kRecBufs] = {0, 0, 0};
   // fate scan: the rays of a chunk that the scan leaves to the trace kernel, 4 B per ray of the largest chunk
-  uint32_t* d_list = nullptr;
-  size_t cap_list = 0;
+  // (one list per workspace: the list of chunk k is read by its trace kernel while the scan of a later chunk may already run)
+  uint32_t* d_list[kRecBufs] = {nullptr, nullptr, nullptr};
+  size_t cap_list[kRecBufs] = {0, 0, 0};
   unsigned long long fate_launches = 0;   // isx_fate_scan_kernel launches enqueued since isx_init (isx_fate_scan_launches)
   int fate_scan = -1;                     // 0 off, 1 on wherever eligible, -1 (default) automatic: fate_scan_auto()
   // overlap > 1: a flux-map call is cut into that many chunks and the binning kernel of chunk k runs on a second stream
@@ -55,6 +56,20 @@ struct State {
   int overlap = 0;
   int overlap_trace_streams = 1;          // 2: consecutive trace kernels alternate between two streams (chunk k+1 fills the tail of chunk k)
   hipStream_t stream2 = nullptr, stream3 = nullptr;
+  // call overlap: an enqueued flux map (isx_fluxmap_device, ROUTE_FLUX_PIPE, explicit bounces) puts its
+  // counter zeroing, fate scan and trace kernel on a trace stream (stream2; with call_overlap_streams = 2 consecutive chunks
+  // alternate between stream2 and stream3) and only its binning kernel on `stream`, so that the next call's scan and trace fill the
+  // launch tails of this one.  Chunk s (counted over calls: call_rot) uses workspace and fate list s mod kRecBufs, and its trace
+  // waits for ev_free[s mod kRecBufs], recorded behind the last kernel that read that workspace.  (Its counter block is the
+  // ring's next, as everywhere: a block comes round again 256 launches later, behind the same waits.)  trace_open: the trace
+  // streams hold work that `stream` has not been joined behind (trace_join()).
+  int call_overlap = -1;                  // 0 off, 1 on wherever eligible, -1 (default) automatic: the same
+  int call_overlap_streams = 2;
+  unsigned call_rot = 0;
+  bool trace_open = false;
+  hipEvent_t ev_free[kRecBufs] = {nullptr, nullptr, nullptr};
+  bool free_set[kRecBufs] = {false, false, false};
+  hipEvent_t ev_join[3] = {nullptr, nullptr, nullptr};   // [0], [1]: tails of stream2 / stream3; [2]: where `stream` stood when they opened
   int pipeline = 1;                       // 1 (default): trace kernel -> HBM -> binning kernel (lean flux map); 0: fused kernel
   uint64_t pipe_chunk = 1ull << 26;       // rays per trace/bin pair (3.4 GB of exit-line workspace at most)
   // work-queue counters of the launches (Work::ctr): a ring of Q_WORDS-word blocks, one per launch, zeroed on the stream
@@ -270,11 +285,13 @@ bool same_grid(const isx_config& a, const isx_config& b) {
          a.exit_port_z == b.exit_port_z;
 }
 
+int sync_all();   // (below, with the call overlap's other helpers)
+
 int ensure_tables(const isx_config* c) {
   if (S.have_tab && same_grid(S.tab_cfg, *c)) return ISX_OK;
   std::vector<double> table, rowtab, coltab;
   host_tables(c, table, rowtab, coltab);
-  HIPCHK(hipStreamSynchronize(S.stream));
+  if (sync_all()) return ISX_ERR_HIP;
   if (table.size() > S.cap_bins) {
     if (S.d_table) HIPCHK(hipFree(S.d_table));
     HIPCHK(hipMalloc(&S.d_table, table.size() * sizeof(double)));
@@ -344,11 +361,52 @@ int next_ctr(hipStream_t stream, uint32_t** ctr) {
   return ISX_OK;
 }
 
+// Call overlap (State::call_overlap).  trace_join(): `stream` waits for what the trace streams hold; every entry but an
+// overlapped isx_fluxmap_device begins with it, so that a caller who knows one stream sees what it saw before.  trace_begin(): the
+// trace streams wait for what `stream` holds now -- whatever ran before an overlapped sequence (another route through workspace 0,
+// the caller's own work) comes first, and with it every earlier user of the workspaces.  sync_all(): nothing is left in flight.
+int pooled_event(hipEvent_t* e) {
+  if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  return ISX_OK;
+}
+int trace_join() {
+  if (!S.trace_open) return ISX_OK;
+  const hipStream_t ts[2] = {S.stream2, S.stream3};
+  for (int i = 0; i < 2; ++i) {
+    if (!ts[i]) continue;
+    if (pooled_event(&S.ev_join[i])) return ISX_ERR_HIP;
+    HIPCHK(hipEventRecord(S.ev_join[i], ts[i]));
+    HIPCHK(hipStreamWaitEvent(S.stream, S.ev_join[i], 0));
+  }
+  S.trace_open = false;
+  return ISX_OK;
+}
+int trace_begin() {
+  if (S.trace_open) return ISX_OK;
+  if (!S.stream2) HIPCHK(hipStreamCreateWithFlags(&S.stream2, hipStreamNonBlocking));
+  if (!S.stream3) HIPCHK(hipStreamCreateWithFlags(&S.stream3, hipStreamNonBlocking));
+  if (pooled_event(&S.ev_join[2])) return ISX_ERR_HIP;
+  HIPCHK(hipEventRecord(S.ev_join[2], S.stream));
+  HIPCHK(hipStreamWaitEvent(S.stream2, S.ev_join[2], 0));
+  HIPCHK(hipStreamWaitEvent(S.stream3, S.ev_join[2], 0));
+  for (int b = 0; b < State::kRecBufs; ++b) S.free_set[b] = false;
+  S.trace_open = true;
+  return ISX_OK;
+}
+int sync_all() {
+  const int rc = trace_join();
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(S.stream));
+  if (S.stream2) HIPCHK(hipStreamSynchronize(S.stream2));
+  if (S.stream3) HIPCHK(hipStreamSynchronize(S.stream3));
+  return ISX_OK;
+}
+
 // pinned staging buffer of at least `bytes` bytes: [0, 64) the census words, [64, ...) a call's result
 int ensure_pin(size_t bytes) {
   bytes += 64 + 4096;   // (+ the last 4 KB: upload_aux's slot for a short list)
   if (bytes > S.cap_pin) {
-    HIPCHK(hipStreamSynchronize(S.stream));
+    if (sync_all()) return ISX_ERR_HIP;
     if (S.h_pin) HIPCHK(hipHostFree(S.h_pin));
     S.h_pin = nullptr; S.cap_pin = 0;
     const size_t cap = bytes < (1u << 18) ? (1u << 18) : bytes;
@@ -379,6 +437,9 @@ constexpr uint64_t kLaunchMax = 1ull << 30;
 
 // the disc list of the current isx_disc_sweep call as isx_bin_discs_kernel wants it (upload_discs_clustered below)
 struct DiscClusters { size_t n = 0, off_ordered = 0, off_clusters = 0, off_perm = 0; int n_clusters = 0; } g_disc_clusters;
+
+// the call being enqueued is isx_fluxmap_device's: the caller collects later, so the next call's trace can start under this one's tail
+bool g_device_call = false;
 
 struct PerPos { uint64_t map_first = 0, rays_per_group = 0; int fold = 1; const double* d_table = nullptr; double width = 0; };
 struct LogSink { double* rec = nullptr; unsigned long long* count = nullptr; uint64_t cap = 0; };
@@ -820,6 +881,7 @@ struct Plan {
   bool compat_lines = false;    // isx_compat_lines_kernel runs between the two (ISX_HITLINE_ORIGIN_COMPAT)
   bool binning = true;          // false: bin_mode 2, a diagnostic: trace only
   bool overlap = false;         // chunks alternate over two streams (S.overlap)
+  bool call_overlap = false;    // the chunks' scans and traces go to a trace stream, ahead of the earlier binning (S.call_overlap)
   size_t slot_doubles = 6;      // doubles per exit record in the workspace
   PatchFn patch_fn = nullptr;   // SINK_PATCH: the kernel (it takes the patches as a fourth argument: patch_tab) instead of fn
   PatchTab patch_tab{};
@@ -1000,6 +1062,9 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     p.compat_lines = compat && d.bin_mode != 2;
     p.binning = d.bin_mode != 2;
     p.overlap = S.overlap > 1 && d.bin_mode == 1 && n >= (uint64_t)S.overlap * 65536;
+    // call overlap: scheduling only.  Enqueued plain flux maps with explicit bounces (chord mode keeps the one stream it had: its
+    // launch tails have not been measured); never together with `overlap` > 1, whatever the call's size
+    p.call_overlap = g_device_call && S.call_overlap != 0 && S.overlap <= 1 && !chord && !beam && !baffle && !scene;
     // the fate scan in front of the headline trace kernel (fate_consts: pencil, Lambertian border, explicit bounces, first strike
     // on the mirror patch): scheduling only -- anything else takes the kernels above whatever the option says
     if (!beam && fate && fate->ok && p.fn == isx_trace_assist_kernel && !p.overlap &&
@@ -1169,12 +1234,13 @@ int mark(hipStream_t stream, size_t* at) {
   *at = S.ev_used++;
   return hip_rc(hipEventRecord(S.ev_pool[*at], stream));
 }
-int span(int kind, size_t* from) {
+int span_on(hipStream_t stream, int kind, size_t* from) {   // (... on the stream that holds the kernel and mark *from)
   const size_t a = *from;
-  const int rc = mark(S.stream, from);
+  const int rc = mark(stream, from);
   if (rc == ISX_OK) S.spans.push_back({a, *from, kind});
   return rc;
 }
+int span(int kind, size_t* from) { return span_on(S.stream, kind, from); }
 
 // ROUTE_FUSED and ROUTE_ASSIST: launches of at most kLaunchMax rays, one span
 int run_single(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
@@ -1201,8 +1267,7 @@ int run_single(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
 // workspace `buf` of the two-kernel pipeline with room for `regions` regions of kRegion 6-double slots and their line counts
 int ensure_regions(size_t regions, int buf) {
   if (regions > S.cap_regions[buf]) {
-    HIPCHK(hipStreamSynchronize(S.stream));
-    if (S.stream2) HIPCHK(hipStreamSynchronize(S.stream2));
+    if (sync_all()) return ISX_ERR_HIP;
     if (S.d_rec[buf]) HIPCHK(hipFree(S.d_rec[buf]));
     if (S.d_rec_counts[buf]) HIPCHK(hipFree(S.d_rec_counts[buf]));
     S.d_rec[buf] = nullptr; S.d_rec_counts[buf] = nullptr; S.cap_regions[buf] = 0;
@@ -1216,12 +1281,12 @@ int ensure_regions(size_t regions, int buf) {
 // lines in it, and a launch cannot have more lines than rays (isx_kernels.hpp: kRegion)
 // list: ... and the fate scan's ray list, 4 B per ray of the largest chunk so far (grown, never shrunk)
 int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles, bool list = false) {
-  if (list && rays > S.cap_list) {
-    HIPCHK(hipStreamSynchronize(S.stream));
-    if (S.d_list) HIPCHK(hipFree(S.d_list));
-    S.d_list = nullptr; S.cap_list = 0;
-    HIPCHK(hipMalloc(&S.d_list, rays * sizeof(uint32_t)));
-    S.cap_list = rays;
+  if (list && rays > S.cap_list[buf]) {
+    if (sync_all()) return ISX_ERR_HIP;
+    if (S.d_list[buf]) HIPCHK(hipFree(S.d_list[buf]));
+    S.d_list[buf] = nullptr; S.cap_list[buf] = 0;
+    HIPCHK(hipMalloc(&S.d_list[buf], rays * sizeof(uint32_t)));
+    S.cap_list[buf] = rays;
   }
   return ensure_regions((rays / (kRegion - 63) + waves + 1) * slot_doubles / 6 + 1, buf);   // (capacity is counted in 6-double slots)
 }
@@ -1255,8 +1320,10 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     dt = db;
   }
   // one trace launch on `st` and the binning of its `cnt` rays from `off` on `sb`, through workspace `buf`.  t: one stream, each
-  // kernel a span of its own from mark *t on; nullptr: an event hands the exit records over from st to sb
-  auto launch_pair = [&](uint64_t off, uint64_t cnt, int buf, hipStream_t st, hipStream_t sb, size_t* t) -> int {
+  // kernel a span of its own from mark *t on; nullptr: an event hands the exit records over from st to sb.  split (call overlap):
+  // both -- *t is a mark on st, the trace span and isx_compat_lines_kernel lie on st, the event that ends them hands over to sb, and
+  // the binning span lies on sb behind it
+  auto launch_pair = [&](uint64_t off, uint64_t cnt, int buf, hipStream_t st, hipStream_t sb, size_t* t, bool split) -> int {
     if (cnt > kLaunchMax) return ISX_ERR_TOO_LARGE;   // (cannot happen: pipeline_chunk <= 2^26)
     // (work units of the binning kernel: quarter regions of 256 exit lines; sixteenths -- 64 lines, one batch -- for a small
     //  launch, whose few thousand lines then spread over as many waves as there are batches)
@@ -1274,31 +1341,36 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
       // trip; both kernels lie in the trace span.
       FateScan fs;
       fs.f = p.fate; fs.seed = w.seed; fs.first = w.first; fs.n = (uint32_t)cnt; fs.pad = 0;
-      fs.list = S.d_list; fs.ctr = w.ctr; fs.stats = w.stats;
+      fs.list = S.d_list[buf]; fs.ctr = w.ctr; fs.stats = w.stats;
       const uint64_t want = (cnt + 4ull * kScanBlock - 1) / (4ull * kScanBlock), full = (uint64_t)S.cu_count * 8ull;
       const int sgrid = S.grid_blocks > 0 ? S.grid_blocks : (int)std::max<uint64_t>(1, std::min(want, full));
       hipLaunchKernelGGL(isx_fate_scan_kernel, dim3(sgrid), dim3(kScanBlock), 0, st, fs);
       HIPCHK(hipGetLastError());
       ++S.fate_launches;
-      const FateList fl{S.d_list, w.ctr + Q_LIST};
+      const FateList fl{S.d_list[buf], w.ctr + Q_LIST};
       hipLaunchKernelGGL(p.list_fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w, fl);
     }
     else hipLaunchKernelGGL(p.fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w);
     HIPCHK(hipGetLastError());
     size_t traced;
-    if (t) r = span(1, t);
+    if (t) r = span_on(st, 1, t);
     else if ((r = mark(st, &traced)) == ISX_OK) r = hip_rc(hipStreamWaitEvent(sb, S.ev_pool[traced], 0));
     if (r) return r;
     if (p.compat_lines) {   // ISX_HITLINE_ORIGIN_COMPAT: the lines the binning kernel is to see (isx_compat_lines_kernel)
-      hipLaunchKernelGGL(isx_compat_lines_kernel, dim3(S.cu_count * 8), dim3(256), 0, sb, S.d_rec[buf], S.d_rec_counts[buf], w.ctr);
+      hipLaunchKernelGGL(isx_compat_lines_kernel, dim3(S.cu_count * 8), dim3(256), 0, split ? st : sb, S.d_rec[buf], S.d_rec_counts[buf], w.ctr);
       HIPCHK(hipGetLastError());
+      if (split && (r = span_on(st, 2, t))) return r;
+    }
+    if (split) {
+      HIPCHK(hipStreamWaitEvent(sb, S.ev_pool[*t], 0));
+      if (p.binning && (r = mark(sb, t))) return r;
     }
     if (p.binning) {
       // (every writing wave of the trace kernel leaves an open region: one per workgroup with an assist wave)
       const uint64_t writers = p.assist ? (uint64_t)tgrid : (uint64_t)tgrid * (uint64_t)(p.block / 64);
       hipLaunchKernelGGL(p.bin, dim3(bin_grid(p, cnt, w.pad, writers, bres)), dim3(p.bblock), p.lds_bin, sb, db, w);
       HIPCHK(hipGetLastError());
-      if (t && (r = span(2, t))) return r;
+      if (t && (r = span_on(sb, 2, t))) return r;
     }
     return ISX_OK;
   };
@@ -1323,7 +1395,7 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
       const int buf = k % State::kRecBufs;
       const hipStream_t st = (S.overlap_trace_streams == 2 && (k & 1)) ? S.stream3 : S.stream;
       if (k >= State::kRecBufs) HIPCHK(hipStreamWaitEvent(st, S.ev_pool[binned[buf]], 0));
-      rc = launch_pair(off, std::min(n - off, chunk), buf, st, S.stream2, nullptr);
+      rc = launch_pair(off, std::min(n - off, chunk), buf, st, S.stream2, nullptr, false);
       if (rc == ISX_OK) rc = mark(S.stream2, &binned[buf]);
       if (rc) return rc;
     }
@@ -1333,11 +1405,34 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     return ISX_OK;
   }
   const uint64_t chunk = std::min(n, S.pipe_chunk);
+  if (p.call_overlap) {
+    // ---- call overlap: the chunk's counter zeroing, scan, trace (and compat lines) on a trace stream, its binning kernel on the
+    // caller's stream behind the event that ends them.  The trace stream does not wait for the binning of the chunk before --
+    // the caller's histogram is the binning kernel's alone -- so the scan and trace of the next chunk, of this call or the
+    // next, run under the tails of this one's kernels.  All kRecBufs workspaces are sized at once: a workspace that grew in the
+    // middle of a sequence would stop it.
+    const size_t waves = (size_t)pick_grid(p, chunk, tres) * (p.block / 64);
+    for (int b = 0; b < State::kRecBufs && rc == ISX_OK; ++b) rc = ensure_pipeline((size_t)chunk, waves, b, p.slot_doubles, p.list_fn != nullptr);
+    if (rc == ISX_OK) rc = trace_begin();
+    for (uint64_t off = 0; off < n && rc == ISX_OK; off += chunk, ++S.call_rot) {
+      const int buf = (int)(S.call_rot % State::kRecBufs);
+      const hipStream_t st = (S.call_overlap_streams == 2 && (S.call_rot & 1)) ? S.stream3 : S.stream2;
+      if (S.free_set[buf]) HIPCHK(hipStreamWaitEvent(st, S.ev_free[buf], 0));
+      size_t t;
+      rc = mark(st, &t);
+      if (rc == ISX_OK) rc = launch_pair(off, std::min(n - off, chunk), buf, st, S.stream, &t, true);
+      if (rc == ISX_OK) rc = pooled_event(&S.ev_free[buf]);
+      if (rc) return rc;
+      HIPCHK(hipEventRecord(S.ev_free[buf], p.binning ? S.stream : st));   // (behind the last kernel that reads the workspace)
+      S.free_set[buf] = true;
+    }
+    return rc;
+  }
   rc = ensure_pipeline((size_t)chunk, (size_t)pick_grid(p, chunk, tres) * (p.block / 64), 0, p.slot_doubles, p.list_fn != nullptr); if (rc) return rc;
   size_t t;
   rc = mark(S.stream, &t);
   for (uint64_t off = 0; off < n && rc == ISX_OK; off += chunk)
-    rc = launch_pair(off, std::min(n - off, chunk), 0, S.stream, S.stream, &t);
+    rc = launch_pair(off, std::min(n - off, chunk), 0, S.stream, S.stream, &t, false);
   return rc;
 }
 
@@ -1403,11 +1498,13 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
     if (p.lds_bin > S.lds_limit) return ISX_ERR_BAD_CONFIG;   // (isx.h: a grid whose tables do not fit the binning kernels' LDS)
     p.beam = beam_source(*bs);
   }
+  if (!p.call_overlap && (rc = trace_join())) return rc;   // (anything else runs on the caller's stream, behind all of an overlapped sequence)
   return p.route == ROUTE_FUSED || p.route == ROUTE_ASSIST ? run_single(p, g, d, wk) : run_pipeline(p, g, d, wk);
 }
 
 // device copy of a caller's detector / disc list in the pooled buffer (no hipMalloc/hipFree per call)
 int upload_aux(const double* host, size_t n_doubles) {
+  if (trace_join()) return ISX_ERR_HIP;
   if (n_doubles > S.cap_aux) {
     HIPCHK(hipStreamSynchronize(S.stream));
     if (S.d_aux) HIPCHK(hipFree(S.d_aux));
@@ -1501,6 +1598,9 @@ int ensure_hist(size_t nb) {
 int collect_stats(isx_stats* out) {
   // the census through the pinned staging buffer: copy and re-zero enqueued, ONE synchronisation (it also covers a result staged
   // by stage_result()); a call that finds nothing enqueued since the last collection has nothing to wait for
+  // (call overlap: the caller's stream is joined behind the trace streams first -- their kernels add to the same census words, and
+  //  the words are zeroed behind both)
+  if (trace_join()) return ISX_ERR_HIP;
   if (!S.pending && S.spans.empty() && !out) return ISX_OK;
   int rcp = ensure_pin(0);
   if (rcp) return rcp;
@@ -1566,8 +1666,8 @@ int run_injected(const Plan& p, const DetGrid& d, const double* lines, uint64_t 
     at += counts[r];
   }
   if (at != n) return ISX_ERR_BAD_ARG;
-  // (blocking copies from pageable memory: whatever the stream held has completed first)
-  HIPCHK(hipStreamSynchronize(S.stream));
+  // (blocking copies from pageable memory: whatever the streams held has completed first)
+  if (sync_all()) return ISX_ERR_HIP;
   HIPCHK(hipMemcpy(S.d_rec[0], rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(S.d_rec_counts[0], counts.data(), regions * sizeof(uint32_t), hipMemcpyHostToDevice));
   Work wk;
@@ -1663,6 +1763,8 @@ int isx_init(int device) {
 
 void isx_shutdown(void) {
   if (!S.init) return;
+  (void)trace_join();
+  S.trace_open = false;
   if (S.stream) (void)hipStreamSynchronize(S.stream);
   if (S.stream2) { (void)hipStreamSynchronize(S.stream2); (void)hipStreamDestroy(S.stream2); S.stream2 = nullptr; }
   if (S.stream3) { (void)hipStreamSynchronize(S.stream3); (void)hipStreamDestroy(S.stream3); S.stream3 = nullptr; }
@@ -1686,8 +1788,14 @@ void isx_shutdown(void) {
   }
   if (S.d_ctr) (void)hipFree(S.d_ctr);
   S.d_ctr = nullptr; S.ctr_next = 0;
-  if (S.d_list) (void)hipFree(S.d_list);
-  S.d_list = nullptr; S.cap_list = 0; S.fate_launches = 0;
+  for (int b = 0; b < State::kRecBufs; ++b) {
+    if (S.d_list[b]) (void)hipFree(S.d_list[b]);
+    S.d_list[b] = nullptr; S.cap_list[b] = 0;
+    if (S.ev_free[b]) (void)hipEventDestroy(S.ev_free[b]);
+    S.ev_free[b] = nullptr; S.free_set[b] = false;
+  }
+  for (hipEvent_t& e : S.ev_join) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+  S.fate_launches = 0; S.call_rot = 0;
   S.attr_lds.clear();
   S.d_table = S.d_rowtab = S.d_coltab = nullptr;
   S.d_hist = S.d_stats = nullptr;
@@ -1708,6 +1816,7 @@ int isx_device_info(char* buf, int buflen) {
 
 int isx_set_option(const char* key, int64_t value) {
   if (!key) return ISX_ERR_BAD_ARG;
+  if (S.init && trace_join()) return ISX_ERR_HIP;   // (an option never changes under an overlapped sequence in flight)
   if (!std::strcmp(key, "bin_mode")) { if (value < 0 || value > 2) return ISX_ERR_BAD_ARG; S.bin_mode = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "blocks_per_cu")) { if (value < 1 || value > 8) return ISX_ERR_BAD_ARG; S.blocks_per_cu = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "sched_mask")) { if (value < 0 || value > 255) return ISX_ERR_BAD_ARG; S.sched_mask = (int)value; return ISX_OK; }
@@ -1717,6 +1826,8 @@ int isx_set_option(const char* key, int64_t value) {
   if (!std::strcmp(key, "bin_blocks_per_cu")) { if (value < 0 || value > 32) return ISX_ERR_BAD_ARG; S.bin_blocks_per_cu = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "bin_block")) { if (value != 256 && value != 512 && value != 1024) return ISX_ERR_BAD_ARG; S.bin_block = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "overlap_trace_streams")) { if (value < 1 || value > 2) return ISX_ERR_BAD_ARG; S.overlap_trace_streams = (int)value; return ISX_OK; }
+  if (!std::strcmp(key, "call_overlap")) { if (value < -1 || value > 1) return ISX_ERR_BAD_ARG; S.call_overlap = (int)value; return ISX_OK; }
+  if (!std::strcmp(key, "call_overlap_streams")) { if (value < 1 || value > 2) return ISX_ERR_BAD_ARG; S.call_overlap_streams = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "overlap")) { if (value < 0 || value > 64) return ISX_ERR_BAD_ARG; S.overlap = (int)value; return ISX_OK; }
   // ("assist_block" 0: back to the default -- 768 threads, 256 for launches below 1e6 rays)
   if (!std::strcmp(key, "assist_block")) {
@@ -1755,8 +1866,7 @@ int isx_last_kernel_ms(double* single_ms, double* trace_ms, double* bin_ms) {
 
 int isx_sync(void) {
   if (!S.init) return ISX_ERR_NOT_INIT;
-  HIPCHK(hipStreamSynchronize(S.stream));
-  return ISX_OK;
+  return sync_all();
 }
 
 int isx_take_stats(isx_stats* stats) {
@@ -1767,7 +1877,10 @@ int isx_take_stats(isx_stats* stats) {
 int isx_fluxmap_device(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t first_ray, uint64_t* d_hits) {
   if (!S.init) return ISX_ERR_NOT_INIT;
   if (!cfg || !d_hits) return ISX_ERR_BAD_ARG;
-  return enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, (unsigned long long*)d_hits, 0, nullptr, 0, 0);
+  g_device_call = true;
+  const int rc = enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, (unsigned long long*)d_hits, 0, nullptr, 0, 0);
+  g_device_call = false;
+  return rc;
 }
 
 int isx_fluxmap(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t first_ray, uint64_t* hits,
@@ -1790,6 +1903,7 @@ int isx_fluxmap(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t 
 int isx_trace_endstates(const isx_config* cfg, uint64_t n, uint64_t seed, uint64_t first, int32_t* status,
                         int32_t* n_points, double* last_point, double* direction) {
   if (!S.init) return ISX_ERR_NOT_INIT;
+  if (trace_join()) return ISX_ERR_HIP;   // (behind an overlapped sequence, as every entry but isx_fluxmap_device)
   if (!cfg || !status || !n_points || !last_point || !direction) return ISX_ERR_BAD_ARG;
   if (n == 0) return ISX_OK;
   if (n > (1ull << 28)) return ISX_ERR_TOO_LARGE;
@@ -1815,6 +1929,7 @@ int isx_trace_endstates(const isx_config* cfg, uint64_t n, uint64_t seed, uint64
 
 int isx_fate_scan(const isx_config* cfg, uint64_t n, uint64_t seed, uint64_t first, int32_t* fate, int32_t* order) {
   if (!S.init) return ISX_ERR_NOT_INIT;
+  if (trace_join()) return ISX_ERR_HIP;   // (behind an overlapped sequence, as every entry but isx_fluxmap_device)
   if (!cfg || !fate || !order) return ISX_ERR_BAD_ARG;
   if (n == 0) return ISX_OK;
   if (n > (1ull << 28)) return ISX_ERR_TOO_LARGE;
@@ -1845,6 +1960,7 @@ int isx_fate_scan_launches(uint64_t* launches) {
 
 int isx_mathprobe(int op, const double* a, const double* b, const double* c, double* out, int32_t n) {
   if (!S.init) return ISX_ERR_NOT_INIT;
+  if (trace_join()) return ISX_ERR_HIP;   // (behind an overlapped sequence, as every entry but isx_fluxmap_device)
   if (!a || !out || n <= 0) return ISX_ERR_BAD_ARG;
   DevBuf<double> ba, bb, bc, bo;
   const size_t bytes = (size_t)n * 8;
@@ -2545,6 +2661,7 @@ int isx_beam_endstates(const isx_config* cfg, const isx_beam_spec* spec, uint64_
   int rc = check_beam_call(cfg, spec);
   if (rc) return rc;
   if (!S.init) return not_initialised();
+  if (trace_join()) return ISX_ERR_HIP;   // (behind an overlapped sequence, as every entry but isx_fluxmap_device)
   if (n == 0) return ISX_OK;
   if (n > (1ull << 28)) return ISX_ERR_TOO_LARGE;
   if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;
@@ -2638,6 +2755,7 @@ int isx_baffle_endstates(const isx_config* cfg, const isx_baffle_spec* spec, uin
   int rc = check_baffle_call(cfg, spec);
   if (rc) return rc;
   if (!S.init) return not_initialised();
+  if (trace_join()) return ISX_ERR_HIP;   // (behind an overlapped sequence, as every entry but isx_fluxmap_device)
   if (n == 0) return ISX_OK;
   if (n > (1ull << 28)) return ISX_ERR_TOO_LARGE;
   if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;
@@ -2716,6 +2834,7 @@ int isx_scene_endstates(const isx_config* cfg, const isx_scene_spec* spec, uint6
   int rc = check_scene_call(cfg, spec, false);
   if (rc) return rc;
   if (!S.init) return not_initialised();
+  if (trace_join()) return ISX_ERR_HIP;   // (behind an overlapped sequence, as every entry but isx_fluxmap_device)
   if (n == 0) return ISX_OK;
   if (n > (1ull << 28)) return ISX_ERR_TOO_LARGE;
   if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;
@@ -2975,6 +3094,7 @@ int isx_view_weight_fov(const isx_view_spec* vspec, double half_angle_deg, doubl
 // tuning builds only (not declared in isx.h): read and clear the binning diagnostics of isx_kernels.hpp
 int isx_diag_read(uint64_t* out48) {
   if (!S.init || !out48) return ISX_ERR_BAD_ARG;
+  if (trace_join()) return ISX_ERR_HIP;   // (behind an overlapped sequence, as every entry but isx_fluxmap_device)
   HIPCHK(hipStreamSynchronize(S.stream));
   HIPCHK(hipMemcpyFromSymbol(out48, HIP_SYMBOL(isx::g_diag), 48 * sizeof(unsigned long long)));
   unsigned long long z[48] = {0};

@@ -161,6 +161,14 @@ int isx_fluxmap(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t 
  * over RCCL) on the library's stream; returns after the kernels are enqueued.
  * isx_sync() waits; isx_take_stats() then returns the census + event time of
  * everything enqueued since the previous isx_take_stats().
+ * ORDER ("call_overlap", below): the kernel that writes d_hits -- the binning
+ * kernel -- runs on isx_stream(), behind whatever the caller enqueued there
+ * before this call (a zeroing of d_hits, an all-reduce of the call before).
+ * The kernels in front of it touch nothing of the caller's and may run on the
+ * library's own streams, ahead of the earlier calls' binning.  Every other
+ * entry point, isx_sync(), isx_take_stats(), isx_set_option() and
+ * isx_shutdown() first order isx_stream() behind those streams: a caller who
+ * knows only isx_stream() sees what a single stream would show.
  */
 int isx_fluxmap_device(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
                        uint64_t* d_hits);
@@ -169,7 +177,10 @@ int isx_take_stats(isx_stats* stats);
 /* The hipStream_t the library launches on (so callers can order work after it). */
 void* isx_stream(void);
 /* HIP-event times (ms) of the kernels collected by the last blocking call / isx_take_stats(), by kind: single-kernel
- * launches, the trace kernel of a two-kernel pipeline (flux map, exit maps, disc sweep), its binning kernel.  Any pointer may be NULL. */
+ * launches, the trace kernel of a two-kernel pipeline (flux map, exit maps, disc sweep), its binning kernel.  Any pointer may be NULL.
+ * Each kind is summed from its own events.  For enqueued calls under "call_overlap" the spans of consecutive calls overlap, and a
+ * span holds the time its kernel spent sharing the machine with the others: the kinds (and isx_stats::t_kernel_ms, their sum) then
+ * add up to more than the wall time of the sequence, and only the wall time compares with a build or a setting without the overlap. */
 int isx_last_kernel_ms(double* single_ms, double* trace_ms, double* bin_ms);
 
 /* Tuning/diagnostic switches.  None of them changes any result (a ray's history is a function of seed and index).
@@ -209,6 +220,14 @@ int isx_last_kernel_ms(double* single_ms, double* trace_ms, double* bin_ms);
  *                  (DESIGN.md 4.2d).  Automatic: chunks of at least 1e7 rays whose expected settled share
  *                  (1 - rho) / ((1 - rho) + port area fraction) is at least 0.5.  Anything else takes the kernels it took before,
  *                  also with 1.  WORKSPACE: 4 B per ray of the largest chunk, kept until isx_shutdown()
+ *   "call_overlap"  a SCHEDULING option, it changes no result: -1 (default) automatic, 1 on wherever eligible, 0 off.  Eligible are
+ *                  isx_fluxmap_device calls that take the two-kernel flux pipeline with explicit bounces, with or without the fate
+ *                  scan, and not with "overlap" > 1.  The chunk's counter zeroing, fate scan, trace kernel and
+ *                  isx_compat_lines_kernel go to a trace stream of the library's, its binning kernel stays on isx_stream() behind an
+ *                  event: the next call's scan and trace run under the launch tails of this one.  Automatic: every
+ *                  eligible call (measured faster from 5e4 to 5e7 rays per call).  "call_overlap_streams" 2 (default): consecutive
+ *                  chunks alternate between two trace streams; 1: one.  WORKSPACE: three exit-line workspaces and three fate
+ *                  lists of the largest chunk instead of one, kept until isx_shutdown()
  *   "overlap", "overlap_trace_streams"  cut a flux-map call into k chunks, binning of chunk i on a second stream while chunk
  *                  i+1 is traced (measured slower on MI355X, default 0)
  *   "disc_pipeline"  1 (default): the shared-ray disc sweep as trace kernel + disc-binning kernel (discs clustered by eight on the
