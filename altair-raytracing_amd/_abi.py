@@ -53,6 +53,7 @@ EXPORTS = [
     "isx_default_scene_spec", "isx_scene_endstates", "isx_fluxmap_scene", "isx_fluxmap_scene_device",
     "isx_default_response_spec", "isx_scene_response", "isx_scene_response_device", "isx_response_reweight",
     "isx_view_frame", "isx_scene_view", "isx_scene_view_device", "isx_view_reweight", "isx_view_weight_fov",
+    "isx_patch_field_frame", "isx_scene_patch_field", "isx_scene_patch_field_device", "isx_patch_field_marginals",
 ]
 
 
@@ -313,6 +314,38 @@ class ViewCounts(C.Structure):
         return np.frombuffer(bytes(self), dtype=np.uint64).copy()
 
 
+PATCH_FIELD_MAX_AXIS, PATCH_FIELD_MAX_BINS = 1024, 1 << 22
+
+
+class PatchFieldSpec(C.Structure):
+    """isx_patch_field_spec (include/isx.h): the selected wall class, the four axis sizes of the field, the patch's frame and the
+    scale of the position part -- both used as given -- and the half extent of the direction part in direction cosines."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("patch", C.c_int32), ("n_x", C.c_int32), ("n_y", C.c_int32),
+                ("n_u", C.c_int32), ("n_v", C.c_int32), ("reserved1", C.c_int32), ("axis", C.c_double * 3), ("e1", C.c_double * 3),
+                ("e2", C.c_double * 3), ("half_extent", C.c_double), ("pos_scale", C.c_double)]
+
+    @property
+    def bins(self):
+        return int(self.n_x) * int(self.n_y) * int(self.n_u) * int(self.n_v)
+
+    def copy(self):
+        s = PatchFieldSpec()
+        C.memmove(C.byref(s), C.byref(self), C.sizeof(PatchFieldSpec))
+        return s
+
+
+class PatchFieldCounts(C.Structure):
+    """isx_patch_field_counts (include/isx.h): the selected rays by what became of them."""
+
+    _fields_ = [("binned", C.c_uint64), ("pos_outside", C.c_uint64), ("dir_outside", C.c_uint64), ("behind", C.c_uint64),
+                ("direct", C.c_uint64)]
+
+    def words(self):
+        """-> the 5 words in the struct's order (the device form's layout)"""
+        return np.frombuffer(bytes(self), dtype=np.uint64).copy()
+
+
 _lib = None
 
 
@@ -405,6 +438,12 @@ def load():
     L.isx_scene_view_device.argtypes = [P(Config), P(SceneSpec), P(ViewSpec), u64, u64, u64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.isx_view_reweight.argtypes = [P(ViewSpec), P(u64), P(ViewCounts), u64, P(dbl), dbl, P(dbl), P(dbl)]
     L.isx_view_weight_fov.argtypes = [P(ViewSpec), dbl, P(dbl)]
+    L.isx_patch_field_frame.argtypes = [P(Config), P(SceneSpec), i32, i32, i32, i32, i32, dbl, P(PatchFieldSpec)]
+    L.isx_scene_patch_field.argtypes = [P(Config), P(SceneSpec), P(PatchFieldSpec), u64, u64, u64, P(u64), P(PatchFieldCounts),
+                                        P(SceneCounts), P(Stats)]
+    L.isx_scene_patch_field_device.argtypes = [P(Config), P(SceneSpec), P(PatchFieldSpec), u64, u64, u64, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
+    L.isx_patch_field_marginals.argtypes = [P(PatchFieldSpec), P(u64), P(u64), P(u64)]
     _lib = L
     return L
 
@@ -1081,6 +1120,59 @@ def view_weight_fov(vspec, half_angle_deg):
     w = np.zeros(nv * nu, dtype=np.float64)
     _chk(load().isx_view_weight_fov(C.byref(vspec), float(half_angle_deg), _p(w, C.c_double)), "isx_view_weight_fov")
     return w.reshape(nv, nu)
+
+
+def patch_field_frame(cfg, scene, patch, n_x, n_y, n_u, n_v, half_extent=1.0):
+    """-> PatchFieldSpec for patch `patch` of the scene: the frame by view_frame's rule, pos_scale so that the cap fills the unit
+    disc of the position part, an n_y x n_x x n_v x n_u field (include/isx.h: isx_patch_field_frame; no GPU needed)."""
+    s = PatchFieldSpec()
+    _chk(load().isx_patch_field_frame(C.byref(cfg), C.byref(scene), int(patch), int(n_x), int(n_y), int(n_u), int(n_v),
+                                      float(half_extent), C.byref(s)), "isx_patch_field_frame")
+    return s
+
+
+def _patch_field_shape(fspec):
+    """the shape of the array a call may touch; (1, 1, 1, 1) for a spec the library refuses (it says so itself)"""
+    ax = [int(fspec.n_y), int(fspec.n_x), int(fspec.n_v), int(fspec.n_u)]
+    ok = all(1 <= a <= PATCH_FIELD_MAX_AXIS for a in ax) and fspec.bins <= PATCH_FIELD_MAX_BINS
+    return tuple(ax) if ok else (1, 1, 1, 1)
+
+
+def scene_patch_field(cfg, scene, fspec, n_rays, seed, first_ray=0):
+    """-> (field[n_y, n_x, n_v, n_u] uint64, PatchFieldCounts, SceneCounts, Stats): the rays wall class fspec.patch of the scene
+    absorbs, binned over where on the patch they land and the direction they arrive from, in the frame of fspec (include/isx.h:
+    isx_scene_patch_field)."""
+    shape = _patch_field_shape(fspec)
+    field = np.zeros(int(np.prod(shape)), dtype=np.uint64)
+    st = Stats()
+    fc = PatchFieldCounts()
+    cnt = SceneCounts()
+    _chk(load().isx_scene_patch_field(C.byref(cfg), C.byref(scene), C.byref(fspec), int(n_rays), int(seed), int(first_ray),
+                                      _p(field, C.c_uint64), C.byref(fc), C.byref(cnt), C.byref(st)), "isx_scene_patch_field")
+    return field.reshape(shape), fc, cnt, st
+
+
+def scene_patch_field_device(cfg, scene, fspec, n_rays, seed, first_ray, d_field_ptr, d_field_counts_ptr, d_scene_counts_ptr):
+    """Enqueue on the library stream, accumulating into device memory at d_field_ptr ([n_y * n_x * n_v * n_u] uint64),
+    d_field_counts_ptr ([5] uint64, PatchFieldCounts' layout) and d_scene_counts_ptr ([36] uint64, SceneCounts' layout)."""
+    _chk(load().isx_scene_patch_field_device(C.byref(cfg), C.byref(scene), C.byref(fspec), int(n_rays), int(seed), int(first_ray),
+                                             C.c_void_p(int(d_field_ptr or 0) or None),
+                                             C.c_void_p(int(d_field_counts_ptr or 0) or None),
+                                             C.c_void_p(int(d_scene_counts_ptr or 0) or None)), "isx_scene_patch_field_device")
+
+
+def patch_field_marginals(fspec, field):
+    """-> (pos_map[n_y, n_x], dir_map[n_v, n_u]) uint64: the two sums of a field; dir_map is what view_reweight takes through a
+    view spec with the same frame (include/isx.h: isx_patch_field_marginals; host only, no GPU needed)."""
+    ny, nx, nv, nu = _patch_field_shape(fspec)
+    f = np.ascontiguousarray(np.asarray(field, dtype=np.uint64).reshape(-1))
+    if f.size < ny * nx * nv * nu:
+        raise ValueError("field has %d words, the spec wants %d" % (f.size, ny * nx * nv * nu))
+    pos = np.zeros(ny * nx, dtype=np.uint64)
+    dr = np.zeros(nv * nu, dtype=np.uint64)
+    _chk(load().isx_patch_field_marginals(C.byref(fspec), _p(f, C.c_uint64), _p(pos, C.c_uint64), _p(dr, C.c_uint64)),
+         "isx_patch_field_marginals")
+    return pos.reshape(ny, nx), dr.reshape(nv, nu)
 
 
 def fluxmap_series(cfgs, n_rays, seed, first_ray=0):

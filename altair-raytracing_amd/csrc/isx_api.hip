@@ -88,6 +88,7 @@ struct State {
   int bin_slots = 1;                            // 1: isx_bin_slots_kernel (slot queues by window length) where the grid allows it
   int lf_global = 0;                            // 1: isx_bin_lightfield_kernel's global form for a field that fits the LDS as well (diagnostic)
   int resp_global = 0;                          // 1: isx_trace_assist_scene_response_kernel's global form for a response that fits the LDS as well (diagnostic)
+  int field_global = 0;                         // 1: isx_trace_assist_scene_field_kernel's global form for a field that fits the LDS as well (diagnostic)
   int view_global = 0;                          // 1: isx_trace_assist_scene_view_kernel's global form for a map that fits the LDS as well (diagnostic)
   int surface_pipeline = 1;                     // 1 (default): the lobe / rough-specular borders and the origin-compat hit line on the assist-wave
                                                 // pipeline (round 5); 0: round 1's fused isx_trace_bin_full_kernel
@@ -711,6 +712,42 @@ int check_view_spec(const isx_view_spec* s, int n_patches) {
 }
 size_t view_bins(const isx_view_spec& s) { return (size_t)s.n_u * (size_t)s.n_v; }
 
+// isx_scene_patch_field: the checked spec and the device arrays of the call (the field [n_y][n_x][n_v][n_u], the five words of
+// isx_patch_field_counts); the scene travels as SceneSink
+struct PatchFieldCall { const isx_patch_field_spec* spec = nullptr; unsigned long long* out = nullptr; unsigned long long* counts = nullptr; };
+static_assert(sizeof(isx_patch_field_counts) == kFieldCounters * sizeof(uint64_t) && offsetof(isx_patch_field_counts, binned) == 8 * kFieldBinned &&
+              offsetof(isx_patch_field_counts, pos_outside) == 8 * kFieldPosOutside &&
+              offsetof(isx_patch_field_counts, dir_outside) == 8 * kFieldDirOutside &&
+              offsetof(isx_patch_field_counts, behind) == 8 * kFieldBehind && offsetof(isx_patch_field_counts, direct) == 8 * kFieldDirect,
+              "isx.h and field_record's counters");
+static_assert(sizeof(isx_patch_field_spec) == 120, "isx.h: isx_patch_field_spec");
+// isx.h: the limits of a patch-field spec; n_patches < 0: no scene is at hand (the host-side helper), the patch index is not looked at
+int check_patch_field_spec(const isx_patch_field_spec* s, int n_patches) {
+  if (s->struct_size != (uint32_t)sizeof(isx_patch_field_spec) || s->reserved0 != 0u || s->reserved1 != 0) return ISX_ERR_BAD_CONFIG;
+  if (n_patches >= 0 && (s->patch < 0 || s->patch >= n_patches)) return ISX_ERR_BAD_CONFIG;
+  const int32_t ax[4] = {s->n_x, s->n_y, s->n_u, s->n_v};
+  long long prod = 1;
+  for (int a = 0; a < 4; ++a) {
+    if (ax[a] < 1 || ax[a] > ISX_PATCH_FIELD_MAX_AXIS) return ISX_ERR_BAD_CONFIG;
+    prod *= ax[a];   // (at most 2^40)
+  }
+  if (prod > ISX_PATCH_FIELD_MAX_BINS) return ISX_ERR_BAD_CONFIG;
+  if (!std::isfinite(s->half_extent) || !(s->half_extent > 0.0 && s->half_extent <= 1.0)) return ISX_ERR_BAD_CONFIG;
+  if (!std::isfinite(s->pos_scale) || !(s->pos_scale > 0.0)) return ISX_ERR_BAD_CONFIG;
+  const double* vec[3] = {s->axis, s->e1, s->e2};
+  for (int k = 0; k < 3; ++k)
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(vec[k][i])) return ISX_ERR_BAD_CONFIG;
+  // (check_beam_call's test of a frame)
+  auto dot = [](const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+  for (int k = 0; k < 3; ++k) {
+    if (!(std::fabs(std::sqrt(dot(vec[k], vec[k])) - 1.0) <= 1e-12)) return ISX_ERR_BAD_CONFIG;
+    if (!(std::fabs(dot(vec[k], vec[(k + 1) % 3])) <= 1e-12)) return ISX_ERR_BAD_CONFIG;
+  }
+  return ISX_OK;
+}
+size_t patch_field_bins(const isx_patch_field_spec& s) { return (size_t)s.n_x * (size_t)s.n_y * (size_t)s.n_u * (size_t)s.n_v; }
+
 // LDS of a workgroup's histogram: 4 B per bin, 16-byte aligned
 size_t hist_lds(int nbins) { return ((size_t)nbins * 4 + 15) & ~(size_t)15; }
 
@@ -823,7 +860,7 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
     d.xm_dir = wp->arrivals; d.xm_pos = wp->absorbed;
     d.nbins = 2 * (wp->spec->n_patches + 2);
     lds = patch_lds() + 64 + sizeof(Geom) + sizeof(DetGrid);
-  } else if (sink == SINK_RESPONSE || sink == SINK_VIEW) {
+  } else if (sink == SINK_RESPONSE || sink == SINK_VIEW || sink == SINK_FIELD) {
     // (isx.h: hit_line_mode and the detector grid are ignored -- no exit line is written, no grid is looked at; the scene and the
     //  response spec were checked by the entry, the patches' words are enqueue's)
     d.hit_line_mode = ISX_HITLINE_LAST_SEGMENT;
@@ -865,6 +902,7 @@ typedef void (*BaffleFn)(const Geom, const DetGrid, const Work, const BaffleTab)
 typedef void (*SceneFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab);
 typedef void (*ResponseFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab, const RespSink);
 typedef void (*ViewFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab, const ViewSink);
+typedef void (*PatchFieldFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab, const PatchFieldSink);
 struct Plan {
   Route route = ROUTE_FUSED;
   KernelFn fn = nullptr;        // the kernel (a pipeline's trace kernel)
@@ -898,6 +936,8 @@ struct Plan {
   RespSink resp{};              // (resp.lds_words: plan_launch's choice of the form; the rest is enqueue's)
   ViewFn view_fn = nullptr;     // isx_scene_view: ROUTE_ASSIST's one kernel (the scene's three arguments, and view the seventh) instead of fn
   ViewSink view{};              // (view.lds_words: plan_launch's choice of the form; the rest is enqueue's)
+  PatchFieldFn field_fn = nullptr;  // isx_scene_patch_field: ROUTE_ASSIST's one kernel (the scene's three arguments, and field the seventh) instead of fn
+  PatchFieldSink field{};       // (field.lds_words: plan_launch's choice of the form; the rest is enqueue's)
 };
 
 // "fate_scan" = -1: where the scan pays (measured on MI355X, docs/LOG.md section 16.3).  A small launch is bound by its longest
@@ -998,6 +1038,27 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     const size_t resident = (size_t)blocks_per_cu(p.view_fn, p.block, p.lds, kResident);
     if (!S.view_global && ((with + 2047) & ~(size_t)2047) * resident <= S.lds_limit) {
       p.view.lds_words = (uint32_t)resp_words;
+      p.lds = with;
+    }
+    return p;
+  }
+  // The scene patch field (isx_scene_patch_field): the same route, shape and rule -- the scene's trace kernel with the field as its
+  // one sink.  Behind the parks lie the frame's doubles and the five counters (kFieldHead bytes, both forms) and, where that costs
+  // no resident workgroup, `resp_words` = n_x * n_y * n_u * n_v u32 words of the field, flushed once per workgroup; else, or with
+  // field_global = 1, one global u64 add per binned ray (isx_kernels.hpp: field_record).  The form is PatchFieldSink::lds_words,
+  // nothing else.
+  if (sink == SINK_FIELD) {
+    p.route = ROUTE_ASSIST;
+    p.field_fn = isx_trace_assist_scene_field_kernel;
+    p.launch_max = std::min(kLaunchMax, S.pipe_chunk);
+    trace_shape(p, small_shape(std::min(n, p.launch_max), S.assist_block_set ? S.assist_block : kSceneBlock), true,
+                resident_unless(S.trace_blocks_per_cu));
+    p.lds += SceneLds::bytes(p.tracers) + kFieldHead;
+    // (the sum in size_t, from the word count: hist_lds takes an int, and a field has up to 2^22 words)
+    const size_t with = p.lds + ((resp_words * 4 + 15) & ~(size_t)15);
+    const size_t resident = (size_t)blocks_per_cu(p.field_fn, p.block, p.lds, kResident);
+    if (!S.field_global && ((with + 2047) & ~(size_t)2047) * resident <= S.lds_limit) {
+      p.field.lds_words = (uint32_t)resp_words;
       p.lds = with;
     }
     return p;
@@ -1244,9 +1305,10 @@ int span(int kind, size_t* from) { return span_on(S.stream, kind, from); }
 
 // ROUTE_FUSED and ROUTE_ASSIST: launches of at most kLaunchMax rays, one span
 int run_single(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
-  const void* fn = p.view_fn ? (const void*)p.view_fn : p.resp_fn ? (const void*)p.resp_fn : p.patch_fn ? (const void*)p.patch_fn : (const void*)p.fn;
+  const void* fn = p.field_fn ? (const void*)p.field_fn : p.view_fn ? (const void*)p.view_fn : p.resp_fn ? (const void*)p.resp_fn : p.patch_fn ? (const void*)p.patch_fn : (const void*)p.fn;
   int rc = set_lds(fn, p.lds); if (rc) return rc;
-  const int per_cu = p.view_fn ? blocks_per_cu(p.view_fn, p.block, p.lds, p.per_cu) :
+  const int per_cu = p.field_fn ? blocks_per_cu(p.field_fn, p.block, p.lds, p.per_cu) :
+                     p.view_fn ? blocks_per_cu(p.view_fn, p.block, p.lds, p.per_cu) :
                      p.resp_fn ? blocks_per_cu(p.resp_fn, p.block, p.lds, p.per_cu) :
                      p.patch_fn ? blocks_per_cu(p.patch_fn, p.block, p.lds, p.per_cu) : blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
   const uint64_t launch_max = p.launch_max ? p.launch_max : kLaunchMax;
@@ -1255,7 +1317,8 @@ int run_single(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
   for (uint64_t off = 0; off < wk.n; off += launch_max) {
     Work w;
     rc = launch_work(wk, off, std::min(wk.n - off, launch_max), 0, S.stream, &w); if (rc) return rc;
-    if (p.view_fn) hipLaunchKernelGGL(p.view_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.view);
+    if (p.field_fn) hipLaunchKernelGGL(p.field_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.field);
+    else if (p.view_fn) hipLaunchKernelGGL(p.view_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.view);
     else if (p.resp_fn) hipLaunchKernelGGL(p.resp_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.resp);
     else if (p.patch_fn) hipLaunchKernelGGL(p.patch_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab);
     else hipLaunchKernelGGL(p.fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w);
@@ -1442,7 +1505,8 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
             const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr, const ExitSink* xm = nullptr,
             const WallSink* wm = nullptr, const FieldSink* lf = nullptr, const OrderSink* oh = nullptr,
             const PatchSink* wp = nullptr, const isx_beam_spec* bs = nullptr, const BaffleSink* bf = nullptr,
-            const SceneSink* sc = nullptr, const ResponseSink* rs = nullptr, const ViewCall* vw = nullptr) {
+            const SceneSink* sc = nullptr, const ResponseSink* rs = nullptr, const ViewCall* vw = nullptr,
+            const PatchFieldCall* pf = nullptr) {
   Geom g;
   FateConsts fate;
   isx_config cb;
@@ -1475,7 +1539,16 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
   const size_t resp_bins = rs ? response_bins(*rs->spec) : 0;
   const size_t resp_words = rs ? (size_t)((sc->spec->patches.n_patches + 2) + 2 * sc->spec->baffles.n_baffles + 3) * resp_bins : 0;
   Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n, bs != nullptr, &fate, bf != nullptr, sc != nullptr,
-                       vw ? view_bins(*vw->spec) : resp_words);
+                       pf ? patch_field_bins(*pf->spec) : vw ? view_bins(*vw->spec) : resp_words);
+  if (pf) {
+    const isx_patch_field_spec& v = *pf->spec;
+    p.field.out = pf->out; p.field.counts = pf->counts;
+    PatchFieldFrame& f = p.field.f;
+    for (int i = 0; i < 3; ++i) { f.axis[i] = v.axis[i]; f.e1[i] = v.e1[i]; f.e2[i] = v.e2[i]; }
+    f.h = v.half_extent; f.s = v.pos_scale; f.inv = 1.0 / c->r_in;   // (isx.h: inv is formed once, here)
+    f.fnx = (double)v.n_x; f.fny = (double)v.n_y; f.fnu = (double)v.n_u; f.fnv = (double)v.n_v;
+    p.field.patch = v.patch; p.field.n_x = v.n_x; p.field.n_u = v.n_u; p.field.n_v = v.n_v;
+  }
   if (vw) {
     const isx_view_spec& v = *vw->spec;
     p.view.out = vw->out; p.view.counts = vw->counts;
@@ -1841,6 +1914,7 @@ int isx_set_option(const char* key, int64_t value) {
   if (!std::strcmp(key, "bin_cols")) { if (value < 0 || value > 2) return ISX_ERR_BAD_ARG; S.bin_cols = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "bin_slots")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.bin_slots = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "lf_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.lf_global = (int)value; return ISX_OK; }
+  if (!std::strcmp(key, "field_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.field_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "view_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.view_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "resp_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.resp_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "surface_pipeline")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.surface_pipeline = (int)value; return ISX_OK; }
@@ -3087,6 +3161,87 @@ int isx_view_weight_fov(const isx_view_spec* vspec, double half_angle_deg, doubl
       weight[(size_t)iv * vspec->n_u + iu] = uc * uc + vc * vc <= s * s ? 1.0 : 0.0;
     }
   }
+  return ISX_OK;
+}
+
+int isx_patch_field_frame(const isx_config* cfg, const isx_scene_spec* scene, int32_t patch, int32_t n_x, int32_t n_y, int32_t n_u,
+                          int32_t n_v, double half_extent, isx_patch_field_spec* out) {
+  if (!cfg || !scene || !out) return ISX_ERR_BAD_ARG;
+  int rc = check_scene_call(cfg, scene, false);
+  if (rc) return rc;
+  if (patch < 0 || patch >= scene->patches.n_patches) return ISX_ERR_BAD_CONFIG;
+  isx_patch_field_spec s;
+  std::memset(&s, 0, sizeof(s));
+  s.struct_size = (uint32_t)sizeof(isx_patch_field_spec);
+  s.patch = patch; s.n_x = n_x; s.n_y = n_y; s.n_u = n_u; s.n_v = n_v; s.half_extent = half_extent;
+  const double* a = scene->patches.patch[patch].axis;
+  double unit[3];   // (isx_view_frame's rule: the spec's axis is the patch's, bit for bit)
+  if (!beam_frame(a, unit, s.e1, s.e2)) return ISX_ERR_BAD_CONFIG;
+  for (int i = 0; i < 3; ++i) s.axis[i] = a[i];
+  // (a cap of half-angle alpha fills the unit disc: 1 / sin(alpha / 2); a cap of zero angle has no scale and is refused below)
+  s.pos_scale = 1.0 / std::sqrt(0.5 * (1.0 - scene->patches.patch[patch].min_dot / cfg->r_in));
+  rc = check_patch_field_spec(&s, scene->patches.n_patches);
+  if (rc) return rc;
+  *out = s;
+  return ISX_OK;
+}
+
+int isx_scene_patch_field_device(const isx_config* cfg, const isx_scene_spec* scene, const isx_patch_field_spec* fspec, uint64_t n_rays,
+                                 uint64_t seed, uint64_t first_ray, uint64_t* d_field, uint64_t* d_field_counts,
+                                 uint64_t* d_scene_counts) {
+  // (what needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one)
+  if (!cfg || !scene || !fspec || !d_field || !d_field_counts || !d_scene_counts) return ISX_ERR_BAD_ARG;
+  int bad = check_scene_call(cfg, scene, false);   // (isx.h: the detector grid is ignored -- isx_scene_endstates' refusals)
+  if (bad == ISX_OK) bad = check_patch_field_spec(fspec, scene->patches.n_patches);
+  if (bad) return bad;
+  if (!S.init) return not_initialised();
+  const SceneSink sc{scene, (unsigned long long*)d_scene_counts};
+  const PatchFieldCall pf{fspec, (unsigned long long*)d_field, (unsigned long long*)d_field_counts};
+  return enqueue(SINK_FIELD, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                 nullptr, nullptr, nullptr, nullptr, nullptr, &sc, nullptr, nullptr, &pf);
+}
+
+int isx_scene_patch_field(const isx_config* cfg, const isx_scene_spec* scene, const isx_patch_field_spec* fspec, uint64_t n_rays,
+                          uint64_t seed, uint64_t first_ray, uint64_t* field, isx_patch_field_counts* field_counts,
+                          isx_scene_counts* scene_counts, isx_stats* stats) {
+  if (!cfg || !scene || !fspec || !field) return ISX_ERR_BAD_ARG;
+  int rc = check_scene_call(cfg, scene, false);
+  if (rc == ISX_OK) rc = check_patch_field_spec(fspec, scene->patches.n_patches);
+  if (rc) return rc;
+  if (!S.init) return not_initialised();
+  // the field and, behind it, the five field counters and the 36 scene counters: one device block, one staged result
+  const size_t nb = patch_field_bins(*fspec), nf = kFieldCounters, nc = kSceneWords, bytes = (nb + nf + nc) * sizeof(unsigned long long);
+  rc = call_open(nb + nf + nc);
+  if (rc) return rc;
+  rc = zero_hist(nb + nf + nc);
+  const SceneSink sc{scene, S.d_hist + nb + nf};
+  const PatchFieldCall pf{fspec, S.d_hist, S.d_hist + nb};
+  if (rc == ISX_OK) rc = enqueue(SINK_FIELD, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sc, nullptr, nullptr, &pf);
+  if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK) {
+    fetch_result(field, nb * sizeof(unsigned long long));
+    const unsigned long long* tail = reinterpret_cast<const unsigned long long*>(S.h_pin + 64) + nb;
+    if (field_counts) std::memcpy(field_counts, tail, nf * sizeof(unsigned long long));
+    if (scene_counts) std::memcpy(scene_counts, tail + nf, nc * sizeof(unsigned long long));
+  }
+  return rc;
+}
+
+int isx_patch_field_marginals(const isx_patch_field_spec* fspec, const uint64_t* field, uint64_t* pos_map, uint64_t* dir_map) {
+  if (!fspec || !field) return ISX_ERR_BAD_ARG;
+  const int rc = check_patch_field_spec(fspec, -1);
+  if (rc) return rc;
+  const size_t np = (size_t)fspec->n_x * (size_t)fspec->n_y, nd = (size_t)fspec->n_u * (size_t)fspec->n_v;
+  if (pos_map) std::memset(pos_map, 0, np * sizeof(uint64_t));
+  if (dir_map) std::memset(dir_map, 0, nd * sizeof(uint64_t));
+  for (size_t p = 0; p < np; ++p)
+    for (size_t k = 0; k < nd; ++k) {
+      const uint64_t c = field[p * nd + k];
+      if (pos_map) pos_map[p] += c;
+      if (dir_map) dir_map[k] += c;
+    }
   return ISX_OK;
 }
 

@@ -123,7 +123,8 @@ __device__ unsigned long long g_diag[48];   // [32..47]: the assist wave of assi
 enum : int { SINK_FLUX = 0, SINK_DZ = 1, SINK_DISC = 2, SINK_PERPOS = 3, SINK_LOG = 4, SINK_DISCPOS = 5, SINK_REC = 6, SINK_EXITMAP = 7, SINK_WALL = 8,
               SINK_LIGHTFIELD = 9, SINK_ORDER = 10, SINK_PATCH = 11,
               SINK_RESPONSE = 12,     // (isx_scene_response: no kernel is built on it -- the host's name for the scene's second sink)
-              SINK_VIEW = 13 };       // (isx_scene_view: likewise, the scene's third sink)
+              SINK_VIEW = 13,         // (isx_scene_view: likewise, the scene's third sink)
+              SINK_FIELD = 14 };      // (isx_scene_patch_field: likewise, the scene's fourth sink)
 
 struct Work {
   uint64_t seed, first, n;    // one launch traces rays [first, first + n), n < 2^31 (a lane keeps a 31-bit offset from `first`)
@@ -2407,6 +2408,77 @@ __device__ __forceinline__ uint32_t view_flush(const ViewSink& s, const uint32_t
   return flushed;
 }
 
+// ------------------------------------------------------------------ scene patch field (isx.h: isx_scene_patch_field)
+// The patch-field sink of a call as the kernel gets it.  The sixteen doubles of the rule (PatchFieldFrame: the frame, h, s,
+// inv = 1 / r_in formed by the host, the four axis sizes as doubles) are copied once into the workgroup's LDS and read there, one
+// wave-uniform read where each is used: neither a scalar register nor a lane of a parked VGPR is held for them through the steps.
+// The pointers, the selected class, three axis sizes and the form stay fields of the kernel argument (`out`: a global_atomic).
+// lds_words: n_x * n_y * n_u * n_v, the workgroup's u32 field in the LDS, or 0: the global form, one u64 add per binned ray.  The
+// workgroup's block behind the parks is [PatchFieldFrame | u32[8]: five counters | field] in both forms (kFieldHead bytes, then
+// the field).
+constexpr int kFieldCounters = 5, kFieldCtrWords = 8, kFieldBinned = 0, kFieldPosOutside = 1, kFieldDirOutside = 2, kFieldBehind = 3, kFieldDirect = 4;
+struct PatchFieldFrame {
+  double axis[3], e1[3], e2[3];
+  double h, s, inv, fnx, fny, fnu, fnv;
+};
+struct PatchFieldSink {
+  unsigned long long* out;
+  unsigned long long* counts;
+  PatchFieldFrame f;
+  int32_t patch, n_x, n_u, n_v;
+  uint32_t lds_words, pad;
+};
+constexpr size_t kFieldHead = sizeof(PatchFieldFrame) + kFieldCtrWords * sizeof(uint32_t);
+static_assert(sizeof(PatchFieldFrame) == 128 && kFieldHead == 160, "the workgroup's block: frame | counters | field, 16-byte steps");
+typedef __attribute__((address_space(3))) PatchFieldFrame LdsFieldFrame;
+// A selected ray's end -- absorbed at a wall arrival of the selected class, j its interaction count with that arrival, q the
+// point of that arrival (Ray::p), d the direction of the segment it arrived on (Ray::v) -- by isx.h's rule, operation for
+// operation: IEEE double, left to right, no fma (-ffp-contract=off), the correctly rounded division and square root.  The
+// position part comes first and leaves one word, the position bin, for the direction part, which is view_record's.  The in-range
+// tests are made on the values floor() would see: NaN and inf compare false.  Both census points of the FIELD build call this and
+// nothing else states the rule.
+__device__ __forceinline__ void field_record(const PatchFieldSink& s, const volatile LdsFieldFrame& f, uint32_t* blk, uint32_t j,
+                                             const V3& q, const V3& d) {
+  if (j == 1u) { atomicAdd(&blk[kFieldDirect], 1u); return; }   // absorbed at its first interaction: straight from the source
+  const double cd = (d.x * f.axis[0] + d.y * f.axis[1]) + d.z * f.axis[2];
+  if (!(cd > 0.0)) { atomicAdd(&blk[kFieldBehind], 1u); return; }
+  uint32_t pbin;
+  {
+    const double inv = f.inv, sc = f.s;
+    const double c = ((q.x * f.axis[0] + q.y * f.axis[1]) + q.z * f.axis[2]) * inv;
+    const double w = sqrt(0.5 / (1.0 + c));
+    const double a = (q.x * f.e1[0] + q.y * f.e1[1]) + q.z * f.e1[2];
+    const double b = (q.x * f.e2[0] + q.y * f.e2[1]) + q.z * f.e2[2];
+    const double X = ((a * inv) * w) * sc, Y = ((b * inv) * w) * sc;
+    const double fnx = f.fnx, fny = f.fny;
+    const double fx = (X + 1.0) * 0.5 * fnx;
+    const double fy = (Y + 1.0) * 0.5 * fny;
+    if (!(fx >= 0.0 && fx < fnx && fy >= 0.0 && fy < fny)) { atomicAdd(&blk[kFieldPosOutside], 1u); return; }
+    pbin = (uint32_t)(int)fy * (uint32_t)s.n_x + (uint32_t)(int)fx;
+  }
+  const double mag = sqrt((d.x * d.x + d.y * d.y) + d.z * d.z);
+  const double a = (d.x * f.e1[0] + d.y * f.e1[1]) + d.z * f.e1[2];
+  const double b = (d.x * f.e2[0] + d.y * f.e2[1]) + d.z * f.e2[2];
+  const double U = -(a / mag), V = -(b / mag);
+  const double h = f.h, fnu = f.fnu, fnv = f.fnv;
+  const double fu = (U + h) / (2.0 * h) * fnu;
+  const double fv = (V + h) / (2.0 * h) * fnv;
+  if (fu >= 0.0 && fu < fnu && fv >= 0.0 && fv < fnv) {
+    const uint32_t bin = (pbin * (uint32_t)s.n_v + (uint32_t)(int)fv) * (uint32_t)s.n_u + (uint32_t)(int)fu;
+    if (s.lds_words != 0u) atomicAdd(&blk[kFieldCtrWords + bin], 1u);   // (binned: the sum of the field, field_flush)
+    else { global_add_u64(s.out + bin, 1ull); atomicAdd(&blk[kFieldBinned], 1u); }
+  } else atomicAdd(&blk[kFieldDirOutside], 1u);
+}
+// one flush of the workgroup's field (the LDS form; the global form has none): returns this thread's share of `binned`
+__device__ __forceinline__ uint32_t field_flush(const PatchFieldSink& s, const uint32_t* blk, uint32_t tid, uint32_t nthr) {
+  uint32_t flushed = 0u;
+  for (uint32_t i = tid; i < s.lds_words; i += nthr) {
+    const uint32_t c = blk[kFieldCtrWords + i];
+    if (c) { global_add_u64(s.out + i, (unsigned long long)c); flushed += c; }
+  }
+  return flushed;
+}
+
 // The segment test of isx.h's contract, operation for operation (IEEE double, left to right, no fma: -ffp-contract=off; / is the
 // correctly rounded one): the baffle that the segment p -> q strikes first -- the smallest f, on equal f the lowest index -- as
 // 2 k + side (side 0: the side the normal points to), or -1.  `skip` is the baffle of the ray's previous interaction (-1: none).
@@ -3117,13 +3189,16 @@ __device__ __forceinline__ void ray_unpack(const uint4& a, const uint4& b, const
 // it ends, by the direction of the segment it arrived on -- view_record at RESP's two census points, with the class kept as RESP
 // keeps it.  The workgroup's u32 block -- four counters, and the map if the launch has one -- lies behind the parks.  No exit
 // lines, no second kernel, no per-ray state.
+// FIELD (isx_scene_patch_field; SCENE only, never with RESP or VIEW): the same rays at the same two points, binned by where on the
+// patch they land and the direction they arrive from -- field_record, which also gets the point of the arrival (Ray::p).  The
+// workgroup's block behind the parks: the frame's doubles, five counters, and the field if the launch has one in the LDS.
 struct FateList { const uint32_t* list; const uint32_t* count; };
 template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false, bool ORDER = false, bool PATCH = false,
-          bool BEAM = false, bool LIST = false, bool BAFFLE = false, bool RESP = false, bool VIEW = false>
+          bool BEAM = false, bool LIST = false, bool BAFFLE = false, bool RESP = false, bool VIEW = false, bool FIELD = false>
 __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk, const PatchTab* tab_arg = nullptr,
                                             const BeamSrc* beam_arg = nullptr, const FateList* list_arg = nullptr,
                                             const BaffleTab* baf_arg = nullptr, const RespSink* resp_arg = nullptr,
-                                            const ViewSink* view_arg = nullptr) {
+                                            const ViewSink* view_arg = nullptr, const PatchFieldSink* field_arg = nullptr) {
   constexpr bool LEAN = SURF == SURF_LAMBERT;
   static_assert(LEAN || (CH == 0 && !RESC), "the chord identity and the BRDF re-scatter pipeline are built for the Lambertian border");
   static_assert(!PATCH || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER), "wall patches: the explicit Lambertian lean path, no other sink");
@@ -3133,6 +3208,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   static_assert(!BAFFLE || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && (!PATCH || SCENE) && (!BEAM || SCENE) && !LIST), "baffles: the explicit Lambertian lean path of the flux pipeline");
   static_assert(!RESP || SCENE, "scene response: the scene's trace, nothing else");
   static_assert(!VIEW || (SCENE && !RESP), "scene view: the scene's trace, nothing else");
+  static_assert(!FIELD || (SCENE && !RESP && !VIEW), "scene patch field: the scene's trace, nothing else");
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned long long* sstat = reinterpret_cast<unsigned long long*>(smem);
   Geom* g_lds = reinterpret_cast<Geom*>(sstat + 8);
@@ -3190,6 +3266,14 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   // VIEW: the workgroup's u32 block behind the parks -- four counters | ViewSink::lds_words of the map (none in the global form)
   if constexpr (VIEW) {
     for (uint32_t b = (uint32_t)tid; b < (uint32_t)kViewCounters + view_arg->lds_words; b += (uint32_t)nthr) rblk[b] = 0u;
+  }
+  // FIELD: the workgroup's block behind the parks -- the frame's doubles | u32[5 counters (of 8 words) | PatchFieldSink::lds_words
+  // of the field (none in the global form)]
+  uint32_t* fblk = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(rblk) + sizeof(PatchFieldFrame));
+  const volatile LdsFieldFrame& fframe = *(const volatile LdsFieldFrame*)rblk;
+  if constexpr (FIELD) {
+    if (tid == 68) *reinterpret_cast<PatchFieldFrame*>(rblk) = field_arg->f;
+    for (uint32_t b = (uint32_t)tid; b < (uint32_t)kFieldCtrWords + field_arg->lds_words; b += (uint32_t)nthr) fblk[b] = 0u;
   }
   if (tid < 8) sstat[tid] = 0ull;
   if (tid == 64) {
@@ -3378,7 +3462,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       // (the end of a ray as two flags -- lane masks in scalar registers -- instead of a status word per lane; a tracer lane's ray
       //  sits on the inner sphere unless it is fresh, so Ray::on is neither read nor written in the steps)
       bool ended = false, susp = false;
-      int eslot = 0;   // RESP, VIEW: the class of the arrival that absorbed the lane's ray
+      int eslot = 0;   // RESP, VIEW, FIELD: the class of the arrival that absorbed the lane's ray
       (void)eslot;
       auto arrive = [&](const V3& q, auto ph, bool record = true) {
         if (WALL && record) wall_record(wspec, hist, wall_nmap, K_INNER, r.j, q, 1u);
@@ -3388,7 +3472,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           const int cls = patch_arrive<true>(ptab, n_patch, pcnt, K_INNER, q, hp);
           st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(hp, g, r, seed, first, K_INNER, q);
           if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
-          if constexpr (RESP || VIEW) { if (st == ST_ABSORBED) eslot = cls; }
+          if constexpr (RESP || VIEW || FIELD) { if (st == ST_ABSORBED) eslot = cls; }
         } else st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(h, g, r, seed, first, K_INNER, q);
         if (st != 0) { run = false; ended = true; susp = st == ST_SUSPENDED; }
       };
@@ -3507,6 +3591,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           if (ORDER) order_record(ospec, hist, false, false, susp, r.j, 0.0);
           if constexpr (RESP) resp_record(*resp_arg, rblk, n_patch, n_baf, susp ? kRespSuspended : eslot, seed, first + (uint64_t)r.offset());
           if constexpr (VIEW) { if (!susp && eslot == view_arg->patch) view_record(*view_arg, rblk, r.j, r.v); }
+          if constexpr (FIELD) { if (!susp && eslot == field_arg->patch) field_record(*field_arg, fframe, fblk, r.j, r.p, r.v); }
         }
         const unsigned long long me = __ballot(ended);
         if (me) {
@@ -3661,7 +3746,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       bool go = have;
       bool given = false;   // BAFFLE: the ray went back to the tracers from inside the step loop
       (void)given;
-      int eslot = 0;        // RESP, VIEW: the slot of the interaction that absorbed the lane's ray (a wall class, or a baffle's side)
+      int eslot = 0;        // RESP, VIEW, FIELD: the slot of the interaction that absorbed the lane's ray (a wall class, or a baffle's side)
       (void)eslot;
       for (;;) {
         if (go) {
@@ -3685,14 +3770,14 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
               atomicAdd(&bcnt[ks], 1u);
               st = baffle_arrive(baf, h, r, seed, first, ks >> 1, ks & 1);
               if (st == ST_ABSORBED) atomicAdd(&bcnt[2 * kMaxBaffles + ks], 1u);
-              if constexpr (RESP || VIEW) eslot = kRespBaffle0 + ks;
+              if constexpr (RESP || VIEW || FIELD) eslot = kRespBaffle0 + ks;
             } else {
               Hot hp = h;
               int cls = 0;
               if (kind != K_BOX) cls = patch_arrive<false>(ptab, n_patch, pcnt, kind, q, hp);
               st = ray_arrive<false, LEAN, CH, PH_DIRECT, true, SURF>(hp, g, r, seed, first, kind, q);
               if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
-              if constexpr (RESP || VIEW) eslot = cls;
+              if constexpr (RESP || VIEW || FIELD) eslot = cls;
             }
           } else if constexpr (PATCH) {
             Hot hp = h;
@@ -3799,6 +3884,9 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       if constexpr (VIEW) {   // (a baffle's side is a slot above every wall class: never the selected one)
         if (ended && st == ST_ABSORBED && eslot == view_arg->patch) view_record(*view_arg, rblk, r.j, r.v);
       }
+      if constexpr (FIELD) {   // (likewise)
+        if (ended && st == ST_ABSORBED && eslot == field_arg->patch) field_record(*field_arg, fframe, fblk, r.j, r.p, r.v);
+      }
       const uint32_t c_ended = (uint32_t)__popcll(__ballot(ended));
       n_ended += c_ended;
       n_exited += (uint32_t)__popcll(__ballot(exited));
@@ -3838,7 +3926,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         n_inc += (unsigned long long)__popcll(__ballot(hit0)) + (unsigned long long)__popcll(__ballot(hit1));
       }
       const unsigned long long m = (PP != 0 || WALL || ORDER || (PATCH && !SCENE)) ? 0ull : __ballot(keep);
-      if (!RESP && !VIEW && m) {   // (RESP, VIEW: no exit lines -- the response / the view is the build's one sink, no kernel follows)
+      if (!RESP && !VIEW && !FIELD && m) {   // (RESP, VIEW, FIELD: no exit lines -- the response / the view / the field is the build's one sink, no kernel follows)
         const uint32_t cnt = (uint32_t)__popcll(m);
         if (cnt > reg_left) {   // close the open region, reserve the next one (kRegion)
           if (lane == 0 && reg_id != 0xffffffffu) d_arg.rec_counts[reg_id] = kRegion - reg_left;
@@ -3965,6 +4053,17 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     }
     __syncthreads();
   }
+  if constexpr (FIELD) {   // one flush of the workgroup's field, then of its five counters; bin_increments = binned
+    const uint32_t flushed = field_flush(*field_arg, fblk, tid_end, (uint32_t)blockDim.x);
+    if (flushed) atomicAdd(&fblk[kFieldBinned], flushed);
+    __syncthreads();
+    if (tid_end < (uint32_t)kFieldCounters) {
+      const uint32_t c = fblk[tid_end];
+      if (c) global_add_u64(field_arg->counts + tid_end, (unsigned long long)c);
+      if (tid_end == (uint32_t)kFieldBinned && c) atomicAdd(&sstat[5], (unsigned long long)c);
+    }
+    __syncthreads();
+  }
   if constexpr (BAFFLE) {   // one flush of the workgroup's counters (the thread index rebuilt, as the beam kernel's)
     uint32_t t3 = tid_end;
     asm volatile("" : "+v"(t3));
@@ -4057,6 +4156,15 @@ isx_trace_assist_scene_view_kernel(const Geom g, const DetGrid d, const Work wk,
                                    const ViewSink view) {
   assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true, false, true>(g, d, wk, &tab, &beam, nullptr, &baf, nullptr,
                                                                                                    &view);
+}
+// the scene patch field (isx_scene_patch_field): the scene kernel with one add per ray absorbed on the selected wall class -- where
+// on the patch it lands and the direction it arrived from, binned in the patch's frame (field_record) -- and no exit lines; the
+// sink is a seventh argument
+extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_SCENE_WAVES, ISX_SCENE_WAVES)))
+isx_trace_assist_scene_field_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab, const BeamSrc beam, const BaffleTab baf,
+                                    const PatchFieldSink field) {
+  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true, false, false, true>(g, d, wk, &tab, &beam, nullptr, &baf,
+                                                                                                          nullptr, nullptr, &field);
 }
 // the flux pipeline behind the fate scan: isx_trace_assist_kernel on the rays of a list; the list is a fourth argument
 extern "C" __global__ void ISX_ASSIST_ATTR

@@ -320,3 +320,21 @@ def scene_view_sharded(trace: Callable, cfg, scene, vspec, n_total: int, seed: i
 
     out = fluxmap_scene_sharded(one, cfg, scene, n_total, seed, first_ray, device)
     return (out[0][:-4].reshape(shape[0]), out[0][-4:]) + tuple(out[1:])
+
+
+def scene_patch_field_sharded(trace: Callable, cfg, scene, fspec, n_total: int, seed: int, first_ray: int = 0, device=None):
+    """The patch field of a scene (altair_raytracing_amd.scene_patch_field) ray-sharded: this rank's contiguous shard through
+    `trace(cfg, scene, fspec, count, seed, first) -> (field, field_counts, scene_counts, stats)`, then ONE SUM all-reduce that
+    carries the field, the 5 field counters, the 36 scene counters and the census -- scene_view_sharded with the field and its
+    five counters in the map's place.  Returns (field[n_y, n_x, n_v, n_u] uint64, field_counts[5] uint64 (binned, pos_outside,
+    dir_outside, behind, direct), patch_arrivals[10] uint64, patch_absorbed[10] uint64, baffle arrivals[4, 2] uint64, baffle
+    absorbed[4, 2] uint64, census dict) -- identical on every rank."""
+    shape = []
+
+    def one(c, sp, count, sd, first):
+        field, fc, cnt, st = trace(c, sp, fspec, count, sd, first)
+        shape.append(field.shape)
+        return np.concatenate([np.asarray(field, dtype=np.uint64).reshape(-1), fc.words()]), cnt, st
+
+    out = fluxmap_scene_sharded(one, cfg, scene, n_total, seed, first_ray, device)
+    return (out[0][:-5].reshape(shape[0]), out[0][-5:]) + tuple(out[1:])

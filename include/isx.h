@@ -207,6 +207,8 @@ int isx_last_kernel_ms(double* single_ms, double* trace_ms, double* bin_ms);
  *                  atomic add per ended ray for a larger one; 1: the global form for every spec (a diagnostic)
  *   "view_global"  0 (default): isx_scene_view keeps a map that fits in the workgroup's LDS there and takes one global atomic
  *                  add per binned ray for a larger one; 1: the global form for every spec (a diagnostic)
+ *   "field_global" 0 (default): isx_scene_patch_field keeps a field that fits in the workgroup's LDS there and takes one global
+ *                  atomic add per binned ray for a larger one; 1: the global form for every spec (a diagnostic)
  *   "bin_block", "bin_blocks_per_cu"  shape of round 2's binning kernel (0 workgroups per CU = what is resident)
  *                  (round 5: "assist_block" 0 = the default again -- 768 threads, 256 for launches below 1e6 rays, 512 for the lobe /
  *                  rough-specular kernels; "rays_per_lane" > 0 sizes every grid for that many rays per tracer lane, 0 = by launch
@@ -912,8 +914,8 @@ int isx_fluxmap_baffle_device(const isx_config* cfg, const isx_baffle_spec* spec
  * (the detector grid included, for the two flux-map calls) and isx_wall_patches of `patches` -- each nested struct_size must be
  * right as well as the outer one.  ISX_ERR_BAD_ARG: a NULL pointer (start_point, start_dir, last_baffle, last_class, counts and
  * stats excepted).  Out of scope: a scene for the other sinks (exit maps, wall map, light field, order histograms, disc sweeps;
- * the fates over the source's sample space are isx_scene_response, the directions a wall detector sees isx_scene_view), the chord
- * mode, the other borders and the BRDF source.
+ * the fates over the source's sample space are isx_scene_response, the directions a wall detector sees isx_scene_view, where on
+ * a patch the light lands isx_scene_patch_field), the chord mode, the other borders and the BRDF source.
  */
 typedef struct isx_scene_spec {
   uint32_t struct_size;        /* sizeof(isx_scene_spec), set by isx_default_scene_spec() */
@@ -1070,8 +1072,8 @@ int isx_response_reweight(const isx_response_spec* rspec, const uint64_t* respon
  * (0, 1], a non-finite frame component, (axis, e1, e2) not orthonormal to 1e-12 by the beam contract's test;
  * ISX_ERR_BAD_ARG: a NULL cfg, scene, vspec or view (device form: d_view, d_view_counts, d_scene_counts).  Without a HIP device:
  * ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT (as isx_fluxmap_scene).
- * Out of scope: more than one patch per call, the position on the patch, views from baffle sides, the isx_macro command line, scenes
- * for the remaining sinks.
+ * Out of scope: more than one patch per call, views from baffle sides, the isx_macro command line, scenes for the remaining sinks
+ * (the position on the patch, jointly with the direction, is isx_scene_patch_field).
  */
 #define ISX_VIEW_MAX_AXIS 1024
 #define ISX_VIEW_MAX_BINS 65536
@@ -1124,6 +1126,97 @@ int isx_view_reweight(const isx_view_spec* vspec, const uint64_t* view, const is
  * vspec or weight; ISX_ERR_BAD_CONFIG: a spec isx_scene_view refuses (as above), a half angle outside [0, 90] or not finite.
  */
 int isx_view_weight_fov(const isx_view_spec* vspec, double half_angle_deg, double* weight /*[n_v * n_u]*/);
+
+/*
+ * Scene patch field: WHERE on a wall patch the light lands and from which direction -- the rays a wall class of a scene absorbs,
+ * binned jointly over the position of the arrival on the patch and the direction they arrive from, in the patch's own frame.
+ * isx_scene_view sums over the patch's surface; this is the joint 4-D quantity, as isx_light_field is for the port after
+ * isx_exit_maps.  What it answers: is the detector's active area (or the sample over a port) evenly lit, does a baffle's shadow edge
+ * fall across it, does the angular picture change from one side of the patch to the other.
+ *
+ * The ray histories are those of isx_fluxmap_scene / isx_scene_endstates for the same (cfg, scene, seed, ray index): nothing of a
+ * history changes.  A ray is SELECTED if and only if its fate slot, as isx_scene_response defines it, equals fspec->patch.  For
+ * every selected ray, with q = last_point, d = direction and n_points as isx_scene_endstates reports them, inv = 1.0 / cfg->r_in
+ * formed once on the host, h = half_extent, s = pos_scale, in this order, in IEEE double, every expression left to right as
+ * written, no fma, / and sqrt correctly rounded:
+ *
+ *       n_points == 2                       : direct += 1, nothing else                      (as isx_scene_view)
+ *       cd = (d.x*axis[0] + d.y*axis[1]) + d.z*axis[2]
+ *       cd > 0.0 is false                   : behind += 1, nothing else                      (NaN included; as isx_scene_view)
+ *       c  = ((q.x*axis[0] + q.y*axis[1]) + q.z*axis[2]) * inv
+ *       w  = sqrt(0.5 / (1.0 + c))
+ *       a  = (q.x*e1[0] + q.y*e1[1]) + q.z*e1[2] ;  b likewise with e2
+ *       X  = ((a * inv) * w) * s ;  Y = ((b * inv) * w) * s
+ *       fx = (X + 1.0) * 0.5 * n_x ; ix = (int)floor(fx)                                     (same with Y, n_y -> iy)
+ *       not (0 <= ix < n_x and 0 <= iy < n_y) : pos_outside += 1, nothing else               (NaN / inf included)
+ *       (iu, iv) from d by isx_scene_view's formulas, operation for operation (mag, a, b, U, V, fu, fv, floor)
+ *       not (0 <= iu < n_u and 0 <= iv < n_v) : dir_outside += 1
+ *       else  field[((iy * n_x + ix) * n_v + iv) * n_u + iu] += 1 ,  binned += 1
+ *
+ * (X, Y) is the Lambert azimuthal equal-area projection of the wall about the patch's axis -- the wall map's projection in another
+ * frame -- scaled so that a cap of half-angle alpha fills the unit disc when s = 1 / sin(alpha / 2): equal areas of the patch are
+ * equal areas of the map.  The antipode of the axis (c = -1) has no image and counts as pos_outside.  The irradiance on the patch
+ * is proportional to count / (N dx dy), dx = 2 / n_x, dy = 2 / n_y; the radiance to count / (N dx dy du dv) in direction-cosine
+ * space, du = 2 h / n_u, dv = 2 h / n_v.  An evenly lit patch under a Lambertian interior gives a flat field inside the two discs.
+ *
+ * For every call: binned + pos_outside + dir_outside + behind + direct == scene_counts.patch_absorbed[patch]; field sums to
+ * binned; stats.bin_increments == binned; behind and direct equal isx_scene_view's for the same patch and frame; with
+ * n_x = n_y = 1 and every position in range the field is isx_scene_view's map and dir_outside its `outside`; the 36 scene counters
+ * and every other field of stats except t_kernel_ms are isx_fluxmap_scene's for the same arguments.  No result depends on any
+ * isx_set_option switch nor on how a job is cut into calls.  cfg->hit_line_mode and the detector-grid fields of cfg are ignored and
+ * never a reason for refusal.  One route whatever the switches say: isx_trace_assist_scene_field_kernel -- the scene's trace
+ * kernel with one add per binned ray, where the census is taken; it writes no exit lines and no kernel follows it.  A field small
+ * enough is kept as u32 words in the workgroup's LDS and flushed once, a larger one (or any, with "field_global" 1) takes one
+ * global u64 add per binned ray.
+ *
+ * Refused, whether or not a device is present: everything isx_scene_endstates refuses of cfg and scene, with its codes;
+ * ISX_ERR_BAD_CONFIG: struct_size != sizeof(isx_patch_field_spec), a non-zero reserved field, patch outside 0 .. n_patches - 1 (so
+ * a scene without patches), an axis size outside 1..ISX_PATCH_FIELD_MAX_AXIS, n_x * n_y * n_u * n_v > ISX_PATCH_FIELD_MAX_BINS,
+ * half_extent not finite or outside (0, 1], pos_scale not finite or not > 0, a non-finite frame component, (axis, e1, e2) not
+ * orthonormal to 1e-12 by the beam contract's test; ISX_ERR_BAD_ARG: a NULL cfg, scene, fspec or field (device form: d_field,
+ * d_field_counts, d_scene_counts).  Without a HIP device: ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT (as
+ * isx_fluxmap_scene).
+ * Out of scope: a position map of the `direct` rays, more than one patch per call, baffle sides, the isx_macro command line, a
+ * scene for the remaining sinks.
+ */
+#define ISX_PATCH_FIELD_MAX_AXIS 1024
+#define ISX_PATCH_FIELD_MAX_BINS (1 << 22)
+typedef struct isx_patch_field_spec {
+  uint32_t struct_size;      /* sizeof(isx_patch_field_spec), set by isx_patch_field_frame(); a spec of another size is refused */
+  uint32_t reserved0;        /* 0 */
+  int32_t patch;             /* 0 .. scene->patches.n_patches - 1 */
+  int32_t n_x, n_y;          /* position bins, each 1 .. ISX_PATCH_FIELD_MAX_AXIS */
+  int32_t n_u, n_v;          /* direction bins, likewise; n_x * n_y * n_u * n_v <= ISX_PATCH_FIELD_MAX_BINS */
+  int32_t reserved1;         /* 0 */
+  double axis[3], e1[3], e2[3];  /* the patch's outward normal and its two in-plane axes: USED AS GIVEN */
+  double half_extent;        /* h in (0, 1]: the direction part covers [-h, h]^2 of the direction cosines */
+  double pos_scale;          /* s > 0: the position part covers [-1, 1]^2 of the scaled projection; USED AS GIVEN */
+} isx_patch_field_spec;      /* 120 bytes */
+typedef struct isx_patch_field_counts { uint64_t binned, pos_outside, dir_outside, behind, direct; } isx_patch_field_counts;   /* 40 bytes */
+
+/* The spec for a patch of a scene: the frame by isx_view_frame's rule, pos_scale = 1.0 / sqrt(0.5 * (1.0 - min_dot / cfg->r_in))
+ * of that patch (the cap fills the unit disc).  Host only, no GPU needed.  ISX_ERR_BAD_CONFIG where that scale is not finite and
+ * positive (a cap of zero angle); otherwise refuses what isx_scene_patch_field refuses (ISX_ERR_BAD_ARG: a NULL cfg, scene or
+ * out). */
+int isx_patch_field_frame(const isx_config* cfg, const isx_scene_spec* scene, int32_t patch, int32_t n_x, int32_t n_y, int32_t n_u,
+                          int32_t n_v, double half_extent, isx_patch_field_spec* out);
+/* Blocking: field[n_y * n_x * n_v * n_u], field_counts and scene_counts (host, zeroed by the callee; field_counts, scene_counts
+ * and stats may be NULL). */
+int isx_scene_patch_field(const isx_config* cfg, const isx_scene_spec* scene, const isx_patch_field_spec* fspec, uint64_t n_rays,
+                          uint64_t seed, uint64_t first_ray, uint64_t* field, isx_patch_field_counts* field_counts,
+                          isx_scene_counts* scene_counts, isx_stats* stats);
+/* ACCUMULATES (+=) into d_field [n_y * n_x * n_v * n_u], d_field_counts (5 words, isx_patch_field_counts' layout) and
+ * d_scene_counts (36 words, isx_scene_counts' layout; none may be NULL) on the library's stream and returns after enqueueing;
+ * isx_sync() / isx_take_stats() as for isx_scene_view_device. */
+int isx_scene_patch_field_device(const isx_config* cfg, const isx_scene_spec* scene, const isx_patch_field_spec* fspec, uint64_t n_rays,
+                                 uint64_t seed, uint64_t first_ray, uint64_t* d_field, uint64_t* d_field_counts /*[5]*/,
+                                 uint64_t* d_scene_counts /*[36]*/);
+/* The two marginals of a field: pos_map[iy * n_x + ix] = the sum over (iv, iu), dir_map[iv * n_u + iu] = the sum over (iy, ix);
+ * either may be NULL.  dir_map is what isx_view_reweight takes, through a view spec with the same frame.  Host only, no GPU
+ * needed.  ISX_ERR_BAD_ARG: a NULL fspec or field; ISX_ERR_BAD_CONFIG: a spec isx_scene_patch_field refuses (the patch index is
+ * not looked at: no scene is given). */
+int isx_patch_field_marginals(const isx_patch_field_spec* fspec, const uint64_t* field, uint64_t* pos_map /*[n_y * n_x]*/,
+                              uint64_t* dir_map /*[n_v * n_u]*/);
 
 /*
  * Series driver (sweepSeries, fluxAtObserverOptimize.C:892-921 / fluxAtObserverFast.C:1641-1673):
