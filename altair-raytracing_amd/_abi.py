@@ -54,6 +54,8 @@ EXPORTS = [
     "isx_default_response_spec", "isx_scene_response", "isx_scene_response_device", "isx_response_reweight",
     "isx_view_frame", "isx_scene_view", "isx_scene_view_device", "isx_view_reweight", "isx_view_weight_fov",
     "isx_patch_field_frame", "isx_scene_patch_field", "isx_scene_patch_field_device", "isx_patch_field_marginals",
+    "isx_default_scene_order_spec", "isx_scene_order_hist", "isx_scene_order_hist_device", "isx_scene_order_reweight",
+    "isx_scene_order_moments",
 ]
 
 
@@ -346,6 +348,25 @@ class PatchFieldCounts(C.Structure):
         return np.frombuffer(bytes(self), dtype=np.uint64).copy()
 
 
+SCENE_ORDER_MAX_ORDERS = 65536
+
+
+class SceneOrderSpec(C.Structure):
+    """isx_scene_order_spec (include/isx.h): orders 0 .. n_orders - 1 per fate slot."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("n_orders", C.c_int32), ("reserved1", C.c_int32)]
+
+
+class SceneOrderCounts(C.Structure):
+    """isx_scene_order_counts (include/isx.h): per fate slot, the rays whose order is n_orders or more."""
+
+    _fields_ = [("overflow", C.c_uint64 * RESPONSE_FATES)]
+
+    def words(self):
+        """-> the 21 words (the device form's layout)"""
+        return np.frombuffer(bytes(self), dtype=np.uint64).copy()
+
+
 _lib = None
 
 
@@ -444,6 +465,15 @@ def load():
     L.isx_scene_patch_field_device.argtypes = [P(Config), P(SceneSpec), P(PatchFieldSpec), u64, u64, u64, C.c_void_p, C.c_void_p,
                                                C.c_void_p]
     L.isx_patch_field_marginals.argtypes = [P(PatchFieldSpec), P(u64), P(u64), P(u64)]
+    L.isx_default_scene_order_spec.argtypes = [P(Config), P(SceneOrderSpec)]
+    L.isx_default_scene_order_spec.restype = None
+    L.isx_scene_order_hist.argtypes = [P(Config), P(SceneSpec), P(SceneOrderSpec), u64, u64, u64, P(u64), P(SceneOrderCounts),
+                                       P(SceneCounts), P(Stats)]
+    L.isx_scene_order_hist_device.argtypes = [P(Config), P(SceneSpec), P(SceneOrderSpec), u64, u64, u64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
+    L.isx_scene_order_reweight.argtypes = [P(Config), P(SceneSpec), P(SceneOrderSpec), P(u64), P(SceneOrderCounts), u64, P(dbl), i32,
+                                           P(dbl), P(dbl)]
+    L.isx_scene_order_moments.argtypes = [P(SceneOrderSpec), P(u64), P(SceneOrderCounts), P(dbl), P(dbl)]
     _lib = L
     return L
 
@@ -1173,6 +1203,90 @@ def patch_field_marginals(fspec, field):
     _chk(load().isx_patch_field_marginals(C.byref(fspec), _p(f, C.c_uint64), _p(pos, C.c_uint64), _p(dr, C.c_uint64)),
          "isx_patch_field_marginals")
     return pos.reshape(ny, nx), dr.reshape(nv, nu)
+
+
+def default_scene_order_spec(cfg):
+    """512 orders per fate slot (no GPU needed)."""
+    s = SceneOrderSpec()
+    load().isx_default_scene_order_spec(C.byref(cfg), C.byref(s))
+    return s
+
+
+def scene_order_spec(n_orders):
+    """-> SceneOrderSpec with orders 0 .. n_orders - 1 per fate slot (checked by the calls)."""
+    s = SceneOrderSpec()
+    s.struct_size = C.sizeof(SceneOrderSpec)
+    s.n_orders = int(n_orders)
+    return s
+
+
+def _scene_orders(ospec):
+    """n_orders of the arrays a call may touch; 1 for a spec the library refuses (it says so itself)."""
+    return int(ospec.n_orders) if 1 <= int(ospec.n_orders) <= SCENE_ORDER_MAX_ORDERS else 1
+
+
+def scene_order_hist(cfg, scene, ospec, n_rays, seed, first_ray=0):
+    """-> (hist[21, n_orders] uint64, SceneOrderCounts, SceneCounts, Stats): the fate of every ray of the scene (scene_response's
+    slots) by its interaction count k; a ray with k >= n_orders is counted in overflow[fate] instead (include/isx.h:
+    isx_scene_order_hist)."""
+    K = _scene_orders(ospec)
+    hist = np.zeros(RESPONSE_FATES * K, dtype=np.uint64)
+    st = Stats()
+    oc = SceneOrderCounts()
+    cnt = SceneCounts()
+    _chk(load().isx_scene_order_hist(C.byref(cfg), C.byref(scene), C.byref(ospec), int(n_rays), int(seed), int(first_ray),
+                                     _p(hist, C.c_uint64), C.byref(oc), C.byref(cnt), C.byref(st)), "isx_scene_order_hist")
+    return hist.reshape(RESPONSE_FATES, K), oc, cnt, st
+
+
+def scene_order_hist_device(cfg, scene, ospec, n_rays, seed, first_ray, d_hist_ptr, d_order_counts_ptr, d_scene_counts_ptr):
+    """Enqueue on the library stream, accumulating into device memory at d_hist_ptr ([21 * n_orders] uint64), d_order_counts_ptr
+    ([21] uint64, SceneOrderCounts' layout) and d_scene_counts_ptr ([36] uint64, SceneCounts' layout)."""
+    _chk(load().isx_scene_order_hist_device(C.byref(cfg), C.byref(scene), C.byref(ospec), int(n_rays), int(seed), int(first_ray),
+                                            C.c_void_p(int(d_hist_ptr or 0) or None),
+                                            C.c_void_p(int(d_order_counts_ptr or 0) or None),
+                                            C.c_void_p(int(d_scene_counts_ptr or 0) or None)), "isx_scene_order_hist_device")
+
+
+def _scene_order_counts(counts):
+    if isinstance(counts, SceneOrderCounts):
+        return counts
+    oc = SceneOrderCounts()
+    w = np.asarray(counts, dtype=np.uint64).reshape(-1)
+    for f in range(RESPONSE_FATES):
+        oc.overflow[f] = int(w[f])
+    return oc
+
+
+def scene_order_reweight(cfg, scene, ospec, hist, counts, launched, scale):
+    """-> (fraction[n_scale, 21], sigma[n_scale, 21]): the fate fractions of the same scene with every reflectance -- the wall's,
+    every patch's, every baffle's -- multiplied by scale[i], from one scene_order_hist result (include/isx.h:
+    isx_scene_order_reweight; host only, no GPU needed)."""
+    K = _scene_orders(ospec)
+    h = np.ascontiguousarray(np.asarray(hist, dtype=np.uint64).reshape(-1))
+    if h.size < RESPONSE_FATES * K:
+        raise ValueError("hist has %d words, the spec wants %d" % (h.size, RESPONSE_FATES * K))
+    t = np.ascontiguousarray(np.asarray(scale, dtype=np.float64).reshape(-1))
+    oc = _scene_order_counts(counts)
+    frac, sig = np.zeros((t.size, RESPONSE_FATES)), np.zeros((t.size, RESPONSE_FATES))
+    _chk(load().isx_scene_order_reweight(C.byref(cfg), C.byref(scene), C.byref(ospec), _p(h, C.c_uint64), C.byref(oc), int(launched),
+                                         _p(t, C.c_double), int(t.size), _p(frac, C.c_double), _p(sig, C.c_double)),
+         "isx_scene_order_reweight")
+    return frac, sig
+
+
+def scene_order_moments(ospec, hist, counts):
+    """-> (mean[21], sd[21]) of the interaction count k per fate slot: the time response in interactions; NaN for an empty row and
+    for a row with overflow (include/isx.h: isx_scene_order_moments; host only, no GPU needed)."""
+    K = _scene_orders(ospec)
+    h = np.ascontiguousarray(np.asarray(hist, dtype=np.uint64).reshape(-1))
+    if h.size < RESPONSE_FATES * K:
+        raise ValueError("hist has %d words, the spec wants %d" % (h.size, RESPONSE_FATES * K))
+    oc = _scene_order_counts(counts)
+    mean, sd = np.zeros(RESPONSE_FATES), np.zeros(RESPONSE_FATES)
+    _chk(load().isx_scene_order_moments(C.byref(ospec), _p(h, C.c_uint64), C.byref(oc), _p(mean, C.c_double), _p(sd, C.c_double)),
+         "isx_scene_order_moments")
+    return mean, sd
 
 
 def fluxmap_series(cfgs, n_rays, seed, first_ray=0):

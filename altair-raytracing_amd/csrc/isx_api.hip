@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <limits>
 #include <map>
 #include <new>
 #include <tuple>
@@ -89,6 +90,8 @@ struct State {
   int lf_global = 0;                            // 1: isx_bin_lightfield_kernel's global form for a field that fits the LDS as well (diagnostic)
   int resp_global = 0;                          // 1: isx_trace_assist_scene_response_kernel's global form for a response that fits the LDS as well (diagnostic)
   int field_global = 0;                         // 1: isx_trace_assist_scene_field_kernel's global form for a field that fits the LDS as well (diagnostic)
+  int sorder_lds_orders = -1;                   // isx_trace_assist_scene_order_kernel: -1 as many orders in the workgroup's LDS as cost no resident workgroup;
+                                                // n > 0: at most n of them; 0: none, one global add per ended ray (diagnostic)
   int view_global = 0;                          // 1: isx_trace_assist_scene_view_kernel's global form for a map that fits the LDS as well (diagnostic)
   int surface_pipeline = 1;                     // 1 (default): the lobe / rough-specular borders and the origin-compat hit line on the assist-wave
                                                 // pipeline (round 5); 0: round 1's fused isx_trace_bin_full_kernel
@@ -748,6 +751,17 @@ int check_patch_field_spec(const isx_patch_field_spec* s, int n_patches) {
 }
 size_t patch_field_bins(const isx_patch_field_spec& s) { return (size_t)s.n_x * (size_t)s.n_y * (size_t)s.n_u * (size_t)s.n_v; }
 
+// isx_scene_order_hist: the checked spec and the device arrays of the call (the histograms [ISX_RESPONSE_FATES][n_orders], the 21
+// words of isx_scene_order_counts); the scene travels as SceneSink
+struct SceneOrderCall { const isx_scene_order_spec* spec = nullptr; unsigned long long* out = nullptr; unsigned long long* overflow = nullptr; };
+static_assert(sizeof(isx_scene_order_spec) == 16 && sizeof(isx_scene_order_counts) == kRespFates * sizeof(uint64_t),
+              "isx.h: isx_scene_order_spec, and sorder_record's overflow counters");
+// isx.h: the limits of a scene order spec
+int check_scene_order_spec(const isx_scene_order_spec* s) {
+  if (s->struct_size != (uint32_t)sizeof(isx_scene_order_spec) || s->reserved0 != 0u || s->reserved1 != 0) return ISX_ERR_BAD_CONFIG;
+  return s->n_orders >= 1 && s->n_orders <= ISX_SCENE_ORDER_MAX_ORDERS ? ISX_OK : ISX_ERR_BAD_CONFIG;
+}
+
 // LDS of a workgroup's histogram: 4 B per bin, 16-byte aligned
 size_t hist_lds(int nbins) { return ((size_t)nbins * 4 + 15) & ~(size_t)15; }
 
@@ -860,7 +874,7 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
     d.xm_dir = wp->arrivals; d.xm_pos = wp->absorbed;
     d.nbins = 2 * (wp->spec->n_patches + 2);
     lds = patch_lds() + 64 + sizeof(Geom) + sizeof(DetGrid);
-  } else if (sink == SINK_RESPONSE || sink == SINK_VIEW || sink == SINK_FIELD) {
+  } else if (sink == SINK_RESPONSE || sink == SINK_VIEW || sink == SINK_FIELD || sink == SINK_SORDER) {
     // (isx.h: hit_line_mode and the detector grid are ignored -- no exit line is written, no grid is looked at; the scene and the
     //  response spec were checked by the entry, the patches' words are enqueue's)
     d.hit_line_mode = ISX_HITLINE_LAST_SEGMENT;
@@ -903,6 +917,7 @@ typedef void (*SceneFn)(const Geom, const DetGrid, const Work, const PatchTab, c
 typedef void (*ResponseFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab, const RespSink);
 typedef void (*ViewFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab, const ViewSink);
 typedef void (*PatchFieldFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab, const PatchFieldSink);
+typedef void (*SceneOrderFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab, const SOrderSink);
 struct Plan {
   Route route = ROUTE_FUSED;
   KernelFn fn = nullptr;        // the kernel (a pipeline's trace kernel)
@@ -938,6 +953,8 @@ struct Plan {
   ViewSink view{};              // (view.lds_words: plan_launch's choice of the form; the rest is enqueue's)
   PatchFieldFn field_fn = nullptr;  // isx_scene_patch_field: ROUTE_ASSIST's one kernel (the scene's three arguments, and field the seventh) instead of fn
   PatchFieldSink field{};       // (field.lds_words: plan_launch's choice of the form; the rest is enqueue's)
+  SceneOrderFn sorder_fn = nullptr; // isx_scene_order_hist: ROUTE_ASSIST's one kernel (the scene's three arguments, and sorder the seventh) instead of fn
+  SOrderSink sorder{};          // (sorder.lds_orders: plan_launch's choice of L; the rest is enqueue's)
 };
 
 // "fate_scan" = -1: where the scan pays (measured on MI355X, docs/LOG.md section 16.3).  A small launch is bound by its longest
@@ -983,7 +1000,8 @@ void trace_shape(Plan& p, Shape sh, bool assist, int per_cu) {
 }
 
 Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bool discs_in_aux, uint64_t n, bool beam = false,
-                 const FateConsts* fate = nullptr, bool baffle = false, bool scene = false, size_t resp_words = 0) {
+                 const FateConsts* fate = nullptr, bool baffle = false, bool scene = false, size_t resp_words = 0,
+                 int n_orders = 0) {
   enum { LAMBERT, LOBE, ROUGH } const border =
       c->surface_model == ISX_SURFACE_LOBE ? LOBE : c->lambertian ? LAMBERT : ROUGH;   // (ISX_SURFACE_ROBAST: Lambertian or rough-specular)
   const bool pencil = c->source_model == ISX_SOURCE_PENCIL;   // (else ISX_SOURCE_BRDF)
@@ -1061,6 +1079,28 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
       p.field.lds_words = (uint32_t)resp_words;
       p.lds = with;
     }
+    return p;
+  }
+  // The scene order histograms (isx_scene_order_hist): the same route and shape -- the scene's trace kernel with the histograms as
+  // its one sink.  Behind the parks lie the overflow counters (kSOrderHead words, always) and the first L orders of each of the
+  // scene's `resp_words` compact slots as u32 words, flushed once per workgroup; the orders from L on take one global u64 add each
+  // (isx_kernels.hpp: sorder_record).  L is as large as the LDS allows without costing a resident workgroup -- the response's
+  // rule, solved for the block's size: the 2 KiB-rounded sum times the resident count stays within lds_limit -- and at most
+  // n_orders; "sorder_lds_orders" >= 0 caps it (0: every order is global).  L is SOrderSink::lds_orders, nothing else.
+  if (sink == SINK_SORDER) {
+    p.route = ROUTE_ASSIST;
+    p.sorder_fn = isx_trace_assist_scene_order_kernel;
+    p.launch_max = std::min(kLaunchMax, S.pipe_chunk);
+    trace_shape(p, small_shape(std::min(n, p.launch_max), S.assist_block_set ? S.assist_block : kSceneBlock), true,
+                resident_unless(S.trace_blocks_per_cu));
+    p.lds += SceneLds::bytes(p.tracers) + kSOrderHead * sizeof(uint32_t);
+    const size_t resident = (size_t)blocks_per_cu(p.sorder_fn, p.block, p.lds, kResident);
+    const size_t cap = (S.lds_limit / resident) & ~(size_t)2047;   // (the largest 2 KiB-rounded size `resident` workgroups can have)
+    const size_t free_words = cap > p.lds ? ((cap - p.lds) & ~(size_t)15) / 4 : 0;
+    size_t L = std::min((size_t)n_orders, free_words / resp_words);
+    if (S.sorder_lds_orders >= 0) L = std::min(L, (size_t)S.sorder_lds_orders);
+    p.sorder.lds_orders = (uint32_t)L;
+    p.lds += (L * resp_words * 4 + 15) & ~(size_t)15;
     return p;
   }
 
@@ -1305,9 +1345,10 @@ int span(int kind, size_t* from) { return span_on(S.stream, kind, from); }
 
 // ROUTE_FUSED and ROUTE_ASSIST: launches of at most kLaunchMax rays, one span
 int run_single(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
-  const void* fn = p.field_fn ? (const void*)p.field_fn : p.view_fn ? (const void*)p.view_fn : p.resp_fn ? (const void*)p.resp_fn : p.patch_fn ? (const void*)p.patch_fn : (const void*)p.fn;
+  const void* fn = p.sorder_fn ? (const void*)p.sorder_fn : p.field_fn ? (const void*)p.field_fn : p.view_fn ? (const void*)p.view_fn : p.resp_fn ? (const void*)p.resp_fn : p.patch_fn ? (const void*)p.patch_fn : (const void*)p.fn;
   int rc = set_lds(fn, p.lds); if (rc) return rc;
-  const int per_cu = p.field_fn ? blocks_per_cu(p.field_fn, p.block, p.lds, p.per_cu) :
+  const int per_cu = p.sorder_fn ? blocks_per_cu(p.sorder_fn, p.block, p.lds, p.per_cu) :
+                     p.field_fn ? blocks_per_cu(p.field_fn, p.block, p.lds, p.per_cu) :
                      p.view_fn ? blocks_per_cu(p.view_fn, p.block, p.lds, p.per_cu) :
                      p.resp_fn ? blocks_per_cu(p.resp_fn, p.block, p.lds, p.per_cu) :
                      p.patch_fn ? blocks_per_cu(p.patch_fn, p.block, p.lds, p.per_cu) : blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
@@ -1317,7 +1358,8 @@ int run_single(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
   for (uint64_t off = 0; off < wk.n; off += launch_max) {
     Work w;
     rc = launch_work(wk, off, std::min(wk.n - off, launch_max), 0, S.stream, &w); if (rc) return rc;
-    if (p.field_fn) hipLaunchKernelGGL(p.field_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.field);
+    if (p.sorder_fn) hipLaunchKernelGGL(p.sorder_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.sorder);
+    else if (p.field_fn) hipLaunchKernelGGL(p.field_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.field);
     else if (p.view_fn) hipLaunchKernelGGL(p.view_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.view);
     else if (p.resp_fn) hipLaunchKernelGGL(p.resp_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.resp);
     else if (p.patch_fn) hipLaunchKernelGGL(p.patch_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab);
@@ -1506,7 +1548,7 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
             const WallSink* wm = nullptr, const FieldSink* lf = nullptr, const OrderSink* oh = nullptr,
             const PatchSink* wp = nullptr, const isx_beam_spec* bs = nullptr, const BaffleSink* bf = nullptr,
             const SceneSink* sc = nullptr, const ResponseSink* rs = nullptr, const ViewCall* vw = nullptr,
-            const PatchFieldCall* pf = nullptr) {
+            const PatchFieldCall* pf = nullptr, const SceneOrderCall* so = nullptr) {
   Geom g;
   FateConsts fate;
   isx_config cb;
@@ -1536,10 +1578,12 @@ int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t f
   wk.seed = seed; wk.first = first; wk.n = n; wk.hist = d_hist; wk.stats = d_stats ? d_stats : S.d_stats;
   wk.ctr = nullptr; wk.sub = 0; wk.pad = 0;
   // (a response keeps the scene's compact slots per bin: P + 2 wall classes, two sides per baffle, port / other exits / suspended)
-  const size_t resp_bins = rs ? response_bins(*rs->spec) : 0;
-  const size_t resp_words = rs ? (size_t)((sc->spec->patches.n_patches + 2) + 2 * sc->spec->baffles.n_baffles + 3) * resp_bins : 0;
+  // (the order histograms keep the same slots per order: resp_bins = 1, and plan_launch chooses how many orders)
+  const size_t resp_bins = rs ? response_bins(*rs->spec) : so ? 1 : 0;
+  const size_t resp_words = rs || so ? (size_t)((sc->spec->patches.n_patches + 2) + 2 * sc->spec->baffles.n_baffles + 3) * resp_bins : 0;
   Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n, bs != nullptr, &fate, bf != nullptr, sc != nullptr,
-                       pf ? patch_field_bins(*pf->spec) : vw ? view_bins(*vw->spec) : resp_words);
+                       pf ? patch_field_bins(*pf->spec) : vw ? view_bins(*vw->spec) : resp_words, so ? so->spec->n_orders : 0);
+  if (so) { p.sorder.out = so->out; p.sorder.overflow = so->overflow; p.sorder.n_orders = (uint32_t)so->spec->n_orders; }
   if (pf) {
     const isx_patch_field_spec& v = *pf->spec;
     p.field.out = pf->out; p.field.counts = pf->counts;
@@ -1915,6 +1959,7 @@ int isx_set_option(const char* key, int64_t value) {
   if (!std::strcmp(key, "bin_slots")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.bin_slots = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "lf_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.lf_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "field_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.field_global = (int)value; return ISX_OK; }
+  if (!std::strcmp(key, "sorder_lds_orders")) { if (value < -1 || value > ISX_SCENE_ORDER_MAX_ORDERS) return ISX_ERR_BAD_ARG; S.sorder_lds_orders = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "view_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.view_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "resp_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.resp_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "surface_pipeline")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.surface_pipeline = (int)value; return ISX_OK; }
@@ -3242,6 +3287,145 @@ int isx_patch_field_marginals(const isx_patch_field_spec* fspec, const uint64_t*
       if (pos_map) pos_map[p] += c;
       if (dir_map) dir_map[k] += c;
     }
+  return ISX_OK;
+}
+
+void isx_default_scene_order_spec(const isx_config* cfg, isx_scene_order_spec* ospec) {
+  (void)cfg;   // (the default does not depend on the configuration)
+  if (!ospec) return;
+  std::memset(ospec, 0, sizeof(*ospec));
+  ospec->struct_size = (uint32_t)sizeof(isx_scene_order_spec);
+  ospec->n_orders = 512;
+}
+
+int isx_scene_order_hist_device(const isx_config* cfg, const isx_scene_spec* scene, const isx_scene_order_spec* ospec,
+                                uint64_t n_rays, uint64_t seed, uint64_t first_ray, uint64_t* d_hist, uint64_t* d_order_counts,
+                                uint64_t* d_scene_counts) {
+  // (what needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one)
+  if (!cfg || !scene || !ospec || !d_hist || !d_order_counts || !d_scene_counts) return ISX_ERR_BAD_ARG;
+  int bad = check_scene_call(cfg, scene, false);   // (isx.h: the detector grid is ignored -- isx_scene_endstates' refusals)
+  if (bad == ISX_OK) bad = check_scene_order_spec(ospec);
+  if (bad) return bad;
+  if (!S.init) return not_initialised();
+  const SceneSink sc{scene, (unsigned long long*)d_scene_counts};
+  const SceneOrderCall so{ospec, (unsigned long long*)d_hist, (unsigned long long*)d_order_counts};
+  return enqueue(SINK_SORDER, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                 nullptr, nullptr, nullptr, nullptr, nullptr, &sc, nullptr, nullptr, nullptr, &so);
+}
+
+int isx_scene_order_hist(const isx_config* cfg, const isx_scene_spec* scene, const isx_scene_order_spec* ospec, uint64_t n_rays,
+                         uint64_t seed, uint64_t first_ray, uint64_t* hist, isx_scene_order_counts* order_counts,
+                         isx_scene_counts* scene_counts, isx_stats* stats) {
+  if (!cfg || !scene || !ospec || !hist) return ISX_ERR_BAD_ARG;
+  int rc = check_scene_call(cfg, scene, false);
+  if (rc == ISX_OK) rc = check_scene_order_spec(ospec);
+  if (rc) return rc;
+  if (!S.init) return not_initialised();
+  // the histograms and, behind them, the 21 overflow counters and the 36 scene counters: one device block, one staged result
+  const size_t nb = (size_t)ISX_RESPONSE_FATES * (size_t)ospec->n_orders, nf = kRespFates, nc = kSceneWords,
+               bytes = (nb + nf + nc) * sizeof(unsigned long long);
+  rc = call_open(nb + nf + nc);
+  if (rc) return rc;
+  rc = zero_hist(nb + nf + nc);
+  const SceneSink sc{scene, S.d_hist + nb + nf};
+  const SceneOrderCall so{ospec, S.d_hist, S.d_hist + nb};
+  if (rc == ISX_OK) rc = enqueue(SINK_SORDER, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sc, nullptr, nullptr, nullptr, &so);
+  if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK) {
+    fetch_result(hist, nb * sizeof(unsigned long long));
+    const unsigned long long* tail = reinterpret_cast<const unsigned long long*>(S.h_pin + 64) + nb;
+    if (order_counts) std::memcpy(order_counts, tail, nf * sizeof(unsigned long long));
+    if (scene_counts) std::memcpy(scene_counts, tail + nf, nc * sizeof(unsigned long long));
+  }
+  return rc;
+}
+
+int isx_scene_order_reweight(const isx_config* cfg, const isx_scene_spec* scene, const isx_scene_order_spec* ospec,
+                             const uint64_t* hist, const isx_scene_order_counts* counts, uint64_t launched, const double* scale,
+                             int32_t n_scale, double* fraction, double* sigma) {
+  if (!cfg || !scene || !ospec || !hist || !counts || n_scale < 0 || (n_scale > 0 && (!scale || !fraction))) return ISX_ERR_BAD_ARG;
+  int rc = check_scene_call(cfg, scene, false);
+  if (rc == ISX_OK) rc = check_scene_order_spec(ospec);
+  if (rc) return rc;
+  for (int f = 0; f < ISX_RESPONSE_FATES; ++f)
+    if (counts->overflow[f] != 0) return ISX_ERR_BAD_CONFIG;
+  if (launched == 0) return ISX_ERR_BAD_CONFIG;
+  // rho_f per absorbing slot; -1: a slot the scene cannot fill
+  const int P = scene->patches.n_patches, nbaf = scene->baffles.n_baffles;
+  double rho[kRespPort];
+  for (int f = 0; f < kRespPort; ++f) rho[f] = -1.0;
+  for (int f = 0; f < P; ++f) rho[f] = scene->patches.patch[f].reflectance;
+  rho[P] = rho[P + 1] = cfg->reflectance;
+  for (int b = 0; b < nbaf; ++b) rho[kRespBaffle0 + 2 * b] = rho[kRespBaffle0 + 2 * b + 1] = scene->baffles.baffle[b].reflectance;
+  for (int32_t i = 0; i < n_scale; ++i) {
+    const double t = scale[i];
+    if (!(std::isfinite(t) && t >= 0)) return ISX_ERR_BAD_ARG;
+    for (int f = 0; f < kRespPort; ++f)
+      if (rho[f] >= 0 && t * rho[f] > 1.0) return ISX_ERR_BAD_ARG;
+  }
+  const double n = (double)launched;
+  const size_t K = (size_t)ospec->n_orders;
+  for (int32_t i = 0; i < n_scale; ++i) {
+    const double t = scale[i];
+    for (int f = 0; f < ISX_RESPONSE_FATES; ++f) {
+      const uint64_t* row = hist + (size_t)f * K;
+      double* frac = fraction + (size_t)i * ISX_RESPONSE_FATES + f;
+      double* sig = sigma ? sigma + (size_t)i * ISX_RESPONSE_FATES + f : nullptr;
+      double s1 = 0, s2 = 0;
+      if (f >= kRespPort) {
+        for (size_t k = 0; k < K; ++k) {
+          const double w = std::pow(t, (double)k), h = (double)row[k];
+          s1 += h * w;
+          s2 += h * w * w;
+        }
+      } else if (rho[f] < 0) {
+        // (nothing can be absorbed there)
+      } else if (rho[f] == 1.0) {
+        s1 = s2 = t == 1.0 ? 0.0 : std::numeric_limits<double>::quiet_NaN();
+      } else {
+        const double a = (1.0 - t * rho[f]) / (1.0 - rho[f]);
+        for (size_t k = 1; k < K; ++k) {
+          const double w = a * std::pow(t, (double)k - 1.0), h = (double)row[k];
+          s1 += h * w;
+          s2 += h * w * w;
+        }
+      }
+      *frac = s1 / n;
+      if (sig) {
+        const double var = s2 - s1 * s1 / n;
+        *sig = std::isnan(var) ? var : std::sqrt(var > 0 ? var : 0.0) / n;
+      }
+    }
+  }
+  return ISX_OK;
+}
+
+int isx_scene_order_moments(const isx_scene_order_spec* ospec, const uint64_t* hist, const isx_scene_order_counts* counts,
+                            double* mean, double* sd) {
+  if (!ospec || !hist || !counts) return ISX_ERR_BAD_ARG;
+  const int rc = check_scene_order_spec(ospec);
+  if (rc) return rc;
+  const size_t K = (size_t)ospec->n_orders;
+  for (int f = 0; f < ISX_RESPONSE_FATES; ++f) {
+    const uint64_t* row = hist + (size_t)f * K;
+    double N = 0, A = 0, B = 0;
+    for (size_t k = 0; k < K; ++k) {
+      const double h = (double)row[k], x = (double)k;
+      N += h;
+      A += x * h;
+      B += x * x * h;
+    }
+    double m = std::numeric_limits<double>::quiet_NaN(), d = m;
+    if (N > 0 && counts->overflow[f] == 0) {
+      m = A / N;
+      const double var = B / N - m * m;
+      d = std::sqrt(var > 0 ? var : 0.0);
+    }
+    if (mean) mean[f] = m;
+    if (sd) sd[f] = d;
+  }
   return ISX_OK;
 }
 

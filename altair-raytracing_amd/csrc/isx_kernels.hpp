@@ -124,7 +124,8 @@ enum : int { SINK_FLUX = 0, SINK_DZ = 1, SINK_DISC = 2, SINK_PERPOS = 3, SINK_LO
               SINK_LIGHTFIELD = 9, SINK_ORDER = 10, SINK_PATCH = 11,
               SINK_RESPONSE = 12,     // (isx_scene_response: no kernel is built on it -- the host's name for the scene's second sink)
               SINK_VIEW = 13,         // (isx_scene_view: likewise, the scene's third sink)
-              SINK_FIELD = 14 };      // (isx_scene_patch_field: likewise, the scene's fourth sink)
+              SINK_FIELD = 14,        // (isx_scene_patch_field: likewise, the scene's fourth sink)
+              SINK_SORDER = 15 };     // (isx_scene_order_hist: likewise, the scene's fifth sink)
 
 struct Work {
   uint64_t seed, first, n;    // one launch traces rays [first, first + n), n < 2^31 (a lane keeps a 31-bit offset from `first`)
@@ -2479,6 +2480,46 @@ __device__ __forceinline__ uint32_t field_flush(const PatchFieldSink& s, const u
   return flushed;
 }
 
+// ------------------------------------------------------------------ scene order histograms (isx.h: isx_scene_order_hist)
+// The order sink of a call as the kernel gets it (a kernel argument of its own, read where it is used): the device histograms
+// [kRespFates][n_orders] and the kRespFates overflow counters (+=), n_orders, and L = lds_orders: the orders 0 .. L - 1 of every
+// compact slot (RESP's: P + 2 wall classes | 2 per baffle | port, other exits, suspended) are u32 words of the workgroup's LDS --
+// an order histogram is peaked at low k, a small hot array in global memory is what RESP's global form pays for -- and the orders
+// L .. n_orders - 1, rare and spread over many addresses, take one global u64 add each.  L = 0: every order is global (the
+// diagnostic form).  The workgroup's block behind the parks is u32[kSOrderHead: the overflow counters by fate slot | slots * L:
+// [compact slot][order]] in either case.
+constexpr int kSOrderHead = 24;
+static_assert(kSOrderHead >= kRespFates && kSOrderHead % 4 == 0, "the overflow counters, in 16-byte steps");
+struct SOrderSink {
+  unsigned long long* out;
+  unsigned long long* overflow;
+  uint32_t n_orders, lds_orders;
+};
+// A ray's end: one add for its fate slot and its order k = Ray::j at the end (an integer every kernel carries: nothing is computed
+// in a bounce step for it, no Philox draw).  Both census points of the SORDER build call this and nothing else states the rule.
+// `out` stays a kernel argument's field: a global_atomic, not a flat one.
+__device__ __forceinline__ void sorder_record(const SOrderSink& s, uint32_t* blk, int n_patch, int n_baf, int fate, uint32_t k) {
+  if (k >= s.n_orders) { atomicAdd(&blk[fate], 1u); return; }
+  if (k < s.lds_orders) {
+    const int c = fate < kRespBaffle0 ? fate : fate < kRespPort ? fate - kRespBaffle0 + (n_patch + 2) : fate - kRespPort + (n_patch + 2) + 2 * n_baf;
+    atomicAdd(&blk[(uint32_t)kSOrderHead + (uint32_t)c * s.lds_orders + k], 1u);
+  } else {
+    global_add_u64(s.out + ((uint32_t)fate * s.n_orders + k), 1ull);
+  }
+}
+// one flush of the workgroup's low orders: compact slot -> fate slot (L = 0: nothing to flush)
+__device__ __forceinline__ void sorder_flush(const SOrderSink& s, const uint32_t* blk, int n_patch, int n_baf, uint32_t tid, uint32_t nthr) {
+  const uint32_t nw = (uint32_t)(n_patch + 2), nb = nw + 2u * (uint32_t)n_baf, words = (nb + 3u) * s.lds_orders;
+  for (uint32_t i = tid; i < words; i += nthr) {
+    const uint32_t c = blk[(uint32_t)kSOrderHead + i];
+    if (c) {
+      const uint32_t cs = i / s.lds_orders, k = i - cs * s.lds_orders;
+      const uint32_t fate = cs < nw ? cs : cs < nb ? cs - nw + (uint32_t)kRespBaffle0 : cs - nb + (uint32_t)kRespPort;
+      global_add_u64(s.out + (fate * s.n_orders + k), (unsigned long long)c);
+    }
+  }
+}
+
 // The segment test of isx.h's contract, operation for operation (IEEE double, left to right, no fma: -ffp-contract=off; / is the
 // correctly rounded one): the baffle that the segment p -> q strikes first -- the smallest f, on equal f the lowest index -- as
 // 2 k + side (side 0: the side the normal points to), or -1.  `skip` is the baffle of the ray's previous interaction (-1: none).
@@ -3192,13 +3233,18 @@ __device__ __forceinline__ void ray_unpack(const uint4& a, const uint4& b, const
 // FIELD (isx_scene_patch_field; SCENE only, never with RESP or VIEW): the same rays at the same two points, binned by where on the
 // patch they land and the direction they arrive from -- field_record, which also gets the point of the arrival (Ray::p).  The
 // workgroup's block behind the parks: the frame's doubles, five counters, and the field if the launch has one in the LDS.
+// SORDER (isx_scene_order_hist; SCENE only, never with RESP, VIEW or FIELD): every ray is binned once, where it ends, at RESP's two
+// census points with RESP's fate slot, by its order Ray::j -- sorder_record, which draws nothing.  The workgroup's block behind the
+// parks: the overflow counters and the low orders of every compact slot; the orders above them go to global memory one by one.
 struct FateList { const uint32_t* list; const uint32_t* count; };
 template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false, bool ORDER = false, bool PATCH = false,
-          bool BEAM = false, bool LIST = false, bool BAFFLE = false, bool RESP = false, bool VIEW = false, bool FIELD = false>
+          bool BEAM = false, bool LIST = false, bool BAFFLE = false, bool RESP = false, bool VIEW = false, bool FIELD = false,
+          bool SORDER = false>
 __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk, const PatchTab* tab_arg = nullptr,
                                             const BeamSrc* beam_arg = nullptr, const FateList* list_arg = nullptr,
                                             const BaffleTab* baf_arg = nullptr, const RespSink* resp_arg = nullptr,
-                                            const ViewSink* view_arg = nullptr, const PatchFieldSink* field_arg = nullptr) {
+                                            const ViewSink* view_arg = nullptr, const PatchFieldSink* field_arg = nullptr,
+                                            const SOrderSink* sorder_arg = nullptr) {
   constexpr bool LEAN = SURF == SURF_LAMBERT;
   static_assert(LEAN || (CH == 0 && !RESC), "the chord identity and the BRDF re-scatter pipeline are built for the Lambertian border");
   static_assert(!PATCH || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER), "wall patches: the explicit Lambertian lean path, no other sink");
@@ -3209,6 +3255,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   static_assert(!RESP || SCENE, "scene response: the scene's trace, nothing else");
   static_assert(!VIEW || (SCENE && !RESP), "scene view: the scene's trace, nothing else");
   static_assert(!FIELD || (SCENE && !RESP && !VIEW), "scene patch field: the scene's trace, nothing else");
+  static_assert(!SORDER || (SCENE && !RESP && !VIEW && !FIELD), "scene order histograms: the scene's trace, nothing else");
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned long long* sstat = reinterpret_cast<unsigned long long*>(smem);
   Geom* g_lds = reinterpret_cast<Geom*>(sstat + 8);
@@ -3274,6 +3321,11 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   if constexpr (FIELD) {
     if (tid == 68) *reinterpret_cast<PatchFieldFrame*>(rblk) = field_arg->f;
     for (uint32_t b = (uint32_t)tid; b < (uint32_t)kFieldCtrWords + field_arg->lds_words; b += (uint32_t)nthr) fblk[b] = 0u;
+  }
+  // SORDER: the workgroup's block behind the parks -- u32[kSOrderHead overflow counters | compact slots x SOrderSink::lds_orders]
+  if constexpr (SORDER) {
+    const uint32_t words = (uint32_t)kSOrderHead + (uint32_t)((n_patch + 2) + 2 * n_baf + 3) * sorder_arg->lds_orders;
+    for (uint32_t b = (uint32_t)tid; b < words; b += (uint32_t)nthr) rblk[b] = 0u;
   }
   if (tid < 8) sstat[tid] = 0ull;
   if (tid == 64) {
@@ -3462,7 +3514,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       // (the end of a ray as two flags -- lane masks in scalar registers -- instead of a status word per lane; a tracer lane's ray
       //  sits on the inner sphere unless it is fresh, so Ray::on is neither read nor written in the steps)
       bool ended = false, susp = false;
-      int eslot = 0;   // RESP, VIEW, FIELD: the class of the arrival that absorbed the lane's ray
+      int eslot = 0;   // RESP, VIEW, FIELD, SORDER: the class of the arrival that absorbed the lane's ray
       (void)eslot;
       auto arrive = [&](const V3& q, auto ph, bool record = true) {
         if (WALL && record) wall_record(wspec, hist, wall_nmap, K_INNER, r.j, q, 1u);
@@ -3472,7 +3524,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           const int cls = patch_arrive<true>(ptab, n_patch, pcnt, K_INNER, q, hp);
           st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(hp, g, r, seed, first, K_INNER, q);
           if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
-          if constexpr (RESP || VIEW || FIELD) { if (st == ST_ABSORBED) eslot = cls; }
+          if constexpr (RESP || VIEW || FIELD || SORDER) { if (st == ST_ABSORBED) eslot = cls; }
         } else st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(h, g, r, seed, first, K_INNER, q);
         if (st != 0) { run = false; ended = true; susp = st == ST_SUSPENDED; }
       };
@@ -3592,6 +3644,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           if constexpr (RESP) resp_record(*resp_arg, rblk, n_patch, n_baf, susp ? kRespSuspended : eslot, seed, first + (uint64_t)r.offset());
           if constexpr (VIEW) { if (!susp && eslot == view_arg->patch) view_record(*view_arg, rblk, r.j, r.v); }
           if constexpr (FIELD) { if (!susp && eslot == field_arg->patch) field_record(*field_arg, fframe, fblk, r.j, r.p, r.v); }
+          if constexpr (SORDER) sorder_record(*sorder_arg, rblk, n_patch, n_baf, susp ? kRespSuspended : eslot, r.j);
         }
         const unsigned long long me = __ballot(ended);
         if (me) {
@@ -3746,7 +3799,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       bool go = have;
       bool given = false;   // BAFFLE: the ray went back to the tracers from inside the step loop
       (void)given;
-      int eslot = 0;        // RESP, VIEW, FIELD: the slot of the interaction that absorbed the lane's ray (a wall class, or a baffle's side)
+      int eslot = 0;        // RESP, VIEW, FIELD, SORDER: the slot of the interaction that absorbed the lane's ray (a wall class, or a baffle's side)
       (void)eslot;
       for (;;) {
         if (go) {
@@ -3770,14 +3823,14 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
               atomicAdd(&bcnt[ks], 1u);
               st = baffle_arrive(baf, h, r, seed, first, ks >> 1, ks & 1);
               if (st == ST_ABSORBED) atomicAdd(&bcnt[2 * kMaxBaffles + ks], 1u);
-              if constexpr (RESP || VIEW || FIELD) eslot = kRespBaffle0 + ks;
+              if constexpr (RESP || VIEW || FIELD || SORDER) eslot = kRespBaffle0 + ks;
             } else {
               Hot hp = h;
               int cls = 0;
               if (kind != K_BOX) cls = patch_arrive<false>(ptab, n_patch, pcnt, kind, q, hp);
               st = ray_arrive<false, LEAN, CH, PH_DIRECT, true, SURF>(hp, g, r, seed, first, kind, q);
               if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
-              if constexpr (RESP || VIEW || FIELD) eslot = cls;
+              if constexpr (RESP || VIEW || FIELD || SORDER) eslot = cls;
             }
           } else if constexpr (PATCH) {
             Hot hp = h;
@@ -3887,6 +3940,10 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       if constexpr (FIELD) {   // (likewise)
         if (ended && st == ST_ABSORBED && eslot == field_arg->patch) field_record(*field_arg, fframe, fblk, r.j, r.p, r.v);
       }
+      if constexpr (SORDER) {
+        if (ended) sorder_record(*sorder_arg, rblk, n_patch, n_baf,
+                                 exited ? (below ? kRespPort : kRespPort + 1) : st == ST_SUSPENDED ? kRespSuspended : eslot, r.j);
+      }
       const uint32_t c_ended = (uint32_t)__popcll(__ballot(ended));
       n_ended += c_ended;
       n_exited += (uint32_t)__popcll(__ballot(exited));
@@ -3926,7 +3983,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         n_inc += (unsigned long long)__popcll(__ballot(hit0)) + (unsigned long long)__popcll(__ballot(hit1));
       }
       const unsigned long long m = (PP != 0 || WALL || ORDER || (PATCH && !SCENE)) ? 0ull : __ballot(keep);
-      if (!RESP && !VIEW && !FIELD && m) {   // (RESP, VIEW, FIELD: no exit lines -- the response / the view / the field is the build's one sink, no kernel follows)
+      if (!RESP && !VIEW && !FIELD && !SORDER && m) {   // (RESP, VIEW, FIELD, SORDER: no exit lines -- the response / the view / the field / the histograms are the build's one sink, no kernel follows)
         const uint32_t cnt = (uint32_t)__popcll(m);
         if (cnt > reg_left) {   // close the open region, reserve the next one (kRegion)
           if (lane == 0 && reg_id != 0xffffffffu) d_arg.rec_counts[reg_id] = kRegion - reg_left;
@@ -4064,6 +4121,19 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     }
     __syncthreads();
   }
+  if constexpr (SORDER) {   // one flush of the workgroup's low orders and of its overflow counters; bin_increments = the histograms' sum:
+    sorder_flush(*sorder_arg, rblk, n_patch, n_baf, tid_end, (uint32_t)blockDim.x);   // every ended ray of the workgroup that did not overflow
+    if (tid_end < (uint32_t)kRespFates) {
+      const uint32_t c = rblk[tid_end];
+      if (c) global_add_u64(sorder_arg->overflow + tid_end, (unsigned long long)c);
+    }
+    if (tid_end == 64u) {   // (the census of the workgroup is complete behind the barrier above: exited + absorbed + suspended = ended)
+      unsigned long long over = 0ull;
+      for (int f = 0; f < kRespFates; ++f) over += (unsigned long long)rblk[f];
+      sstat[5] = sstat[1] + sstat[3] + sstat[4] - over;
+    }
+    __syncthreads();
+  }
   if constexpr (BAFFLE) {   // one flush of the workgroup's counters (the thread index rebuilt, as the beam kernel's)
     uint32_t t3 = tid_end;
     asm volatile("" : "+v"(t3));
@@ -4165,6 +4235,14 @@ isx_trace_assist_scene_field_kernel(const Geom g, const DetGrid d, const Work wk
                                     const PatchFieldSink field) {
   assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true, false, false, true>(g, d, wk, &tab, &beam, nullptr, &baf,
                                                                                                           nullptr, nullptr, &field);
+}
+// the scene order histograms (isx_scene_order_hist): the scene kernel with one add per ended ray -- its fate by its interaction
+// count (sorder_record), the low orders in the workgroup's LDS -- and no exit lines; the sink is a seventh argument
+extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_SCENE_WAVES, ISX_SCENE_WAVES)))
+isx_trace_assist_scene_order_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab, const BeamSrc beam, const BaffleTab baf,
+                                    const SOrderSink sorder) {
+  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true, false, false, false, true>(
+      g, d, wk, &tab, &beam, nullptr, &baf, nullptr, nullptr, nullptr, &sorder);
 }
 // the flux pipeline behind the fate scan: isx_trace_assist_kernel on the rays of a list; the list is a fourth argument
 extern "C" __global__ void ISX_ASSIST_ATTR

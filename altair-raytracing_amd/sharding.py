@@ -338,3 +338,21 @@ def scene_patch_field_sharded(trace: Callable, cfg, scene, fspec, n_total: int, 
 
     out = fluxmap_scene_sharded(one, cfg, scene, n_total, seed, first_ray, device)
     return (out[0][:-5].reshape(shape[0]), out[0][-5:]) + tuple(out[1:])
+
+
+def scene_order_hist_sharded(trace: Callable, cfg, scene, ospec, n_total: int, seed: int, first_ray: int = 0, device=None):
+    """The order histograms of a scene (altair_raytracing_amd.scene_order_hist) ray-sharded: this rank's contiguous shard through
+    `trace(cfg, scene, ospec, count, seed, first) -> (hist, order_counts, scene_counts, stats)`, then ONE SUM all-reduce that
+    carries the histograms, the 21 overflow counters, the 36 scene counters and the census -- scene_patch_field_sharded with the
+    histograms and their overflow counters in the field's place.  Returns (hist[21, n_orders] uint64, overflow[21] uint64,
+    patch_arrivals[10] uint64, patch_absorbed[10] uint64, baffle arrivals[4, 2] uint64, baffle absorbed[4, 2] uint64, census
+    dict) -- identical on every rank."""
+    shape = []
+
+    def one(c, sp, count, sd, first):
+        hist, oc, cnt, st = trace(c, sp, ospec, count, sd, first)
+        shape.append(hist.shape)
+        return np.concatenate([np.asarray(hist, dtype=np.uint64).reshape(-1), oc.words()]), cnt, st
+
+    out = fluxmap_scene_sharded(one, cfg, scene, n_total, seed, first_ray, device)
+    return (out[0][:-21].reshape(shape[0]), out[0][-21:]) + tuple(out[1:])

@@ -209,6 +209,9 @@ int isx_last_kernel_ms(double* single_ms, double* trace_ms, double* bin_ms);
  *                  add per binned ray for a larger one; 1: the global form for every spec (a diagnostic)
  *   "field_global" 0 (default): isx_scene_patch_field keeps a field that fits in the workgroup's LDS there and takes one global
  *                  atomic add per binned ray for a larger one; 1: the global form for every spec (a diagnostic)
+ *   "sorder_lds_orders"  how many orders of every fate slot isx_scene_order_hist keeps as u32 words in the workgroup's LDS: -1
+ *                  (default) as many as fit without costing a resident workgroup, n > 0 at most n of those, 0 none -- one
+ *                  global atomic add per ended ray (a diagnostic).  It changes no result.
  *   "bin_block", "bin_blocks_per_cu"  shape of round 2's binning kernel (0 workgroups per CU = what is resident)
  *                  (round 5: "assist_block" 0 = the default again -- 768 threads, 256 for launches below 1e6 rays, 512 for the lobe /
  *                  rough-specular kernels; "rays_per_lane" > 0 sizes every grid for that many rays per tracer lane, 0 = by launch
@@ -839,7 +842,8 @@ int isx_fluxmap_beam_device(const isx_config* cfg, const isx_beam_spec* spec, ui
  * 4 B per bin, 32 B per row, 64 B per column -- do not fit the binning kernels' LDS (the device's once isx_init() has asked it,
  * 160 KiB before; the default 180 x 90 grid fits).  ISX_ERR_BAD_ARG: a NULL pointer (last_baffle, counts and
  * stats excepted).  Without a HIP device: ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT.
- * Out of scope: baffles for the other sinks (exit maps, wall map, light field, order histograms, disc sweeps), and the chord mode.
+ * Out of scope: baffles for the other sinks (exit maps, wall map, light field, disc sweeps; order histograms with baffles are the
+ * scene's: isx_scene_order_hist), and the chord mode.
  * The beam source and the wall patches combine with baffles in the scene calls below (isx_fluxmap_scene).
  */
 #define ISX_MAX_BAFFLES 4
@@ -913,9 +917,10 @@ int isx_fluxmap_baffle_device(const isx_config* cfg, const isx_baffle_spec* spec
  * same codes and whether or not a device is present: everything isx_fluxmap_beam refuses of `beam`, isx_fluxmap_baffle of `baffles`
  * (the detector grid included, for the two flux-map calls) and isx_wall_patches of `patches` -- each nested struct_size must be
  * right as well as the outer one.  ISX_ERR_BAD_ARG: a NULL pointer (start_point, start_dir, last_baffle, last_class, counts and
- * stats excepted).  Out of scope: a scene for the other sinks (exit maps, wall map, light field, order histograms, disc sweeps;
- * the fates over the source's sample space are isx_scene_response, the directions a wall detector sees isx_scene_view, where on
- * a patch the light lands isx_scene_patch_field), the chord mode, the other borders and the BRDF source.
+ * stats excepted).  Out of scope: a scene for the other sinks (exit maps, wall map, light field, disc sweeps; the fates over the
+ * source's sample space are isx_scene_response, the directions a wall detector sees isx_scene_view, where on a patch the light
+ * lands isx_scene_patch_field, the fates by bounce order isx_scene_order_hist), the chord mode, the other borders and the BRDF
+ * source.
  */
 typedef struct isx_scene_spec {
   uint32_t struct_size;        /* sizeof(isx_scene_spec), set by isx_default_scene_spec() */
@@ -989,7 +994,8 @@ int isx_fluxmap_scene_device(const isx_config* cfg, const isx_scene_spec* spec, 
  * ISX_ERR_BAD_CONFIG: struct_size != sizeof(isx_response_spec), reserved0 != 0, an axis outside 1..ISX_RESPONSE_MAX_AXIS,
  * B > ISX_RESPONSE_MAX_BINS; ISX_ERR_BAD_ARG: a NULL cfg, scene, rspec or response (device form: d_response, d_counts).  Without a
  * HIP device: ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT (as isx_fluxmap_scene).
- * Out of scope: the isx_macro command line, a binning over the first-strike point on the wall, a response of the other sinks.
+ * Out of scope: the isx_macro command line, a binning over the first-strike point on the wall, a response of the other sinks (the
+ * fates by bounce order are isx_scene_order_hist).
  */
 #define ISX_RESPONSE_FATES 21
 #define ISX_RESPONSE_MAX_AXIS 1024
@@ -1073,7 +1079,7 @@ int isx_response_reweight(const isx_response_spec* rspec, const uint64_t* respon
  * ISX_ERR_BAD_ARG: a NULL cfg, scene, vspec or view (device form: d_view, d_view_counts, d_scene_counts).  Without a HIP device:
  * ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT (as isx_fluxmap_scene).
  * Out of scope: more than one patch per call, views from baffle sides, the isx_macro command line, scenes for the remaining sinks
- * (the position on the patch, jointly with the direction, is isx_scene_patch_field).
+ * (the position on the patch, jointly with the direction, is isx_scene_patch_field; the bounce order is isx_scene_order_hist).
  */
 #define ISX_VIEW_MAX_AXIS 1024
 #define ISX_VIEW_MAX_BINS 65536
@@ -1177,7 +1183,7 @@ int isx_view_weight_fov(const isx_view_spec* vspec, double half_angle_deg, doubl
  * d_field_counts, d_scene_counts).  Without a HIP device: ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT (as
  * isx_fluxmap_scene).
  * Out of scope: a position map of the `direct` rays, more than one patch per call, baffle sides, the isx_macro command line, a
- * scene for the remaining sinks.
+ * scene for the remaining sinks (the bounce order is isx_scene_order_hist).
  */
 #define ISX_PATCH_FIELD_MAX_AXIS 1024
 #define ISX_PATCH_FIELD_MAX_BINS (1 << 22)
@@ -1217,6 +1223,98 @@ int isx_scene_patch_field_device(const isx_config* cfg, const isx_scene_spec* sc
  * not looked at: no scene is given). */
 int isx_patch_field_marginals(const isx_patch_field_spec* fspec, const uint64_t* field, uint64_t* pos_map /*[n_y * n_x]*/,
                               uint64_t* dir_map /*[n_v * n_u]*/);
+
+/*
+ * Scene order histograms: the fates of a scene's rays by bounce order -- after how many interactions the light of a scene ends
+ * where it ends.  What isx_order_hist and isx_order_reweight answer for the bare sphere, for a sphere with a lamp, baffles and wall
+ * detectors: one trace gives every fate's fraction along a whole ageing curve of the coating (isx_scene_order_reweight: the sphere
+ * multiplier against rho) and the time response of every fate in interactions (isx_scene_order_moments).
+ *
+ * The ray histories are those of isx_fluxmap_scene / isx_scene_endstates for the same (cfg, scene, seed, ray index): nothing of a
+ * history changes.  For every traced ray:
+ *
+ *   f, the fate slot, exactly as isx_scene_response defines it (0 .. 20, ISX_RESPONSE_FATES);
+ *   k = n_points - 2 if ISX_RAY_EXITED, else n_points - 1, with n_points as isx_scene_endstates reports it -- isx_order_hist's
+ *   rule: the ray's interaction count, interactions with baffles included, so that the sum of k over all rays is stats.wall_hits;
+ *   if k >= n_orders: overflow[f] += 1 and nothing else; otherwise hist[f * n_orders + k] += 1.
+ *
+ * For every call: the sum of row f plus overflow[f] is the row sum isx_scene_response gives for f -- rows 0..9
+ * counts.patch_absorbed, rows 10..17 counts.baffle.absorbed, row 18 counted_below_z, rows 18 + 19 exited, row 20 suspended;
+ * stats.bin_increments is the sum of hist; with every overflow zero the sum of k * hist[f][k] is stats.wall_hits.  `counts` and
+ * every other field of stats except t_kernel_ms are isx_fluxmap_scene's for the same arguments.  No result depends on any
+ * isx_set_option switch nor on how a job is cut into calls.  cfg->hit_line_mode and the detector-grid fields of cfg are ignored and
+ * never a reason for refusal.  Slots the scene cannot fill stay 0.
+ *
+ * With isx_default_scene_spec (the pencil, no baffle, no patch) and the same cfg and n_orders: row 18 is isx_order_hist's class 0,
+ * row 19 class 1, row 0 + row 1 class 2, row 20 class 3, and the overflows likewise.
+ *
+ * One route whatever the switches say: isx_trace_assist_scene_order_kernel -- the scene's trace kernel with one add per ended ray,
+ * where the census is taken; it draws nothing, writes no exit lines, and no kernel follows it.  An order histogram is peaked at
+ * low k: the first L orders of every slot the scene can fill are kept as u32 words in the workgroup's LDS and flushed once, the
+ * orders from L on -- rare, spread over many addresses -- take one global u64 add each ("sorder_lds_orders": L).
+ *
+ * Refused, whether or not a device is present: everything isx_scene_endstates refuses of cfg and scene, with its codes;
+ * ISX_ERR_BAD_CONFIG: struct_size != sizeof(isx_scene_order_spec), a non-zero reserved field, n_orders outside
+ * 1..ISX_SCENE_ORDER_MAX_ORDERS; ISX_ERR_BAD_ARG: a NULL cfg, scene, ospec or hist (device form: d_hist, d_order_counts,
+ * d_scene_counts).  Without a HIP device: ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT (as
+ * isx_fluxmap_scene).
+ * Out of scope: a reweighting of the wall alone where patches or baffles reflect at another value (it needs a counter per ray),
+ * path lengths in cm, a joint histogram over order and source bin, the isx_macro command line.
+ */
+#define ISX_SCENE_ORDER_MAX_ORDERS 65536
+typedef struct isx_scene_order_spec {
+  uint32_t struct_size;      /* sizeof(isx_scene_order_spec), set by isx_default_scene_order_spec(); a spec of another size is refused */
+  uint32_t reserved0;        /* 0 */
+  int32_t n_orders;          /* orders 0 .. n_orders - 1 per fate slot; 1..ISX_SCENE_ORDER_MAX_ORDERS */
+  int32_t reserved1;         /* 0 */
+} isx_scene_order_spec;      /* 16 bytes */
+typedef struct isx_scene_order_counts { uint64_t overflow[ISX_RESPONSE_FATES]; } isx_scene_order_counts;   /* 168 bytes */
+
+/* n_orders = 512.  Host only, no GPU needed. */
+void isx_default_scene_order_spec(const isx_config* cfg, isx_scene_order_spec* ospec);
+/* Blocking: hist[ISX_RESPONSE_FATES * n_orders], order_counts and scene_counts (host, zeroed by the callee; order_counts,
+ * scene_counts and stats may be NULL). */
+int isx_scene_order_hist(const isx_config* cfg, const isx_scene_spec* scene, const isx_scene_order_spec* ospec, uint64_t n_rays,
+                         uint64_t seed, uint64_t first_ray, uint64_t* hist, isx_scene_order_counts* order_counts,
+                         isx_scene_counts* scene_counts, isx_stats* stats);
+/* ACCUMULATES (+=) into d_hist [ISX_RESPONSE_FATES * n_orders], d_order_counts (21 words, isx_scene_order_counts' layout) and
+ * d_scene_counts (36 words, isx_scene_counts' layout; none may be NULL) on the library's stream and returns after enqueueing;
+ * isx_sync() / isx_take_stats() as for isx_fluxmap_scene_device. */
+int isx_scene_order_hist_device(const isx_config* cfg, const isx_scene_spec* scene, const isx_scene_order_spec* ospec,
+                                uint64_t n_rays, uint64_t seed, uint64_t first_ray, uint64_t* d_hist,
+                                uint64_t* d_order_counts /*[21]*/, uint64_t* d_scene_counts /*[36]*/);
+/*
+ * The fate fractions of the same scene with EVERY reflectance multiplied by t = scale[i] -- cfg->reflectance, every patch's and
+ * every baffle's: the ageing of the whole interior -- from one isx_scene_order_hist result.  Host only, no GPU needed.  Where all
+ * reflecting surfaces carry the wall's coating, t = rho / rho0.  A history that survived s absorption tests keeps the weight t^s;
+ * with rho_f the reflectance of the surface slot f absorbs on (patch f for f < P, the wall for the classes P and P + 1, baffle
+ * (f - 10) / 2 for the slots 10..17):
+ *
+ *   rows 18, 19, 20 (every interaction survived):  w_k = pow(t, k)                                       k = 0 .. n_orders - 1
+ *   rows 0..17 (absorbed at interaction k):        w_k = a_f * pow(t, k - 1),  a_f = (1 - t * rho_f) / (1 - rho_f)   k = 1 .. n_orders - 1
+ *       (an absorbed ray has k >= 1: hist[f][0] is 0 by construction and is not looked at)
+ *   S1 = sum over k of hist[f][k] * w_k ;  S2 = sum over k of hist[f][k] * w_k * w_k      (in increasing k)
+ *   fraction[i * 21 + f] = S1 / launched
+ *   sigma[i * 21 + f]    = sqrt(max(0, S2 - S1 * S1 / launched)) / launched
+ *
+ * -- isx_order_reweight's estimator.  At t == 1 a fraction is the row's sum / launched exactly.  A row with rho_f == 1 is empty by
+ * construction: its fraction and sigma are NaN for t != 1 and 0 for t == 1.  A slot the scene cannot fill (a wall class above
+ * P + 1, a baffle the scene does not have) gives 0 and 0.  sigma may be NULL.
+ * ISX_ERR_BAD_CONFIG: a spec or a scene isx_scene_order_hist refuses, any overflow[f] != 0, launched == 0; ISX_ERR_BAD_ARG: a NULL
+ * cfg, scene, ospec, hist or counts, n_scale < 0, a NULL scale or fraction with n_scale > 0, a t that is negative or not finite,
+ * a t for which t * rho is above 1 for any surface of the scene.
+ */
+int isx_scene_order_reweight(const isx_config* cfg, const isx_scene_spec* scene, const isx_scene_order_spec* ospec,
+                             const uint64_t* hist, const isx_scene_order_counts* counts, uint64_t launched, const double* scale,
+                             int32_t n_scale, double* fraction /*[n_scale][21]*/, double* sigma /*[n_scale][21]*/);
+/*
+ * The time response in interactions: mean and standard deviation of k per fate slot.  Host only, no GPU needed.  With
+ * N = sum over k of hist[f][k], A = sum of k * hist[f][k], B = sum of k * k * hist[f][k] (as doubles, in increasing k):
+ * mean[f] = A / N, sd[f] = sqrt(max(0, B / N - mean[f] * mean[f])).  NaN for an empty row and for a row with overflow[f] != 0.
+ * Either output may be NULL.  ISX_ERR_BAD_ARG: a NULL ospec, hist or counts; ISX_ERR_BAD_CONFIG: a spec isx_scene_order_hist refuses.
+ */
+int isx_scene_order_moments(const isx_scene_order_spec* ospec, const uint64_t* hist, const isx_scene_order_counts* counts,
+                            double* mean /*[21]*/, double* sd /*[21]*/);
 
 /*
  * Series driver (sweepSeries, fluxAtObserverOptimize.C:892-921 / fluxAtObserverFast.C:1641-1673):
