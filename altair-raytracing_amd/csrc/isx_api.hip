@@ -43,12 +43,12 @@ struct State {
   size_t cap_aux = 0;
   // two-kernel pipeline of the headline flux map: exit lines in HBM, in regions of kRegion 48-byte slots + lines per region
   static constexpr int kRecBufs = 3;      // workspaces: chunk k uses buffer k mod 3 (the overlapped pipeline keeps up to 3 in flight)
-  double* d_rec[kRecBufs] = {nullptr, nullptr, nullptr};
-  uint32_t* d_rec_counts[kRecBufs] = {nullptr, nullptr, nullptr};
+  double* d_rec[kRecBufs] = {};
+  uint32_t* d_rec_counts[kRecBufs] = {};
   size_t cap_regions[kRecBufs] = {0, 0, 0};
   // fate scan: the rays of a chunk that the scan leaves to the trace kernel, 4 B per ray of the largest chunk
   // (one list per workspace: the list of chunk k is read by its trace kernel while the scan of a later chunk may already run)
-  uint32_t* d_list[kRecBufs] = {nullptr, nullptr, nullptr};
+  uint32_t* d_list[kRecBufs] = {};
   size_t cap_list[kRecBufs] = {0, 0, 0};
   unsigned long long fate_launches = 0;   // isx_fate_scan_kernel launches enqueued since isx_init (isx_fate_scan_launches)
   int fate_scan = -1;                     // 0 off, 1 on wherever eligible, -1 (default) automatic: fate_scan_auto()
@@ -68,9 +68,9 @@ struct State {
   int call_overlap_streams = 2;
   unsigned call_rot = 0;
   bool trace_open = false;
-  hipEvent_t ev_free[kRecBufs] = {nullptr, nullptr, nullptr};
+  hipEvent_t ev_free[kRecBufs] = {};
   bool free_set[kRecBufs] = {false, false, false};
-  hipEvent_t ev_join[3] = {nullptr, nullptr, nullptr};   // [0], [1]: tails of stream2 / stream3; [2]: where `stream` stood when they opened
+  hipEvent_t ev_join[3] = {};   // [0], [1]: tails of stream2 / stream3; [2]: where `stream` stood when they opened
   int pipeline = 1;                       // 1 (default): trace kernel -> HBM -> binning kernel (lean flux map); 0: fused kernel
   uint64_t pipe_chunk = 1ull << 26;       // rays per trace/bin pair (3.4 GB of exit-line workspace at most)
   // work-queue counters of the launches (Work::ctr): a ring of Q_WORDS-word blocks, one per launch, zeroed on the stream
@@ -336,10 +336,9 @@ Shape small_shape(uint64_t n, int block_default) {
 // resident -- workgroups of `fn` (workgroup size `block`, `lds` bytes of dynamic LDS) on one CU at a time (queried once, cached)
 constexpr int kResident = -1;
 int resident_unless(int option) { return option > 0 ? option : kResident; }
-template <class F>
-int blocks_per_cu(F fn, int block, size_t lds, int per_cu) {
+int blocks_per_cu(const void* fn, int block, size_t lds, int per_cu) {
   if (per_cu != kResident) return per_cu;
-  const auto key = std::make_tuple((const void*)fn, block, lds);
+  const auto key = std::make_tuple(fn, block, lds);
   const auto it = S.occ.find(key);
   if (it != S.occ.end()) return it->second;
   int nb = 0;
@@ -541,6 +540,18 @@ PatchTab patch_table(const isx_config& c, const isx_wall_patch_spec& s) {
 // LDS of the patch kernel's block behind the rings: the table and its 2 (P + 2) u32 counters
 size_t patch_lds() { return (sizeof(PatchTab) + 2 * (kMaxPatches + 2) * sizeof(uint32_t) + 15) & ~(size_t)15; }
 
+// isx.h: an orthonormal frame, each length and each dot product to 1e-12 (the beam's, a view's, a patch field's: the one
+// statement of the test)
+bool check_frame(const double* axis, const double* e1, const double* e2) {
+  const double* vec[3] = {axis, e1, e2};
+  auto dot = [](const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+  for (int k = 0; k < 3; ++k) {
+    if (!(std::fabs(std::sqrt(dot(vec[k], vec[k])) - 1.0) <= 1e-12)) return false;
+    if (!(std::fabs(dot(vec[k], vec[(k + 1) % 3])) <= 1e-12)) return false;
+  }
+  return true;
+}
+
 // isx.h: the limits of a beam spec and the scope of the call (the explicit Lambertian lean path, either hit line)
 int check_beam_call(const isx_config* c, const isx_beam_spec* s) {
   if (!config_abi_ok(c) || s->struct_size != (uint32_t)sizeof(isx_beam_spec)) return ISX_ERR_BAD_CONFIG;
@@ -554,12 +565,8 @@ int check_beam_call(const isx_config* c, const isx_beam_spec* s) {
   if (!std::isfinite(s->radius) || !std::isfinite(s->cos_min) || s->radius < 0.0) return ISX_ERR_BAD_CONFIG;
   if (s->angular_law != ISX_BEAM_UNIFORM && s->angular_law != ISX_BEAM_LAMBERT) return ISX_ERR_BAD_CONFIG;
   if (s->cos_min > 1.0 || s->cos_min < (s->angular_law == ISX_BEAM_LAMBERT ? 0.0 : -1.0)) return ISX_ERR_BAD_CONFIG;
+  if (!check_frame(s->axis, s->e1, s->e2)) return ISX_ERR_BAD_CONFIG;
   auto dot = [](const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
-  for (int k = 1; k < 4; ++k) {
-    if (!(std::fabs(std::sqrt(dot(vec[k], vec[k])) - 1.0) <= 1e-12)) return ISX_ERR_BAD_CONFIG;
-    const double* o = vec[k == 3 ? 1 : k + 1];
-    if (!(std::fabs(dot(vec[k], o)) <= 1e-12)) return ISX_ERR_BAD_CONFIG;
-  }
   // (the disc's centre strictly inside the inner sphere, every start point strictly inside the world box; a start outside the
   //  inner sphere -- a disc that overhangs the wall -- takes the generic search, as a pencil there does)
   const double ro = std::sqrt(dot(s->origin, s->origin));
@@ -671,8 +678,7 @@ int check_scene_call(const isx_config* c, const isx_scene_spec* s, bool grid) {
   return rc;
 }
 
-// isx_scene_response: the checked spec and the device array of the call ([ISX_RESPONSE_FATES][B]); the scene travels as SceneSink
-struct ResponseSink { const isx_response_spec* spec = nullptr; unsigned long long* out = nullptr; };
+// isx_scene_response: the device array of the call is [ISX_RESPONSE_FATES][B] (SceneMap below; the scene travels as SceneSink)
 static_assert(ISX_RESPONSE_FATES == kRespFates && kRespBaffle0 == ISX_MAX_WALL_PATCHES + 2 &&
               kRespPort == kRespBaffle0 + 2 * ISX_MAX_BAFFLES && kRespSuspended == kRespPort + 2, "isx.h and resp_record's slots");
 // isx.h: the limits of a response spec
@@ -687,9 +693,7 @@ int check_response_spec(const isx_response_spec* s) {
 }
 size_t response_bins(const isx_response_spec& s) { return (size_t)s.n[0] * s.n[1] * s.n[2] * s.n[3]; }
 
-// isx_scene_view: the checked spec and the device arrays of the call (the map [n_v][n_u], the four words of isx_view_counts); the
-// scene travels as SceneSink
-struct ViewCall { const isx_view_spec* spec = nullptr; unsigned long long* out = nullptr; unsigned long long* counts = nullptr; };
+// isx_scene_view: the device arrays of the call are the map [n_v][n_u] and the four words of isx_view_counts
 static_assert(sizeof(isx_view_counts) == kViewCounters * sizeof(uint64_t) && offsetof(isx_view_counts, binned) == 8 * kViewBinned &&
               offsetof(isx_view_counts, outside) == 8 * kViewOutside && offsetof(isx_view_counts, behind) == 8 * kViewBehind &&
               offsetof(isx_view_counts, direct) == 8 * kViewDirect, "isx.h and view_record's counters");
@@ -705,19 +709,12 @@ int check_view_spec(const isx_view_spec* s, int n_patches) {
   for (int k = 0; k < 3; ++k)
     for (int i = 0; i < 3; ++i)
       if (!std::isfinite(vec[k][i])) return ISX_ERR_BAD_CONFIG;
-  // (check_beam_call's test of a frame)
-  auto dot = [](const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
-  for (int k = 0; k < 3; ++k) {
-    if (!(std::fabs(std::sqrt(dot(vec[k], vec[k])) - 1.0) <= 1e-12)) return ISX_ERR_BAD_CONFIG;
-    if (!(std::fabs(dot(vec[k], vec[(k + 1) % 3])) <= 1e-12)) return ISX_ERR_BAD_CONFIG;
-  }
-  return ISX_OK;
+  return check_frame(s->axis, s->e1, s->e2) ? ISX_OK : ISX_ERR_BAD_CONFIG;
 }
 size_t view_bins(const isx_view_spec& s) { return (size_t)s.n_u * (size_t)s.n_v; }
 
-// isx_scene_patch_field: the checked spec and the device arrays of the call (the field [n_y][n_x][n_v][n_u], the five words of
-// isx_patch_field_counts); the scene travels as SceneSink
-struct PatchFieldCall { const isx_patch_field_spec* spec = nullptr; unsigned long long* out = nullptr; unsigned long long* counts = nullptr; };
+// isx_scene_patch_field: the device arrays of the call are the field [n_y][n_x][n_v][n_u] and the five words of
+// isx_patch_field_counts
 static_assert(sizeof(isx_patch_field_counts) == kFieldCounters * sizeof(uint64_t) && offsetof(isx_patch_field_counts, binned) == 8 * kFieldBinned &&
               offsetof(isx_patch_field_counts, pos_outside) == 8 * kFieldPosOutside &&
               offsetof(isx_patch_field_counts, dir_outside) == 8 * kFieldDirOutside &&
@@ -741,19 +738,12 @@ int check_patch_field_spec(const isx_patch_field_spec* s, int n_patches) {
   for (int k = 0; k < 3; ++k)
     for (int i = 0; i < 3; ++i)
       if (!std::isfinite(vec[k][i])) return ISX_ERR_BAD_CONFIG;
-  // (check_beam_call's test of a frame)
-  auto dot = [](const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
-  for (int k = 0; k < 3; ++k) {
-    if (!(std::fabs(std::sqrt(dot(vec[k], vec[k])) - 1.0) <= 1e-12)) return ISX_ERR_BAD_CONFIG;
-    if (!(std::fabs(dot(vec[k], vec[(k + 1) % 3])) <= 1e-12)) return ISX_ERR_BAD_CONFIG;
-  }
-  return ISX_OK;
+  return check_frame(s->axis, s->e1, s->e2) ? ISX_OK : ISX_ERR_BAD_CONFIG;
 }
 size_t patch_field_bins(const isx_patch_field_spec& s) { return (size_t)s.n_x * (size_t)s.n_y * (size_t)s.n_u * (size_t)s.n_v; }
 
-// isx_scene_order_hist: the checked spec and the device arrays of the call (the histograms [ISX_RESPONSE_FATES][n_orders], the 21
-// words of isx_scene_order_counts); the scene travels as SceneSink
-struct SceneOrderCall { const isx_scene_order_spec* spec = nullptr; unsigned long long* out = nullptr; unsigned long long* overflow = nullptr; };
+// isx_scene_order_hist: the device arrays of the call are the histograms [ISX_RESPONSE_FATES][n_orders] and the 21 words of
+// isx_scene_order_counts
 static_assert(sizeof(isx_scene_order_spec) == 16 && sizeof(isx_scene_order_counts) == kRespFates * sizeof(uint64_t),
               "isx.h: isx_scene_order_spec, and sorder_record's overflow counters");
 // isx.h: the limits of a scene order spec
@@ -762,13 +752,78 @@ int check_scene_order_spec(const isx_scene_order_spec* s) {
   return s->n_orders >= 1 && s->n_orders <= ISX_SCENE_ORDER_MAX_ORDERS ? ISX_OK : ISX_ERR_BAD_CONFIG;
 }
 
+// The scene-map sink of a call -- isx_scene_response, isx_scene_view, isx_scene_patch_field, isx_scene_order_hist: which of the
+// four (its SINK_*), its spec (the isx_*_spec of that sink), the device array of the map and the device array of its own counters
+// behind it (`tail`: isx_view_counts, isx_patch_field_counts, isx_scene_order_counts; a response has none).  The scene travels as
+// SceneSink next to it.
+struct SceneMap {
+  int sink = 0;
+  const void* spec = nullptr;
+  unsigned long long *out = nullptr, *tail = nullptr;
+  const isx_response_spec& response() const { return *static_cast<const isx_response_spec*>(spec); }
+  const isx_view_spec& view() const { return *static_cast<const isx_view_spec*>(spec); }
+  const isx_patch_field_spec& field() const { return *static_cast<const isx_patch_field_spec*>(spec); }
+  const isx_scene_order_spec& order() const { return *static_cast<const isx_scene_order_spec*>(spec); }
+};
+// isx.h: the limits of the spec of a scene map in a scene of `n_patches` patches, and the words of its two arrays
+int scene_map_shape(const SceneMap& m, int n_patches, size_t& body, size_t& tail) {
+  int rc;
+  switch (m.sink) {
+    case SINK_RESPONSE:
+      if ((rc = check_response_spec(&m.response()))) return rc;
+      body = (size_t)ISX_RESPONSE_FATES * response_bins(m.response()); tail = 0;
+      return ISX_OK;
+    case SINK_VIEW:
+      if ((rc = check_view_spec(&m.view(), n_patches))) return rc;
+      body = view_bins(m.view()); tail = kViewCounters;
+      return ISX_OK;
+    case SINK_FIELD:
+      if ((rc = check_patch_field_spec(&m.field(), n_patches))) return rc;
+      body = patch_field_bins(m.field()); tail = kFieldCounters;
+      return ISX_OK;
+    case SINK_SORDER:
+      if ((rc = check_scene_order_spec(&m.order()))) return rc;
+      body = (size_t)ISX_RESPONSE_FATES * (size_t)m.order().n_orders; tail = kRespFates;
+      return ISX_OK;
+  }
+  return ISX_ERR_BAD_ARG;
+}
+
 // LDS of a workgroup's histogram: 4 B per bin, 16-byte aligned
 size_t hist_lds(int nbins) { return ((size_t)nbins * 4 + 15) & ~(size_t)15; }
 
+// One call as the launch path sees it: the sink, the configuration, the rays [first, first + n) of `seed`, where the histogram and
+// the census go, and whatever the sink needs besides -- every entry point names the fields it sets (in this order), the rest
+// stay empty.
+struct Call {
+  int sink = SINK_FLUX;
+  const isx_config* c = nullptr;
+  uint64_t n = 0, seed = 0, first = 0;
+  unsigned long long* d_hist = nullptr;    // the histogram (device); nullptr for the sinks that carry their own arrays
+  unsigned long long* d_stats = nullptr;   // the census words (device); nullptr: S.d_stats
+  int nbins_override = 0;                  // bins of a caller-supplied detector or disc list
+  const double* d_discs = nullptr;         // the disc list (device), the discs' radius and half thickness
+  double disc_r = 0, disc_h = 0;
+  const PerPos* pp = nullptr;              // SINK_PERPOS, SINK_DISCPOS
+  const LogSink* lg = nullptr;             // SINK_LOG
+  const ExitSink* xm = nullptr;            // SINK_EXITMAP
+  const WallSink* wm = nullptr;            // SINK_WALL
+  const FieldSink* lf = nullptr;           // SINK_LIGHTFIELD
+  const OrderSink* oh = nullptr;           // SINK_ORDER
+  const PatchSink* wp = nullptr;           // SINK_PATCH
+  const isx_beam_spec* bs = nullptr;       // SINK_FLUX with a beam source (a scene: enqueue sets it)
+  const BaffleSink* bf = nullptr;          // SINK_FLUX with baffles (a scene: enqueue sets it)
+  const SceneSink* sc = nullptr;           // a scene: isx_fluxmap_scene and the four scene maps
+  const SceneMap* map = nullptr;           // SINK_RESPONSE, SINK_VIEW, SINK_FIELD, SINK_SORDER
+};
 // The DetGrid of a call's sink, checked, and the dynamic LDS of its fused kernel (histogram + tables, census, Geom, DetGrid).
-int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d_discs, double disc_r, double disc_h,
-              const PerPos* pp, const LogSink* lg, const ExitSink* xm, const WallSink* wm, const FieldSink* lf, const OrderSink* oh,
-              const PatchSink* wp, const isx_beam_spec* bs, DetGrid& d, size_t& lds) {
+int sink_grid(const Call& k, DetGrid& d, size_t& lds) {
+  const int sink = k.sink, nbins_override = k.nbins_override;
+  const isx_config* c = k.c;
+  const double* d_discs = k.d_discs;
+  const double disc_r = k.disc_r, disc_h = k.disc_h;
+  const PerPos* pp = k.pp; const LogSink* lg = k.lg; const ExitSink* xm = k.xm; const WallSink* wm = k.wm; const FieldSink* lf = k.lf;
+  const OrderSink* oh = k.oh; const PatchSink* wp = k.wp; const isx_beam_spec* bs = k.bs;
   std::memset(&d, 0, sizeof(d));
   d.portz = c->exit_port_z;
   d.hit_line_mode = c->hit_line_mode;
@@ -907,20 +962,29 @@ int sink_grid(int sink, const isx_config* c, int nbins_override, const double* d
 //                   the order histograms: one assist-wave kernel whose waves bin every ray where it ends
 //  ROUTE_FUSED      one kernel that traces and bins: everything the routes above do not serve
 enum Route { ROUTE_FUSED, ROUTE_ASSIST, ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_FIELD_PIPE, ROUTE_DISC_PIPE };
-typedef void (*KernelFn)(const Geom, const DetGrid, const Work);
 typedef void (*BinFn)(const DetGrid, const Work);
-typedef void (*PatchFn)(const Geom, const DetGrid, const Work, const PatchTab);
-typedef void (*BeamFn)(const Geom, const DetGrid, const Work, const BeamSrc);
-typedef void (*ListFn)(const Geom, const DetGrid, const Work, const FateList);
-typedef void (*BaffleFn)(const Geom, const DetGrid, const Work, const BaffleTab);
-typedef void (*SceneFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab);
-typedef void (*ResponseFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab, const RespSink);
-typedef void (*ViewFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab, const ViewSink);
-typedef void (*PatchFieldFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab, const PatchFieldSink);
-typedef void (*SceneOrderFn)(const Geom, const DetGrid, const Work, const PatchTab, const BeamSrc, const BaffleTab, const SOrderSink);
+// A trace kernel: its address and what it takes behind (Geom, DetGrid, Work).  The constructors read the tail off the kernel's
+// own signature, so a kernel cannot be paired with the wrong arguments; launch_trace() is the one place that passes them.
+enum Tail { TAIL_NONE, TAIL_PATCH, TAIL_BEAM, TAIL_LIST, TAIL_BAFFLE, TAIL_SCENE, TAIL_RESPONSE, TAIL_VIEW, TAIL_FIELD, TAIL_SORDER };
+struct TraceKernel {
+  const void* fn = nullptr;
+  Tail tail = TAIL_NONE;
+  template <class... A> using Fn = void (*)(const Geom, const DetGrid, const Work, const A...);
+  TraceKernel() = default;
+  TraceKernel(Fn<> f) : fn((const void*)f), tail(TAIL_NONE) {}
+  TraceKernel(Fn<PatchTab> f) : fn((const void*)f), tail(TAIL_PATCH) {}
+  TraceKernel(Fn<BeamSrc> f) : fn((const void*)f), tail(TAIL_BEAM) {}
+  TraceKernel(Fn<FateList> f) : fn((const void*)f), tail(TAIL_LIST) {}
+  TraceKernel(Fn<BaffleTab> f) : fn((const void*)f), tail(TAIL_BAFFLE) {}
+  TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab> f) : fn((const void*)f), tail(TAIL_SCENE) {}
+  TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab, RespSink> f) : fn((const void*)f), tail(TAIL_RESPONSE) {}
+  TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab, ViewSink> f) : fn((const void*)f), tail(TAIL_VIEW) {}
+  TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab, PatchFieldSink> f) : fn((const void*)f), tail(TAIL_FIELD) {}
+  TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab, SOrderSink> f) : fn((const void*)f), tail(TAIL_SORDER) {}
+};
 struct Plan {
   Route route = ROUTE_FUSED;
-  KernelFn fn = nullptr;        // the kernel (a pipeline's trace kernel)
+  TraceKernel fn;               // the kernel (a pipeline's trace kernel); its tail is taken from the members below
   int block = kBlock;           // its workgroup size
   size_t lds = 0;               // its dynamic LDS
   int tracers = 0;              // its tracer waves per workgroup
@@ -936,26 +1000,42 @@ struct Plan {
   bool overlap = false;         // chunks alternate over two streams (S.overlap)
   bool call_overlap = false;    // the chunks' scans and traces go to a trace stream, ahead of the earlier binning (S.call_overlap)
   size_t slot_doubles = 6;      // doubles per exit record in the workspace
-  PatchFn patch_fn = nullptr;   // SINK_PATCH: the kernel (it takes the patches as a fourth argument: patch_tab) instead of fn
-  PatchTab patch_tab{};
   uint64_t launch_max = 0;      // ROUTE_FUSED / ROUTE_ASSIST: rays per launch (0: kLaunchMax)
-  BeamFn beam_fn = nullptr;     // isx_fluxmap_beam: the pipeline's trace kernel (it takes the source as a fourth argument: beam) instead of fn
-  BeamSrc beam{};
-  ListFn list_fn = nullptr;     // ROUTE_FLUX_PIPE behind the fate scan: isx_fate_scan_kernel, then this kernel on the rays it left, instead of fn
+  TraceKernel list;             // ROUTE_FLUX_PIPE behind the fate scan: isx_fate_scan_kernel, then this kernel on the rays it left, instead
+                                // of fn (which a chunk below the automatic rule's size still takes: launch_pair)
   FateConsts fate{};
   bool fate_auto = false;       // "fate_scan" -1: the rule's ray count is looked at per chunk (launch_pair)
-  BaffleFn baffle_fn = nullptr; // isx_fluxmap_baffle: the pipeline's trace kernel (it takes the baffles as a fourth argument: baffles) instead of fn
-  BaffleTab baffles{};
-  SceneFn scene_fn = nullptr;   // isx_fluxmap_scene: the pipeline's trace kernel (patch_tab, beam and baffles are its fourth to sixth arguments) instead of fn
-  ResponseFn resp_fn = nullptr; // isx_scene_response: ROUTE_ASSIST's one kernel (the scene's three arguments, and resp the seventh) instead of fn
-  RespSink resp{};              // (resp.lds_words: plan_launch's choice of the form; the rest is enqueue's)
-  ViewFn view_fn = nullptr;     // isx_scene_view: ROUTE_ASSIST's one kernel (the scene's three arguments, and view the seventh) instead of fn
-  ViewSink view{};              // (view.lds_words: plan_launch's choice of the form; the rest is enqueue's)
-  PatchFieldFn field_fn = nullptr;  // isx_scene_patch_field: ROUTE_ASSIST's one kernel (the scene's three arguments, and field the seventh) instead of fn
-  PatchFieldSink field{};       // (field.lds_words: plan_launch's choice of the form; the rest is enqueue's)
-  SceneOrderFn sorder_fn = nullptr; // isx_scene_order_hist: ROUTE_ASSIST's one kernel (the scene's three arguments, and sorder the seventh) instead of fn
-  SOrderSink sorder{};          // (sorder.lds_orders: plan_launch's choice of L; the rest is enqueue's)
+  // the kernels' trailing arguments (launch_trace): enqueue fills the three tables, plan_scene_map the sink of a scene map
+  PatchTab patch_tab{};         // SINK_PATCH; a scene
+  BeamSrc beam{};               // isx_fluxmap_beam; a scene
+  BaffleTab baffles{};          // isx_fluxmap_baffle; a scene
+  RespSink resp{};              // isx_scene_response (resp.lds_words: the form of the kernel)
+  ViewSink view{};              // isx_scene_view (view.lds_words: the form)
+  PatchFieldSink field{};       // isx_scene_patch_field (field.lds_words: the form)
+  SOrderSink sorder{};          // isx_scene_order_hist (sorder.lds_orders: the orders kept in LDS)
 };
+
+// The one place a trace kernel is launched: (g, d, w) and the tail its signature names, as hipLaunchKernelGGL would pass them.
+// `fl`: the fate scan's list, for TAIL_LIST.  The caller asks hipGetLastError().
+void launch_trace(const Plan& p, const TraceKernel& k, int grid, hipStream_t stream, const Geom& g, const DetGrid& d, const Work& w,
+                  const FateList* fl = nullptr) {
+  const void* args[7] = {&g, &d, &w};
+  int na = 3;
+  switch (k.tail) {
+    case TAIL_NONE: break;
+    case TAIL_PATCH: args[na++] = &p.patch_tab; break;
+    case TAIL_BEAM: args[na++] = &p.beam; break;
+    case TAIL_LIST: args[na++] = fl; break;
+    case TAIL_BAFFLE: args[na++] = &p.baffles; break;
+    default:   // a scene: its three tables, then the sink of a scene map
+      args[na++] = &p.patch_tab; args[na++] = &p.beam; args[na++] = &p.baffles;
+      if (k.tail == TAIL_RESPONSE) args[na++] = &p.resp;
+      else if (k.tail == TAIL_VIEW) args[na++] = &p.view;
+      else if (k.tail == TAIL_FIELD) args[na++] = &p.field;
+      else if (k.tail == TAIL_SORDER) args[na++] = &p.sorder;
+  }
+  (void)hipLaunchKernel(k.fn, dim3(grid), dim3(p.block), const_cast<void**>(args), p.lds, stream);
+}
 
 // "fate_scan" = -1: where the scan pays (measured on MI355X, docs/LOG.md section 16.3).  A small launch is bound by its longest
 // ray, and a second launch in front of it only adds to that: trace + binning of the default configuration with the scan against
@@ -999,9 +1079,101 @@ void trace_shape(Plan& p, Shape sh, bool assist, int per_cu) {
   p.assist = assist;
 }
 
-Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bool discs_in_aux, uint64_t n, bool beam = false,
-                 const FateConsts* fate = nullptr, bool baffle = false, bool scene = false, size_t resp_words = 0,
-                 int n_orders = 0) {
+// The shape and the LDS of a scene map's one kernel.  A scene map (isx_scene_response, isx_scene_view, isx_scene_patch_field,
+// isx_scene_order_hist) has one route whatever the switches say, as the scene has: the scene's trace kernel `fn` with the map as
+// its one sink (check_scene_call: the explicit Lambertian lean path), in the scene's shape, the scene's three blocks behind the
+// rings; no exit lines, no second kernel.  Launches are cut at pipeline_chunk as the scene's are.  Behind the parks lie `head`
+// bytes the kernel always keeps there (counters, a frame) and then up to `units` units of `unit` u32 words each of the map itself,
+// flushed once per workgroup: as many of them as cost no resident workgroup -- as many workgroups as the occupancy query of the
+// grid finds without the block still fit the LDS with it.  What does not lie in LDS takes one global u64 add per record.
+//   (two 640-thread workgroups: 68.8 KiB each without the block, 80 KiB to be had -- 2864 words; the sum is taken over 2 KiB
+//    steps so that the device's allocation granule cannot turn "fits" into one workgroup fewer)
+// With cap the largest 2 KiB-rounded size `resident` workgroups can have, a block of w words fits -- the 2 KiB-rounded sum of
+// p.lds and the 16-byte-rounded 4 w times the resident count stays within lds_limit -- exactly when w <= room: both roundings are
+// to multiples that cap and cap - p.lds rounded down already are.  So one expression serves the maps that lie in LDS whole or not
+// at all (one unit: the map) and the order histograms (a unit per order: as many orders as fit).  All sums in size_t: a field has
+// up to 2^22 words.  Returns the units that went to LDS; p.lds has their bytes.
+size_t plan_scene_map_lds(Plan& p, TraceKernel fn, uint64_t n, size_t head, size_t unit, size_t units) {
+  p.route = ROUTE_ASSIST;
+  p.fn = fn;
+  p.launch_max = std::min(kLaunchMax, S.pipe_chunk);
+  // (the kernel is built for five waves per SIMD: 640 threads -- nine tracer waves and the assist wave -- are what two
+  //  workgroups of a CU may have, unless assist_block was set)
+  trace_shape(p, small_shape(std::min(n, p.launch_max), S.assist_block_set ? S.assist_block : kSceneBlock), true,
+              resident_unless(S.trace_blocks_per_cu));
+  p.lds += SceneLds::bytes(p.tracers) + head;
+  const size_t resident = (size_t)blocks_per_cu(p.fn.fn, p.block, p.lds, kResident);
+  const size_t cap = (S.lds_limit / resident) & ~(size_t)2047;
+  const size_t room = cap > p.lds ? ((cap - p.lds) & ~(size_t)15) / 4 : 0;
+  const size_t kept = std::min(units, room / unit);
+  p.lds += (kept * unit * 4 + 15) & ~(size_t)15;
+  return kept;
+}
+
+// The plan of a scene map and the kernel's sink struct, from the call's SceneMap: per map the kernel, what it keeps behind the
+// parks in both forms, the words of the map and the switch that sends all of them to global memory (a diagnostic).
+Plan plan_scene_map(const Call& k) {
+  const SceneMap& m = *k.map;
+  const isx_scene_spec& sc = *k.sc->spec;
+  // (the scene's compact slots: P + 2 wall classes, two sides per baffle, port / other exits / suspended)
+  const size_t slots = (size_t)((sc.patches.n_patches + 2) + 2 * sc.baffles.n_baffles + 3);
+  Plan p;
+  switch (m.sink) {
+    case SINK_RESPONSE: {   // (isx_kernels.hpp: resp_record) the slots times the bins, whole or not at all; "resp_global"
+      const isx_response_spec& s = m.response();
+      const size_t words = slots * response_bins(s);
+      p.resp.lds_words = (uint32_t)(words * plan_scene_map_lds(p, isx_trace_assist_scene_response_kernel, k.n, 0, words,
+                                                               S.resp_global ? 0 : 1));
+      p.resp.out = m.out;
+      for (int a = 0; a < 4; ++a) p.resp.n[a] = (uint32_t)s.n[a];
+      p.resp.B = (uint32_t)response_bins(s);
+      break;
+    }
+    case SINK_VIEW: {   // (view_record) behind the four counters the n_u * n_v words of the map, whole or not at all; "view_global"
+      const isx_view_spec& v = m.view();
+      p.view.lds_words = (uint32_t)(view_bins(v) * plan_scene_map_lds(p, isx_trace_assist_scene_view_kernel, k.n,
+                                                                      kViewCounters * sizeof(uint32_t), view_bins(v), S.view_global ? 0 : 1));
+      p.view.out = m.out; p.view.counts = m.tail;
+      for (int i = 0; i < 3; ++i) { p.view.axis[i] = v.axis[i]; p.view.e1[i] = v.e1[i]; p.view.e2[i] = v.e2[i]; }
+      p.view.h = v.half_extent; p.view.fnu = (double)v.n_u; p.view.fnv = (double)v.n_v;
+      p.view.patch = v.patch; p.view.n_u = v.n_u;
+      break;
+    }
+    case SINK_FIELD: {   // (field_record) behind the frame's doubles and the five counters (kFieldHead bytes) the n_x * n_y * n_u * n_v
+                         // words of the field, whole or not at all; "field_global"
+      const isx_patch_field_spec& v = m.field();
+      p.field.lds_words = (uint32_t)(patch_field_bins(v) * plan_scene_map_lds(p, isx_trace_assist_scene_field_kernel, k.n,
+                                                                              kFieldHead, patch_field_bins(v), S.field_global ? 0 : 1));
+      p.field.out = m.out; p.field.counts = m.tail;
+      PatchFieldFrame& f = p.field.f;
+      for (int i = 0; i < 3; ++i) { f.axis[i] = v.axis[i]; f.e1[i] = v.e1[i]; f.e2[i] = v.e2[i]; }
+      f.h = v.half_extent; f.s = v.pos_scale; f.inv = 1.0 / k.c->r_in;   // (isx.h: inv is formed once, here)
+      f.fnx = (double)v.n_x; f.fny = (double)v.n_y; f.fnu = (double)v.n_u; f.fnv = (double)v.n_v;
+      p.field.patch = v.patch; p.field.n_x = v.n_x; p.field.n_u = v.n_u; p.field.n_v = v.n_v;
+      break;
+    }
+    default: {   // SINK_SORDER (sorder_record): behind the overflow counters (kSOrderHead words, always) the first L orders of each
+                 // slot; the orders from L on take one global u64 add each.  L is as large as fits and at most n_orders;
+                 // "sorder_lds_orders" >= 0 caps it (0: every order is global).  L is SOrderSink::lds_orders, nothing else.
+      const isx_scene_order_spec& s = m.order();
+      size_t orders = (size_t)s.n_orders;
+      if (S.sorder_lds_orders >= 0) orders = std::min(orders, (size_t)S.sorder_lds_orders);
+      p.sorder.lds_orders = (uint32_t)plan_scene_map_lds(p, isx_trace_assist_scene_order_kernel, k.n,
+                                                         kSOrderHead * sizeof(uint32_t), slots, orders);
+      p.sorder.out = m.out; p.sorder.overflow = m.tail; p.sorder.n_orders = (uint32_t)s.n_orders;
+    }
+  }
+  return p;
+}
+
+// fate: the fate scan's constants of the call's configuration (nullptr: no trace kernel will run -- the injected-record entries)
+Plan plan_launch(const Call& k, const DetGrid& d, size_t lds, const FateConsts* fate = nullptr) {
+  if (k.map) return plan_scene_map(k);
+  const int sink = k.sink;
+  const isx_config* c = k.c;
+  const uint64_t n = k.n;
+  const bool beam = k.bs != nullptr, baffle = k.bf != nullptr, scene = k.sc != nullptr;
+  const bool discs_in_aux = k.d_discs == S.d_aux;   // (the list upload_discs_clustered left there)
   enum { LAMBERT, LOBE, ROUGH } const border =
       c->surface_model == ISX_SURFACE_LOBE ? LOBE : c->lambertian ? LAMBERT : ROUGH;   // (ISX_SURFACE_ROBAST: Lambertian or rough-specular)
   const bool pencil = c->source_model == ISX_SOURCE_PENCIL;   // (else ISX_SOURCE_BRDF)
@@ -1016,93 +1188,6 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
   // was set (measured 47.1 against 48.3 ms and 33.4 against 34.0 ms for 5e7 rays, profiles/r05_surface_shapes.json)
   const int ablock = (border != LAMBERT && !S.assist_block_set) ? 512 : S.assist_block;
   Plan p;
-
-  // The scene response (isx_scene_response) has one route whatever the switches say, as the scene has: the scene's trace kernel with
-  // the response as its one sink (check_scene_call: the explicit Lambertian lean path), in the scene's shape, the scene's three
-  // blocks behind the rings; no exit lines, no second kernel.  Launches are cut at pipeline_chunk as the scene's are.  The
-  // kernel has two forms (isx_kernels.hpp: resp_record): `resp_words` u32 words -- the scene's compact slots times the bins --
-  // behind the parks, flushed once per workgroup, where that block costs no resident workgroup (as many workgroups as the
-  // occupancy query of the grid finds without it still fit the LDS with it); else, or with resp_global = 1, one global u64 add
-  // per ended ray.  The form is RespSink::lds_words, nothing else.
-  if (sink == SINK_RESPONSE) {
-    p.route = ROUTE_ASSIST;
-    p.resp_fn = isx_trace_assist_scene_response_kernel;
-    p.launch_max = std::min(kLaunchMax, S.pipe_chunk);
-    trace_shape(p, small_shape(std::min(n, p.launch_max), S.assist_block_set ? S.assist_block : kSceneBlock), true,
-                resident_unless(S.trace_blocks_per_cu));
-    p.lds += SceneLds::bytes(p.tracers);
-    // (two 640-thread workgroups: 68.8 KiB each without the block, 80 KiB to be had -- 2864 words; the sum is taken over
-    //  2 KiB steps so that the device's allocation granule cannot turn "fits" into one workgroup fewer)
-    const size_t with = p.lds + hist_lds((int)resp_words);
-    const size_t resident = (size_t)blocks_per_cu(p.resp_fn, p.block, p.lds, kResident);
-    if (!S.resp_global && ((with + 2047) & ~(size_t)2047) * resident <= S.lds_limit) {
-      p.resp.lds_words = (uint32_t)resp_words;
-      p.lds = with;
-    }
-    return p;
-  }
-  // The scene view (isx_scene_view): the same route, shape and rule -- the scene's trace kernel with the view as its one sink.
-  // Behind the parks lie the four counters (both forms) and, where that costs no resident workgroup, `resp_words` = n_u * n_v u32
-  // words of the map, flushed once per workgroup; else, or with view_global = 1, one global u64 add per binned ray
-  // (isx_kernels.hpp: view_record).  The form is ViewSink::lds_words, nothing else.
-  if (sink == SINK_VIEW) {
-    p.route = ROUTE_ASSIST;
-    p.view_fn = isx_trace_assist_scene_view_kernel;
-    p.launch_max = std::min(kLaunchMax, S.pipe_chunk);
-    trace_shape(p, small_shape(std::min(n, p.launch_max), S.assist_block_set ? S.assist_block : kSceneBlock), true,
-                resident_unless(S.trace_blocks_per_cu));
-    p.lds += SceneLds::bytes(p.tracers) + kViewCounters * sizeof(uint32_t);
-    const size_t with = p.lds + hist_lds((int)resp_words);
-    const size_t resident = (size_t)blocks_per_cu(p.view_fn, p.block, p.lds, kResident);
-    if (!S.view_global && ((with + 2047) & ~(size_t)2047) * resident <= S.lds_limit) {
-      p.view.lds_words = (uint32_t)resp_words;
-      p.lds = with;
-    }
-    return p;
-  }
-  // The scene patch field (isx_scene_patch_field): the same route, shape and rule -- the scene's trace kernel with the field as its
-  // one sink.  Behind the parks lie the frame's doubles and the five counters (kFieldHead bytes, both forms) and, where that costs
-  // no resident workgroup, `resp_words` = n_x * n_y * n_u * n_v u32 words of the field, flushed once per workgroup; else, or with
-  // field_global = 1, one global u64 add per binned ray (isx_kernels.hpp: field_record).  The form is PatchFieldSink::lds_words,
-  // nothing else.
-  if (sink == SINK_FIELD) {
-    p.route = ROUTE_ASSIST;
-    p.field_fn = isx_trace_assist_scene_field_kernel;
-    p.launch_max = std::min(kLaunchMax, S.pipe_chunk);
-    trace_shape(p, small_shape(std::min(n, p.launch_max), S.assist_block_set ? S.assist_block : kSceneBlock), true,
-                resident_unless(S.trace_blocks_per_cu));
-    p.lds += SceneLds::bytes(p.tracers) + kFieldHead;
-    // (the sum in size_t, from the word count: hist_lds takes an int, and a field has up to 2^22 words)
-    const size_t with = p.lds + ((resp_words * 4 + 15) & ~(size_t)15);
-    const size_t resident = (size_t)blocks_per_cu(p.field_fn, p.block, p.lds, kResident);
-    if (!S.field_global && ((with + 2047) & ~(size_t)2047) * resident <= S.lds_limit) {
-      p.field.lds_words = (uint32_t)resp_words;
-      p.lds = with;
-    }
-    return p;
-  }
-  // The scene order histograms (isx_scene_order_hist): the same route and shape -- the scene's trace kernel with the histograms as
-  // its one sink.  Behind the parks lie the overflow counters (kSOrderHead words, always) and the first L orders of each of the
-  // scene's `resp_words` compact slots as u32 words, flushed once per workgroup; the orders from L on take one global u64 add each
-  // (isx_kernels.hpp: sorder_record).  L is as large as the LDS allows without costing a resident workgroup -- the response's
-  // rule, solved for the block's size: the 2 KiB-rounded sum times the resident count stays within lds_limit -- and at most
-  // n_orders; "sorder_lds_orders" >= 0 caps it (0: every order is global).  L is SOrderSink::lds_orders, nothing else.
-  if (sink == SINK_SORDER) {
-    p.route = ROUTE_ASSIST;
-    p.sorder_fn = isx_trace_assist_scene_order_kernel;
-    p.launch_max = std::min(kLaunchMax, S.pipe_chunk);
-    trace_shape(p, small_shape(std::min(n, p.launch_max), S.assist_block_set ? S.assist_block : kSceneBlock), true,
-                resident_unless(S.trace_blocks_per_cu));
-    p.lds += SceneLds::bytes(p.tracers) + kSOrderHead * sizeof(uint32_t);
-    const size_t resident = (size_t)blocks_per_cu(p.sorder_fn, p.block, p.lds, kResident);
-    const size_t cap = (S.lds_limit / resident) & ~(size_t)2047;   // (the largest 2 KiB-rounded size `resident` workgroups can have)
-    const size_t free_words = cap > p.lds ? ((cap - p.lds) & ~(size_t)15) / 4 : 0;
-    size_t L = std::min((size_t)n_orders, free_words / resp_words);
-    if (S.sorder_lds_orders >= 0) L = std::min(L, (size_t)S.sorder_lds_orders);
-    p.sorder.lds_orders = (uint32_t)L;
-    p.lds += (L * resp_words * 4 + 15) & ~(size_t)15;
-    return p;
-  }
 
   // The flux pipeline's trace kernels without an assist wave serve the lean cases (pencil source, either trace mode; BRDF source,
   // explicit trace).  Those with one serve, unless surface_pipeline = 0, the origin-compat hit line as well (the assist wave writes
@@ -1129,7 +1214,7 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
   if (sink == SINK_FLUX && (beam || baffle || (flux_served && S.pipeline && S.bin_mode != 0))) {
     if (scene) {
       p.route = ROUTE_FLUX_PIPE;
-      p.scene_fn = isx_trace_assist_scene_kernel;
+      p.fn = isx_trace_assist_scene_kernel;
       // (the kernel is built for five waves per SIMD: 640 threads -- nine tracer waves and the assist wave -- are what two
       //  workgroups of a CU may have, unless assist_block was set)
       trace_shape(p, small_shape(std::min(n, S.pipe_chunk), S.assist_block_set ? S.assist_block : kSceneBlock), true,
@@ -1137,12 +1222,12 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
       p.lds += SceneLds::bytes(p.tracers);
     } else if (beam) {
       p.route = ROUTE_FLUX_PIPE;
-      p.beam_fn = isx_trace_assist_beam_kernel;
+      p.fn = isx_trace_assist_beam_kernel;
       trace_shape(p, small_shape(std::min(n, S.pipe_chunk), S.assist_block), true, resident_unless(S.trace_blocks_per_cu));
       p.lds += beam_lds(p.tracers);
     } else if (baffle) {
       p.route = ROUTE_FLUX_PIPE;
-      p.baffle_fn = isx_trace_assist_baffle_kernel;
+      p.fn = isx_trace_assist_baffle_kernel;
       trace_shape(p, small_shape(std::min(n, S.pipe_chunk), S.assist_block), true, resident_unless(S.trace_blocks_per_cu));
       p.lds += kBaffleLds;
     } else
@@ -1168,9 +1253,9 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     p.call_overlap = g_device_call && S.call_overlap != 0 && S.overlap <= 1 && !chord && !beam && !baffle && !scene;
     // the fate scan in front of the headline trace kernel (fate_consts: pencil, Lambertian border, explicit bounces, first strike
     // on the mirror patch): scheduling only -- anything else takes the kernels above whatever the option says
-    if (!beam && fate && fate->ok && p.fn == isx_trace_assist_kernel && !p.overlap &&
+    if (!beam && fate && fate->ok && p.fn.fn == (const void*)isx_trace_assist_kernel && !p.overlap &&
         (S.fate_scan == 1 || (S.fate_scan < 0 && fate_scan_auto(c, std::min(n, S.pipe_chunk))))) {
-      p.list_fn = isx_trace_assist_list_kernel;
+      p.list = isx_trace_assist_list_kernel;
       p.fate = *fate;
       p.fate_auto = S.fate_scan < 0;   // (the largest chunk passes the rule; a shorter last chunk is asked again)
     }
@@ -1243,7 +1328,7 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     Shape sh = small_shape(std::min(n, kLaunchMax), ablock);
     trace_shape(p, sh, true, resident_unless(S.trace_blocks_per_cu));
     p.lds += hist_lds(d.nbins);
-    if (sh.block > 512 && !S.assist_block_set && blocks_per_cu(p.fn, sh.block, p.lds, kResident) < 2) {
+    if (sh.block > 512 && !S.assist_block_set && blocks_per_cu(p.fn.fn, sh.block, p.lds, kResident) < 2) {
       sh.block = 512;
       trace_shape(p, sh, true, resident_unless(S.trace_blocks_per_cu));
       p.lds += hist_lds(d.nbins);
@@ -1260,7 +1345,7 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
     Shape sh = small_shape(std::min(n, kLaunchMax), ablock);
     trace_shape(p, sh, true, resident_unless(S.trace_blocks_per_cu));
     p.lds += hist_lds(d.nbins);
-    if (sh.block > 512 && !S.assist_block_set && blocks_per_cu(p.fn, sh.block, p.lds, kResident) < 2) {
+    if (sh.block > 512 && !S.assist_block_set && blocks_per_cu(p.fn.fn, sh.block, p.lds, kResident) < 2) {
       sh.block = 512;
       trace_shape(p, sh, true, resident_unless(S.trace_blocks_per_cu));
       p.lds += hist_lds(d.nbins);
@@ -1273,7 +1358,7 @@ Plan plan_launch(int sink, const isx_config* c, const DetGrid& d, size_t lds, bo
   // Launches are cut at pipeline_chunk, which bounds what a workgroup's u32 counters can see.
   if (sink == SINK_PATCH) {
     p.route = ROUTE_ASSIST;
-    p.patch_fn = isx_trace_assist_patch_kernel;
+    p.fn = isx_trace_assist_patch_kernel;
     p.launch_max = std::min(kLaunchMax, S.pipe_chunk);
     trace_shape(p, small_shape(std::min(n, p.launch_max), S.assist_block), true, resident_unless(S.trace_blocks_per_cu));
     p.lds += patch_lds();
@@ -1345,25 +1430,15 @@ int span(int kind, size_t* from) { return span_on(S.stream, kind, from); }
 
 // ROUTE_FUSED and ROUTE_ASSIST: launches of at most kLaunchMax rays, one span
 int run_single(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
-  const void* fn = p.sorder_fn ? (const void*)p.sorder_fn : p.field_fn ? (const void*)p.field_fn : p.view_fn ? (const void*)p.view_fn : p.resp_fn ? (const void*)p.resp_fn : p.patch_fn ? (const void*)p.patch_fn : (const void*)p.fn;
-  int rc = set_lds(fn, p.lds); if (rc) return rc;
-  const int per_cu = p.sorder_fn ? blocks_per_cu(p.sorder_fn, p.block, p.lds, p.per_cu) :
-                     p.field_fn ? blocks_per_cu(p.field_fn, p.block, p.lds, p.per_cu) :
-                     p.view_fn ? blocks_per_cu(p.view_fn, p.block, p.lds, p.per_cu) :
-                     p.resp_fn ? blocks_per_cu(p.resp_fn, p.block, p.lds, p.per_cu) :
-                     p.patch_fn ? blocks_per_cu(p.patch_fn, p.block, p.lds, p.per_cu) : blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
+  int rc = set_lds(p.fn.fn, p.lds); if (rc) return rc;
+  const int per_cu = blocks_per_cu(p.fn.fn, p.block, p.lds, p.per_cu);
   const uint64_t launch_max = p.launch_max ? p.launch_max : kLaunchMax;
   size_t t;
   rc = mark(S.stream, &t); if (rc) return rc;
   for (uint64_t off = 0; off < wk.n; off += launch_max) {
     Work w;
     rc = launch_work(wk, off, std::min(wk.n - off, launch_max), 0, S.stream, &w); if (rc) return rc;
-    if (p.sorder_fn) hipLaunchKernelGGL(p.sorder_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.sorder);
-    else if (p.field_fn) hipLaunchKernelGGL(p.field_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.field);
-    else if (p.view_fn) hipLaunchKernelGGL(p.view_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.view);
-    else if (p.resp_fn) hipLaunchKernelGGL(p.resp_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab, p.beam, p.baffles, p.resp);
-    else if (p.patch_fn) hipLaunchKernelGGL(p.patch_fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w, p.patch_tab);
-    else hipLaunchKernelGGL(p.fn, dim3(pick_grid(p, w.n, per_cu)), dim3(p.block), p.lds, S.stream, g, d, w);
+    launch_trace(p, p.fn, pick_grid(p, w.n, per_cu), S.stream, g, d, w);
     HIPCHK(hipGetLastError());
   }
   return span(0, &t);
@@ -1406,15 +1481,14 @@ void clustered_discs(DetGrid& d) {
 
 // ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_FIELD_PIPE and ROUTE_DISC_PIPE: a trace launch and a binning launch per chunk of at most pipe_chunk rays
 int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk) {
-  int rc = set_lds(p.scene_fn ? (const void*)p.scene_fn : p.beam_fn ? (const void*)p.beam_fn : p.baffle_fn ? (const void*)p.baffle_fn : p.list_fn ? (const void*)p.list_fn : (const void*)p.fn, p.lds);
-  if (rc == ISX_OK && p.list_fn) rc = set_lds((const void*)p.fn, p.lds);   // (a chunk below the automatic rule's size takes it)
+  // (behind the fate scan the list kernel sizes the grid; a chunk below the automatic rule's size still takes p.fn)
+  const TraceKernel& lead = p.list.fn ? p.list : p.fn;
+  int rc = set_lds(lead.fn, p.lds);
+  if (rc == ISX_OK && p.list.fn) rc = set_lds(p.fn.fn, p.lds);
   if (rc == ISX_OK) rc = set_lds((const void*)p.bin, p.lds_bin);
   if (rc) return rc;
-  const int tres = p.scene_fn ? blocks_per_cu(p.scene_fn, p.block, p.lds, p.per_cu) :
-                   p.beam_fn ? blocks_per_cu(p.beam_fn, p.block, p.lds, p.per_cu) :
-                   p.baffle_fn ? blocks_per_cu(p.baffle_fn, p.block, p.lds, p.per_cu) :
-                   p.list_fn ? blocks_per_cu(p.list_fn, p.block, p.lds, p.per_cu) : blocks_per_cu(p.fn, p.block, p.lds, p.per_cu);
-  const int bres = blocks_per_cu(p.bin, p.bblock, p.lds_bin, p.bin_per_cu);
+  const int tres = blocks_per_cu(lead.fn, p.block, p.lds, p.per_cu);
+  const int bres = blocks_per_cu((const void*)p.bin, p.bblock, p.lds_bin, p.bin_per_cu);
   // what the two kernels see: a flux map's trace kernel keeps no histogram; the disc sweep's kernels walk the discs in cluster order
   DetGrid dt = d, db = d;
   if (p.route != ROUTE_DISC_PIPE) {
@@ -1437,10 +1511,9 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     dt.rec_lines = db.rec_lines = S.d_rec[buf];
     dt.rec_counts = db.rec_counts = S.d_rec_counts[buf];
     const int tgrid = pick_grid(p, cnt, tres);
-    if (p.scene_fn) hipLaunchKernelGGL(p.scene_fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w, p.patch_tab, p.beam, p.baffles);
-    else if (p.beam_fn) hipLaunchKernelGGL(p.beam_fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w, p.beam);
-    else if (p.baffle_fn) hipLaunchKernelGGL(p.baffle_fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w, p.baffles);
-    else if (p.list_fn && (!p.fate_auto || cnt >= kFateMinRays)) {
+    const bool scan = p.list.fn && (!p.fate_auto || cnt >= kFateMinRays);
+    const FateList fl{S.d_list[buf], w.ctr + Q_LIST};
+    if (scan) {
       // the scan settles what the wall absorbs and leaves the rest in S.d_list, their number in ctr[Q_LIST] (zeroed with the
       // launch's other counters); the trace kernel's grid is sized from the chunk, an upper bound.  Same stream, no host round
       // trip; both kernels lie in the trace span.
@@ -1452,10 +1525,8 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
       hipLaunchKernelGGL(isx_fate_scan_kernel, dim3(sgrid), dim3(kScanBlock), 0, st, fs);
       HIPCHK(hipGetLastError());
       ++S.fate_launches;
-      const FateList fl{S.d_list[buf], w.ctr + Q_LIST};
-      hipLaunchKernelGGL(p.list_fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w, fl);
     }
-    else hipLaunchKernelGGL(p.fn, dim3(tgrid), dim3(p.block), p.lds, st, g, dt, w);
+    launch_trace(p, scan ? p.list : p.fn, tgrid, st, g, dt, w, &fl);
     HIPCHK(hipGetLastError());
     size_t traced;
     if (t) r = span_on(st, 1, t);
@@ -1517,7 +1588,7 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     // next, run under the tails of this one's kernels.  All kRecBufs workspaces are sized at once: a workspace that grew in the
     // middle of a sequence would stop it.
     const size_t waves = (size_t)pick_grid(p, chunk, tres) * (p.block / 64);
-    for (int b = 0; b < State::kRecBufs && rc == ISX_OK; ++b) rc = ensure_pipeline((size_t)chunk, waves, b, p.slot_doubles, p.list_fn != nullptr);
+    for (int b = 0; b < State::kRecBufs && rc == ISX_OK; ++b) rc = ensure_pipeline((size_t)chunk, waves, b, p.slot_doubles, p.list.fn != nullptr);
     if (rc == ISX_OK) rc = trace_begin();
     for (uint64_t off = 0; off < n && rc == ISX_OK; off += chunk, ++S.call_rot) {
       const int buf = (int)(S.call_rot % State::kRecBufs);
@@ -1533,7 +1604,7 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     }
     return rc;
   }
-  rc = ensure_pipeline((size_t)chunk, (size_t)pick_grid(p, chunk, tres) * (p.block / 64), 0, p.slot_doubles, p.list_fn != nullptr); if (rc) return rc;
+  rc = ensure_pipeline((size_t)chunk, (size_t)pick_grid(p, chunk, tres) * (p.block / 64), 0, p.slot_doubles, p.list.fn != nullptr); if (rc) return rc;
   size_t t;
   rc = mark(S.stream, &t);
   for (uint64_t off = 0; off < n && rc == ISX_OK; off += chunk)
@@ -1541,79 +1612,48 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
   return rc;
 }
 
-// enqueue one call's launches, accumulating into d_hist (device) and S.d_stats (or d_stats)
-int enqueue(int sink, const isx_config* c, uint64_t n, uint64_t seed, uint64_t first, unsigned long long* d_hist,
-            int nbins_override, const double* d_discs, double disc_r, double disc_h, const PerPos* pp = nullptr,
-            const LogSink* lg = nullptr, unsigned long long* d_stats = nullptr, const ExitSink* xm = nullptr,
-            const WallSink* wm = nullptr, const FieldSink* lf = nullptr, const OrderSink* oh = nullptr,
-            const PatchSink* wp = nullptr, const isx_beam_spec* bs = nullptr, const BaffleSink* bf = nullptr,
-            const SceneSink* sc = nullptr, const ResponseSink* rs = nullptr, const ViewCall* vw = nullptr,
-            const PatchFieldCall* pf = nullptr, const SceneOrderCall* so = nullptr) {
+// enqueue one call's launches, accumulating into k.d_hist (device) and S.d_stats (or k.d_stats)
+int enqueue(const Call& call) {
+  Call k = call;   // (the scene's parts and the beam's configuration are filled in below)
   Geom g;
   FateConsts fate;
   isx_config cb;
   // (a scene is its beam, its baffles -- whose counters are the last 16 of the scene's 36 -- and its patches)
   BaffleSink sc_bf;
-  if (sc) { bs = &sc->spec->beam; sc_bf.spec = &sc->spec->baffles; sc_bf.counts = sc->counts + 2 * (kMaxPatches + 2); bf = &sc_bf; }
-  if (bs && config_abi_ok(c) && bs->struct_size == (uint32_t)sizeof(isx_beam_spec)) { cb = beam_config(*c, *bs); c = &cb; }
-  int rc = prepare_geom(c, &g, &fate);
+  const SceneSink* sc = k.sc;
+  if (sc) { k.bs = &sc->spec->beam; sc_bf.spec = &sc->spec->baffles; sc_bf.counts = sc->counts + 2 * (kMaxPatches + 2); k.bf = &sc_bf; }
+  if (k.bs && config_abi_ok(k.c) && k.bs->struct_size == (uint32_t)sizeof(isx_beam_spec)) { cb = beam_config(*k.c, *k.bs); k.c = &cb; }
+  int rc = prepare_geom(k.c, &g, &fate);
   if (rc) return rc;
-  if (n > ISX_MAX_RAYS_PER_CALL) return ISX_ERR_TOO_LARGE;
-  if (first > UINT64_MAX - n) return ISX_ERR_BAD_ARG;   // first + n (the exclusive end of the index range) must be representable
+  if (k.n > ISX_MAX_RAYS_PER_CALL) return ISX_ERR_TOO_LARGE;
+  if (k.first > UINT64_MAX - k.n) return ISX_ERR_BAD_ARG;   // first + n (the exclusive end of the index range) must be representable
   DetGrid d;
   size_t lds = 0;
-  rc = sink_grid(sink, c, nbins_override, d_discs, disc_r, disc_h, pp, lg, xm, wm, lf, oh, wp, bs, d, lds);
-  if (rc == ISX_OK && bf) {
-    rc = check_baffle_call(c, bf->spec);
+  rc = sink_grid(k, d, lds);
+  if (rc == ISX_OK && k.bf) {
+    rc = check_baffle_call(k.c, k.bf->spec);
     if (S.bin_mode == 2) d.bin_mode = 1;   // (isx.h: the trace-only diagnostic does not apply to the baffles)
   }
   if (rc == ISX_OK && sc) {
-    rc = check_patch_call(c, &sc->spec->patches);
+    rc = check_patch_call(k.c, &sc->spec->patches);
     // (the patches travel in the exit maps' words of DetGrid, as SINK_PATCH's do: a flux map's trace kernel has no other use for them)
     d.xm_nx = sc->spec->patches.n_patches;
     d.xm_dir = sc->counts; d.xm_pos = sc->counts + (kMaxPatches + 2);
   }
-  if (rc || n == 0) return rc;
+  if (rc || k.n == 0) return rc;
   Work wk;
-  wk.seed = seed; wk.first = first; wk.n = n; wk.hist = d_hist; wk.stats = d_stats ? d_stats : S.d_stats;
+  wk.seed = k.seed; wk.first = k.first; wk.n = k.n; wk.hist = k.d_hist; wk.stats = k.d_stats ? k.d_stats : S.d_stats;
   wk.ctr = nullptr; wk.sub = 0; wk.pad = 0;
-  // (a response keeps the scene's compact slots per bin: P + 2 wall classes, two sides per baffle, port / other exits / suspended)
-  // (the order histograms keep the same slots per order: resp_bins = 1, and plan_launch chooses how many orders)
-  const size_t resp_bins = rs ? response_bins(*rs->spec) : so ? 1 : 0;
-  const size_t resp_words = rs || so ? (size_t)((sc->spec->patches.n_patches + 2) + 2 * sc->spec->baffles.n_baffles + 3) * resp_bins : 0;
-  Plan p = plan_launch(sink, c, d, lds, d_discs == S.d_aux, n, bs != nullptr, &fate, bf != nullptr, sc != nullptr,
-                       pf ? patch_field_bins(*pf->spec) : vw ? view_bins(*vw->spec) : resp_words, so ? so->spec->n_orders : 0);
-  if (so) { p.sorder.out = so->out; p.sorder.overflow = so->overflow; p.sorder.n_orders = (uint32_t)so->spec->n_orders; }
-  if (pf) {
-    const isx_patch_field_spec& v = *pf->spec;
-    p.field.out = pf->out; p.field.counts = pf->counts;
-    PatchFieldFrame& f = p.field.f;
-    for (int i = 0; i < 3; ++i) { f.axis[i] = v.axis[i]; f.e1[i] = v.e1[i]; f.e2[i] = v.e2[i]; }
-    f.h = v.half_extent; f.s = v.pos_scale; f.inv = 1.0 / c->r_in;   // (isx.h: inv is formed once, here)
-    f.fnx = (double)v.n_x; f.fny = (double)v.n_y; f.fnu = (double)v.n_u; f.fnv = (double)v.n_v;
-    p.field.patch = v.patch; p.field.n_x = v.n_x; p.field.n_u = v.n_u; p.field.n_v = v.n_v;
-  }
-  if (vw) {
-    const isx_view_spec& v = *vw->spec;
-    p.view.out = vw->out; p.view.counts = vw->counts;
-    for (int i = 0; i < 3; ++i) { p.view.axis[i] = v.axis[i]; p.view.e1[i] = v.e1[i]; p.view.e2[i] = v.e2[i]; }
-    p.view.h = v.half_extent; p.view.fnu = (double)v.n_u; p.view.fnv = (double)v.n_v;
-    p.view.patch = v.patch; p.view.n_u = v.n_u;
-  }
-  if (rs) {
-    p.resp.out = rs->out;
-    for (int a = 0; a < 4; ++a) p.resp.n[a] = (uint32_t)rs->spec->n[a];
-    p.resp.B = (uint32_t)resp_bins;
-  }
-  if (bf) {
+  Plan p = plan_launch(k, d, lds, &fate);
+  if (k.bf) {
     if (p.lds_bin > S.lds_limit) return ISX_ERR_BAD_CONFIG;   // (isx.h: a grid whose tables do not fit the binning kernels' LDS)
-    p.baffles = baffle_table(*c, *bf->spec, bf->counts);
+    p.baffles = baffle_table(*k.c, *k.bf->spec, k.bf->counts);
   }
-  if (sink == SINK_PATCH) p.patch_tab = patch_table(*c, *wp->spec);
-  if (sc) p.patch_tab = patch_table(*c, sc->spec->patches);
-  if (bs) {
+  if (k.sink == SINK_PATCH) p.patch_tab = patch_table(*k.c, *k.wp->spec);
+  if (sc) p.patch_tab = patch_table(*k.c, sc->spec->patches);
+  if (k.bs) {
     if (p.lds_bin > S.lds_limit) return ISX_ERR_BAD_CONFIG;   // (isx.h: a grid whose tables do not fit the binning kernels' LDS)
-    p.beam = beam_source(*bs);
+    p.beam = beam_source(*k.bs);
   }
   if (!p.call_overlap && (rc = trace_join())) return rc;   // (anything else runs on the caller's stream, behind all of an overlapped sequence)
   return p.route == ROUTE_FUSED || p.route == ROUTE_ASSIST ? run_single(p, g, d, wk) : run_pipeline(p, g, d, wk);
@@ -1757,6 +1797,46 @@ int call_open(size_t bins) {
 }
 int zero_hist(size_t bins) { return hip_rc(hipMemsetAsync(S.d_hist, 0, bins * sizeof(unsigned long long), S.stream)); }
 int call_close(int rc, isx_stats* stats) { const int rc2 = collect_stats(stats); return rc ? rc : rc2; }
+// what an entry point answers before isx_init(): ISX_ERR_NO_DEVICE where no HIP device is to be had, else ISX_ERR_NOT_INIT
+int not_initialised() {
+  int count = 0;
+  return (hipGetDeviceCount(&count) != hipSuccess || count <= 0) ? ISX_ERR_NO_DEVICE : ISX_ERR_NOT_INIT;
+}
+
+// The body of the eight scene-map entries.  `k`: the call without its sinks; `m`: the map with the caller's arrays -- device
+// arrays for a _device entry, which enqueues and returns; else host arrays (the map's own counters and `scene_counts` may be
+// NULL), filled from one device block, one staged result: the map and, behind it, its own counters and the 36 scene counters.
+// (What needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one.  isx.h: the
+// detector grid is ignored -- isx_scene_endstates' refusals.)
+int scene_map_call(Call k, const isx_scene_spec* scene, SceneMap m, uint64_t* scene_counts, bool device, isx_stats* stats) {
+  if (!k.c || !scene || !m.spec || !m.out) return ISX_ERR_BAD_ARG;
+  if (device && ((m.sink != SINK_RESPONSE && !m.tail) || !scene_counts)) return ISX_ERR_BAD_ARG;
+  size_t nb = 0, nt = 0;
+  const size_t nc = kSceneWords;
+  int rc = check_scene_call(k.c, scene, false);
+  if (rc == ISX_OK) rc = scene_map_shape(m, scene->patches.n_patches, nb, nt);
+  if (rc) return rc;
+  if (!S.init) return not_initialised();
+  SceneSink sc{scene, (unsigned long long*)scene_counts};
+  k.sc = &sc; k.map = &m;
+  if (device) return enqueue(k);
+  unsigned long long *body = m.out, *tail = m.tail;
+  const size_t bytes = (nb + nt + nc) * sizeof(unsigned long long);
+  rc = call_open(nb + nt + nc);
+  if (rc) return rc;
+  rc = zero_hist(nb + nt + nc);
+  m.out = S.d_hist; m.tail = S.d_hist + nb; sc.counts = S.d_hist + nb + nt;
+  if (rc == ISX_OK) rc = enqueue(k);
+  if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
+  rc = call_close(rc, stats);
+  if (rc == ISX_OK) {
+    fetch_result(body, nb * sizeof(unsigned long long));
+    const unsigned long long* h = reinterpret_cast<const unsigned long long*>(S.h_pin + 64) + nb;
+    if (tail) std::memcpy(tail, h, nt * sizeof(unsigned long long));
+    if (scene_counts) std::memcpy(scene_counts, h + nt, nc * sizeof(unsigned long long));
+  }
+  return rc;
+}
 
 // isx_bin_injected_lines / isx_bin_injected_segments: the binning kernel of plan `p` on `n` caller-supplied records laid out as
 // `counts` says (one entry per region), through the pipeline's own workspace, queue words and launch helpers -- what
@@ -1764,11 +1844,11 @@ int call_close(int rc, isx_stats* stats) { const int rc2 = collect_stats(stats);
 // the workspace -- 6: exit lines, the caller's rows as they are; 8: exit segments (isx_trace_assist_disc_kernel), the caller's rows
 // of 7 doubles and a zero.  The slots of a region that hold no record carry `loud` (a whole slot).
 int run_injected(const Plan& p, const DetGrid& d, const double* lines, uint64_t n, const std::vector<uint32_t>& counts,
-                 uint32_t pad, const double* loud, unsigned long long* d_hist, size_t slot = 6) {
+                 uint32_t pad, const double* loud, size_t slot = 6) {
   const size_t regions = counts.size();
   const size_t row = slot == 8 ? 7 : slot;   // doubles per record of the caller
   int rc = set_lds((const void*)p.bin, p.lds_bin); if (rc) return rc;
-  const int bres = blocks_per_cu(p.bin, p.bblock, p.lds_bin, p.bin_per_cu);
+  const int bres = blocks_per_cu((const void*)p.bin, p.bblock, p.lds_bin, p.bin_per_cu);
   rc = ensure_regions(slot == 6 ? regions + 1 : (regions + 1) * slot / 6 + 1, 0); if (rc) return rc;   // (capacity is counted in 6-double slots)
   std::vector<double> rec(regions * (size_t)kRegion * slot);
   for (size_t s = 0; s < rec.size(); s += slot) std::memcpy(&rec[s], loud, slot * sizeof(double));
@@ -1788,7 +1868,7 @@ int run_injected(const Plan& p, const DetGrid& d, const double* lines, uint64_t 
   HIPCHK(hipMemcpy(S.d_rec[0], rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(S.d_rec_counts[0], counts.data(), regions * sizeof(uint32_t), hipMemcpyHostToDevice));
   Work wk;
-  wk.seed = 0; wk.first = 0; wk.n = n; wk.hist = d_hist; wk.stats = S.d_stats; wk.ctr = nullptr; wk.sub = 0; wk.pad = 0;
+  wk.seed = 0; wk.first = 0; wk.n = n; wk.hist = S.d_hist; wk.stats = S.d_stats; wk.ctr = nullptr; wk.sub = 0; wk.pad = 0;
   Work w;
   rc = launch_work(wk, 0, n, pad, S.stream, &w); if (rc) return rc;                       // (the queue words, zeroed)
   HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(w.ctr + Q_REGIONS), (int)regions, 1, S.stream));   // (what the trace kernel would have counted)
@@ -1997,7 +2077,8 @@ int isx_fluxmap_device(const isx_config* cfg, uint64_t n_rays, uint64_t seed, ui
   if (!S.init) return ISX_ERR_NOT_INIT;
   if (!cfg || !d_hits) return ISX_ERR_BAD_ARG;
   g_device_call = true;
-  const int rc = enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, (unsigned long long*)d_hits, 0, nullptr, 0, 0);
+  const int rc = enqueue({.sink = SINK_FLUX, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray,
+                         .d_hist = (unsigned long long*)d_hits});
   g_device_call = false;
   return rc;
 }
@@ -2012,7 +2093,7 @@ int isx_fluxmap(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t 
   rc = call_open(nb);
   if (rc) return rc;
   rc = zero_hist(nb);
-  if (rc == ISX_OK) rc = enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, S.d_hist, 0, nullptr, 0, 0);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_FLUX, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .d_hist = S.d_hist});
   if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
   rc = call_close(rc, stats);
   if (rc == ISX_OK) fetch_result(hits, bytes);
@@ -2118,7 +2199,8 @@ int isx_disc_sweep(const isx_config* cfg, const double* centers_axes, int32_t n_
   g_disc_clusters = DiscClusters();
   rc = S.disc_pipeline ? upload_discs_clustered(centers_axes, (size_t)n_disc, radius, half_thick) : upload_aux(centers_axes, (size_t)n_disc * 6);
   if (rc == ISX_OK) rc = zero_hist((size_t)n_disc);
-  if (rc == ISX_OK) rc = enqueue(SINK_DISC, cfg, n_rays, seed, first_ray, S.d_hist, n_disc, S.d_aux, radius, half_thick);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_DISC, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .d_hist = S.d_hist,
+                                 .nbins_override = n_disc, .d_discs = S.d_aux, .disc_r = radius, .disc_h = half_thick});
   if (rc == ISX_OK) rc = copy_out(hits, S.d_hist, (size_t)n_disc * sizeof(unsigned long long));
   return call_close(rc, stats);
 }
@@ -2136,9 +2218,9 @@ int isx_disc_sweep_per_position(const isx_config* cfg, const double* centers_axe
   rc = upload_aux(centers_axes, (size_t)n_disc * 6);
   if (rc == ISX_OK) rc = zero_hist((size_t)n_disc);
   const PerPos pp{first_ray, rays_per_position, 1};
-  if (rc == ISX_OK)
-    rc = enqueue(SINK_DISCPOS, cfg, (uint64_t)n_disc * rays_per_position, seed, first_ray, S.d_hist, n_disc, S.d_aux, radius,
-                 half_thick, &pp);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_DISCPOS, .c = cfg, .n = (uint64_t)n_disc * rays_per_position, .seed = seed,
+                                 .first = first_ray, .d_hist = S.d_hist, .nbins_override = n_disc, .d_discs = S.d_aux,
+                                 .disc_r = radius, .disc_h = half_thick, .pp = &pp});
   if (rc == ISX_OK) rc = copy_out(hits, S.d_hist, (size_t)n_disc * sizeof(unsigned long long));
   return call_close(rc, stats);
 }
@@ -2158,9 +2240,8 @@ int isx_fluxmap_per_position(const isx_config* cfg, uint64_t rays_per_position, 
   if (rc) return rc;
   const PerPos pp{first_ray, rays_per_position, fold};
   rc = zero_hist(nb);
-  if (rc == ISX_OK)
-    rc = enqueue(SINK_PERPOS, cfg, n_groups * rays_per_position, seed, first_ray + first_group * rays_per_position,
-                 S.d_hist, 0, nullptr, 0, 0, &pp);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_PERPOS, .c = cfg, .n = n_groups * rays_per_position, .seed = seed,
+                                 .first = first_ray + first_group * rays_per_position, .d_hist = S.d_hist, .pp = &pp});
   if (rc == ISX_OK) rc = copy_out(hits, S.d_hist, nb * sizeof(unsigned long long));
   return call_close(rc, stats);
 }
@@ -2174,7 +2255,8 @@ int isx_trace_rays_detector(const isx_config* cfg, const double* detector, doubl
   rc = upload_aux(detector, 6);
   if (rc == ISX_OK) rc = zero_hist(1);
   const PerPos pp{first_ray, n_rays > 0 ? n_rays : 1, 1, S.d_aux, width};   // (S.d_aux: after the upload, which may move it)
-  if (rc == ISX_OK) rc = enqueue(SINK_PERPOS, cfg, n_rays, seed, first_ray, S.d_hist, 1, nullptr, 0, 0, &pp);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_PERPOS, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray,
+                                 .d_hist = S.d_hist, .nbins_override = 1, .pp = &pp});
   unsigned long long h = 0;
   if (rc == ISX_OK) rc = stage_result(S.d_hist, sizeof(h));
   rc = call_close(rc, stats);
@@ -2199,7 +2281,8 @@ int isx_exit_directions(const isx_config* cfg, uint64_t n_rays, uint64_t seed, u
   if (rc == ISX_OK) rc = hip_rc(hipMemsetAsync(d_cnt.p, 0, 8, S.stream));
   if (rc == ISX_OK) rc = zero_hist(1);
   const LogSink lg{d_rec.p, d_cnt.p, capacity};
-  if (rc == ISX_OK) rc = enqueue(SINK_LOG, cfg, n_rays, seed, first_ray, S.d_hist, 0, nullptr, 0, 0, nullptr, &lg);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_LOG, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .d_hist = S.d_hist,
+                                 .lg = &lg});
   unsigned long long total = 0;
   if (rc == ISX_OK) rc = hip_rc(hipStreamSynchronize(S.stream));
   if (rc == ISX_OK) rc = hip_rc(hipMemcpy(&total, d_cnt.p, 8, hipMemcpyDeviceToHost));
@@ -2239,9 +2322,10 @@ int isx_fluxmap_series(const isx_config* cfgs, int32_t n_cfg, uint64_t n_rays, u
   if (rc == ISX_OK) rc = zero_hist(nb * (size_t)n_cfg);
   // every configuration is enqueued back to back (no host round trip in between); configuration k
   // uses the ray indices [first_ray + k*n_rays, +n_rays) so the maps are statistically independent
-  for (int k = 0; k < n_cfg && rc == ISX_OK; ++k)
-    rc = enqueue(SINK_FLUX, &cfgs[k], n_rays, seed, first_ray + (uint64_t)k * n_rays, S.d_hist + (size_t)k * nb, 0, nullptr,
-                 0, 0, nullptr, nullptr, d_st.p + (size_t)k * 8);
+  for (int k = 0; k < n_cfg && rc == ISX_OK; ++k) {
+    rc = enqueue({.sink = SINK_FLUX, .c = &cfgs[k], .n = n_rays, .seed = seed, .first = first_ray + (uint64_t)k * n_rays,
+                 .d_hist = S.d_hist + (size_t)k * nb, .d_stats = d_st.p + (size_t)k * 8});
+  }
   std::vector<unsigned long long> hst((size_t)n_cfg * 8);
   if (rc == ISX_OK) rc = copy_out(hits, S.d_hist, nb * (size_t)n_cfg * sizeof(unsigned long long));
   if (rc == ISX_OK) rc = copy_out(hst.data(), d_st.p, hst.size() * 8);
@@ -2265,7 +2349,8 @@ int isx_exit_dz_hist(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint
   int rc = call_open((size_t)nbins);
   if (rc) return rc;
   rc = zero_hist((size_t)nbins);
-  if (rc == ISX_OK) rc = enqueue(SINK_DZ, cfg, n_rays, seed, first_ray, S.d_hist, nbins, nullptr, 0, 0);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_DZ, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .d_hist = S.d_hist,
+                                 .nbins_override = nbins});
   if (rc == ISX_OK) rc = copy_out(hist, S.d_hist, (size_t)nbins * sizeof(unsigned long long));
   return call_close(rc, stats);
 }
@@ -2286,7 +2371,7 @@ int isx_exit_maps_device(const isx_config* cfg, const isx_exit_map_spec* spec, u
   if (!S.init) return ISX_ERR_NOT_INIT;
   if (!cfg || !spec || !d_counts) return ISX_ERR_BAD_ARG;
   const ExitSink xm{spec, (unsigned long long*)d_dir_map, (unsigned long long*)d_pos_map, (unsigned long long*)d_counts};
-  return enqueue(SINK_EXITMAP, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, &xm);
+  return enqueue({.sink = SINK_EXITMAP, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .xm = &xm});
 }
 
 int isx_exit_maps(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
@@ -2303,7 +2388,7 @@ int isx_exit_maps(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t
   // the call's accumulators in the pooled histogram: direction map | plane map | the five counters
   const ExitSink xm{spec, ndir ? S.d_hist : nullptr, npos ? S.d_hist + ndir : nullptr, S.d_hist + ndir + npos};
   rc = zero_hist(words);
-  if (rc == ISX_OK) rc = enqueue(SINK_EXITMAP, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, &xm);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_EXITMAP, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .xm = &xm});
   if (rc == ISX_OK) rc = stage_result(S.d_hist, words * sizeof(unsigned long long));
   rc = call_close(rc, stats);
   if (rc == ISX_OK) {
@@ -2316,12 +2401,6 @@ int isx_exit_maps(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t
     }
   }
   return rc;
-}
-
-// what an entry point answers before isx_init(): ISX_ERR_NO_DEVICE where no HIP device is to be had, else ISX_ERR_NOT_INIT
-static int not_initialised() {
-  int count = 0;
-  return (hipGetDeviceCount(&count) != hipSuccess || count <= 0) ? ISX_ERR_NO_DEVICE : ISX_ERR_NOT_INIT;
 }
 
 void isx_default_wall_map_spec(const isx_config* cfg, isx_wall_map_spec* spec) {
@@ -2337,7 +2416,7 @@ int isx_wall_map_device(const isx_config* cfg, const isx_wall_map_spec* spec, ui
   if (!S.init) return not_initialised();
   if (!cfg || !spec || !d_wall_map || !d_counts) return ISX_ERR_BAD_ARG;
   const WallSink wm{spec, (unsigned long long*)d_wall_map, (unsigned long long*)d_counts};
-  return enqueue(SINK_WALL, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, &wm);
+  return enqueue({.sink = SINK_WALL, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .wm = &wm});
 }
 
 int isx_wall_map(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
@@ -2353,7 +2432,7 @@ int isx_wall_map(const isx_config* cfg, const isx_wall_map_spec* spec, uint64_t 
   // the call's accumulators in the pooled histogram: the map | the four counters
   const WallSink wm{spec, S.d_hist, S.d_hist + nmap};
   rc = zero_hist(words);
-  if (rc == ISX_OK) rc = enqueue(SINK_WALL, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, &wm);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_WALL, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .wm = &wm});
   if (rc == ISX_OK) rc = stage_result(S.d_hist, words * sizeof(unsigned long long));
   rc = call_close(rc, stats);
   if (rc == ISX_OK) {
@@ -2378,7 +2457,7 @@ int isx_light_field_device(const isx_config* cfg, const isx_exit_map_spec* spec,
   if (bad) return bad;
   if (!S.init) return not_initialised();
   const FieldSink lf{spec, (unsigned long long*)d_field, (unsigned long long*)d_counts};
-  return enqueue(SINK_LIGHTFIELD, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &lf);
+  return enqueue({.sink = SINK_LIGHTFIELD, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .lf = &lf});
 }
 
 int isx_light_field(const isx_config* cfg, const isx_exit_map_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
@@ -2395,7 +2474,7 @@ int isx_light_field(const isx_config* cfg, const isx_exit_map_spec* spec, uint64
   // memory (up to 32 MiB: not through the staging buffer), the counters through the staging buffer.
   const FieldSink lf{spec, S.d_hist, S.d_hist + nfield};
   rc = zero_hist(nfield + 4);
-  if (rc == ISX_OK) rc = enqueue(SINK_LIGHTFIELD, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &lf);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_LIGHTFIELD, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .lf = &lf});
   if (rc == ISX_OK) rc = copy_out(field, S.d_hist, nfield * sizeof(unsigned long long));
   if (rc == ISX_OK) rc = stage_result(S.d_hist + nfield, 4 * sizeof(unsigned long long));
   rc = call_close(rc, stats);
@@ -2424,9 +2503,10 @@ static int inject_layout(uint64_t n, const uint32_t* region_counts, int32_t n_re
   return ISX_OK;
 }
 
-static int bin_injected_lines(const isx_config* cfg, int32_t sink, const isx_exit_map_spec* spec, const double* lines, uint64_t n,
+// (the staging copies are std::vectors: no exception crosses the ABI)
+int isx_bin_injected_lines(const isx_config* cfg, int32_t sink, const isx_exit_map_spec* spec, const double* lines, uint64_t n,
                            const uint32_t* region_counts, int32_t n_regions, int32_t unit, uint64_t* out_a, uint64_t* out_b,
-                           uint64_t* counts, uint64_t* bin_increments) {
+                           uint64_t* counts, uint64_t* bin_increments) try {
   // ---- what needs no device (isx.h: the refusals)
   if (!cfg || (n && !lines)) return ISX_ERR_BAD_ARG;
   if (sink != ISX_INJECT_FLUX && sink != ISX_INJECT_EXIT_MAPS && sink != ISX_INJECT_LIGHT_FIELD) return ISX_ERR_BAD_ARG;
@@ -2485,17 +2565,18 @@ static int bin_injected_lines(const isx_config* cfg, int32_t sink, const isx_exi
     const int ksink = sink == ISX_INJECT_FLUX ? SINK_FLUX : sink == ISX_INJECT_EXIT_MAPS ? SINK_EXITMAP : SINK_LIGHTFIELD;
     const ExitSink xm{spec, na ? S.d_hist : nullptr, nb ? S.d_hist + na : nullptr, S.d_hist + na + nb};
     const FieldSink lf{spec, S.d_hist, S.d_hist + na};
+    const Call call{.sink = ksink, .c = cfg, .n = n, .xm = &xm, .lf = &lf};
     DetGrid d;
     size_t lds = 0;
-    rc = sink_grid(ksink, cfg, 0, nullptr, 0, 0, nullptr, nullptr, &xm, nullptr, &lf, nullptr, nullptr, nullptr, d, lds);
+    rc = sink_grid(call, d, lds);
     if (rc == ISX_OK) {
-      const Plan p = plan_launch(ksink, cfg, d, lds, false, n);
+      const Plan p = plan_launch(call, d, lds);
       const Route want = sink == ISX_INJECT_FLUX ? ROUTE_FLUX_PIPE : sink == ISX_INJECT_EXIT_MAPS ? ROUTE_EXIT_PIPE : ROUTE_FIELD_PIPE;
       if (p.route != want || !p.bin || !p.binning || p.slot_doubles != 6) rc = ISX_ERR_BAD_CONFIG;   // (no binning kernel answers this call)
       else {
         const double loud[6] = {0.0, 0.0, cfg->exit_port_z + 0.5 * cfg->det_distance, 0.0, 0.0, -1.0};
         const uint32_t pad = unit == ISX_INJECT_UNIT_AUTO ? (n < 1000000ull ? 2u : 0u) : (uint32_t)unit;
-        rc = run_injected(p, d, lines, n, layout, pad, loud, S.d_hist);
+        rc = run_injected(p, d, lines, n, layout, pad, loud);
       }
     }
   }
@@ -2507,22 +2588,14 @@ static int bin_injected_lines(const isx_config* cfg, int32_t sink, const isx_exi
   for (size_t k = 0; k < nc; ++k) counts[k] += host[na + nb + k];
   if (bin_increments) *bin_increments = st.bin_increments;
   return ISX_OK;
+} catch (const std::bad_alloc&) {
+  return ISX_ERR_TOO_LARGE;
 }
 
-int isx_bin_injected_lines(const isx_config* cfg, int32_t sink, const isx_exit_map_spec* spec, const double* lines, uint64_t n,
-                           const uint32_t* region_counts, int32_t n_regions, int32_t unit, uint64_t* out_a, uint64_t* out_b,
-                           uint64_t* counts, uint64_t* bin_increments) {
-  // (the staging copies are std::vectors: no exception crosses the ABI)
-  try {
-    return bin_injected_lines(cfg, sink, spec, lines, n, region_counts, n_regions, unit, out_a, out_b, counts, bin_increments);
-  } catch (const std::bad_alloc&) {
-    return ISX_ERR_TOO_LARGE;
-  }
-}
-
-static int bin_injected_segments(const isx_config* cfg, const double* centers_axes, int32_t n_disc, double radius, double half_thick,
-                                 const double* segments, uint64_t n, const uint32_t* region_counts, int32_t n_regions, int32_t unit,
-                                 uint64_t* hits, uint64_t* bin_increments) {
+// (the staging copies are std::vectors: no exception crosses the ABI)
+int isx_bin_injected_segments(const isx_config* cfg, const double* centers_axes, int32_t n_disc, double radius, double half_thick,
+                              const double* segments, uint64_t n, const uint32_t* region_counts, int32_t n_regions, int32_t unit,
+                              uint64_t* hits, uint64_t* bin_increments) try {
   // ---- what needs no device (isx.h: the refusals)
   if (!cfg || !centers_axes || !hits || (n && !segments)) return ISX_ERR_BAD_ARG;
   if (n_disc < 1 || n_disc > 36000) return ISX_ERR_BAD_ARG;   // (sink_grid's limit for a disc list)
@@ -2566,11 +2639,12 @@ static int bin_injected_segments(const isx_config* cfg, const double* centers_ax
   rc = S.disc_pipeline ? upload_discs_clustered(centers_axes, (size_t)n_disc, radius, half_thick) : ISX_ERR_BAD_CONFIG;
   if (rc == ISX_OK) rc = zero_hist((size_t)n_disc);
   if (rc == ISX_OK) {
+    const Call call{.sink = SINK_DISC, .c = cfg, .n = n, .nbins_override = n_disc, .d_discs = S.d_aux, .disc_r = radius, .disc_h = half_thick};
     DetGrid d;
     size_t lds = 0;
-    rc = sink_grid(SINK_DISC, cfg, n_disc, S.d_aux, radius, half_thick, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d, lds);
+    rc = sink_grid(call, d, lds);
     if (rc == ISX_OK) {
-      const Plan p = plan_launch(SINK_DISC, cfg, d, lds, true, n);
+      const Plan p = plan_launch(call, d, lds);
       if (p.route != ROUTE_DISC_PIPE || p.bin != isx_bin_discs_kernel || p.slot_doubles != 8) rc = ISX_ERR_BAD_CONFIG;   // (the fused kernel answers isx_disc_sweep)
       else {
         clustered_discs(d);
@@ -2578,7 +2652,7 @@ static int bin_injected_segments(const isx_config* cfg, const double* centers_ax
         const double* c0 = centers_axes;
         const double loud[8] = {c0[0] - c0[3], c0[1] - c0[4], c0[2] - c0[5], c0[3], c0[4], c0[5], 2.0, 0.0};
         const uint32_t pad = unit == ISX_INJECT_UNIT_AUTO ? (n < 1000000ull ? 2u : 0u) : (uint32_t)unit;
-        rc = run_injected(p, d, segments, n, layout, pad, loud, S.d_hist, 8);
+        rc = run_injected(p, d, segments, n, layout, pad, loud, 8);
       }
     }
   }
@@ -2588,18 +2662,8 @@ static int bin_injected_segments(const isx_config* cfg, const double* centers_ax
   for (int32_t k = 0; k < n_disc; ++k) hits[k] += host[(size_t)k];
   if (bin_increments) *bin_increments = st.bin_increments;
   return ISX_OK;
-}
-
-int isx_bin_injected_segments(const isx_config* cfg, const double* centers_axes, int32_t n_disc, double radius, double half_thick,
-                              const double* segments, uint64_t n, const uint32_t* region_counts, int32_t n_regions, int32_t unit,
-                              uint64_t* hits, uint64_t* bin_increments) {
-  // (the staging copies are std::vectors: no exception crosses the ABI)
-  try {
-    return bin_injected_segments(cfg, centers_axes, n_disc, radius, half_thick, segments, n, region_counts, n_regions, unit, hits,
-                                 bin_increments);
-  } catch (const std::bad_alloc&) {
-    return ISX_ERR_TOO_LARGE;
-  }
+} catch (const std::bad_alloc&) {
+  return ISX_ERR_TOO_LARGE;
 }
 
 void isx_default_order_hist_spec(const isx_config* cfg, isx_order_hist_spec* spec) {
@@ -2620,8 +2684,7 @@ int isx_order_hist_device(const isx_config* cfg, const isx_order_hist_spec* spec
   if (!S.init) return not_initialised();
   const OrderSink oh{spec, (unsigned long long*)d_hist, spec->n_dz > 0 ? (unsigned long long*)d_port_dz : nullptr,
                      (unsigned long long*)d_counts};
-  return enqueue(SINK_ORDER, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, &oh);
+  return enqueue({.sink = SINK_ORDER, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .oh = &oh});
 }
 
 int isx_order_hist(const isx_config* cfg, const isx_order_hist_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
@@ -2638,8 +2701,7 @@ int isx_order_hist(const isx_config* cfg, const isx_order_hist_spec* spec, uint6
   // the call's accumulators in the pooled histogram: the four histograms | the port's dz | the five counters
   const OrderSink oh{spec, S.d_hist, nd ? S.d_hist + nh : nullptr, S.d_hist + nh + nd};
   rc = zero_hist(words);
-  if (rc == ISX_OK) rc = enqueue(SINK_ORDER, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, &oh);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_ORDER, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .oh = &oh});
   if (rc == ISX_OK) rc = stage_result(S.d_hist, words * sizeof(unsigned long long));
   rc = call_close(rc, stats);
   if (rc == ISX_OK) {
@@ -2711,8 +2773,7 @@ int isx_wall_patches_device(const isx_config* cfg, const isx_wall_patch_spec* sp
   if (bad) return bad;
   if (!S.init) return not_initialised();
   const PatchSink wp{spec, (unsigned long long*)d_arrivals, (unsigned long long*)d_absorbed};
-  return enqueue(SINK_PATCH, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, &wp);
+  return enqueue({.sink = SINK_PATCH, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .wp = &wp});
 }
 
 int isx_wall_patches(const isx_config* cfg, const isx_wall_patch_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
@@ -2727,8 +2788,7 @@ int isx_wall_patches(const isx_config* cfg, const isx_wall_patch_spec* spec, uin
   // the call's accumulators in the pooled histogram: arrivals | absorbed
   const PatchSink wp{spec, S.d_hist, S.d_hist + nc};
   rc = zero_hist(words);
-  if (rc == ISX_OK) rc = enqueue(SINK_PATCH, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, nullptr, &wp);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_PATCH, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .wp = &wp});
   if (rc == ISX_OK) rc = stage_result(S.d_hist, words * sizeof(unsigned long long));
   rc = call_close(rc, stats);
   if (rc == ISX_OK) {
@@ -2815,8 +2875,8 @@ int isx_fluxmap_beam_device(const isx_config* cfg, const isx_beam_spec* spec, ui
   const int bad = check_beam_call(cfg, spec);
   if (bad) return bad;
   if (!S.init) return not_initialised();
-  return enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, (unsigned long long*)d_hits, 0, nullptr, 0, 0, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, nullptr, nullptr, nullptr, spec);
+  return enqueue({.sink = SINK_FLUX, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray,
+                 .d_hist = (unsigned long long*)d_hits, .bs = spec});
 }
 
 int isx_fluxmap_beam(const isx_config* cfg, const isx_beam_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
@@ -2831,8 +2891,8 @@ int isx_fluxmap_beam(const isx_config* cfg, const isx_beam_spec* spec, uint64_t 
   rc = call_open(nb);
   if (rc) return rc;
   rc = zero_hist(nb);
-  if (rc == ISX_OK) rc = enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, S.d_hist, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, spec);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_FLUX, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .d_hist = S.d_hist,
+                                 .bs = spec});
   if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
   rc = call_close(rc, stats);
   if (rc == ISX_OK) fetch_result(hits, bytes);
@@ -2908,8 +2968,8 @@ int isx_fluxmap_baffle_device(const isx_config* cfg, const isx_baffle_spec* spec
   if (bad) return bad;
   if (!S.init) return not_initialised();
   const BaffleSink bf{spec, (unsigned long long*)d_counts};
-  return enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, (unsigned long long*)d_hits, 0, nullptr, 0, 0, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &bf);
+  return enqueue({.sink = SINK_FLUX, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray,
+                 .d_hist = (unsigned long long*)d_hits, .bf = &bf});
 }
 
 int isx_fluxmap_baffle(const isx_config* cfg, const isx_baffle_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
@@ -2925,8 +2985,8 @@ int isx_fluxmap_baffle(const isx_config* cfg, const isx_baffle_spec* spec, uint6
   if (rc) return rc;
   rc = zero_hist(nb + nc);
   const BaffleSink bf{spec, S.d_hist + nb};
-  if (rc == ISX_OK) rc = enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, S.d_hist, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, &bf);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_FLUX, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .d_hist = S.d_hist,
+                                 .bf = &bf});
   if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
   rc = call_close(rc, stats);
   if (rc == ISX_OK) {
@@ -2995,8 +3055,8 @@ int isx_fluxmap_scene_device(const isx_config* cfg, const isx_scene_spec* spec, 
   if (bad) return bad;
   if (!S.init) return not_initialised();
   const SceneSink sc{spec, (unsigned long long*)d_counts};
-  return enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, (unsigned long long*)d_hits, 0, nullptr, 0, 0, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sc);
+  return enqueue({.sink = SINK_FLUX, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray,
+                 .d_hist = (unsigned long long*)d_hits, .sc = &sc});
 }
 
 int isx_fluxmap_scene(const isx_config* cfg, const isx_scene_spec* spec, uint64_t n_rays, uint64_t seed, uint64_t first_ray,
@@ -3011,8 +3071,8 @@ int isx_fluxmap_scene(const isx_config* cfg, const isx_scene_spec* spec, uint64_
   if (rc) return rc;
   rc = zero_hist(nb + nc);
   const SceneSink sc{spec, S.d_hist + nb};
-  if (rc == ISX_OK) rc = enqueue(SINK_FLUX, cfg, n_rays, seed, first_ray, S.d_hist, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sc);
+  if (rc == ISX_OK) rc = enqueue({.sink = SINK_FLUX, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray, .d_hist = S.d_hist,
+                                 .sc = &sc});
   if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
   rc = call_close(rc, stats);
   if (rc == ISX_OK) {
@@ -3032,41 +3092,14 @@ void isx_default_response_spec(const isx_config* cfg, isx_response_spec* spec) {
 
 int isx_scene_response_device(const isx_config* cfg, const isx_scene_spec* scene, const isx_response_spec* rspec, uint64_t n_rays,
                               uint64_t seed, uint64_t first_ray, uint64_t* d_response, uint64_t* d_counts) {
-  // (what needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one)
-  if (!cfg || !scene || !rspec || !d_response || !d_counts) return ISX_ERR_BAD_ARG;
-  int bad = check_scene_call(cfg, scene, false);   // (isx.h: the detector grid is ignored -- isx_scene_endstates' refusals)
-  if (bad == ISX_OK) bad = check_response_spec(rspec);
-  if (bad) return bad;
-  if (!S.init) return not_initialised();
-  const SceneSink sc{scene, (unsigned long long*)d_counts};
-  const ResponseSink rs{rspec, (unsigned long long*)d_response};
-  return enqueue(SINK_RESPONSE, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, nullptr, nullptr, nullptr, &sc, &rs);
+  return scene_map_call({.sink = SINK_RESPONSE, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray}, scene,
+                        SceneMap{SINK_RESPONSE, rspec, (unsigned long long*)d_response, nullptr}, d_counts, true, nullptr);
 }
 
 int isx_scene_response(const isx_config* cfg, const isx_scene_spec* scene, const isx_response_spec* rspec, uint64_t n_rays,
                        uint64_t seed, uint64_t first_ray, uint64_t* response, isx_scene_counts* counts, isx_stats* stats) {
-  if (!cfg || !scene || !rspec || !response) return ISX_ERR_BAD_ARG;
-  int rc = check_scene_call(cfg, scene, false);
-  if (rc == ISX_OK) rc = check_response_spec(rspec);
-  if (rc) return rc;
-  if (!S.init) return not_initialised();
-  // the response and, behind it, the 36 counters: one device block, one staged result
-  const size_t nb = (size_t)ISX_RESPONSE_FATES * response_bins(*rspec), nc = kSceneWords, bytes = (nb + nc) * sizeof(unsigned long long);
-  rc = call_open(nb + nc);
-  if (rc) return rc;
-  rc = zero_hist(nb + nc);
-  const SceneSink sc{scene, S.d_hist + nb};
-  const ResponseSink rs{rspec, S.d_hist};
-  if (rc == ISX_OK) rc = enqueue(SINK_RESPONSE, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sc, &rs);
-  if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
-  rc = call_close(rc, stats);
-  if (rc == ISX_OK) {
-    fetch_result(response, nb * sizeof(unsigned long long));
-    if (counts) std::memcpy(counts, reinterpret_cast<const unsigned long long*>(S.h_pin + 64) + nb, nc * sizeof(unsigned long long));
-  }
-  return rc;
+  return scene_map_call({.sink = SINK_RESPONSE, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray}, scene,
+                        SceneMap{SINK_RESPONSE, rspec, (unsigned long long*)response, nullptr}, (uint64_t*)counts, false, stats);
 }
 
 int isx_response_reweight(const isx_response_spec* rspec, const uint64_t* response, const double* weight, double* fraction,
@@ -3126,43 +3159,16 @@ int isx_view_frame(const isx_config* cfg, const isx_scene_spec* scene, int32_t p
 
 int isx_scene_view_device(const isx_config* cfg, const isx_scene_spec* scene, const isx_view_spec* vspec, uint64_t n_rays,
                           uint64_t seed, uint64_t first_ray, uint64_t* d_view, uint64_t* d_view_counts, uint64_t* d_scene_counts) {
-  // (what needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one)
-  if (!cfg || !scene || !vspec || !d_view || !d_view_counts || !d_scene_counts) return ISX_ERR_BAD_ARG;
-  int bad = check_scene_call(cfg, scene, false);   // (isx.h: the detector grid is ignored -- isx_scene_endstates' refusals)
-  if (bad == ISX_OK) bad = check_view_spec(vspec, scene->patches.n_patches);
-  if (bad) return bad;
-  if (!S.init) return not_initialised();
-  const SceneSink sc{scene, (unsigned long long*)d_scene_counts};
-  const ViewCall vw{vspec, (unsigned long long*)d_view, (unsigned long long*)d_view_counts};
-  return enqueue(SINK_VIEW, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, nullptr, nullptr, nullptr, &sc, nullptr, &vw);
+  return scene_map_call({.sink = SINK_VIEW, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray}, scene,
+                        SceneMap{SINK_VIEW, vspec, (unsigned long long*)d_view, (unsigned long long*)d_view_counts}, d_scene_counts,
+                        true, nullptr);
 }
 
 int isx_scene_view(const isx_config* cfg, const isx_scene_spec* scene, const isx_view_spec* vspec, uint64_t n_rays, uint64_t seed,
                    uint64_t first_ray, uint64_t* view, isx_view_counts* view_counts, isx_scene_counts* scene_counts, isx_stats* stats) {
-  if (!cfg || !scene || !vspec || !view) return ISX_ERR_BAD_ARG;
-  int rc = check_scene_call(cfg, scene, false);
-  if (rc == ISX_OK) rc = check_view_spec(vspec, scene->patches.n_patches);
-  if (rc) return rc;
-  if (!S.init) return not_initialised();
-  // the map and, behind it, the four view counters and the 36 scene counters: one device block, one staged result
-  const size_t nb = view_bins(*vspec), nv = kViewCounters, nc = kSceneWords, bytes = (nb + nv + nc) * sizeof(unsigned long long);
-  rc = call_open(nb + nv + nc);
-  if (rc) return rc;
-  rc = zero_hist(nb + nv + nc);
-  const SceneSink sc{scene, S.d_hist + nb + nv};
-  const ViewCall vw{vspec, S.d_hist, S.d_hist + nb};
-  if (rc == ISX_OK) rc = enqueue(SINK_VIEW, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sc, nullptr, &vw);
-  if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
-  rc = call_close(rc, stats);
-  if (rc == ISX_OK) {
-    fetch_result(view, nb * sizeof(unsigned long long));
-    const unsigned long long* tail = reinterpret_cast<const unsigned long long*>(S.h_pin + 64) + nb;
-    if (view_counts) std::memcpy(view_counts, tail, nv * sizeof(unsigned long long));
-    if (scene_counts) std::memcpy(scene_counts, tail + nv, nc * sizeof(unsigned long long));
-  }
-  return rc;
+  return scene_map_call({.sink = SINK_VIEW, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray}, scene,
+                        SceneMap{SINK_VIEW, vspec, (unsigned long long*)view, (unsigned long long*)view_counts},
+                        (uint64_t*)scene_counts, false, stats);
 }
 
 int isx_view_reweight(const isx_view_spec* vspec, const uint64_t* view, const isx_view_counts* view_counts, uint64_t launched,
@@ -3234,44 +3240,17 @@ int isx_patch_field_frame(const isx_config* cfg, const isx_scene_spec* scene, in
 int isx_scene_patch_field_device(const isx_config* cfg, const isx_scene_spec* scene, const isx_patch_field_spec* fspec, uint64_t n_rays,
                                  uint64_t seed, uint64_t first_ray, uint64_t* d_field, uint64_t* d_field_counts,
                                  uint64_t* d_scene_counts) {
-  // (what needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one)
-  if (!cfg || !scene || !fspec || !d_field || !d_field_counts || !d_scene_counts) return ISX_ERR_BAD_ARG;
-  int bad = check_scene_call(cfg, scene, false);   // (isx.h: the detector grid is ignored -- isx_scene_endstates' refusals)
-  if (bad == ISX_OK) bad = check_patch_field_spec(fspec, scene->patches.n_patches);
-  if (bad) return bad;
-  if (!S.init) return not_initialised();
-  const SceneSink sc{scene, (unsigned long long*)d_scene_counts};
-  const PatchFieldCall pf{fspec, (unsigned long long*)d_field, (unsigned long long*)d_field_counts};
-  return enqueue(SINK_FIELD, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, nullptr, nullptr, nullptr, &sc, nullptr, nullptr, &pf);
+  return scene_map_call({.sink = SINK_FIELD, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray}, scene,
+                        SceneMap{SINK_FIELD, fspec, (unsigned long long*)d_field, (unsigned long long*)d_field_counts}, d_scene_counts,
+                        true, nullptr);
 }
 
 int isx_scene_patch_field(const isx_config* cfg, const isx_scene_spec* scene, const isx_patch_field_spec* fspec, uint64_t n_rays,
                           uint64_t seed, uint64_t first_ray, uint64_t* field, isx_patch_field_counts* field_counts,
                           isx_scene_counts* scene_counts, isx_stats* stats) {
-  if (!cfg || !scene || !fspec || !field) return ISX_ERR_BAD_ARG;
-  int rc = check_scene_call(cfg, scene, false);
-  if (rc == ISX_OK) rc = check_patch_field_spec(fspec, scene->patches.n_patches);
-  if (rc) return rc;
-  if (!S.init) return not_initialised();
-  // the field and, behind it, the five field counters and the 36 scene counters: one device block, one staged result
-  const size_t nb = patch_field_bins(*fspec), nf = kFieldCounters, nc = kSceneWords, bytes = (nb + nf + nc) * sizeof(unsigned long long);
-  rc = call_open(nb + nf + nc);
-  if (rc) return rc;
-  rc = zero_hist(nb + nf + nc);
-  const SceneSink sc{scene, S.d_hist + nb + nf};
-  const PatchFieldCall pf{fspec, S.d_hist, S.d_hist + nb};
-  if (rc == ISX_OK) rc = enqueue(SINK_FIELD, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sc, nullptr, nullptr, &pf);
-  if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
-  rc = call_close(rc, stats);
-  if (rc == ISX_OK) {
-    fetch_result(field, nb * sizeof(unsigned long long));
-    const unsigned long long* tail = reinterpret_cast<const unsigned long long*>(S.h_pin + 64) + nb;
-    if (field_counts) std::memcpy(field_counts, tail, nf * sizeof(unsigned long long));
-    if (scene_counts) std::memcpy(scene_counts, tail + nf, nc * sizeof(unsigned long long));
-  }
-  return rc;
+  return scene_map_call({.sink = SINK_FIELD, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray}, scene,
+                        SceneMap{SINK_FIELD, fspec, (unsigned long long*)field, (unsigned long long*)field_counts},
+                        (uint64_t*)scene_counts, false, stats);
 }
 
 int isx_patch_field_marginals(const isx_patch_field_spec* fspec, const uint64_t* field, uint64_t* pos_map, uint64_t* dir_map) {
@@ -3301,45 +3280,17 @@ void isx_default_scene_order_spec(const isx_config* cfg, isx_scene_order_spec* o
 int isx_scene_order_hist_device(const isx_config* cfg, const isx_scene_spec* scene, const isx_scene_order_spec* ospec,
                                 uint64_t n_rays, uint64_t seed, uint64_t first_ray, uint64_t* d_hist, uint64_t* d_order_counts,
                                 uint64_t* d_scene_counts) {
-  // (what needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one)
-  if (!cfg || !scene || !ospec || !d_hist || !d_order_counts || !d_scene_counts) return ISX_ERR_BAD_ARG;
-  int bad = check_scene_call(cfg, scene, false);   // (isx.h: the detector grid is ignored -- isx_scene_endstates' refusals)
-  if (bad == ISX_OK) bad = check_scene_order_spec(ospec);
-  if (bad) return bad;
-  if (!S.init) return not_initialised();
-  const SceneSink sc{scene, (unsigned long long*)d_scene_counts};
-  const SceneOrderCall so{ospec, (unsigned long long*)d_hist, (unsigned long long*)d_order_counts};
-  return enqueue(SINK_SORDER, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, nullptr, nullptr, nullptr, &sc, nullptr, nullptr, nullptr, &so);
+  return scene_map_call({.sink = SINK_SORDER, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray}, scene,
+                        SceneMap{SINK_SORDER, ospec, (unsigned long long*)d_hist, (unsigned long long*)d_order_counts}, d_scene_counts,
+                        true, nullptr);
 }
 
 int isx_scene_order_hist(const isx_config* cfg, const isx_scene_spec* scene, const isx_scene_order_spec* ospec, uint64_t n_rays,
                          uint64_t seed, uint64_t first_ray, uint64_t* hist, isx_scene_order_counts* order_counts,
                          isx_scene_counts* scene_counts, isx_stats* stats) {
-  if (!cfg || !scene || !ospec || !hist) return ISX_ERR_BAD_ARG;
-  int rc = check_scene_call(cfg, scene, false);
-  if (rc == ISX_OK) rc = check_scene_order_spec(ospec);
-  if (rc) return rc;
-  if (!S.init) return not_initialised();
-  // the histograms and, behind them, the 21 overflow counters and the 36 scene counters: one device block, one staged result
-  const size_t nb = (size_t)ISX_RESPONSE_FATES * (size_t)ospec->n_orders, nf = kRespFates, nc = kSceneWords,
-               bytes = (nb + nf + nc) * sizeof(unsigned long long);
-  rc = call_open(nb + nf + nc);
-  if (rc) return rc;
-  rc = zero_hist(nb + nf + nc);
-  const SceneSink sc{scene, S.d_hist + nb + nf};
-  const SceneOrderCall so{ospec, S.d_hist, S.d_hist + nb};
-  if (rc == ISX_OK) rc = enqueue(SINK_SORDER, cfg, n_rays, seed, first_ray, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sc, nullptr, nullptr, nullptr, &so);
-  if (rc == ISX_OK) rc = stage_result(S.d_hist, bytes);
-  rc = call_close(rc, stats);
-  if (rc == ISX_OK) {
-    fetch_result(hist, nb * sizeof(unsigned long long));
-    const unsigned long long* tail = reinterpret_cast<const unsigned long long*>(S.h_pin + 64) + nb;
-    if (order_counts) std::memcpy(order_counts, tail, nf * sizeof(unsigned long long));
-    if (scene_counts) std::memcpy(scene_counts, tail + nf, nc * sizeof(unsigned long long));
-  }
-  return rc;
+  return scene_map_call({.sink = SINK_SORDER, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray}, scene,
+                        SceneMap{SINK_SORDER, ospec, (unsigned long long*)hist, (unsigned long long*)order_counts},
+                        (uint64_t*)scene_counts, false, stats);
 }
 
 int isx_scene_order_reweight(const isx_config* cfg, const isx_scene_spec* scene, const isx_scene_order_spec* ospec,
