@@ -11,7 +11,7 @@ or through the `altair_raytracing_amd` shim at the repo root.
 """
 from . import _abi as abi  # noqa: F401
 from . import sharding  # noqa: F401
-from .sharding import shard, step_slice, fluxmap_sharded, disc_sweep_sharded, exit_maps_sharded, wall_map_sharded, light_field_sharded, order_hist_sharded, wall_patches_sharded, fluxmap_beam_sharded, fluxmap_baffle_sharded, fluxmap_scene_sharded, scene_response_sharded, scene_view_sharded, scene_patch_field_sharded, scene_order_hist_sharded  # noqa: F401
+from .sharding import shard, step_slice, fluxmap_sharded, disc_sweep_sharded, exit_maps_sharded, wall_map_sharded, light_field_sharded, order_hist_sharded, wall_patches_sharded, fluxmap_beam_sharded, fluxmap_baffle_sharded, fluxmap_scene_sharded, scene_response_sharded, scene_view_sharded, scene_patch_field_sharded, scene_order_hist_sharded, scene_path_hist_sharded  # noqa: F401
 from ._abi import (  # noqa: F401
     Config, Stats, IsxError, default_config, init, shutdown, device_info, set_option, fluxmap, fluxmap_device, sync,
     take_stats, last_kernel_ms, trace_endstates, fate_scan, fate_scan_launches, disc_sweep, disc_sweep_per_position, exit_dz_hist, fluxmap_per_position, trace_rays_detector, exit_directions, fluxmap_series, detector_table, mathprobe, load, LIB_PATH, EXPORTS,
@@ -30,6 +30,8 @@ from ._abi import (  # noqa: F401
     PatchFieldSpec, PatchFieldCounts, patch_field_frame, scene_patch_field, scene_patch_field_device, patch_field_marginals,
     SceneOrderSpec, SceneOrderCounts, default_scene_order_spec, scene_order_spec, scene_order_hist, scene_order_hist_device,
     scene_order_reweight, scene_order_moments, SCENE_ORDER_MAX_ORDERS,
+    ScenePathSpec, ScenePathCounts, default_scene_path_spec, scene_path_spec, scene_path_hist, scene_path_hist_device,
+    scene_path_moments, scene_path_decay, SCENE_PATH_MAX_BINS, LIGHT_CM_PER_NS,
     SOURCE_PENCIL, SOURCE_BRDF, RAY_EXITED, RAY_ABSORBED, RAY_SUSPENDED,
 )
 
@@ -58,4 +60,7 @@ __all__ = ["abi", "sharding", "shard", "step_slice", "fluxmap_sharded", "disc_sw
            "SceneOrderSpec", "SceneOrderCounts", "default_scene_order_spec", "scene_order_spec", "scene_order_hist",
            "scene_order_hist_device", "scene_order_reweight", "scene_order_moments", "SCENE_ORDER_MAX_ORDERS",
            "scene_order_hist_sharded",
+           "ScenePathSpec", "ScenePathCounts", "default_scene_path_spec", "scene_path_spec", "scene_path_hist",
+           "scene_path_hist_device", "scene_path_moments", "scene_path_decay", "SCENE_PATH_MAX_BINS", "LIGHT_CM_PER_NS",
+           "scene_path_hist_sharded",
            "SOURCE_PENCIL", "SOURCE_BRDF", "RAY_EXITED", "RAY_ABSORBED", "RAY_SUSPENDED"]

@@ -56,6 +56,8 @@ EXPORTS = [
     "isx_patch_field_frame", "isx_scene_patch_field", "isx_scene_patch_field_device", "isx_patch_field_marginals",
     "isx_default_scene_order_spec", "isx_scene_order_hist", "isx_scene_order_hist_device", "isx_scene_order_reweight",
     "isx_scene_order_moments",
+    "isx_default_scene_path_spec", "isx_scene_path_hist", "isx_scene_path_hist_device", "isx_scene_path_moments",
+    "isx_scene_path_decay",
 ]
 
 
@@ -367,6 +369,28 @@ class SceneOrderCounts(C.Structure):
         return np.frombuffer(bytes(self), dtype=np.uint64).copy()
 
 
+SCENE_PATH_MAX_BINS = 65536
+LIGHT_CM_PER_NS = 29.9792458
+
+
+class ScenePathSpec(C.Structure):
+    """isx_scene_path_spec (include/isx.h): bins 0 .. n_bins - 1 of width bin_cm per fate slot."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("n_bins", C.c_int32), ("reserved1", C.c_int32),
+                ("bin_cm", C.c_double)]
+
+
+class ScenePathCounts(C.Structure):
+    """isx_scene_path_counts (include/isx.h): per fate slot, the rays beyond the last bin and the sum of the bit patterns of L
+    modulo 2^64."""
+
+    _fields_ = [("overflow", C.c_uint64 * RESPONSE_FATES), ("checksum", C.c_uint64 * RESPONSE_FATES)]
+
+    def words(self):
+        """-> the 42 words (the device form's layout)"""
+        return np.frombuffer(bytes(self), dtype=np.uint64).copy()
+
+
 _lib = None
 
 
@@ -474,6 +498,14 @@ def load():
     L.isx_scene_order_reweight.argtypes = [P(Config), P(SceneSpec), P(SceneOrderSpec), P(u64), P(SceneOrderCounts), u64, P(dbl), i32,
                                            P(dbl), P(dbl)]
     L.isx_scene_order_moments.argtypes = [P(SceneOrderSpec), P(u64), P(SceneOrderCounts), P(dbl), P(dbl)]
+    L.isx_default_scene_path_spec.argtypes = [P(Config), P(ScenePathSpec)]
+    L.isx_default_scene_path_spec.restype = None
+    L.isx_scene_path_hist.argtypes = [P(Config), P(SceneSpec), P(ScenePathSpec), u64, u64, u64, P(u64), P(ScenePathCounts),
+                                      P(SceneCounts), P(Stats)]
+    L.isx_scene_path_hist_device.argtypes = [P(Config), P(SceneSpec), P(ScenePathSpec), u64, u64, u64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]
+    L.isx_scene_path_moments.argtypes = [P(ScenePathSpec), P(u64), P(ScenePathCounts), P(dbl), P(dbl)]
+    L.isx_scene_path_decay.argtypes = [P(ScenePathSpec), P(u64), P(ScenePathCounts), i32, i32, P(dbl), P(dbl)]
     _lib = L
     return L
 
@@ -1287,6 +1319,92 @@ def scene_order_moments(ospec, hist, counts):
     _chk(load().isx_scene_order_moments(C.byref(ospec), _p(h, C.c_uint64), C.byref(oc), _p(mean, C.c_double), _p(sd, C.c_double)),
          "isx_scene_order_moments")
     return mean, sd
+
+
+def default_scene_path_spec(cfg):
+    """1024 bins of r_in / 4 cm per fate slot (no GPU needed)."""
+    s = ScenePathSpec()
+    load().isx_default_scene_path_spec(C.byref(cfg), C.byref(s))
+    return s
+
+
+def scene_path_spec(n_bins, bin_cm):
+    """-> ScenePathSpec with bins 0 .. n_bins - 1 of width bin_cm per fate slot (checked by the calls)."""
+    s = ScenePathSpec()
+    s.struct_size = C.sizeof(ScenePathSpec)
+    s.n_bins = int(n_bins)
+    s.bin_cm = float(bin_cm)
+    return s
+
+
+def _scene_path_bins(pspec):
+    """n_bins of the arrays a call may touch; 1 for a spec the library refuses (it says so itself)."""
+    return int(pspec.n_bins) if 1 <= int(pspec.n_bins) <= SCENE_PATH_MAX_BINS else 1
+
+
+def scene_path_hist(cfg, scene, pspec, n_rays, seed, first_ray=0):
+    """-> (hist[21, n_bins] uint64, ScenePathCounts, SceneCounts, Stats): the fate of every ray of the scene (scene_response's
+    slots) by its path length L in cm, bin (int)(L / bin_cm); a ray beyond the last bin is counted in overflow[fate] instead, and
+    checksum[fate] sums the bit patterns of L modulo 2^64 (include/isx.h: isx_scene_path_hist).  Time is L / LIGHT_CM_PER_NS."""
+    K = _scene_path_bins(pspec)
+    hist = np.zeros(RESPONSE_FATES * K, dtype=np.uint64)
+    st = Stats()
+    pc = ScenePathCounts()
+    cnt = SceneCounts()
+    _chk(load().isx_scene_path_hist(C.byref(cfg), C.byref(scene), C.byref(pspec), int(n_rays), int(seed), int(first_ray),
+                                    _p(hist, C.c_uint64), C.byref(pc), C.byref(cnt), C.byref(st)), "isx_scene_path_hist")
+    return hist.reshape(RESPONSE_FATES, K), pc, cnt, st
+
+
+def scene_path_hist_device(cfg, scene, pspec, n_rays, seed, first_ray, d_hist_ptr, d_path_counts_ptr, d_scene_counts_ptr):
+    """Enqueue on the library stream, accumulating into device memory at d_hist_ptr ([21 * n_bins] uint64), d_path_counts_ptr
+    ([42] uint64, ScenePathCounts' layout) and d_scene_counts_ptr ([36] uint64, SceneCounts' layout)."""
+    _chk(load().isx_scene_path_hist_device(C.byref(cfg), C.byref(scene), C.byref(pspec), int(n_rays), int(seed), int(first_ray),
+                                           C.c_void_p(int(d_hist_ptr or 0) or None),
+                                           C.c_void_p(int(d_path_counts_ptr or 0) or None),
+                                           C.c_void_p(int(d_scene_counts_ptr or 0) or None)), "isx_scene_path_hist_device")
+
+
+def _scene_path_counts(counts):
+    if isinstance(counts, ScenePathCounts):
+        return counts
+    pc = ScenePathCounts()
+    w = np.asarray(counts, dtype=np.uint64).reshape(-1)
+    for f in range(RESPONSE_FATES):
+        pc.overflow[f] = int(w[f])
+        if w.size >= 2 * RESPONSE_FATES:
+            pc.checksum[f] = int(w[RESPONSE_FATES + f])
+    return pc
+
+
+def _scene_path_rows(pspec, hist):
+    K = _scene_path_bins(pspec)
+    h = np.ascontiguousarray(np.asarray(hist, dtype=np.uint64).reshape(-1))
+    if h.size < RESPONSE_FATES * K:
+        raise ValueError("hist has %d words, the spec wants %d" % (h.size, RESPONSE_FATES * K))
+    return h
+
+
+def scene_path_moments(pspec, hist, counts):
+    """-> (mean_cm[21], sd_cm[21]) of the path length per fate slot, from the bin centres; NaN for an empty row and for a row with
+    overflow (include/isx.h: isx_scene_path_moments; host only, no GPU needed)."""
+    h = _scene_path_rows(pspec, hist)
+    pc = _scene_path_counts(counts)
+    mean, sd = np.zeros(RESPONSE_FATES), np.zeros(RESPONSE_FATES)
+    _chk(load().isx_scene_path_moments(C.byref(pspec), _p(h, C.c_uint64), C.byref(pc), _p(mean, C.c_double), _p(sd, C.c_double)),
+         "isx_scene_path_moments")
+    return mean, sd
+
+
+def scene_path_decay(pspec, hist, counts, fate, lo_bin):
+    """-> (tau_cm, sigma_cm): the decay constant of row `fate`'s tail from bin lo_bin on, the maximum-likelihood estimate for a
+    geometric law over the bins (include/isx.h: isx_scene_path_decay; host only, no GPU needed)."""
+    h = _scene_path_rows(pspec, hist)
+    pc = _scene_path_counts(counts)
+    tau, sig = C.c_double(0.0), C.c_double(0.0)
+    _chk(load().isx_scene_path_decay(C.byref(pspec), _p(h, C.c_uint64), C.byref(pc), int(fate), int(lo_bin), C.byref(tau),
+                                     C.byref(sig)), "isx_scene_path_decay")
+    return tau.value, sig.value
 
 
 def fluxmap_series(cfgs, n_rays, seed, first_ray=0):

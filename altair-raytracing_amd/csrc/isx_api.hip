@@ -92,6 +92,8 @@ struct State {
   int field_global = 0;                         // 1: isx_trace_assist_scene_field_kernel's global form for a field that fits the LDS as well (diagnostic)
   int sorder_lds_orders = -1;                   // isx_trace_assist_scene_order_kernel: -1 as many orders in the workgroup's LDS as cost no resident workgroup;
                                                 // n > 0: at most n of them; 0: none, one global add per ended ray (diagnostic)
+  int spath_lds_bins = -1;                      // isx_trace_assist_scene_path_kernel: -1 as many bins in the workgroup's LDS as cost no resident workgroup;
+                                                // n > 0: at most n of them; 0: none, one global add per ended ray (diagnostic)
   int view_global = 0;                          // 1: isx_trace_assist_scene_view_kernel's global form for a map that fits the LDS as well (diagnostic)
   int surface_pipeline = 1;                     // 1 (default): the lobe / rough-specular borders and the origin-compat hit line on the assist-wave
                                                 // pipeline (round 5); 0: round 1's fused isx_trace_bin_full_kernel
@@ -752,10 +754,21 @@ int check_scene_order_spec(const isx_scene_order_spec* s) {
   return s->n_orders >= 1 && s->n_orders <= ISX_SCENE_ORDER_MAX_ORDERS ? ISX_OK : ISX_ERR_BAD_CONFIG;
 }
 
-// The scene-map sink of a call -- isx_scene_response, isx_scene_view, isx_scene_patch_field, isx_scene_order_hist: which of the
-// four (its SINK_*), its spec (the isx_*_spec of that sink), the device array of the map and the device array of its own counters
-// behind it (`tail`: isx_view_counts, isx_patch_field_counts, isx_scene_order_counts; a response has none).  The scene travels as
-// SceneSink next to it.
+// isx_scene_path_hist: the device arrays of the call are the histograms [ISX_RESPONSE_FATES][n_bins] and the 42 words of
+// isx_scene_path_counts
+static_assert(sizeof(isx_scene_path_spec) == 24 && sizeof(isx_scene_path_counts) == 2 * kRespFates * sizeof(uint64_t),
+              "isx.h: isx_scene_path_spec, and spath_record's overflow counters and checksums");
+// isx.h: the limits of a scene path spec
+int check_scene_path_spec(const isx_scene_path_spec* s) {
+  if (s->struct_size != (uint32_t)sizeof(isx_scene_path_spec) || s->reserved0 != 0u || s->reserved1 != 0) return ISX_ERR_BAD_CONFIG;
+  if (!(s->n_bins >= 1 && s->n_bins <= ISX_SCENE_PATH_MAX_BINS)) return ISX_ERR_BAD_CONFIG;
+  return std::isfinite(s->bin_cm) && s->bin_cm > 0.0 ? ISX_OK : ISX_ERR_BAD_CONFIG;
+}
+
+// The scene-map sink of a call -- isx_scene_response, isx_scene_view, isx_scene_patch_field, isx_scene_order_hist,
+// isx_scene_path_hist: which of the five (its SINK_*), its spec (the isx_*_spec of that sink), the device array of the map and
+// the device array of its own counters behind it (`tail`: isx_view_counts, isx_patch_field_counts, isx_scene_order_counts,
+// isx_scene_path_counts; a response has none).  The scene travels as SceneSink next to it.
 struct SceneMap {
   int sink = 0;
   const void* spec = nullptr;
@@ -764,6 +777,7 @@ struct SceneMap {
   const isx_view_spec& view() const { return *static_cast<const isx_view_spec*>(spec); }
   const isx_patch_field_spec& field() const { return *static_cast<const isx_patch_field_spec*>(spec); }
   const isx_scene_order_spec& order() const { return *static_cast<const isx_scene_order_spec*>(spec); }
+  const isx_scene_path_spec& path() const { return *static_cast<const isx_scene_path_spec*>(spec); }
 };
 // isx.h: the limits of the spec of a scene map in a scene of `n_patches` patches, and the words of its two arrays
 int scene_map_shape(const SceneMap& m, int n_patches, size_t& body, size_t& tail) {
@@ -784,6 +798,10 @@ int scene_map_shape(const SceneMap& m, int n_patches, size_t& body, size_t& tail
     case SINK_SORDER:
       if ((rc = check_scene_order_spec(&m.order()))) return rc;
       body = (size_t)ISX_RESPONSE_FATES * (size_t)m.order().n_orders; tail = kRespFates;
+      return ISX_OK;
+    case SINK_SPATH:
+      if ((rc = check_scene_path_spec(&m.path()))) return rc;
+      body = (size_t)ISX_RESPONSE_FATES * (size_t)m.path().n_bins; tail = 2 * kRespFates;
       return ISX_OK;
   }
   return ISX_ERR_BAD_ARG;
@@ -813,8 +831,8 @@ struct Call {
   const PatchSink* wp = nullptr;           // SINK_PATCH
   const isx_beam_spec* bs = nullptr;       // SINK_FLUX with a beam source (a scene: enqueue sets it)
   const BaffleSink* bf = nullptr;          // SINK_FLUX with baffles (a scene: enqueue sets it)
-  const SceneSink* sc = nullptr;           // a scene: isx_fluxmap_scene and the four scene maps
-  const SceneMap* map = nullptr;           // SINK_RESPONSE, SINK_VIEW, SINK_FIELD, SINK_SORDER
+  const SceneSink* sc = nullptr;           // a scene: isx_fluxmap_scene and the five scene maps
+  const SceneMap* map = nullptr;           // SINK_RESPONSE, SINK_VIEW, SINK_FIELD, SINK_SORDER, SINK_SPATH
 };
 // The DetGrid of a call's sink, checked, and the dynamic LDS of its fused kernel (histogram + tables, census, Geom, DetGrid).
 int sink_grid(const Call& k, DetGrid& d, size_t& lds) {
@@ -929,7 +947,7 @@ int sink_grid(const Call& k, DetGrid& d, size_t& lds) {
     d.xm_dir = wp->arrivals; d.xm_pos = wp->absorbed;
     d.nbins = 2 * (wp->spec->n_patches + 2);
     lds = patch_lds() + 64 + sizeof(Geom) + sizeof(DetGrid);
-  } else if (sink == SINK_RESPONSE || sink == SINK_VIEW || sink == SINK_FIELD || sink == SINK_SORDER) {
+  } else if (sink == SINK_RESPONSE || sink == SINK_VIEW || sink == SINK_FIELD || sink == SINK_SORDER || sink == SINK_SPATH) {
     // (isx.h: hit_line_mode and the detector grid are ignored -- no exit line is written, no grid is looked at; the scene and the
     //  response spec were checked by the entry, the patches' words are enqueue's)
     d.hit_line_mode = ISX_HITLINE_LAST_SEGMENT;
@@ -965,7 +983,7 @@ enum Route { ROUTE_FUSED, ROUTE_ASSIST, ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_
 typedef void (*BinFn)(const DetGrid, const Work);
 // A trace kernel: its address and what it takes behind (Geom, DetGrid, Work).  The constructors read the tail off the kernel's
 // own signature, so a kernel cannot be paired with the wrong arguments; launch_trace() is the one place that passes them.
-enum Tail { TAIL_NONE, TAIL_PATCH, TAIL_BEAM, TAIL_LIST, TAIL_BAFFLE, TAIL_SCENE, TAIL_RESPONSE, TAIL_VIEW, TAIL_FIELD, TAIL_SORDER };
+enum Tail { TAIL_NONE, TAIL_PATCH, TAIL_BEAM, TAIL_LIST, TAIL_BAFFLE, TAIL_SCENE, TAIL_RESPONSE, TAIL_VIEW, TAIL_FIELD, TAIL_SORDER, TAIL_SPATH };
 struct TraceKernel {
   const void* fn = nullptr;
   Tail tail = TAIL_NONE;
@@ -981,6 +999,7 @@ struct TraceKernel {
   TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab, ViewSink> f) : fn((const void*)f), tail(TAIL_VIEW) {}
   TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab, PatchFieldSink> f) : fn((const void*)f), tail(TAIL_FIELD) {}
   TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab, SOrderSink> f) : fn((const void*)f), tail(TAIL_SORDER) {}
+  TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab, SPathSink> f) : fn((const void*)f), tail(TAIL_SPATH) {}
 };
 struct Plan {
   Route route = ROUTE_FUSED;
@@ -1013,6 +1032,7 @@ struct Plan {
   ViewSink view{};              // isx_scene_view (view.lds_words: the form)
   PatchFieldSink field{};       // isx_scene_patch_field (field.lds_words: the form)
   SOrderSink sorder{};          // isx_scene_order_hist (sorder.lds_orders: the orders kept in LDS)
+  SPathSink spath{};            // isx_scene_path_hist (spath.lds_bins: the bins kept in LDS)
 };
 
 // The one place a trace kernel is launched: (g, d, w) and the tail its signature names, as hipLaunchKernelGGL would pass them.
@@ -1033,6 +1053,7 @@ void launch_trace(const Plan& p, const TraceKernel& k, int grid, hipStream_t str
       else if (k.tail == TAIL_VIEW) args[na++] = &p.view;
       else if (k.tail == TAIL_FIELD) args[na++] = &p.field;
       else if (k.tail == TAIL_SORDER) args[na++] = &p.sorder;
+      else if (k.tail == TAIL_SPATH) args[na++] = &p.spath;
   }
   (void)hipLaunchKernel(k.fn, dim3(grid), dim3(p.block), const_cast<void**>(args), p.lds, stream);
 }
@@ -1080,7 +1101,7 @@ void trace_shape(Plan& p, Shape sh, bool assist, int per_cu) {
 }
 
 // The shape and the LDS of a scene map's one kernel.  A scene map (isx_scene_response, isx_scene_view, isx_scene_patch_field,
-// isx_scene_order_hist) has one route whatever the switches say, as the scene has: the scene's trace kernel `fn` with the map as
+// isx_scene_order_hist, isx_scene_path_hist) has one route whatever the switches say, as the scene has: the scene's trace kernel `fn` with the map as
 // its one sink (check_scene_call: the explicit Lambertian lean path), in the scene's shape, the scene's three blocks behind the
 // rings; no exit lines, no second kernel.  Launches are cut at pipeline_chunk as the scene's are.  Behind the parks lie `head`
 // bytes the kernel always keeps there (counters, a frame) and then up to `units` units of `unit` u32 words each of the map itself,
@@ -1152,7 +1173,7 @@ Plan plan_scene_map(const Call& k) {
       p.field.patch = v.patch; p.field.n_x = v.n_x; p.field.n_u = v.n_u; p.field.n_v = v.n_v;
       break;
     }
-    default: {   // SINK_SORDER (sorder_record): behind the overflow counters (kSOrderHead words, always) the first L orders of each
+    case SINK_SORDER: {   // (sorder_record): behind the overflow counters (kSOrderHead words, always) the first L orders of each
                  // slot; the orders from L on take one global u64 add each.  L is as large as fits and at most n_orders;
                  // "sorder_lds_orders" >= 0 caps it (0: every order is global).  L is SOrderSink::lds_orders, nothing else.
       const isx_scene_order_spec& s = m.order();
@@ -1161,6 +1182,17 @@ Plan plan_scene_map(const Call& k) {
       p.sorder.lds_orders = (uint32_t)plan_scene_map_lds(p, isx_trace_assist_scene_order_kernel, k.n,
                                                          kSOrderHead * sizeof(uint32_t), slots, orders);
       p.sorder.out = m.out; p.sorder.overflow = m.tail; p.sorder.n_orders = (uint32_t)s.n_orders;
+      break;
+    }
+    default: {   // SINK_SPATH (spath_record): SINK_SORDER's hybrid form.  Behind the side arrays of the two rings, the checksums and the
+                 // overflow counters (kSPathHeadBytes, always) the first B bins of each slot; the bins from B on take one global
+                 // u64 add each.  B is as large as fits and at most n_bins; "spath_lds_bins" >= 0 caps it (0: every bin is
+                 // global).  B is SPathSink::lds_bins, nothing else.
+      const isx_scene_path_spec& s = m.path();
+      size_t bins = (size_t)s.n_bins;
+      if (S.spath_lds_bins >= 0) bins = std::min(bins, (size_t)S.spath_lds_bins);
+      p.spath.lds_bins = (uint32_t)plan_scene_map_lds(p, isx_trace_assist_scene_path_kernel, k.n, kSPathHeadBytes, slots, bins);
+      p.spath.out = m.out; p.spath.counts = m.tail; p.spath.bin_cm = s.bin_cm; p.spath.n_bins = (uint32_t)s.n_bins;
     }
   }
   return p;
@@ -1803,7 +1835,7 @@ int not_initialised() {
   return (hipGetDeviceCount(&count) != hipSuccess || count <= 0) ? ISX_ERR_NO_DEVICE : ISX_ERR_NOT_INIT;
 }
 
-// The body of the eight scene-map entries.  `k`: the call without its sinks; `m`: the map with the caller's arrays -- device
+// The body of the ten scene-map entries.  `k`: the call without its sinks; `m`: the map with the caller's arrays -- device
 // arrays for a _device entry, which enqueues and returns; else host arrays (the map's own counters and `scene_counts` may be
 // NULL), filled from one device block, one staged result: the map and, behind it, its own counters and the 36 scene counters.
 // (What needs no device is answered first: a NULL argument or a refused spec is the same answer with and without one.  isx.h: the
@@ -2040,6 +2072,7 @@ int isx_set_option(const char* key, int64_t value) {
   if (!std::strcmp(key, "lf_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.lf_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "field_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.field_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "sorder_lds_orders")) { if (value < -1 || value > ISX_SCENE_ORDER_MAX_ORDERS) return ISX_ERR_BAD_ARG; S.sorder_lds_orders = (int)value; return ISX_OK; }
+  if (!std::strcmp(key, "spath_lds_bins")) { if (value < -1 || value > ISX_SCENE_PATH_MAX_BINS) return ISX_ERR_BAD_ARG; S.spath_lds_bins = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "view_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.view_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "resp_global")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.resp_global = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "surface_pipeline")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.surface_pipeline = (int)value; return ISX_OK; }
@@ -3377,6 +3410,81 @@ int isx_scene_order_moments(const isx_scene_order_spec* ospec, const uint64_t* h
     if (mean) mean[f] = m;
     if (sd) sd[f] = d;
   }
+  return ISX_OK;
+}
+
+void isx_default_scene_path_spec(const isx_config* cfg, isx_scene_path_spec* pspec) {
+  if (!pspec) return;
+  std::memset(pspec, 0, sizeof(*pspec));
+  pspec->struct_size = (uint32_t)sizeof(isx_scene_path_spec);
+  pspec->n_bins = 1024;
+  pspec->bin_cm = cfg ? cfg->r_in / 4 : 0.0;
+}
+
+int isx_scene_path_hist_device(const isx_config* cfg, const isx_scene_spec* scene, const isx_scene_path_spec* pspec, uint64_t n_rays,
+                               uint64_t seed, uint64_t first_ray, uint64_t* d_hist, uint64_t* d_path_counts,
+                               uint64_t* d_scene_counts) {
+  return scene_map_call({.sink = SINK_SPATH, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray}, scene,
+                        SceneMap{SINK_SPATH, pspec, (unsigned long long*)d_hist, (unsigned long long*)d_path_counts}, d_scene_counts,
+                        true, nullptr);
+}
+
+int isx_scene_path_hist(const isx_config* cfg, const isx_scene_spec* scene, const isx_scene_path_spec* pspec, uint64_t n_rays,
+                        uint64_t seed, uint64_t first_ray, uint64_t* hist, isx_scene_path_counts* path_counts,
+                        isx_scene_counts* scene_counts, isx_stats* stats) {
+  return scene_map_call({.sink = SINK_SPATH, .c = cfg, .n = n_rays, .seed = seed, .first = first_ray}, scene,
+                        SceneMap{SINK_SPATH, pspec, (unsigned long long*)hist, (unsigned long long*)path_counts},
+                        (uint64_t*)scene_counts, false, stats);
+}
+
+int isx_scene_path_moments(const isx_scene_path_spec* pspec, const uint64_t* hist, const isx_scene_path_counts* counts,
+                           double* mean_cm, double* sd_cm) {
+  if (!pspec || !hist || !counts) return ISX_ERR_BAD_ARG;
+  const int rc = check_scene_path_spec(pspec);
+  if (rc) return rc;
+  const size_t K = (size_t)pspec->n_bins;
+  for (int f = 0; f < ISX_RESPONSE_FATES; ++f) {
+    const uint64_t* row = hist + (size_t)f * K;
+    double N = 0, A = 0, B = 0;
+    for (size_t k = 0; k < K; ++k) {
+      const double h = (double)row[k], x = ((double)k + 0.5) * pspec->bin_cm;
+      N += h;
+      A += x * h;
+      B += x * x * h;
+    }
+    double m = std::numeric_limits<double>::quiet_NaN(), d = m;
+    if (N > 0 && counts->overflow[f] == 0) {
+      m = A / N;
+      const double var = B / N - m * m;
+      d = std::sqrt(var > 0 ? var : 0.0);
+    }
+    if (mean_cm) mean_cm[f] = m;
+    if (sd_cm) sd_cm[f] = d;
+  }
+  return ISX_OK;
+}
+
+int isx_scene_path_decay(const isx_scene_path_spec* pspec, const uint64_t* hist, const isx_scene_path_counts* counts, int32_t f,
+                         int32_t lo_bin, double* tau_cm, double* sigma_cm) {
+  if (!pspec || !hist || !counts || !tau_cm || !sigma_cm) return ISX_ERR_BAD_ARG;
+  const int rc = check_scene_path_spec(pspec);
+  if (rc) return rc;
+  if (f < 0 || f >= ISX_RESPONSE_FATES || lo_bin < 0 || lo_bin >= pspec->n_bins) return ISX_ERR_BAD_ARG;
+  if (counts->overflow[f] != 0) return ISX_ERR_BAD_CONFIG;
+  const uint64_t* row = hist + (size_t)f * (size_t)pspec->n_bins;
+  double N = 0, Sm = 0;
+  for (int32_t ib = lo_bin; ib < pspec->n_bins; ++ib) {
+    const double h = (double)row[ib];
+    Sm += (double)(ib - lo_bin) * h;
+    N += h;
+  }
+  if (!(N > 0)) return ISX_ERR_BAD_CONFIG;
+  const double m = Sm / N;
+  if (!(m > 0)) return ISX_ERR_BAD_CONFIG;
+  const double r = m / (1.0 + m);
+  const double lr = std::log(r);
+  *tau_cm = -pspec->bin_cm / lr;
+  *sigma_cm = pspec->bin_cm / (lr * lr) / std::sqrt(N * m * (1.0 + m));
   return ISX_OK;
 }
 

@@ -125,7 +125,8 @@ enum : int { SINK_FLUX = 0, SINK_DZ = 1, SINK_DISC = 2, SINK_PERPOS = 3, SINK_LO
               SINK_RESPONSE = 12,     // (isx_scene_response: no kernel is built on it -- the host's name for the scene's second sink)
               SINK_VIEW = 13,         // (isx_scene_view: likewise, the scene's third sink)
               SINK_FIELD = 14,        // (isx_scene_patch_field: likewise, the scene's fourth sink)
-              SINK_SORDER = 15 };     // (isx_scene_order_hist: likewise, the scene's fifth sink)
+              SINK_SORDER = 15,       // (isx_scene_order_hist: likewise, the scene's fifth sink)
+              SINK_SPATH = 16 };      // (isx_scene_path_hist: likewise, the scene's sixth sink)
 
 struct Work {
   uint64_t seed, first, n;    // one launch traces rays [first, first + n), n < 2^31 (a lane keeps a 31-bit offset from `first`)
@@ -2520,6 +2521,74 @@ __device__ __forceinline__ void sorder_flush(const SOrderSink& s, const uint32_t
   }
 }
 
+// ------------------------------------------------------------------ scene path histograms (isx.h: isx_scene_path_hist)
+// The path sink of a call as the kernel gets it (a kernel argument of its own, read where it is used): the device histograms
+// [kRespFates][n_bins] (+=), the 2 kRespFates words of isx_scene_path_counts (overflow by fate slot, then checksum by fate slot;
+// +=), the bin width in cm, n_bins, and B = lds_bins: the bins 0 .. B - 1 of every compact slot (RESP's) are u32 words of the
+// workgroup's LDS, the bins from B on take one global u64 add each (B = 0: every bin is global, the diagnostic form).
+// This is the one scene sink with per-ray state: a lane carries L, the ray's path length so far, and L follows the ray through
+// every hand-over -- the queue records are full (the resume ring uses both spare words), so L travels in a side array parallel to
+// each ring, at the record's slot.  The workgroup's block behind the parks:
+//   double[kPendCap] | double[kResumeCap]         L of the records of the pending / the resume ring
+//   u64[kSPathHead]                                the checksums by fate slot (64-bit LDS adds)
+//   u32[kSPathHead]                                the overflow counters by fate slot
+//   u32[slots * B]                                 [compact slot][bin]
+// The parked first segment of a fresh beam ray: a ray parked at its first wall point (NaN in the direction's x) has no use for
+// the direction's y -- the interaction forms a new direction from the point alone -- so this build parks the segment's length
+// there: the park keeps its six doubles per ray.
+constexpr int kSPathHead = 24;
+static_assert(kSPathHead >= kRespFates && kSPathHead % 4 == 0, "the checksums and the overflow counters, in 16-byte steps");
+struct SPathSink {
+  unsigned long long* out;
+  unsigned long long* counts;
+  double bin_cm;
+  uint32_t n_bins, lds_bins;
+};
+// isx.h's segment rule, operation for operation (IEEE double, left to right, no fma: -ffp-contract=off; sqrt is the correctly
+// rounded one): the length of the segment a -> b.
+__device__ __forceinline__ double spath_segment(const V3& a, const V3& b) {
+  const double dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
+  return sqrt((dx * dx + dy * dy) + dz * dz);
+}
+// The one place L grows: the ray's point `from` is about to become `to`.  Every arrival of the SPATH build calls this -- the
+// tracers' on the inner sphere, the assist wave's on a baffle and on a boundary, the parking of a fresh ray's first segment.
+__device__ __forceinline__ void spath_advance(double& L, const V3& from, const V3& to) { L = L + spath_segment(from, to); }
+// The leg to the world box is not counted; a ray that is counted below z (slot 18) gets the part of it up to the port plane:
+// p the last interaction point, q the point on the box, portz = cfg->exit_port_z.  A NaN f compares false: nothing is added.
+__device__ __forceinline__ void spath_exit_tail(double& L, const V3& p, const V3& q, double portz) {
+  const double s = spath_segment(p, q);
+  const double f = (portz - p.z) / (q.z - p.z);
+  L = L + ((f > 0.0 && f <= 1.0) ? s * f : 0.0);
+}
+// A ray's end: its checksum word, and one add for its fate slot and its bin -- isx.h's rule: fb = L / bin_cm, overflow unless
+// fb < n_bins (a NaN overflows), else bin (int)fb.  Both census points of the SPATH build call this and nothing else states the
+// rule.  `out` stays a kernel argument's field: a global_atomic, not a flat one.
+__device__ __forceinline__ void spath_record(const SPathSink& s, unsigned long long* cks, uint32_t* blk, int n_patch, int n_baf,
+                                             int fate, double L) {
+  atomicAdd(&cks[fate], (unsigned long long)__double_as_longlong(L));
+  const double fb = L / s.bin_cm;
+  if (!(fb < (double)s.n_bins)) { atomicAdd(&blk[fate], 1u); return; }
+  const uint32_t ib = (uint32_t)(int)fb;
+  if (ib < s.lds_bins) {
+    const int c = fate < kRespBaffle0 ? fate : fate < kRespPort ? fate - kRespBaffle0 + (n_patch + 2) : fate - kRespPort + (n_patch + 2) + 2 * n_baf;
+    atomicAdd(&blk[(uint32_t)kSPathHead + (uint32_t)c * s.lds_bins + ib], 1u);
+  } else {
+    global_add_u64(s.out + ((uint32_t)fate * s.n_bins + ib), 1ull);
+  }
+}
+// one flush of the workgroup's low bins: compact slot -> fate slot (B = 0: nothing to flush)
+__device__ __forceinline__ void spath_flush(const SPathSink& s, const uint32_t* blk, int n_patch, int n_baf, uint32_t tid, uint32_t nthr) {
+  const uint32_t nw = (uint32_t)(n_patch + 2), nb = nw + 2u * (uint32_t)n_baf, words = (nb + 3u) * s.lds_bins;
+  for (uint32_t i = tid; i < words; i += nthr) {
+    const uint32_t c = blk[(uint32_t)kSPathHead + i];
+    if (c) {
+      const uint32_t cs = i / s.lds_bins, k = i - cs * s.lds_bins;
+      const uint32_t fate = cs < nw ? cs : cs < nb ? cs - nw + (uint32_t)kRespBaffle0 : cs - nb + (uint32_t)kRespPort;
+      global_add_u64(s.out + (fate * s.n_bins + k), (unsigned long long)c);
+    }
+  }
+}
+
 // The segment test of isx.h's contract, operation for operation (IEEE double, left to right, no fma: -ffp-contract=off; / is the
 // correctly rounded one): the baffle that the segment p -> q strikes first -- the smallest f, on equal f the lowest index -- as
 // 2 k + side (side 0: the side the normal points to), or -1.  `skip` is the baffle of the ray's previous interaction (-1: none).
@@ -3131,6 +3200,9 @@ isx_trace_log_lean_kernel(const Geom g, const DetGrid d, const Work wk) { persis
 // stretch without hand-overs, e.g. a tiny port opening with a large bounce limit or a down-clocked device, is not a failure):
 // a wave that gives up raises stats[7] and the host reports ISX_ERR_HIP instead of hanging the device.
 constexpr uint32_t kPendCap = 512, kResumeCap = 128;
+// SPATH (isx_scene_path_hist): the side arrays of the two rings, and with them everything the build keeps in front of its bins
+constexpr size_t kSPathRingBytes = (size_t)(kPendCap + kResumeCap) * sizeof(double);
+constexpr size_t kSPathHeadBytes = kSPathRingBytes + (size_t)kSPathHead * (sizeof(unsigned long long) + sizeof(uint32_t));
 #ifndef ISX_DONATE_MAX
 #define ISX_DONATE_MAX 32     // a tracer wave with at most this many rays left after the launch's queue ran dry gives them away (0: never;
                               // measured, trace kernel of 5e7 headline rays / of the 1e7-ray disc sweep: 0: 11.35 / 7.13 ms, 16: 11.27 / 6.79,
@@ -3236,15 +3308,20 @@ __device__ __forceinline__ void ray_unpack(const uint4& a, const uint4& b, const
 // SORDER (isx_scene_order_hist; SCENE only, never with RESP, VIEW or FIELD): every ray is binned once, where it ends, at RESP's two
 // census points with RESP's fate slot, by its order Ray::j -- sorder_record, which draws nothing.  The workgroup's block behind the
 // parks: the overflow counters and the low orders of every compact slot; the orders above them go to global memory one by one.
+// SPATH (isx_scene_path_hist; SCENE only, never with RESP, VIEW, FIELD or SORDER): the one sink with state carried through the steps.
+// A lane holds L, the path length of its ray: zero where the ray starts, advanced wherever its point is replaced (spath_advance:
+// the tracers' arrival, the assist wave's ray_arrive and baffle_arrive, the parking of a fresh ray's first segment), handed over
+// in a side array parallel to each ring.  The leg to the world box is not counted; the exit's tail up to the port plane is formed
+// where the exit is taken.  Every ray is binned once at RESP's two census points -- spath_record.
 struct FateList { const uint32_t* list; const uint32_t* count; };
 template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false, bool ORDER = false, bool PATCH = false,
           bool BEAM = false, bool LIST = false, bool BAFFLE = false, bool RESP = false, bool VIEW = false, bool FIELD = false,
-          bool SORDER = false>
+          bool SORDER = false, bool SPATH = false>
 __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk, const PatchTab* tab_arg = nullptr,
                                             const BeamSrc* beam_arg = nullptr, const FateList* list_arg = nullptr,
                                             const BaffleTab* baf_arg = nullptr, const RespSink* resp_arg = nullptr,
                                             const ViewSink* view_arg = nullptr, const PatchFieldSink* field_arg = nullptr,
-                                            const SOrderSink* sorder_arg = nullptr) {
+                                            const SOrderSink* sorder_arg = nullptr, const SPathSink* spath_arg = nullptr) {
   constexpr bool LEAN = SURF == SURF_LAMBERT;
   static_assert(LEAN || (CH == 0 && !RESC), "the chord identity and the BRDF re-scatter pipeline are built for the Lambertian border");
   static_assert(!PATCH || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER), "wall patches: the explicit Lambertian lean path, no other sink");
@@ -3256,6 +3333,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   static_assert(!VIEW || (SCENE && !RESP), "scene view: the scene's trace, nothing else");
   static_assert(!FIELD || (SCENE && !RESP && !VIEW), "scene patch field: the scene's trace, nothing else");
   static_assert(!SORDER || (SCENE && !RESP && !VIEW && !FIELD), "scene order histograms: the scene's trace, nothing else");
+  static_assert(!SPATH || (SCENE && !RESP && !VIEW && !FIELD && !SORDER), "scene path histograms: the scene's trace, nothing else");
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned long long* sstat = reinterpret_cast<unsigned long long*>(smem);
   Geom* g_lds = reinterpret_cast<Geom*>(sstat + 8);
@@ -3327,6 +3405,18 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     const uint32_t words = (uint32_t)kSOrderHead + (uint32_t)((n_patch + 2) + 2 * n_baf + 3) * sorder_arg->lds_orders;
     for (uint32_t b = (uint32_t)tid; b < words; b += (uint32_t)nthr) rblk[b] = 0u;
   }
+  // SPATH: the workgroup's block behind the parks -- double[kPendCap] | double[kResumeCap] (L of the rings' records: written and
+  // read with the records, never cleared) | u64[kSPathHead] checksums | u32[kSPathHead overflow counters | compact slots x
+  // SPathSink::lds_bins]
+  double* pend_L = reinterpret_cast<double*>(rblk);
+  double* resume_L = pend_L + kPendCap;
+  unsigned long long* pcks = reinterpret_cast<unsigned long long*>(resume_L + kResumeCap);
+  uint32_t* pblk = reinterpret_cast<uint32_t*>(pcks + kSPathHead);
+  if constexpr (SPATH) {
+    const uint32_t words = (uint32_t)(3 * kSPathHead) + (uint32_t)((n_patch + 2) + 2 * n_baf + 3) * spath_arg->lds_bins;
+    uint32_t* z = reinterpret_cast<uint32_t*>(pcks);
+    for (uint32_t b = (uint32_t)tid; b < words; b += (uint32_t)nthr) z[b] = 0u;
+  }
   if (tid < 8) sstat[tid] = 0ull;
   if (tid == 64) {
     *g_lds = g_arg;
@@ -3372,6 +3462,8 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     if constexpr (LIST) n_list = (uint32_t)__builtin_amdgcn_readfirstlane((int)((GlbU32*)list_arg->count)[0]);
     Ray r;
     ray_start(g, r, 0);
+    double L = 0.0;                    // SPATH: the path length of the lane's ray so far
+    (void)L;
     bool run = false, hand = false;    // hand: the lane's ray waits to be handed to the assist wave
     // (-DISX_DIAG, tools/diag_trace.py: cycles [16] refill, [17] bounce steps, [18] census, [19] hand-over; [23] trips, [24] lanes
     //  running / [25] still waiting to be handed over at the top of a trip, [26] hand-overs refused for lack of room, [27] rays
@@ -3393,9 +3485,12 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           const uint32_t take = want < avail ? want : avail;
           const bool mine = !(run || hand) && rank < take;
           uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a, c = a, e = a;
+          double lq = 0.0;
+          (void)lq;
           if (mine) {
             const uint4* src = resume_q + 4 * ((hd + rank) & (kResumeCap - 1));
             a = src[0]; b = src[1]; c = src[2]; e = src[3];
+            if constexpr (SPATH) lq = resume_L[(hd + rank) & (kResumeCap - 1)];
           }
           __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
           uint32_t won = 0;
@@ -3410,6 +3505,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
             ray_unpack(a, b, c, e, r);
             r.on = K_INNER;
             r.cw[0] = 0u; r.cw[1] = 0u; r.cw[2] = e.z; r.cw[3] = e.w;
+            if constexpr (SPATH) L = lq;
             run = true;
           }
           if (lane == 0) __hip_atomic_fetch_sub(&Q->busy, take, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -3448,6 +3544,18 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
                 if constexpr (SCENE) {   // a baffle in the way of the ray's own first segment: parked as its start, the assist wave's
                   double f0;
                   if (next_hit_s1<true>(h, g, t.p, t.v, K_NONE, q) && baffle_segment(baf, n_baf, t.p, q, -1, f0) < 0) {
+                    // SPATH: the first segment's length, while its start is in hand, parked in v.y.  INVARIANT of this build: the
+                    // direction of a fresh ray parked at its first wall point is payload, not a direction -- v.x is the NaN mark,
+                    // v.y the length, and the lane's r.v keeps both until the ray's first interaction overwrites r.v (the
+                    // Lambertian ray_arrive forms the new direction from the point alone; a ray absorbed there keeps them to its
+                    // census, where SPATH reads no direction).  Nothing may read r.v of such a ray: VIEW and FIELD, which read
+                    // r.v at the census, are excluded from SPATH by assist_body's static_assert, and such a ray is never packed
+                    // into a queue record (it arrives in step 0 of the trip that took it).
+                    if constexpr (SPATH) {
+                      double l0 = 0.0;
+                      spath_advance(l0, t.p, q);
+                      t.v.y = l0;
+                    }
                     t.p = q; t.v.x = __builtin_nan("");
                   }
                 } else
@@ -3464,6 +3572,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
               r.ido = next + rank; r.j = 0; r.on = K_NONE; r.tgt = false; r.k = 0;
               r.p.x = park[0 * 64 + slot]; r.p.y = park[1 * 64 + slot]; r.p.z = park[2 * 64 + slot];
               r.v.x = park[3 * 64 + slot]; r.v.y = park[4 * 64 + slot]; r.v.z = park[5 * 64 + slot];
+              if constexpr (SPATH) L = r.v.x != r.v.x ? r.v.y : 0.0;   // (at its first wall point: the parked length; else at its start)
               run = true;
             }
             __builtin_amdgcn_wave_barrier();
@@ -3514,7 +3623,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       // (the end of a ray as two flags -- lane masks in scalar registers -- instead of a status word per lane; a tracer lane's ray
       //  sits on the inner sphere unless it is fresh, so Ray::on is neither read nor written in the steps)
       bool ended = false, susp = false;
-      int eslot = 0;   // RESP, VIEW, FIELD, SORDER: the class of the arrival that absorbed the lane's ray
+      int eslot = 0;   // RESP, VIEW, FIELD, SORDER, SPATH: the class of the arrival that absorbed the lane's ray
       (void)eslot;
       auto arrive = [&](const V3& q, auto ph, bool record = true) {
         if (WALL && record) wall_record(wspec, hist, wall_nmap, K_INNER, r.j, q, 1u);
@@ -3522,9 +3631,10 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         if constexpr (PATCH) {
           Hot hp = h;
           const int cls = patch_arrive<true>(ptab, n_patch, pcnt, K_INNER, q, hp);
+          if constexpr (SPATH) spath_advance(L, r.p, q);   // (a fresh ray sits at q already -- its parked length is in L: + 0.0)
           st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(hp, g, r, seed, first, K_INNER, q);
           if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
-          if constexpr (RESP || VIEW || FIELD || SORDER) { if (st == ST_ABSORBED) eslot = cls; }
+          if constexpr (RESP || VIEW || FIELD || SORDER || SPATH) { if (st == ST_ABSORBED) eslot = cls; }
         } else st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(h, g, r, seed, first, K_INNER, q);
         if (st != 0) { run = false; ended = true; susp = st == ST_SUSPENDED; }
       };
@@ -3645,6 +3755,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           if constexpr (VIEW) { if (!susp && eslot == view_arg->patch) view_record(*view_arg, rblk, r.j, r.v); }
           if constexpr (FIELD) { if (!susp && eslot == field_arg->patch) field_record(*field_arg, fframe, fblk, r.j, r.p, r.v); }
           if constexpr (SORDER) sorder_record(*sorder_arg, rblk, n_patch, n_baf, susp ? kRespSuspended : eslot, r.j);
+          if constexpr (SPATH) spath_record(*spath_arg, pcks, pblk, n_patch, n_baf, susp ? kRespSuspended : eslot, L);
         }
         const unsigned long long me = __ballot(ended);
         if (me) {
@@ -3675,6 +3786,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
             const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
             // (the surface the ray sits on: none for a fresh ray -- Geom::q0_ok = 0 --, else the inner sphere)
             ray_pack(pend_q + 4 * ((base + rank) & (kPendCap - 1)), r, (r.j == 0u && !r.scattered()) ? (uint32_t)K_NONE : (uint32_t)K_INNER, 0u);
+            if constexpr (SPATH) pend_L[(base + rank) & (kPendCap - 1)] = L;
             hand = false;
           }
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -3722,6 +3834,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
               // (the record the assist wave writes for a ray that returns: at the top of a trip a lane with an odd interaction
               //  count holds words 2-3 of its block j/2 in cw[2..3] -- bounce_words)
               ray_pack(resume_q + 4 * ((base + rank) & (kResumeCap - 1)), r, r.cw[2], r.cw[3]);
+              if constexpr (SPATH) resume_L[(base + rank) & (kResumeCap - 1)] = L;
               run = false;
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -3782,11 +3895,14 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       const bool have = (uint32_t)lane < take;
       Ray r;
       ray_start(g, r, 0);
+      double L = 0.0;       // SPATH: the path length of the lane's ray so far
+      (void)L;
       if (have) {
         const uint4* src = pend_q + 4 * ((hd + (uint32_t)lane) & (kPendCap - 1));
         const uint4 a = src[0], b = src[1], c = src[2], e = src[3];
         ray_unpack(a, b, c, e, r);
         r.on = (int)e.z;
+        if constexpr (SPATH) L = pend_L[(hd + (uint32_t)lane) & (kPendCap - 1)];
         if constexpr (BAFFLE) r.tgt = false;   // (explicit bounces only: the flag's bit is never set, and need not be carried)
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");          // (the slots are free once they have been read)
@@ -3799,7 +3915,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       bool go = have;
       bool given = false;   // BAFFLE: the ray went back to the tracers from inside the step loop
       (void)given;
-      int eslot = 0;        // RESP, VIEW, FIELD, SORDER: the slot of the interaction that absorbed the lane's ray (a wall class, or a baffle's side)
+      int eslot = 0;        // RESP, VIEW, FIELD, SORDER, SPATH: the slot of the interaction that absorbed the lane's ray (a wall class, or a baffle's side)
       (void)eslot;
       for (;;) {
         if (go) {
@@ -3819,18 +3935,27 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
             double bf;
             const int ks = baffle_segment(baf, n_baf, r.p, q, baffle_skip(r.on), bf);
             if (ks >= 0) {
+              if constexpr (SPATH) {
+                const V3 x = baffle_point(r.p, q, bf);
+                spath_advance(L, r.p, x);
+                r.p = x;
+              } else
               r.p = baffle_point(r.p, q, bf);
               atomicAdd(&bcnt[ks], 1u);
               st = baffle_arrive(baf, h, r, seed, first, ks >> 1, ks & 1);
               if (st == ST_ABSORBED) atomicAdd(&bcnt[2 * kMaxBaffles + ks], 1u);
-              if constexpr (RESP || VIEW || FIELD || SORDER) eslot = kRespBaffle0 + ks;
+              if constexpr (RESP || VIEW || FIELD || SORDER || SPATH) eslot = kRespBaffle0 + ks;
             } else {
               Hot hp = h;
               int cls = 0;
               if (kind != K_BOX) cls = patch_arrive<false>(ptab, n_patch, pcnt, kind, q, hp);
+              if constexpr (SPATH) {   // (the leg to the world box is not counted: the exit's tail is formed here, with both points in hand)
+                if (kind != K_BOX) spath_advance(L, r.p, q);
+                else if (q.z < portz) spath_exit_tail(L, r.p, q, portz);
+              }
               st = ray_arrive<false, LEAN, CH, PH_DIRECT, true, SURF>(hp, g, r, seed, first, kind, q);
               if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
-              if constexpr (RESP || VIEW || FIELD || SORDER) eslot = cls;
+              if constexpr (RESP || VIEW || FIELD || SORDER || SPATH) eslot = cls;
             }
           } else if constexpr (PATCH) {
             Hot hp = h;
@@ -3891,6 +4016,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
                   cw2 = wv[2]; cw3 = wv[3];
                 }
                 ray_pack(resume_q + 4 * ((pubr + rank) & (kResumeCap - 1)), r, cw2, cw3);
+                if constexpr (SPATH) resume_L[(pubr + rank) & (kResumeCap - 1)] = L;
                 go = false; given = true;
               }
               __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -3917,6 +4043,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         if (go) {
           const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(gm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)gm, 0u));
           ray_pack(pend_q + 4 * ((base + rank) & (kPendCap - 1)), r, (uint32_t)r.on, 0u);
+          if constexpr (SPATH) pend_L[(base + rank) & (kPendCap - 1)] = L;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         if (lane == 0) add(&Q->pend_pub, cnt);
@@ -3943,6 +4070,10 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       if constexpr (SORDER) {
         if (ended) sorder_record(*sorder_arg, rblk, n_patch, n_baf,
                                  exited ? (below ? kRespPort : kRespPort + 1) : st == ST_SUSPENDED ? kRespSuspended : eslot, r.j);
+      }
+      if constexpr (SPATH) {
+        if (ended) spath_record(*spath_arg, pcks, pblk, n_patch, n_baf,
+                                exited ? (below ? kRespPort : kRespPort + 1) : st == ST_SUSPENDED ? kRespSuspended : eslot, L);
       }
       const uint32_t c_ended = (uint32_t)__popcll(__ballot(ended));
       n_ended += c_ended;
@@ -3983,7 +4114,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         n_inc += (unsigned long long)__popcll(__ballot(hit0)) + (unsigned long long)__popcll(__ballot(hit1));
       }
       const unsigned long long m = (PP != 0 || WALL || ORDER || (PATCH && !SCENE)) ? 0ull : __ballot(keep);
-      if (!RESP && !VIEW && !FIELD && !SORDER && m) {   // (RESP, VIEW, FIELD, SORDER: no exit lines -- the response / the view / the field / the histograms are the build's one sink, no kernel follows)
+      if (!RESP && !VIEW && !FIELD && !SORDER && !SPATH && m) {   // (RESP, VIEW, FIELD, SORDER, SPATH: no exit lines -- the response / the view / the field / the histograms are the build's one sink, no kernel follows)
         const uint32_t cnt = (uint32_t)__popcll(m);
         if (cnt > reg_left) {   // close the open region, reserve the next one (kRegion)
           if (lane == 0 && reg_id != 0xffffffffu) d_arg.rec_counts[reg_id] = kRegion - reg_left;
@@ -4134,6 +4265,21 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     }
     __syncthreads();
   }
+  if constexpr (SPATH) {   // one flush of the workgroup's low bins, its overflow counters and its checksums; bin_increments as SORDER's
+    spath_flush(*spath_arg, pblk, n_patch, n_baf, tid_end, (uint32_t)blockDim.x);
+    if (tid_end < (uint32_t)kRespFates) {
+      const uint32_t c = pblk[tid_end];
+      if (c) global_add_u64(spath_arg->counts + tid_end, (unsigned long long)c);
+      const unsigned long long k = pcks[tid_end];
+      if (k) global_add_u64(spath_arg->counts + (uint32_t)kRespFates + tid_end, k);
+    }
+    if (tid_end == 64u) {
+      unsigned long long over = 0ull;
+      for (int f = 0; f < kRespFates; ++f) over += (unsigned long long)pblk[f];
+      sstat[5] = sstat[1] + sstat[3] + sstat[4] - over;
+    }
+    __syncthreads();
+  }
   if constexpr (BAFFLE) {   // one flush of the workgroup's counters (the thread index rebuilt, as the beam kernel's)
     uint32_t t3 = tid_end;
     asm volatile("" : "+v"(t3));
@@ -4243,6 +4389,15 @@ isx_trace_assist_scene_order_kernel(const Geom g, const DetGrid d, const Work wk
                                     const SOrderSink sorder) {
   assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true, false, false, false, true>(
       g, d, wk, &tab, &beam, nullptr, &baf, nullptr, nullptr, nullptr, &sorder);
+}
+// the scene path histograms (isx_scene_path_hist): the scene kernel with the path length of every ray carried through its steps
+// and hand-overs (spath_advance) and one add per ended ray -- its fate by its path length (spath_record), the low bins in the
+// workgroup's LDS -- and no exit lines; the sink is a seventh argument
+extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_SCENE_WAVES, ISX_SCENE_WAVES)))
+isx_trace_assist_scene_path_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab, const BeamSrc beam, const BaffleTab baf,
+                                   const SPathSink spath) {
+  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true, false, false, false, false, true>(
+      g, d, wk, &tab, &beam, nullptr, &baf, nullptr, nullptr, nullptr, nullptr, &spath);
 }
 // the flux pipeline behind the fate scan: isx_trace_assist_kernel on the rays of a list; the list is a fourth argument
 extern "C" __global__ void ISX_ASSIST_ATTR

@@ -356,3 +356,22 @@ def scene_order_hist_sharded(trace: Callable, cfg, scene, ospec, n_total: int, s
 
     out = fluxmap_scene_sharded(one, cfg, scene, n_total, seed, first_ray, device)
     return (out[0][:-21].reshape(shape[0]), out[0][-21:]) + tuple(out[1:])
+
+
+def scene_path_hist_sharded(trace: Callable, cfg, scene, pspec, n_total: int, seed: int, first_ray: int = 0, device=None):
+    """The path histograms of a scene (altair_raytracing_amd.scene_path_hist) ray-sharded: this rank's contiguous shard through
+    `trace(cfg, scene, pspec, count, seed, first) -> (hist, path_counts, scene_counts, stats)`, then ONE SUM all-reduce that
+    carries the histograms, the 21 overflow counters, the 21 checksums, the 36 scene counters and the census --
+    scene_order_hist_sharded with the path counts in the order counts' place.  The checksums are sums modulo 2^64: they travel as
+    int64 words like the rest, and the all-reduce's wrapping sum is theirs.  Returns (hist[21, n_bins] uint64, overflow[21]
+    uint64, checksum[21] uint64, patch_arrivals[10] uint64, patch_absorbed[10] uint64, baffle arrivals[4, 2] uint64, baffle
+    absorbed[4, 2] uint64, census dict) -- identical on every rank."""
+    shape = []
+
+    def one(c, sp, count, sd, first):
+        hist, pc, cnt, st = trace(c, sp, pspec, count, sd, first)
+        shape.append(hist.shape)
+        return np.concatenate([np.asarray(hist, dtype=np.uint64).reshape(-1), pc.words()]), cnt, st
+
+    out = fluxmap_scene_sharded(one, cfg, scene, n_total, seed, first_ray, device)
+    return (out[0][:-42].reshape(shape[0]), out[0][-42:-21], out[0][-21:]) + tuple(out[1:])

@@ -212,6 +212,9 @@ int isx_last_kernel_ms(double* single_ms, double* trace_ms, double* bin_ms);
  *   "sorder_lds_orders"  how many orders of every fate slot isx_scene_order_hist keeps as u32 words in the workgroup's LDS: -1
  *                  (default) as many as fit without costing a resident workgroup, n > 0 at most n of those, 0 none -- one
  *                  global atomic add per ended ray (a diagnostic).  It changes no result.
+ *   "spath_lds_bins"  how many bins of every fate slot isx_scene_path_hist keeps as u32 words in the workgroup's LDS: -1
+ *                  (default) as many as fit without costing a resident workgroup, n > 0 at most n of those, 0 none -- one
+ *                  global atomic add per ended ray (a diagnostic).  It changes no result.
  *   "bin_block", "bin_blocks_per_cu"  shape of round 2's binning kernel (0 workgroups per CU = what is resident)
  *                  (round 5: "assist_block" 0 = the default again -- 768 threads, 256 for launches below 1e6 rays, 512 for the lobe /
  *                  rough-specular kernels; "rays_per_lane" > 0 sizes every grid for that many rays per tracer lane, 0 = by launch
@@ -575,7 +578,8 @@ int isx_bin_injected_segments(const isx_config* cfg, const double* centers_axes 
  * interactions survived k absorption tests, so the histories traced at reflectance rho0 = cfg->reflectance are the histories at
  * any rho <= rho0 with weight (rho / rho0)^k: one trace gives the port throughput along a whole reflectance curve
  * (isx_order_reweight).  The mean path per bounce is 4 r_in / 3, so the same histogram is the sphere's time response at the
- * resolution of one mean chord; the census reports only its mean, wall_hits / launched.  No path length is measured.
+ * resolution of one mean chord; the census reports only its mean, wall_hits / launched.  No path length is measured here (with a
+ * scene: isx_scene_path_hist).
  *
  * For every traced ray take status and n_points as isx_trace_endstates reports them for that ray index (for ISX_SOURCE_BRDF
  * the scattered ray, as there) and v, its final direction:
@@ -1259,7 +1263,7 @@ int isx_patch_field_marginals(const isx_patch_field_spec* fspec, const uint64_t*
  * d_scene_counts).  Without a HIP device: ISX_ERR_NO_DEVICE; with one but before isx_init(): ISX_ERR_NOT_INIT (as
  * isx_fluxmap_scene).
  * Out of scope: a reweighting of the wall alone where patches or baffles reflect at another value (it needs a counter per ray),
- * path lengths in cm, a joint histogram over order and source bin, the isx_macro command line.
+ * a joint histogram over order and source bin, the isx_macro command line (path lengths in cm are isx_scene_path_hist).
  */
 #define ISX_SCENE_ORDER_MAX_ORDERS 65536
 typedef struct isx_scene_order_spec {
@@ -1315,6 +1319,103 @@ int isx_scene_order_reweight(const isx_config* cfg, const isx_scene_spec* scene,
  */
 int isx_scene_order_moments(const isx_scene_order_spec* ospec, const uint64_t* hist, const isx_scene_order_counts* counts,
                             double* mean /*[21]*/, double* sd /*[21]*/);
+
+/*
+ * Scene path histograms: the fates of a scene's rays by path length -- how much path, in cm, the light of a scene has travelled
+ * where it ends: the temporal impulse response of every fate (time = L / 29.9792458 cm/ns; no call converts).  The bounce order
+ * (isx_scene_order_hist) is a time axis only at the resolution of one mean chord and only for a bare sphere; with a lamp, baffles
+ * and detector caps the legs run from a few cm to 2 r_in.
+ *
+ * The ray histories are those of isx_fluxmap_scene / isx_scene_endstates for the same (cfg, scene, seed, ray index): nothing of a
+ * history changes.  For every traced ray, f is the fate slot exactly as isx_scene_response defines it (0 .. 20,
+ * ISX_RESPONSE_FATES), and L its path length:
+ *
+ *   Track points.  X_0 is the start point of the beam contract; X_i every point the ray's point becomes -- a baffle crossing x,
+ *   the boundary point q of a wall arrival, the world box: the points n_points counts.
+ *   Segments (all arithmetic IEEE double, left to right as written, no fma, the correctly rounded sqrt):
+ *       d = X_i - X_{i-1} (componentwise) ;  s_i = sqrt((d.x * d.x + d.y * d.y) + d.z * d.z)
+ *       L = 0.0, then L = L + s_i in order of i
+ *   Which segments count.  ISX_RAY_ABSORBED and ISX_RAY_SUSPENDED: all n_points - 1.  ISX_RAY_EXITED: the n_points - 2 up to the
+ *   last interaction point -- the leg to the world box is an artefact of the box.  Slot 18 (counted below z) then adds the leg up
+ *   to the port plane: with p = X_{n-2}, q = X_{n-1} and s the length of that leg by the rule above,
+ *       f = (cfg->exit_port_z - p.z) / (q.z - p.z) ;  L = L + ((f > 0.0 && f <= 1.0) ? s * f : 0.0)        (a NaN f: 0.0)
+ *   so a last interaction point already below the plane adds nothing.  Slot 19 adds nothing.
+ *   Binning.  fb = L / bin_cm; if (fb < (double)n_bins) is false (a NaN included): overflow[f] += 1; otherwise
+ *   hist[f * n_bins + (int)fb] += 1.  An fb equal to an integer lands in the upper bin; fb == n_bins is overflow.
+ *   Checksum.  For every ray, overflowed or not: checksum[f] += the 64 bits of L as an unsigned integer, modulo 2^64 -- the parity
+ *   instrument: a histogram cannot see a last-bit difference in L, a modular sum of bit patterns sees every one; it does not
+ *   depend on the order of the rays and adds over calls.
+ *
+ * For every call: the sum of row f plus overflow[f] is the row sum isx_scene_response gives for f; stats.bin_increments is the sum
+ * of hist; `scene_counts` and every other field of stats except t_kernel_ms are isx_fluxmap_scene's for the same arguments; with
+ * n_bins 1 and bin_cm 1e300 hist[f][0] is the response's row and every overflow 0.  No result, the checksums included, depends on
+ * any isx_set_option switch nor on how a job is cut into calls.  cfg->hit_line_mode and the detector-grid fields of cfg are
+ * ignored and never a reason for refusal.  Slots the scene cannot fill stay 0.
+ *
+ * One route whatever the switches say: isx_trace_assist_scene_path_kernel -- the scene's trace kernel with one double more per
+ * ray, advanced wherever the ray's point is replaced and handed over with the ray, and one add per ended ray where the census
+ * is taken; it draws nothing, writes no exit lines, and no kernel follows it.  The first B bins of every slot the scene can fill
+ * are u32 words in the workgroup's LDS, flushed once, with the overflow counters and the checksums; the bins from B on take one
+ * global u64 add each ("spath_lds_bins": B).
+ *
+ * Refused, whether or not a device is present: everything isx_scene_endstates refuses of cfg and scene, with its codes;
+ * ISX_ERR_BAD_CONFIG: struct_size != sizeof(isx_scene_path_spec), a non-zero reserved field, n_bins outside
+ * 1..ISX_SCENE_PATH_MAX_BINS, a bin_cm that is not finite or not > 0; ISX_ERR_BAD_ARG: a NULL cfg, scene, pspec or hist (device
+ * form: d_hist, d_path_counts, d_scene_counts).  Without a HIP device: ISX_ERR_NO_DEVICE; with one but before isx_init():
+ * ISX_ERR_NOT_INIT (as isx_fluxmap_scene).
+ * Out of scope: path histograms for the bare-sphere calls and the other borders, a joint histogram over path and order or source
+ * bin, the convolution with a pulse shape, the isx_macro command line.
+ */
+#define ISX_SCENE_PATH_MAX_BINS 65536
+typedef struct isx_scene_path_spec {
+  uint32_t struct_size;      /* sizeof(isx_scene_path_spec), set by isx_default_scene_path_spec(); a spec of another size is refused */
+  uint32_t reserved0;        /* 0 */
+  int32_t n_bins;            /* bins 0 .. n_bins - 1 per fate slot; 1..ISX_SCENE_PATH_MAX_BINS */
+  int32_t reserved1;         /* 0 */
+  double bin_cm;             /* width of a bin in cm; finite, > 0 */
+} isx_scene_path_spec;       /* 24 bytes */
+typedef struct isx_scene_path_counts {
+  uint64_t overflow[ISX_RESPONSE_FATES];   /* per fate slot, the rays with L / bin_cm not below n_bins */
+  uint64_t checksum[ISX_RESPONSE_FATES];   /* per fate slot, the sum of the bit patterns of L modulo 2^64 */
+} isx_scene_path_counts;     /* 336 bytes */
+
+/* n_bins = 1024, bin_cm = cfg->r_in / 4.  Host only, no GPU needed. */
+void isx_default_scene_path_spec(const isx_config* cfg, isx_scene_path_spec* pspec);
+/* Blocking: hist[ISX_RESPONSE_FATES * n_bins], path_counts and scene_counts (host, zeroed by the callee; path_counts,
+ * scene_counts and stats may be NULL). */
+int isx_scene_path_hist(const isx_config* cfg, const isx_scene_spec* scene, const isx_scene_path_spec* pspec, uint64_t n_rays,
+                        uint64_t seed, uint64_t first_ray, uint64_t* hist, isx_scene_path_counts* path_counts,
+                        isx_scene_counts* scene_counts, isx_stats* stats);
+/* ACCUMULATES (+=, the checksums modulo 2^64) into d_hist [ISX_RESPONSE_FATES * n_bins], d_path_counts (42 words,
+ * isx_scene_path_counts' layout) and d_scene_counts (36 words, isx_scene_counts' layout; none may be NULL) on the library's stream
+ * and returns after enqueueing; isx_sync() / isx_take_stats() as for isx_fluxmap_scene_device. */
+int isx_scene_path_hist_device(const isx_config* cfg, const isx_scene_spec* scene, const isx_scene_path_spec* pspec,
+                               uint64_t n_rays, uint64_t seed, uint64_t first_ray, uint64_t* d_hist,
+                               uint64_t* d_path_counts /*[42]*/, uint64_t* d_scene_counts /*[36]*/);
+/*
+ * Mean and standard deviation of the path length per fate slot, in cm, from the bin centres x_ib = (ib + 0.5) * bin_cm.  Host
+ * only, no GPU needed.  With N = sum over ib of hist[f][ib], A = sum of x_ib * hist[f][ib], B = sum of x_ib * x_ib * hist[f][ib]
+ * (as doubles, in increasing ib): mean_cm[f] = A / N, sd_cm[f] = sqrt(max(0, B / N - mean_cm[f] * mean_cm[f])) --
+ * isx_scene_order_moments' formulas.  NaN for an empty row and for a row with overflow[f] != 0.  Either output may be NULL.
+ * ISX_ERR_BAD_ARG: a NULL pspec, hist or counts; ISX_ERR_BAD_CONFIG: a spec isx_scene_path_hist refuses.
+ */
+int isx_scene_path_moments(const isx_scene_path_spec* pspec, const uint64_t* hist, const isx_scene_path_counts* counts,
+                           double* mean_cm /*[21]*/, double* sd_cm /*[21]*/);
+/*
+ * The decay constant of the tail of row f from bin lo_bin on: the maximum-likelihood estimate for a geometric law over the bins.
+ * Host only, no GPU needed.  With N the rays in the bins ib >= lo_bin and m the mean of (ib - lo_bin) over them -- S = sum of
+ * (double)(ib - lo_bin) * (double)hist[f][ib] and N = sum of (double)hist[f][ib], in increasing ib, m = S / N:
+ *
+ *   r        = m / (1.0 + m)
+ *   tau_cm   = -bin_cm / log(r)
+ *   sigma_cm = bin_cm / (log(r) * log(r)) / sqrt(N * m * (1.0 + m))
+ *
+ * In time: tau_cm / 29.9792458 ns.  ISX_ERR_BAD_CONFIG: a spec isx_scene_path_hist refuses,
+ * overflow[f] != 0, N == 0, m == 0; ISX_ERR_BAD_ARG: f outside 0..20, lo_bin outside 0..n_bins - 1, a NULL pspec, hist, counts,
+ * tau_cm or sigma_cm.
+ */
+int isx_scene_path_decay(const isx_scene_path_spec* pspec, const uint64_t* hist, const isx_scene_path_counts* counts, int32_t f,
+                         int32_t lo_bin, double* tau_cm, double* sigma_cm);
 
 /*
  * Series driver (sweepSeries, fluxAtObserverOptimize.C:892-921 / fluxAtObserverFast.C:1641-1673):

@@ -33,7 +33,8 @@ NO_SCRATCH = ("isx_bin_cols_kernel", "isx_bin_slots_kernel", "isx_bin_lines_kern
               "isx_trace_assist_patch_kernel", "isx_trace_assist_beam_kernel", "isx_trace_assist_baffle_kernel",
               "isx_trace_assist_list_kernel", "isx_fate_scan_kernel", "isx_trace_assist_scene_kernel",
               "isx_trace_assist_scene_response_kernel", "isx_trace_assist_scene_view_kernel",
-              "isx_trace_assist_scene_field_kernel", "isx_trace_assist_scene_order_kernel")
+              "isx_trace_assist_scene_field_kernel", "isx_trace_assist_scene_order_kernel",
+              "isx_trace_assist_scene_path_kernel")
 
 
 def compile_isa(extra, keep=None):
