@@ -14,7 +14,7 @@ from . import sharding  # noqa: F401
 from .sharding import shard, step_slice, fluxmap_sharded, disc_sweep_sharded, exit_maps_sharded, wall_map_sharded, light_field_sharded, order_hist_sharded, wall_patches_sharded, fluxmap_beam_sharded, fluxmap_baffle_sharded, fluxmap_scene_sharded, scene_response_sharded, scene_view_sharded, scene_patch_field_sharded, scene_order_hist_sharded, scene_path_hist_sharded  # noqa: F401
 from ._abi import (  # noqa: F401
     Config, Stats, IsxError, default_config, init, shutdown, device_info, set_option, fluxmap, fluxmap_device, sync,
-    take_stats, last_kernel_ms, trace_endstates, fate_scan, fate_scan_launches, disc_sweep, disc_sweep_per_position, exit_dz_hist, fluxmap_per_position, trace_rays_detector, exit_directions, fluxmap_series, detector_table, mathprobe, load, LIB_PATH, EXPORTS,
+    take_stats, last_kernel_ms, trace_endstates, fate_scan, fate_scan_launches, exit_scan_counts, disc_sweep, disc_sweep_per_position, exit_dz_hist, fluxmap_per_position, trace_rays_detector, exit_directions, fluxmap_series, detector_table, mathprobe, load, LIB_PATH, EXPORTS,
     ExitMapSpec, ExitMapCounts, default_exit_map_spec, exit_maps, exit_maps_device,
     WallMapSpec, WallMapCounts, default_wall_map_spec, wall_map, wall_map_device,
     LightFieldCounts, default_light_field_spec, light_field, light_field_device,
@@ -36,7 +36,7 @@ from ._abi import (  # noqa: F401
 )
 
 __all__ = ["abi", "sharding", "shard", "step_slice", "fluxmap_sharded", "disc_sweep_sharded", "exit_maps_sharded", "wall_map_sharded", "light_field_sharded", "order_hist_sharded", "Config", "Stats", "IsxError", "default_config", "init", "shutdown", "device_info", "set_option",
-           "fluxmap", "fluxmap_device", "fluxmap_per_position", "trace_rays_detector", "exit_directions", "fluxmap_series", "sync", "take_stats", "last_kernel_ms", "trace_endstates", "fate_scan", "fate_scan_launches", "disc_sweep", "disc_sweep_per_position", "exit_dz_hist",
+           "fluxmap", "fluxmap_device", "fluxmap_per_position", "trace_rays_detector", "exit_directions", "fluxmap_series", "sync", "take_stats", "last_kernel_ms", "trace_endstates", "fate_scan", "fate_scan_launches", "exit_scan_counts", "disc_sweep", "disc_sweep_per_position", "exit_dz_hist",
            "detector_table", "mathprobe", "load", "LIB_PATH", "EXPORTS",
            "ExitMapSpec", "ExitMapCounts", "default_exit_map_spec", "exit_maps", "exit_maps_device",
            "WallMapSpec", "WallMapCounts", "default_wall_map_spec", "wall_map", "wall_map_device",

@@ -39,7 +39,7 @@ INJECT_MAX_LINES, INJECT_MAX_REGIONS = 1 << 20, 1024   # (the flux sink also wan
 EXPORTS = [
     "isx_default_config", "isx_init", "isx_shutdown", "isx_strerror", "isx_last_hip_error", "isx_abi_version", "isx_stream_version",
     "isx_device_info", "isx_fluxmap", "isx_fluxmap_device", "isx_sync", "isx_take_stats", "isx_stream",
-    "isx_set_option", "isx_mathprobe", "isx_trace_endstates", "isx_fate_scan", "isx_fate_scan_launches", "isx_disc_sweep", "isx_detector_table",
+    "isx_set_option", "isx_mathprobe", "isx_trace_endstates", "isx_fate_scan", "isx_fate_scan_launches", "isx_exit_scan_counts", "isx_disc_sweep", "isx_detector_table",
     "isx_exit_dz_hist", "isx_fluxmap_per_position", "isx_trace_rays_detector", "isx_exit_directions",
     "isx_fluxmap_series", "isx_disc_sweep_per_position", "isx_last_kernel_ms",
     "isx_default_exit_map_spec", "isx_exit_maps", "isx_exit_maps_device",
@@ -420,6 +420,7 @@ def load():
     L.isx_trace_endstates.argtypes = [P(Config), u64, u64, u64, P(i32), P(i32), P(dbl), P(dbl)]
     L.isx_fate_scan.argtypes = [P(Config), u64, u64, u64, P(i32), P(i32)]
     L.isx_fate_scan_launches.argtypes = [P(u64)]
+    L.isx_exit_scan_counts.argtypes = [P(u64), P(u64), P(u64)]
     L.isx_disc_sweep.argtypes = [P(Config), P(dbl), i32, dbl, dbl, u64, u64, u64, P(u64), P(Stats)]
     L.isx_disc_sweep_per_position.argtypes = [P(Config), P(dbl), i32, dbl, dbl, u64, u64, u64, P(u64), P(Stats)]
     L.isx_last_kernel_ms.argtypes = [P(dbl), P(dbl), P(dbl)]
@@ -595,6 +596,13 @@ def fate_scan_launches():
     n = C.c_uint64(0)
     _chk(load().isx_fate_scan_launches(C.byref(n)), "isx_fate_scan_launches")
     return int(n.value)
+
+
+def exit_scan_counts():
+    """-> (accepted, list_b, redo) of the "exit_scan" path since init() (include/isx.h: isx_exit_scan_counts)"""
+    a, b, r = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _chk(load().isx_exit_scan_counts(C.byref(a), C.byref(b), C.byref(r)), "isx_exit_scan_counts")
+    return int(a.value), int(b.value), int(r.value)
 
 
 def disc_sweep(cfg, centers_axes, radius, half_thick, n_rays, seed, first_ray=0):

@@ -52,6 +52,17 @@ struct State {
   size_t cap_list[kRecBufs] = {0, 0, 0};
   unsigned long long fate_launches = 0;   // isx_fate_scan_kernel launches enqueued since isx_init (isx_fate_scan_launches)
   int fate_scan = -1;                     // 0 off, 1 on wherever eligible, -1 (default) automatic: fate_scan_auto()
+  // exit lines from the words, behind the fate scan: per workspace the list of the rays isx_exit_lines_kernel
+  // leaves to the trace kernel (4 B per ray), the side entry of every line slot (8 B) and the chunk's redo list ([0] count,
+  // [1] overflow, [2..] entries); d_list then holds the scan's {offset, j} pairs (8 B per ray)
+  int exit_scan = -1;                     // 0 off, 1 on wherever eligible, -1 (default) automatic: where the fate scan's rule says so
+  int64_t exit_eps_scale = 1;             // test option: every bound the exit-line kernel hands to the binning kernel is multiplied by it
+  uint32_t* d_list_b[kRecBufs] = {};
+  uint2* d_side[kRecBufs] = {};
+  unsigned long long* d_redo[kRecBufs] = {};
+  size_t cap_exit_rays[kRecBufs] = {0, 0, 0}, cap_side[kRecBufs] = {0, 0, 0}, cap_redo[kRecBufs] = {0, 0, 0};
+  bool list_pairs[kRecBufs] = {false, false, false};   // d_list[b] has room for pairs
+  unsigned long long* d_exit_totals = nullptr;   // [3] accepted, list B, redo entries since isx_init (isx_exit_scan_counts)
   // overlap > 1: a flux-map call is cut into that many chunks and the binning kernel of chunk k runs on a second stream
   // while the trace kernel of chunk k+1 runs on the first
   int overlap = 0;
@@ -1024,6 +1035,8 @@ struct Plan {
                                 // of fn (which a chunk below the automatic rule's size still takes: launch_pair)
   FateConsts fate{};
   bool fate_auto = false;       // "fate_scan" -1: the rule's ray count is looked at per chunk (launch_pair)
+  bool exit_lines = false;      // behind the scan: isx_exit_lines_kernel settles the clean port exits, the list kernel traces the rest,
+  uint32_t w_exit = 0;          //   isx_redo_kernel follows the binning kernel; w_exit = ceil(W_leave + MARG)
   // the kernels' trailing arguments (launch_trace): enqueue fills the three tables, plan_scene_map the sink of a scene map
   PatchTab patch_tab{};         // SINK_PATCH; a scene
   BeamSrc beam{};               // isx_fluxmap_beam; a scene
@@ -1090,6 +1103,13 @@ int bin_grid(const Plan& p, uint64_t cnt, uint32_t pad, uint64_t writers, int pe
   return want < (uint64_t)full ? (int)want : full;
 }
 
+// workgroups of isx_exit_lines_kernel for a chunk of `cnt` rays: its list is at most the chunk, eight entries per lane, four
+// workgroups of four waves per CU at most (every wave leaves an open region)
+int exit_grid(uint64_t cnt) {
+  if (S.grid_blocks > 0) return S.grid_blocks;
+  const uint64_t want = (cnt + 8ull * kExitBlock - 1) / (8ull * kExitBlock), full = (uint64_t)S.cu_count * 4ull;
+  return (int)std::max<uint64_t>(1, std::min(want, full));
+}
 // the shape of a trace kernel with or without an assist wave: workgroup, tracer waves, grid, LDS (census, Geom, DetGrid, and
 // with an assist wave the queues and rings)
 void trace_shape(Plan& p, Shape sh, bool assist, int per_cu) {
@@ -1285,11 +1305,18 @@ Plan plan_launch(const Call& k, const DetGrid& d, size_t lds, const FateConsts* 
     p.call_overlap = g_device_call && S.call_overlap != 0 && S.overlap <= 1 && !chord && !beam && !baffle && !scene;
     // the fate scan in front of the headline trace kernel (fate_consts: pencil, Lambertian border, explicit bounces, first strike
     // on the mirror patch): scheduling only -- anything else takes the kernels above whatever the option says
-    if (!beam && fate && fate->ok && p.fn.fn == (const void*)isx_trace_assist_kernel && !p.overlap &&
-        (S.fate_scan == 1 || (S.fate_scan < 0 && fate_scan_auto(c, std::min(n, S.pipe_chunk))))) {
+    const bool fate_ok = !beam && fate && fate->ok && p.fn.fn == (const void*)isx_trace_assist_kernel && !p.overlap;
+    // exit lines from the words behind the scan: the scan's eligibility, the last-segment hit line, the
+    // column-slot binning kernel.  "exit_scan" 1 brings the scan with it (unless "fate_scan" is 0); -1 follows the scan's rule.
+    const uint64_t w_exit = fate_ok ? (uint64_t)fate->w_leave + 2ull * kFateMarg + 2ull : ~0ull;
+    const bool exit_ok = fate_ok && S.fate_scan != 0 && !compat && cols && p.binning && w_exit <= 0xffffffffull;
+    const bool exit_on = exit_ok && (S.exit_scan == 1 || (S.exit_scan < 0 && fate_scan_auto(c, std::min(n, S.pipe_chunk))));
+    if (fate_ok && (exit_on || S.fate_scan == 1 || (S.fate_scan < 0 && fate_scan_auto(c, std::min(n, S.pipe_chunk))))) {
       p.list = isx_trace_assist_list_kernel;
       p.fate = *fate;
-      p.fate_auto = S.fate_scan < 0;   // (the largest chunk passes the rule; a shorter last chunk is asked again)
+      p.fate_auto = S.fate_scan < 0 && !(exit_on && S.exit_scan == 1);   // (the largest chunk passes the rule; a shorter last chunk is asked again)
+      p.exit_lines = exit_on;
+      p.w_exit = exit_on ? (uint32_t)w_exit : 0u;
     }
     if (p.lds_bin <= S.lds_limit || beam || baffle) return p;   // (beam, baffles: enqueue refuses a binning kernel whose LDS does not fit)
     p = Plan();   // (a binning kernel whose LDS does not fit: the fused kernel below)
@@ -1492,15 +1519,50 @@ int ensure_regions(size_t regions, int buf) {
 // ... for a chunk of `rays` rays traced by `waves` waves: every region but a wave's last is closed with more than kRegion - 64
 // lines in it, and a launch cannot have more lines than rays (isx_kernels.hpp: kRegion)
 // list: ... and the fate scan's ray list, 4 B per ray of the largest chunk so far (grown, never shrunk)
-int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles, bool list = false) {
-  if (list && rays > S.cap_list[buf]) {
+// exit_waves > 0: ... and what isx_exit_lines_kernel needs: the list as {offset, j} pairs, list B, a side
+// entry per line slot, the redo list; its waves leave an open region each, as the trace kernel's writers do
+constexpr size_t kRedoMin = 1u << 22;   // entries: what a test-sized chunk can send with its bounds scaled up (exit_eps_scale)
+int ensure_pipeline(size_t rays, size_t waves, int buf, size_t slot_doubles, bool list = false, size_t exit_waves = 0) {
+  const bool pairs = exit_waves > 0;
+  if (list && (rays > S.cap_list[buf] || (pairs && !S.list_pairs[buf]))) {
     if (sync_all()) return ISX_ERR_HIP;
     if (S.d_list[buf]) HIPCHK(hipFree(S.d_list[buf]));
-    S.d_list[buf] = nullptr; S.cap_list[buf] = 0;
-    HIPCHK(hipMalloc(&S.d_list[buf], rays * sizeof(uint32_t)));
-    S.cap_list[buf] = rays;
+    const size_t cap = std::max(rays, S.cap_list[buf]);
+    const bool wide = pairs || S.list_pairs[buf];
+    S.d_list[buf] = nullptr; S.cap_list[buf] = 0; S.list_pairs[buf] = false;
+    HIPCHK(hipMalloc(&S.d_list[buf], cap * sizeof(uint32_t) * (wide ? 2 : 1)));
+    S.cap_list[buf] = cap; S.list_pairs[buf] = wide;
   }
-  return ensure_regions((rays / (kRegion - 63) + waves + 1) * slot_doubles / 6 + 1, buf);   // (capacity is counted in 6-double slots)
+  const size_t regions = (rays / (kRegion - 63) + waves + exit_waves + 1) * slot_doubles / 6 + 1;   // (capacity is counted in 6-double slots)
+  int rc = ensure_regions(regions, buf);
+  if (rc || !pairs) return rc;
+  if (rays > S.cap_exit_rays[buf]) {
+    if (sync_all()) return ISX_ERR_HIP;
+    if (S.d_list_b[buf]) HIPCHK(hipFree(S.d_list_b[buf]));
+    S.d_list_b[buf] = nullptr; S.cap_exit_rays[buf] = 0;
+    HIPCHK(hipMalloc(&S.d_list_b[buf], rays * sizeof(uint32_t)));
+    S.cap_exit_rays[buf] = rays;
+  }
+  if (S.cap_regions[buf] > S.cap_side[buf]) {
+    if (sync_all()) return ISX_ERR_HIP;
+    if (S.d_side[buf]) HIPCHK(hipFree(S.d_side[buf]));
+    S.d_side[buf] = nullptr; S.cap_side[buf] = 0;
+    HIPCHK(hipMalloc(&S.d_side[buf], S.cap_regions[buf] * kRegion * sizeof(uint2)));
+    S.cap_side[buf] = S.cap_regions[buf];
+  }
+  const size_t redo = std::max(kRedoMin, rays / 4);
+  if (redo > S.cap_redo[buf]) {
+    if (sync_all()) return ISX_ERR_HIP;
+    if (S.d_redo[buf]) HIPCHK(hipFree(S.d_redo[buf]));
+    S.d_redo[buf] = nullptr; S.cap_redo[buf] = 0;
+    HIPCHK(hipMalloc(&S.d_redo[buf], (redo + 2) * sizeof(unsigned long long)));
+    S.cap_redo[buf] = redo;
+  }
+  if (!S.d_exit_totals) {
+    HIPCHK(hipMalloc(&S.d_exit_totals, 3 * sizeof(unsigned long long)));
+    HIPCHK(hipMemset(S.d_exit_totals, 0, 3 * sizeof(unsigned long long)));
+  }
+  return ISX_OK;
 }
 
 // what the disc sweep's two kernels see of the list upload_discs_clustered left in the aux buffer: the discs in cluster order
@@ -1544,19 +1606,38 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     dt.rec_counts = db.rec_counts = S.d_rec_counts[buf];
     const int tgrid = pick_grid(p, cnt, tres);
     const bool scan = p.list.fn && (!p.fate_auto || cnt >= kFateMinRays);
-    const FateList fl{S.d_list[buf], w.ctr + Q_LIST};
+    const bool exitl = scan && p.exit_lines;
+    const int egrid = exitl ? exit_grid(cnt) : 0;
+    const FateList fl{exitl ? S.d_list_b[buf] : S.d_list[buf], w.ctr + (exitl ? Q_LISTB : Q_LIST)};
+    db.log_rec = exitl ? reinterpret_cast<double*>(S.d_side[buf]) : nullptr;
+    db.log_count = exitl ? S.d_redo[buf] : nullptr;
+    db.log_cap = exitl ? (uint64_t)S.cap_redo[buf] : 0;
     if (scan) {
       // the scan settles what the wall absorbs and leaves the rest in S.d_list, their number in ctr[Q_LIST] (zeroed with the
       // launch's other counters); the trace kernel's grid is sized from the chunk, an upper bound.  Same stream, no host round
       // trip; both kernels lie in the trace span.
       FateScan fs;
-      fs.f = p.fate; fs.seed = w.seed; fs.first = w.first; fs.n = (uint32_t)cnt; fs.pad = 0;
+      fs.f = p.fate; fs.seed = w.seed; fs.first = w.first; fs.n = (uint32_t)cnt; fs.pairs = exitl ? 1u : 0u;
       fs.list = S.d_list[buf]; fs.ctr = w.ctr; fs.stats = w.stats;
       const uint64_t want = (cnt + 4ull * kScanBlock - 1) / (4ull * kScanBlock), full = (uint64_t)S.cu_count * 8ull;
       const int sgrid = S.grid_blocks > 0 ? S.grid_blocks : (int)std::max<uint64_t>(1, std::min(want, full));
       hipLaunchKernelGGL(isx_fate_scan_kernel, dim3(sgrid), dim3(kScanBlock), 0, st, fs);
       HIPCHK(hipGetLastError());
       ++S.fate_launches;
+    }
+    if (exitl) {
+      // the clean port exits among them are settled from their words; list B is what the trace kernel takes.  Same stream, inside
+      // the trace span.
+      ExitScan es;
+      es.g = g; es.seed = w.seed; es.first = w.first;
+      es.list_a = reinterpret_cast<const uint2*>(S.d_list[buf]); es.list_b = S.d_list_b[buf]; es.ctr = w.ctr; es.stats = w.stats;
+      es.totals = S.d_exit_totals; es.rec_lines = S.d_rec[buf]; es.rec_counts = S.d_rec_counts[buf]; es.side = S.d_side[buf];
+      es.redo = S.d_redo[buf];
+      es.rho_thr = p.fate.rho_thr; es.never = p.fate.never; es.w_exit = p.w_exit; es.j_cap = p.fate.j_cap; es.limit = p.fate.limit; es.pad = 0;
+      es.reach = 2.1 * (1.001 * g.r_in + std::fabs(d.portz) + d.R + d.rho_d);
+      es.portz = d.portz; es.det_R = d.R; es.half_w2 = d.half_w2; es.eps_scale = (double)S.exit_eps_scale;
+      hipLaunchKernelGGL(isx_exit_lines_kernel, dim3(egrid), dim3(kExitBlock), 0, st, es);
+      HIPCHK(hipGetLastError());
     }
     launch_trace(p, scan ? p.list : p.fn, tgrid, st, g, dt, w, &fl);
     HIPCHK(hipGetLastError());
@@ -1575,9 +1656,13 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     }
     if (p.binning) {
       // (every writing wave of the trace kernel leaves an open region: one per workgroup with an assist wave)
-      const uint64_t writers = p.assist ? (uint64_t)tgrid : (uint64_t)tgrid * (uint64_t)(p.block / 64);
+      const uint64_t writers = (p.assist ? (uint64_t)tgrid : (uint64_t)tgrid * (uint64_t)(p.block / 64)) + (uint64_t)egrid * (kExitBlock / 64);
       hipLaunchKernelGGL(p.bin, dim3(bin_grid(p, cnt, w.pad, writers, bres)), dim3(p.bblock), p.lds_bin, sb, db, w);
       HIPCHK(hipGetLastError());
+      if (exitl) {   // what the binning kernel would not decide on an approximate line: the ray traced, the reference's test (inside the binning span)
+        hipLaunchKernelGGL(isx_redo_kernel, dim3(S.grid_blocks > 0 ? S.grid_blocks : 64), dim3(256), 0, sb, g, db, w, S.d_exit_totals);
+        HIPCHK(hipGetLastError());
+      }
       if (t && (r = span_on(sb, 2, t))) return r;
     }
     return ISX_OK;
@@ -1613,6 +1698,7 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     return ISX_OK;
   }
   const uint64_t chunk = std::min(n, S.pipe_chunk);
+  const size_t exit_waves = p.exit_lines ? (size_t)exit_grid(chunk) * (kExitBlock / 64) : 0;   // (the largest chunk's: its grid is the largest)
   if (p.call_overlap) {
     // ---- call overlap: the chunk's counter zeroing, scan, trace (and compat lines) on a trace stream, its binning kernel on the
     // caller's stream behind the event that ends them.  The trace stream does not wait for the binning of the chunk before --
@@ -1620,7 +1706,7 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     // next, run under the tails of this one's kernels.  All kRecBufs workspaces are sized at once: a workspace that grew in the
     // middle of a sequence would stop it.
     const size_t waves = (size_t)pick_grid(p, chunk, tres) * (p.block / 64);
-    for (int b = 0; b < State::kRecBufs && rc == ISX_OK; ++b) rc = ensure_pipeline((size_t)chunk, waves, b, p.slot_doubles, p.list.fn != nullptr);
+    for (int b = 0; b < State::kRecBufs && rc == ISX_OK; ++b) rc = ensure_pipeline((size_t)chunk, waves, b, p.slot_doubles, p.list.fn != nullptr, exit_waves);
     if (rc == ISX_OK) rc = trace_begin();
     for (uint64_t off = 0; off < n && rc == ISX_OK; off += chunk, ++S.call_rot) {
       const int buf = (int)(S.call_rot % State::kRecBufs);
@@ -1636,7 +1722,7 @@ int run_pipeline(const Plan& p, const Geom& g, const DetGrid& d, const Work& wk)
     }
     return rc;
   }
-  rc = ensure_pipeline((size_t)chunk, (size_t)pick_grid(p, chunk, tres) * (p.block / 64), 0, p.slot_doubles, p.list.fn != nullptr); if (rc) return rc;
+  rc = ensure_pipeline((size_t)chunk, (size_t)pick_grid(p, chunk, tres) * (p.block / 64), 0, p.slot_doubles, p.list.fn != nullptr, exit_waves); if (rc) return rc;
   size_t t;
   rc = mark(S.stream, &t);
   for (uint64_t off = 0; off < n && rc == ISX_OK; off += chunk)
@@ -2020,10 +2106,17 @@ void isx_shutdown(void) {
   for (int b = 0; b < State::kRecBufs; ++b) {
     if (S.d_list[b]) (void)hipFree(S.d_list[b]);
     S.d_list[b] = nullptr; S.cap_list[b] = 0;
+    if (S.d_list_b[b]) (void)hipFree(S.d_list_b[b]);
+    if (S.d_side[b]) (void)hipFree(S.d_side[b]);
+    if (S.d_redo[b]) (void)hipFree(S.d_redo[b]);
+    S.d_list_b[b] = nullptr; S.d_side[b] = nullptr; S.d_redo[b] = nullptr;
+    S.cap_exit_rays[b] = S.cap_side[b] = S.cap_redo[b] = 0; S.list_pairs[b] = false;
     if (S.ev_free[b]) (void)hipEventDestroy(S.ev_free[b]);
     S.ev_free[b] = nullptr; S.free_set[b] = false;
   }
   for (hipEvent_t& e : S.ev_join) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+  if (S.d_exit_totals) (void)hipFree(S.d_exit_totals);
+  S.d_exit_totals = nullptr;
   S.fate_launches = 0; S.call_rot = 0;
   S.attr_lds.clear();
   S.d_table = S.d_rowtab = S.d_coltab = nullptr;
@@ -2078,6 +2171,9 @@ int isx_set_option(const char* key, int64_t value) {
   if (!std::strcmp(key, "surface_pipeline")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.surface_pipeline = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "ray_sub")) { if (value < 0 || value > (1 << 20)) return ISX_ERR_BAD_ARG; S.ray_sub = (int)value; return ISX_OK; }
   if (!std::strcmp(key, "fate_scan")) { if (value < -1 || value > 1) return ISX_ERR_BAD_ARG; S.fate_scan = (int)value; return ISX_OK; }
+  if (!std::strcmp(key, "exit_scan")) { if (value < -1 || value > 1) return ISX_ERR_BAD_ARG; S.exit_scan = (int)value; return ISX_OK; }
+  // (test option: a bound can be made wider, never narrower)
+  if (!std::strcmp(key, "exit_eps_scale")) { if (value < 1 || value > 1000000000ll) return ISX_ERR_BAD_ARG; S.exit_eps_scale = value; return ISX_OK; }
   if (!std::strcmp(key, "pipeline")) { if (value < 0 || value > 1) return ISX_ERR_BAD_ARG; S.pipeline = (int)value; return ISX_OK; }
   // (a launch addresses its rays by 30-bit offsets -- bits 30 and 31 of Ray::ido are flags in the queue records -- and counts
   //  them in 32 bits: the documented maximum of a chunk is 2^26 rays, 3.4 GB of exit-line workspace)
@@ -2188,6 +2284,19 @@ int isx_fate_scan_launches(uint64_t* launches) {
   if (!S.init) return ISX_ERR_NOT_INIT;
   if (!launches) return ISX_ERR_BAD_ARG;
   *launches = S.fate_launches;
+  return ISX_OK;
+}
+
+int isx_exit_scan_counts(uint64_t* accepted, uint64_t* list_b, uint64_t* redo) {
+  if (!S.init) return ISX_ERR_NOT_INIT;
+  unsigned long long t[3] = {0, 0, 0};
+  if (S.d_exit_totals) {   // (allocated with the first launch that takes the path)
+    if (sync_all()) return ISX_ERR_HIP;
+    HIPCHK(hipMemcpy(t, S.d_exit_totals, sizeof(t), hipMemcpyDeviceToHost));
+  }
+  if (accepted) *accepted = t[0];
+  if (list_b) *list_b = t[1];
+  if (redo) *redo = t[2];
   return ISX_OK;
 }
 

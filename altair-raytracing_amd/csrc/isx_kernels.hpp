@@ -141,9 +141,10 @@ struct Work {
   uint32_t* ctr;
   uint32_t sub, pad;          // pad (binning kernels): work units are (quarter regions) >> pad -- 0, or 2 for small launches (64-line units)
 };
-// ctr[Q_SCAN]: the ray queue of the fate scan (64-bit, as Q_RAYS), ctr[Q_LIST]: rays it left to the trace kernel (isx_fate_scan_kernel).
+// ctr[Q_SCAN]: the ray queue of the fate scan (64-bit, as Q_RAYS), ctr[Q_LIST]: rays it left to the trace kernel (isx_fate_scan_kernel),
+// ctr[Q_LISTB]: those of them that isx_exit_lines_kernel left to the trace kernel.
 enum : int { Q_RAYS = 0 /* 64-bit: words 0-1 (it keeps counting after the last ray) */, Q_REGIONS = 2, Q_BIN = 3,
-             Q_SCAN = 4 /* 64-bit: words 4-5 */, Q_LIST = 6, Q_WORDS = 8 };
+             Q_SCAN = 4 /* 64-bit: words 4-5 */, Q_LIST = 6, Q_LISTB = 7, Q_WORDS = 8 };
 // SINK_REC: a wave appends its exit lines to a private REGION of kRegion slots of the workspace and reserves the next one
 // (one atomic on ctr[Q_REGIONS]) when a trip's lines no longer fit; rec_counts[region] = lines in it.  A region is closed with
 // at least kRegion - 63 lines unless it is a wave's last, so a launch of n rays on W waves needs at most
@@ -516,7 +517,7 @@ __device__ __forceinline__ void walk_columns(const D& d, uint32_t* __restrict__ 
 // four forms and g of BOTH candidates are packed binary32 operations -- the same expressions in the same order as walk_columns,
 // hence the same error bound and band -- 12 v_pk instructions for two candidates where one at a time took 4 + 5 each.  The second
 // candidate of the last step of an odd window is masked.  Tiers 2 and 3 as in walk_columns, for whichever of the two needs them.
-constexpr int kDeferCapW = 252;   // (the deferred list of a wave: 256 words -- count, three spare, 252 entries)
+constexpr int kDeferCapW = 252;   // (the deferred list of a wave: kDeferHead words in front -- count, side entries, redo list -- and 252 entries)
 // Tiers 2 and 3 of the decision for candidate (row ir, column jr) of the line at src6 (walk_columns: binary64 about the original point
 // with its 2.1e-9 band, then the reference's own test from the detector table).
 template <class D>
@@ -545,6 +546,47 @@ __device__ __forceinline__ bool decide_exact(const D& d, const double* __restric
     hit = check_intersection(tab + 6 * (size_t)(ir * d.n_phi + jr), d.half_w2, P, V);
   }
   return hit;
+}
+// The same for a line that isx_exit_lines_kernel formed from the ray's words: the ray's own line passes
+// within eps of it -- its point nearest to O lies within eps, its direction within eps / (|Q - c| + R) for every detector centre c.
+// Binary64 alone, and only where the sign of g is the same on every line that close: 0 miss, 1 hit, 2 not decided here (the
+// candidate goes to isx_redo_kernel, which traces the ray).  g is formed about Q, the point of the line nearest to O, where its
+// three terms do not cancel; its change over those lines is bounded term by term, every magnitude at its largest over them:
+//   |d dot| <= eps / R, |d num| <= eps, |d mdv| <= 4 eps, |d ddw| <= 2 (D + eps) eps, D = |Q - c|.
+// On top of that 1e-13 S_P, S_P = 2 |P - c|^2-ish + half_w2 as tier 2 has it: the rounding of this evaluation (< 25 u S_P: the
+// forms are re-based from P) and of the reference's own test on the ray's line, which in units of g is at most ~50 u S_P whatever
+// |dot| is (the 1 / dot of its intersection parameter cancels against the dot^2 of g).  The reference's |dot| < 1e-10 cut is
+// decided only outside eps / R + 1e-14.  Tier 3 is the reference's test on the reference's line: never run here.
+template <class D>
+__device__ __forceinline__ int decide_approx(const D& d, const double* __restrict__ rowt, const ColX* __restrict__ colx,
+                                             const double* __restrict__ src6, int ir, int jr, float eps32) {
+  const double sd = rowt[4 * ir + 0], cd = rowt[4 * ir + 1], zz = rowt[4 * ir + 2], ad = rowt[4 * ir + 3];
+  const double cph = colx[jr].c, sph = colx[jr].s;
+  V3 P, V;
+  load_line(src6, P, V);
+  const double pz = P.z - zz;
+  const double dotd = fma(sd * V.y, cph, fma(-(sd * V.x), sph, -(cd * V.z)));
+  const double numd = fma(sd * P.y, cph, fma(-(sd * P.x), sph, -(cd * pz)));
+  const double m2dv = fma(2.0 * (ad * V.x), cph, fma(2.0 * (ad * V.y), sph, -2.0 * fma(P.x, V.x, fma(P.y, V.y, pz * V.z))));
+  const double f0 = fma(P.x, P.x, fma(P.y, P.y, fma(ad, ad, pz * pz)));
+  const double f1c = -2.0 * (ad * P.x), f2c = -2.0 * (ad * P.y);
+  const double ddwd = fma(f1c, cph, fma(f2c, sph, f0 - d.half_w2));
+  const double scale_p = fma(2.0, f0 + (fabs(f1c) + fabs(f2c)), d.half_w2);
+  // the forms about Q = P + t0 V (|V| = 1): the same g, magnitudes that do not grow with |P|
+  const double e = (double)eps32, R = d.R;
+  const double t0 = -fma(P.x, V.x, fma(P.y, V.y, (P.z - d.portz) * V.z));
+  const double numq = fma(t0, dotd, numd), mdvq = fma(-2.0, t0, m2dv);
+  const double a_dot = fabs(dotd) + e / R;
+  const double a_num = fabs(numq) + e;
+  const double a_mdv = fabs(mdvq) + 4.0 * e;
+  const double ddwq = fma(t0, t0 - m2dv, ddwd);
+  const double gq = fma(dotd, fma(dotd, ddwq, numq * mdvq), numq * numq);
+  const double Dq = sqrt(fmax(ddwq, 0.0) + d.half_w2) + e;
+  const double a_ddw = fabs(ddwq) + 2.0 * (Dq * e);
+  const double dg = fma(2.0 * a_dot, fma(e / R, a_ddw, (a_dot * Dq) * e),
+                        fma(fma(e / R, a_num, a_dot * e), a_mdv, fma(4.0 * e, a_dot * a_num, 2.0 * (a_num * e))));
+  if (fabs(dotd) < 1.000001e-10 + (e / R + 1e-14) || !(fabs(gq) > fma(1.25, dg, 1e-13 * scale_p))) return 2;
+  return gq < 0.0 ? 1 : 0;
 }
 
 struct __align__(16) ColP { float c0, c1, s0, s1; uint32_t off0, off1, pad0, pad1; };
@@ -984,15 +1026,38 @@ __device__ __forceinline__ void walk_lines_packed(const D& d, uint32_t* __restri
 constexpr int kClasses = 7, kQueueCap = 128;   // a class never holds more than 63 + 64 slots
 constexpr int kSlotWaveWords = kClasses * kQueueCap + 16 + 64;   // LDS words per wave: queues, counters, owner marks
 constexpr int kDeferCap = kDeferCapW;   // candidates a wave can put aside for tiers 2 and 3
-constexpr int kColWaveWords = kClasses * kQueueCap + 16 + 64 + 4 + kDeferCap;   // the same + the deferred list (count, 3 spare, entries)
+constexpr int kDeferHead = 8;   // words in front of the deferred list's entries: [0] count, [1..2] the unit's side entries (0: none), [4..5] the redo list, [6..7] its capacity
+constexpr int kColWaveWords = kClasses * kQueueCap + 16 + 64 + kDeferHead + kDeferCap;   // the same + the deferred list (head, entries)
 constexpr int kPiece = 16, kLongest = 24;
 struct SlotQueues {
   LdsWord* q;         // [kClasses][kQueueCap]
   LdsInt* tail;       // [8] slots pushed per class (running)
   LdsInt* head;       // [8] slots popped per class (running)
   const ColP* colp;   // column-pair table of the workgroup (isx_bin_slots_kernel)
-  LdsWord* defer;     // [4 + kDeferCap] isx_bin_cols_kernel: [0] = entries held, [4..] = candidates that wait for tiers 2 and 3
+  LdsWord* defer;     // [kDeferHead + kDeferCap] isx_bin_cols_kernel: [0] = entries held, [kDeferHead..] = candidates that wait for tiers 2 and 3
+                      // [1..2]: a unit of lines that isx_exit_lines_kernel wrote -- per line of the unit {eps as
+                      // binary32 bits, the ray's offset}; 0: exact lines, today's path.  [4..5] the chunk's redo list ([0] entries,
+                      // [1] overflow, [2..] offset | bin << 32: candidates left to isx_redo_kernel), [6..7] its capacity.  Kept here and
+                      // read where they are used: the kernel has no scalar register to hold them across the walk
 };
+__device__ __forceinline__ const uint2* defer_side(const SlotQueues& sq) {
+  volatile LdsWord* df = sq.defer;
+  return reinterpret_cast<const uint2*>((uintptr_t)((unsigned long long)df[1] | ((unsigned long long)df[2] << 32)));
+}
+// a candidate of an approximate line that this kernel must not decide: to the redo list (one lane; the batched form is flush_deferred's)
+// a side entry {eps bits, offset} as one 8-byte global load
+__device__ __forceinline__ uint2 side_load(const uint2* side, int i) {
+  const unsigned long long w = ((__attribute__((address_space(1))) const unsigned long long*)side)[i];
+  return make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+}
+__device__ __forceinline__ void redo_push(const SlotQueues& sq, uint32_t id, uint32_t bin) {
+  volatile LdsWord* df = sq.defer;
+  GlbU64* redo = (GlbU64*)(uintptr_t)((unsigned long long)df[4] | ((unsigned long long)df[5] << 32));
+  const unsigned long long cap = (unsigned long long)df[6] | ((unsigned long long)df[7] << 32);
+  const unsigned long long pos = __hip_atomic_fetch_add(redo, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (pos < cap) redo[2ull + pos] = (unsigned long long)id | ((unsigned long long)bin << 32);
+  else redo[1] = 1ull;
+}
 __device__ __forceinline__ int slot_class(int cnt) {   // cnt in 1..kLongest
   return cnt <= 4 ? 0 : (cnt <= 12 ? (cnt - 3) >> 1 : (cnt <= 16 ? 5 : 6));
 }
@@ -1018,9 +1083,32 @@ __device__ __forceinline__ void flush_deferred(const D& d, uint32_t* __restrict_
 #pragma unroll 1
   for (uint32_t base = 0; base < n; base += 64u) {
     const bool have = base + (uint32_t)lane < n;
-    const uint32_t e = have ? df[4u + base + (uint32_t)lane] : 0u;
+    const uint32_t e = have ? df[(uint32_t)kDeferHead + base + (uint32_t)lane] : 0u;
     const int line = (int)(e & 255u), jr = (int)((e >> 8) & 255u), ir = (int)((e >> 16) & 255u);
     bool hit = false;
+    const uint2* side = defer_side(sq);
+    if (side) {   // (wave-uniform) lines formed from the rays' words: those with eps > 0 are decided only where every line within eps agrees
+      uint2 se = make_uint2(0u, 0u);
+      if (have) se = side_load(side, line);
+      const float e = __uint_as_float(se.x);
+      int res = 0;
+      if (have) res = e > 0.f ? decide_approx(d, rowt, colx, lines + 6 * line, ir, jr, e) : (int)decide_exact(d, rowt, colx, lines + 6 * line, ir, jr);
+      hit = res == 1;
+      const unsigned long long rm = __ballot(res == 2);
+      if (rm) {   // one atomic for the wave's entries
+        GlbU64* redo = (GlbU64*)(uintptr_t)((unsigned long long)df[4] | ((unsigned long long)df[5] << 32));
+        const unsigned long long cap = (unsigned long long)df[6] | ((unsigned long long)df[7] << 32);
+        unsigned long long pos = 0ull;
+        if (lane == 0) pos = __hip_atomic_fetch_add(redo, (unsigned long long)__popcll(rm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t plo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pos), phi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(pos >> 32));
+        if (res == 2) {
+          const unsigned long long at = (((unsigned long long)phi << 32) | plo) +
+                                        __builtin_amdgcn_mbcnt_hi((uint32_t)(rm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rm, 0u));
+          if (at < cap) redo[2ull + at] = (unsigned long long)se.y | ((unsigned long long)(uint32_t)(ir * d.n_phi + jr) << 32);
+          else redo[1] = 1ull;
+        }
+      }
+    } else
     if (have) hit = decide_exact(d, rowt, colx, lines + 6 * line, ir, jr);
     if (hit) __hip_atomic_fetch_add(reinterpret_cast<LdsU32*>((__attribute__((address_space(3))) void*)hist) + (ir * d.n_phi + jr), 1u,
                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1474,6 +1562,18 @@ __device__ __forceinline__ void consume_cols(const D& d, uint32_t* __restrict__ 
     const double Mv = fabs(e0) + (fabs(e1) + fabs(e2)), Mf = fabs(f0) + (fabs(f1) + fabs(f2));
     const double Sg = fma(Md, fma(Md, Mf, Mn * Mv), Mn * Mn);
     band32 = Sg >= 1e-6 ? (float)(1.4e-6 * Sg) * 1.000001f + 1e-30f : __builtin_inff();
+    const uint2* side = defer_side(sq);
+    if (side) {   // (wave-uniform) a unit of lines formed from the rays' words: the ray's own line lies within eps of this one
+      // What g can change by over the lines within eps (decide_approx has the terms), from the column's magnitudes: with |dot| <= 1.5,
+      // e <= (e / R) Mn (Mn holds R) and D R <= (D^2 + R^2) / 2 <= (Mf + half_w2 + Mn^2) / 2 every term is at most a multiple of
+      // (e / R) Tg, Tg = Mf + Mn Mv + Mn^2 + half_w2; the multiples add up to 10.25, and to less than 11 with every magnitude at
+      // its largest over those lines while e / R <= 1e-3 (beyond that nothing is decided here).  eps holds the reference's own
+      // rounding on the ray's line as well (isx_exit_lines_kernel).
+      const float tg = (float)(fma(Mn, Mn + Mv, Mf) + d.half_w2);
+      const float e = __uint_as_float(side_load(side, line).x);
+      const float er = e * rcp_cull((float)R) * 1.0001f;
+      if (e > 0.f) band32 = er <= 1e-3f ? fmaf(1.001f, band32, (13.8f * er) * tg) : __builtin_inff();
+    }
   }
   typedef __attribute__((address_space(3))) uint32_t LdsU32;
   typedef __attribute__((address_space(3))) unsigned char LdsByte;
@@ -1534,11 +1634,15 @@ __device__ __forceinline__ void consume_cols(const D& d, uint32_t* __restrict__ 
         const uint32_t pos = __hip_atomic_fetch_add(reinterpret_cast<LdsCnt*>(sq.defer), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #endif
         if (pos < (uint32_t)kDeferCap) {
-          ((volatile LdsWord*)sq.defer)[4u + pos] = (uint32_t)line | ((uint32_t)j << 8) | ((uint32_t)ir << 16);
+          ((volatile LdsWord*)sq.defer)[(uint32_t)kDeferHead + pos] = (uint32_t)line | ((uint32_t)j << 8) | ((uint32_t)ir << 16);
         } else {
           int jr = j;
           asm volatile("" : "+v"(jr));
-          hit = decide_exact(d, rowt, colx, src6 + (jr - j), ir, jr);
+          uint2 se = make_uint2(0u, 0u);
+          const uint2* side = defer_side(sq);
+          if (side) se = side_load(side, line + (jr - j));
+          if (__uint_as_float(se.x) > 0.f) redo_push(sq, se.y, (uint32_t)(ir * d.n_phi + jr));   // (no room to put it aside: the ray is traced)
+          else hit = decide_exact(d, rowt, colx, src6 + (jr - j), ir, jr);
         }
         if (t == 0) hit0 = hit; else hit1 = hit;
       }
@@ -5024,7 +5128,11 @@ isx_bin_cols_kernel(const DetGrid d_arg, const Work wk) {
   LdsInt* mrk = sq.head + 8;
   sq.defer = (LdsWord*)(mrk + 64);
   if (lane < 16) sq.tail[lane] = 0;
-  if (lane == 0) sq.defer[0] = 0u;
+  if (lane == 0) {
+    const unsigned long long rp = (unsigned long long)(uintptr_t)d_arg.log_count, rcap = d_arg.log_cap;
+    sq.defer[0] = 0u; sq.defer[1] = 0u; sq.defer[2] = 0u; sq.defer[3] = 0u;
+    sq.defer[4] = (uint32_t)rp; sq.defer[5] = (uint32_t)(rp >> 32); sq.defer[6] = (uint32_t)rcap; sq.defer[7] = (uint32_t)(rcap >> 32);
+  }
   __syncthreads();
   typedef __attribute__((address_space(3))) DetGrid LdsDetGrid;
   const volatile LdsDetGrid& d = *(const volatile LdsDetGrid*)d_lds;
@@ -5039,10 +5147,17 @@ isx_bin_cols_kernel(const DetGrid d_arg, const Work wk) {
     unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)unit);
     const uint32_t region = unit >> ushift;
     if (region >= n_regions) break;
-    const uint32_t r_lines = (uint32_t)__builtin_amdgcn_readfirstlane((int)d_arg.rec_counts[region]);
+    // (bit 31 of a region's count: isx_exit_lines_kernel wrote it -- its lines have a side entry each)
+    const uint32_t r_word = (uint32_t)__builtin_amdgcn_readfirstlane((int)d_arg.rec_counts[region]);
+    const uint32_t r_lines = r_word & 0x7fffffffu;
     const uint32_t q_first = (unit & ((1u << ushift) - 1u)) * (kRegion >> ushift);
     const uint32_t n_lines = r_lines < q_first + (kRegion >> ushift) ? r_lines : q_first + (kRegion >> ushift);
     const double* lines = d_arg.rec_lines + 6ull * ((uint64_t)region * kRegion + q_first);   // the unit's lines
+    {   // the unit's side entries, where the walks and flush_deferred look for them (every walk of the wave's last unit has ended)
+      const unsigned long long sp = (r_word >> 31) ? (unsigned long long)(uintptr_t)(reinterpret_cast<const uint2*>(d_arg.log_rec) + ((uint64_t)region * kRegion + q_first)) : 0ull;
+      if (lane == 0) { sq.defer[1] = (uint32_t)sp; sq.defer[2] = (uint32_t)(sp >> 32); }
+      __builtin_amdgcn_wave_barrier();
+    }
     struct { int n_phi, n_theta; double half_w2, portz, R; const double* table; } dcol;
     dcol.n_phi = d.n_phi; dcol.n_theta = d.n_theta; dcol.half_w2 = d.half_w2; dcol.portz = d_arg.portz; dcol.R = d_arg.R; dcol.table = d.table;
 #pragma unroll 1
@@ -5134,6 +5249,7 @@ isx_bin_cols_kernel(const DetGrid d_arg, const Work wk) {
 // Runs ahead of isx_trace_assist_list_kernel on the same chunk: every ray of [first, first + n) is walked over its Philox words
 // (fate_block, isx_device.hpp) until it is settled as absorbed -- launched, absorbed and wall_hits of the census are all it adds
 // to the result -- or left to the trace kernel: its 32-bit offset is appended to the chunk's list, ctr[Q_LIST] counts them.
+// (FateScan::pairs: {offset, j} with j the interaction the scan stopped at, 8 bytes, for isx_exit_lines_kernel -- DESIGN.md section 4.2f.)
 // Persistent waves, lane = ray, integer arithmetic only.  A trip is kScanBlocks Philox blocks (two interactions each) per lane,
 // evaluated for every lane without a branch: fate_block states the rule on lane masks, and the wave decides once per trip whether
 // any of its rays can meet one of the two bounds on j within the trip (then fate_block<true>, else fate_block<false>).  A lane
@@ -5159,8 +5275,8 @@ constexpr uint32_t kScanBatch = ISX_SCAN_BATCH;   // offsets a wave collects bef
 struct FateScan {
   FateConsts f;
   uint64_t seed, first;
-  uint32_t n, pad;               // rays of the chunk (< 2^31)
-  uint32_t* list;                // [n] at least
+  uint32_t n, pairs;             // rays of the chunk (< 2^31); pairs: the list holds {offset, j} (8 bytes) for isx_exit_lines_kernel
+  uint32_t* list;                // [n] at least ([2 n] with pairs)
   uint32_t* ctr;                 // the launch's counter block (Work::ctr)
   unsigned long long* stats;     // Work::stats
 };
@@ -5168,11 +5284,14 @@ extern "C" __global__ void __launch_bounds__(kScanBlock)
 isx_fate_scan_kernel(const FateScan a) {
   __shared__ unsigned long long s_cen[2];   // settled rays, their wall hits
   __shared__ uint32_t s_batch[kScanBlock / 64][kScanBatch + 64];
+  __shared__ uint16_t s_stop[kScanBlock / 64][kScanBatch + 64];   // the interaction each of them stopped at (j <= J_CAP)
   const int tid = threadIdx.x, lane = tid & 63;
   if (tid < 2) s_cen[tid] = 0ull;
   __syncthreads();
   typedef __attribute__((address_space(3))) uint32_t LdsU32;
+  typedef __attribute__((address_space(3))) uint16_t LdsU16;
   volatile LdsU32* batch = (volatile LdsU32*)s_batch[__builtin_amdgcn_readfirstlane(tid >> 6)];
+  volatile LdsU16* stop = (volatile LdsU16*)s_stop[__builtin_amdgcn_readfirstlane(tid >> 6)];
   uint32_t n_batch = 0;     // per wave: offsets in the batch
   // append the wave's batch to the list: base + i < rays left over so far <= n, inside the list
   auto flush_batch = [&]() {
@@ -5180,7 +5299,12 @@ isx_fate_scan_kernel(const FateScan a) {
     if (lane == 0) base = atomicAdd(a.ctr + Q_LIST, n_batch);
     base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
     __builtin_amdgcn_wave_barrier();
-    for (uint32_t i = (uint32_t)lane; i < n_batch; i += 64u) a.list[base + i] = batch[i];
+    if (a.pairs) {   // (base + i < n: inside the 2 n words of the list)
+      uint2* pl = reinterpret_cast<uint2*>(a.list);
+      for (uint32_t i = (uint32_t)lane; i < n_batch; i += 64u) pl[base + i] = make_uint2(batch[i], (uint32_t)stop[i]);
+    } else {
+      for (uint32_t i = (uint32_t)lane; i < n_batch; i += 64u) a.list[base + i] = batch[i];
+    }
     __builtin_amdgcn_wave_barrier();
     n_batch = 0;
   };
@@ -5256,6 +5380,7 @@ isx_fate_scan_kernel(const FateScan a) {
       if (__builtin_amdgcn_inverse_ballot_w64(lm)) {   // (n_batch < kScanBatch here, rank < 64: inside the wave's block)
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(lm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lm, 0u));
         batch[n_batch + rank] = c0 - (uint32_t)first;   // the ray's offset in the chunk
+        stop[n_batch + rank] = (uint16_t)(2u * jb + (__builtin_amdgcn_inverse_ballot_w64(odd) ? 1u : 0u));   // ... and where it stopped
       }
       n_batch += (uint32_t)__popcll(lm);
       if (n_batch >= kScanBatch) flush_batch();
@@ -5288,6 +5413,247 @@ isx_fate_diag_kernel(const FateConsts f, uint64_t seed, uint64_t first, uint64_t
   const unsigned long long bit = 1ull << (threadIdx.x & 63u);
   fate[i] = (absorbed & bit) ? ST_ABSORBED : FATE_TRACE;
   order[i] = (int32_t)(2u * jb + ((odd & bit) ? 1u : 0u));
+}
+
+// ------------------------------------------------------------------ exit lines from the words
+// Runs between the fate scan and isx_trace_assist_list_kernel.  An entry {offset, j} of the scan's list is a ray that has
+// provably reached interaction j on the mirror patch.  If word wa_j sends it into the port opening by more than the scan's margin
+// and the straight line from there provably clears the rim and the outer sphere, the ray's exit line is r_in s_{j-1} -> r_in s_j
+// up to a drift that is bounded per ray: the line is formed here, with the functions the trace kernels use, and goes to the
+// region workspace with its bound (eps) and the ray's offset in a side entry.  Bit 31 of a region's count marks the regions this
+// kernel wrote.  Every other ray goes to list B (batched as the scan batches its list), which the trace kernel takes.
+// Accept tests (p', V' the approximate point and direction; eps_p, eps_V their bounds):
+//   rules 1-4 of fate_block at j, rule 4 by the mirror image of its margin: wa_j >= W_leave + MARG
+//   chord |r_in s_j - p'| >= kExitChord r_in;  p'.V' < 0;  V'.z <= -kExitMinDz
+//   on the planes z = zcut_in (1 - 1e-6), zcut_out, zcut_out (1 + 1e-6) the line lies inside the rim cone (the middle one: inside
+//   the outer ball) by more than its own deviation there: the solid cone is convex, so no root of the cone lies between the
+//   planes, and a root outside them fails `rr in [rin2, rout2]` by 2e-6; the far root of the outer sphere lies below zcut_out
+//   the generic search on (p', V') ends on the box, and its point lies below portz by more than its deviation
+constexpr int kExitBlock = 256;
+constexpr uint32_t kExitBatch = 512;
+constexpr double kExitChord = 0.05, kExitMinDz = 0.02;
+constexpr double kExitStep = 32.0 * 0x1.0p-53;   // |delta| grows by at most this much (x r_in^2) per S1' step (section 4.2d)
+struct ExitScan {
+  Geom g;
+  uint64_t seed, first;
+  const uint2* list_a;           // the scan's list: {offset, j}, ctr[Q_LIST] entries
+  uint32_t* list_b;              // the rays left to the trace kernel, ctr[Q_LISTB] counts them
+  uint32_t* ctr;                 // the launch's counter block
+  unsigned long long* stats;     // Work::stats
+  unsigned long long* totals;    // [3] accepted, list B, redo entries since isx_init (isx_exit_scan_counts)
+  double* rec_lines;             // the region workspace, as DetGrid has it
+  uint32_t* rec_counts;
+  uint2* side;                   // per slot of the workspace: {eps as binary32 bits, the ray's offset}
+  unsigned long long* redo;      // the chunk's redo list: [0] entries, [1] overflow -- zeroed here
+  uint32_t rho_thr, never, w_exit, j_cap;   // FateConsts' words; w_exit = ceil(W_leave + MARG)
+  int limit, pad;
+  double reach;                  // 2.1 (1.001 r_in + |portz| + R + rho_d): what a direction error moves the line by near the detectors
+  double portz, det_R, half_w2;  // DetGrid's
+  double eps_scale;              // test option exit_eps_scale (>= 1)
+};
+extern "C" __global__ void __launch_bounds__(kExitBlock)
+isx_exit_lines_kernel(const ExitScan a) {
+  __shared__ unsigned long long s_wall;
+  __shared__ uint32_t s_batch[kExitBlock / 64][kExitBatch + 64];
+  const int tid = threadIdx.x, lane = tid & 63;
+  if (tid == 0) s_wall = 0ull;
+  if (blockIdx.x == 0 && tid == 0) { a.redo[0] = 0ull; a.redo[1] = 0ull; }
+  __syncthreads();
+  typedef __attribute__((address_space(3))) uint32_t LdsU32;
+  volatile LdsU32* batch = (volatile LdsU32*)s_batch[__builtin_amdgcn_readfirstlane(tid >> 6)];
+  uint32_t n_batch = 0, n_left = 0;   // per wave: offsets in the batch, rays sent to list B
+  auto flush_batch = [&]() {   // (base + i < entries of list A <= rays of the chunk: inside list B)
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(a.ctr + Q_LISTB, n_batch);
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    __builtin_amdgcn_wave_barrier();
+    for (uint32_t i = (uint32_t)lane; i < n_batch; i += 64u) a.list_b[base + i] = batch[i];
+    __builtin_amdgcn_wave_barrier();
+    n_left += n_batch;
+    n_batch = 0;
+  };
+  const Hot h = make_hot(a.g);
+  // the pencil's first strike, as the trace kernels find it
+  V3 q0;
+  bool q0_ok;
+  {
+    V3 s0, d0;
+    s0.x = a.g.src[0]; s0.y = a.g.src[1]; s0.z = a.g.src[2];
+    d0.x = a.g.dir0[0]; d0.y = a.g.dir0[1]; d0.z = a.g.dir0[2];
+    q0 = s0;
+    q0_ok = next_hit_s1<true>(h, a.g, s0, d0, K_NONE, q0);
+  }
+  const double rin = a.g.r_in, Hb = a.g.H;
+  const double zA = a.g.zcut_in * (1.0 - 1e-6), zB = a.g.zcut_out, zC = a.g.zcut_out * (1.0 + 1e-6);
+  const double tanc = sqrt(a.g.k2);
+  const double rhoA = tanc * fabs(zA), rhoB = sqrt(fmax(a.g.rout2 - zB * zB, 0.0)) * (1.0 - 1e-6), rhoC = tanc * fabs(zC);
+  const uint32_t n_a = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.ctr[Q_LIST]);
+  const uint32_t stride = (uint32_t)(kExitBlock / 64) * gridDim.x * 64u;
+  uint32_t reg_id = 0xffffffffu, reg_slot = 0, reg_left = 0;
+  uint32_t n_wall = 0;      // per lane (an entry adds at most J_CAP + 1, a lane sees at most 2^26 / 64 entries)
+  uint32_t n_acc = 0;       // per wave
+  for (uint32_t base = ((uint32_t)blockIdx.x * (uint32_t)(kExitBlock / 64) + (uint32_t)(tid >> 6)) * 64u; base < n_a; base += stride) {
+    const uint32_t k = base + (uint32_t)lane;
+    const bool have = k < n_a;
+    uint2 ent = make_uint2(0u, 0u);
+    if (have) ent = a.list_a[k];
+    const uint32_t off = ent.x, j = ent.y;
+    bool acc = false;
+    V3 P, V;
+    P.x = P.y = P.z = V.x = V.y = V.z = 0.0;
+    float eps32 = 0.f;
+    if (have) {
+      const uint64_t ray = a.first + (uint64_t)off;
+      const bool odd = (j & 1u) != 0u;
+      uint32_t w[4];
+      draw_block(a.seed, ray, j >> 1, 0u, w);
+      const uint32_t wa = odd ? w[2] : w[0], wb = odd ? w[3] : w[1];
+      bool ok = q0_ok && j < a.j_cap && (a.never != 0u || wb < a.rho_thr) && (int)j + 2 <= a.limit && wa >= a.w_exit;
+      if (ok) {
+        // r_in s_{j-1}, the point the emission of interaction j - 1 aimed at (interact_chord's expressions), and the length of
+        // that emission's chord, r_in |s_{j-1} - s_{j-2}|: the drift of |p| reaches the point through it
+        auto wall_point = [&](uint32_t pa, uint32_t pb) {
+          const double zz = sphere_z(pa);
+          const double s2 = sqrt_unit(fma(-zz, zz, 1.0));
+          double sf, cf;
+          circle_point_psi(fma((double)pb, h.psi_k1, h.psi_k0), cf, sf);
+          const double rxy = rin * s2;
+          V3 t;
+          t.x = rxy * cf; t.y = rxy * sf; t.z = rin * zz;
+          return t;
+        };
+        V3 p = q0;
+        double prev2 = rin * rin;   // (j = 0: the point is the first strike itself)
+        if (j != 0u) {
+          uint32_t w2[4] = {0u, 0u, 0u, 0u};
+          if (j >= 2u || !odd) draw_block(a.seed, ray, (j >> 1) - 1u, 0u, w2);   // (j = 1: block 0 holds both)
+          p = odd ? wall_point(w[0], w[1]) : wall_point(w2[2], w2[3]);
+          V3 pp = q0;
+          if (j >= 2u) pp = odd ? wall_point(w2[2], w2[3]) : wall_point(w2[0], w2[1]);
+          pp.x = p.x - pp.x; pp.y = p.y - pp.y; pp.z = p.z - pp.z;
+          prev2 = dot3(pp, pp);
+          ok = prev2 >= (kExitChord * kExitChord) * (rin * rin);
+        }
+        // the emission of interaction j (interact<LEAN>'s expressions), then what leaves rule S1' gets: a unit direction
+        {
+          const double zs = sphere_z(wa);
+          const double rs = sqrt_unit(fma(-zs, zs, 1.0));
+          double sf, cf;
+          circle_point_psi(fma((double)wb, h.psi_k1, h.psi_k0), cf, sf);
+          const double Rrs = rin * rs;
+          V.x = fma(Rrs, cf, -p.x); V.y = fma(Rrs, sf, -p.y); V.z = fma(rin, zs, -p.z);
+        }
+        const double ch2 = dot3(V, V);
+        ok = ok && ch2 >= (kExitChord * kExitChord) * (rin * rin);
+        const double chord = sqrt(ch2);
+        unit_dir(V);
+        ok = ok && dot3(p, V) < -1e-3 * rin && V.z <= -kExitMinDz;
+        if (ok) {
+          // the bounds: the point (drift of |p|^2 over j + 2 steps, divided by the length of the chord that led to it -- known to
+          // 1e-6 of the floor, since the chord's own start lies within the scan's bound of 130 words of r_in s_{j-2}), the direction
+          const double eps_p = fma(((double)(j + 2u) * kExitStep + 4e-15) * (rin * rin), 1.001 / sqrt(prev2), 1e-14 * rin);
+          const double eps_V = fma(2.1, eps_p / chord, 2e-14);
+          const double iz = 1.0 / V.z;
+          // a plane z = zp: the line's point there lies within `rho` of the axis by more than 2.5 (eps_p + t eps_V) / |V.z| + 1e-9 rho
+          auto inside = [&](double zp, double rho) {
+            const double t = (zp - p.z) * iz;
+            const double x = fma(t, V.x, p.x), y = fma(t, V.y, p.y);
+            const double lim = rho * (1.0 - 1e-9) - 2.5 * fma(t, eps_V, eps_p) * (-iz);
+            return t > 0.0 && lim > 0.0 && fma(x, x, y * y) < lim * lim;
+          };
+          ok = inside(zA, rhoA) && inside(zB, rhoB) && inside(zC, rhoC);
+          if (ok) {
+            const int kind = next_hit_generic(a.g, p, V, K_INNER, P);
+            const double eps_box = 2.5 * fma(4.0 * Hb, eps_V, eps_p) + 1e-9 * Hb;
+            ok = kind == K_BOX && P.z < a.portz - eps_box;
+            // ... and what tier 1 of the binning kernel needs on top of its own rounding band: the reference's rounding on the ray's
+            // line, 1e-13 S_P in units of g with S_P <= 4 (|P - O|^2 + R^2) + half_w2, as a length: tier 1 widens by 13.8 (eps / R) Tg, Tg >= R^2
+            const double wz = P.z - a.portz;
+            const double eps_ref = 1e-14 * fma(4.0, fma(P.x, P.x, fma(P.y, P.y, fma(wz, wz, a.det_R * a.det_R))), a.half_w2) / a.det_R;
+            const double eps_line = (eps_p + a.reach * eps_V + 4e-15 * Hb + eps_ref) * a.eps_scale;
+            eps32 = (float)eps_line * 1.0001f + 1e-30f;
+          }
+        }
+      }
+      acc = ok;
+    }
+    // ---- the accepted lines: into the wave's region, as the assist wave of the trace kernel writes its own
+    const unsigned long long m = __ballot(acc);
+    if (m) {
+      const uint32_t cnt = (uint32_t)__popcll(m);
+      if (cnt > reg_left) {   // close the open region, reserve the next one
+        if (lane == 0 && reg_id != 0xffffffffu) a.rec_counts[reg_id] = (kRegion - reg_left) | 0x80000000u;
+        uint32_t id = 0;
+        if (lane == 0) id = atomicAdd(a.ctr + Q_REGIONS, 1u);
+        reg_id = (uint32_t)__builtin_amdgcn_readfirstlane((int)id);
+        reg_slot = 0; reg_left = kRegion;
+      }
+      if (acc) {
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        const uint64_t slot = (uint64_t)reg_id * kRegion + (uint64_t)(reg_slot + rank);
+        double2* dst = reinterpret_cast<double2*>(a.rec_lines + 6ull * slot);
+        dst[0] = make_double2(P.x, P.y); dst[1] = make_double2(P.z, V.x); dst[2] = make_double2(V.y, V.z);
+        a.side[slot] = make_uint2(__float_as_uint(eps32), off);
+        n_wall += j + 1u;
+      }
+      reg_slot += cnt; reg_left -= cnt;
+      n_acc += cnt;
+    }
+    // ---- the others: to list B
+    const unsigned long long lm = __ballot(have && !acc);
+    if (lm) {
+      if (have && !acc) {   // (n_batch < kExitBatch here, rank < 64: inside the wave's block)
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(lm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lm, 0u));
+        batch[n_batch + rank] = off;
+      }
+      n_batch += (uint32_t)__popcll(lm);
+      if (n_batch >= kExitBatch) flush_batch();
+    }
+  }
+  if (n_batch) flush_batch();
+  if (lane == 0 && reg_id != 0xffffffffu) a.rec_counts[reg_id] = (kRegion - reg_left) | 0x80000000u;
+  atomicAdd(&s_wall, (unsigned long long)n_wall);
+  if (lane == 0) {
+    if (n_acc) {   // launched, exited, counted below the port plane
+      global_add_u64(a.stats + 0, (unsigned long long)n_acc); global_add_u64(a.stats + 1, (unsigned long long)n_acc);
+      global_add_u64(a.stats + 2, (unsigned long long)n_acc); global_add_u64(a.totals + 0, (unsigned long long)n_acc);
+    }
+    if (n_left) global_add_u64(a.totals + 1, (unsigned long long)n_left);
+  }
+  __syncthreads();
+  if (tid == 0 && s_wall) global_add_u64(a.stats + 6, s_wall);
+}
+
+// The candidates the binning kernel left undecided on an approximate line (flush_deferred, consume_cols): the ray is traced from
+// interaction 0 as the end-state kernels trace it, and the reference's test on its own exit line decides the listed bin.
+// Runs behind the binning kernel; d.log_count is the chunk's redo list, wk the launch's Work.
+extern "C" __global__ void __launch_bounds__(256)
+isx_redo_kernel(const Geom g, const DetGrid d, const Work wk, unsigned long long* __restrict__ totals) {
+  const unsigned long long held = d.log_count[0];
+  const unsigned long long n = held < d.log_cap ? held : d.log_cap;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (held) global_add_u64(totals + 2, held);
+    if (d.log_count[1] != 0ull || held > d.log_cap) global_add_u64(wk.stats + 7, 1ull);   // entries were lost: the launch is reported as failed
+  }
+  const Hot h = make_hot(g);
+  unsigned long long hits = 0ull;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * blockDim.x) {
+    const unsigned long long e = d.log_count[2ull + i];
+    const uint32_t off = (uint32_t)e, bin = (uint32_t)(e >> 32);
+    Ray r;
+    ray_start(g, r, off);
+    int st;
+    for (;;) {
+      st = ray_step<false>(h, g, r, wk.seed, wk.first);
+      if (st != 0) break;
+    }
+    if (st == ST_EXITED && r.p.z < d.portz && bin < (uint32_t)d.nbins &&
+        check_intersection(d.table + 6 * (size_t)bin, d.half_w2, r.p, r.v)) {
+      global_add_u64(wk.hist + bin, 1ull);
+      ++hits;
+    }
+  }
+  if (hits) global_add_u64(wk.stats + 5, hits);
 }
 
 // ------------------------------------------------------------------ per-ray end states (parity tests)

@@ -228,6 +228,15 @@ int isx_last_kernel_ms(double* single_ms, double* trace_ms, double* bin_ms);
  *                  (DESIGN.md 4.2d).  Automatic: chunks of at least 1e7 rays whose expected settled share
  *                  (1 - rho) / ((1 - rho) + port area fraction) is at least 0.5.  Anything else takes the kernels it took before,
  *                  also with 1.  WORKSPACE: 4 B per ray of the largest chunk, kept until isx_shutdown()
+ *   "exit_scan"    changes no result: -1 (default) automatic, 1 on wherever eligible, 0 off.  Behind the fate scan (its
+ *                  eligibility; "exit_scan" 1 brings the scan with it unless "fate_scan" is 0), with the last-segment hit line and
+ *                  the column-slot binning kernel: isx_exit_lines_kernel forms the exit line of every ray that leaves cleanly
+ *                  through the port from the ray's Philox words, with a proven bound on its deviation; the trace kernel runs on
+ *                  the rest; the binning kernel decides a candidate of such a line only where every line within the bound gives
+ *                  the same answer, and isx_redo_kernel traces the few rays that are left.  Automatic: the fate
+ *                  scan's rule.  Anything else takes the kernels it took before, also with 1.  WORKSPACE: 24 B per ray of the
+ *                  largest chunk and 8 B per exit-line slot, kept until isx_shutdown().  "exit_eps_scale" (tests; >= 1, default 1)
+ *                  multiplies every bound, so that a test-sized run reaches the redo kernel
  *   "call_overlap"  a SCHEDULING option, it changes no result: -1 (default) automatic, 1 on wherever eligible, 0 off.  Eligible are
  *                  isx_fluxmap_device calls that take the two-kernel flux pipeline with explicit bounces, with or without the fate
  *                  scan, and not with "overlap" > 1.  The chunk's counter zeroing, fate scan, trace kernel and
@@ -270,6 +279,9 @@ int isx_trace_endstates(const isx_config* cfg, uint64_t n_rays, uint64_t seed, u
 int isx_fate_scan(const isx_config* cfg, uint64_t n_rays, uint64_t seed, uint64_t first_ray, int32_t* fate, int32_t* order);
 /* Chunks that took the scan since isx_init (one isx_fate_scan_kernel launch each): shows which path a call took (tests). */
 int isx_fate_scan_launches(uint64_t* launches);
+/* The "exit_scan" path since isx_init (tests; any pointer may be NULL): rays whose exit line isx_exit_lines_kernel formed from
+ * their words, rays it left to the trace kernel, and candidates the binning kernel left to isx_redo_kernel.  Synchronises. */
+int isx_exit_scan_counts(uint64_t* accepted, uint64_t* list_b, uint64_t* redo);
 
 /*
  * Physical-disc sweep (integratingSphereDetectorSweep.C:31-105,145-172): n_disc
