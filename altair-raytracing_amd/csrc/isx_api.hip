@@ -16,6 +16,7 @@
 #include <map>
 #include <new>
 #include <tuple>
+#include <variant>
 #include <vector>
 
 using namespace isx;
@@ -693,7 +694,7 @@ int check_scene_call(const isx_config* c, const isx_scene_spec* s, bool grid) {
 
 // isx_scene_response: the device array of the call is [ISX_RESPONSE_FATES][B] (SceneMap below; the scene travels as SceneSink)
 static_assert(ISX_RESPONSE_FATES == kRespFates && kRespBaffle0 == ISX_MAX_WALL_PATCHES + 2 &&
-              kRespPort == kRespBaffle0 + 2 * ISX_MAX_BAFFLES && kRespSuspended == kRespPort + 2, "isx.h and resp_record's slots");
+              kRespPort == kRespBaffle0 + 2 * ISX_MAX_BAFFLES && kRespSuspended == kRespPort + 2, "isx.h and MapEnd::fate()'s slots");
 // isx.h: the limits of a response spec
 int check_response_spec(const isx_response_spec* s) {
   if (s->struct_size != (uint32_t)sizeof(isx_response_spec) || s->reserved0 != 0u) return ISX_ERR_BAD_CONFIG;
@@ -709,7 +710,7 @@ size_t response_bins(const isx_response_spec& s) { return (size_t)s.n[0] * s.n[1
 // isx_scene_view: the device arrays of the call are the map [n_v][n_u] and the four words of isx_view_counts
 static_assert(sizeof(isx_view_counts) == kViewCounters * sizeof(uint64_t) && offsetof(isx_view_counts, binned) == 8 * kViewBinned &&
               offsetof(isx_view_counts, outside) == 8 * kViewOutside && offsetof(isx_view_counts, behind) == 8 * kViewBehind &&
-              offsetof(isx_view_counts, direct) == 8 * kViewDirect, "isx.h and view_record's counters");
+              offsetof(isx_view_counts, direct) == 8 * kViewDirect, "isx.h and ViewMap's counters");
 static_assert(sizeof(isx_view_spec) == 104, "isx.h: isx_view_spec");
 // isx.h: the limits of a view spec; n_patches < 0: no scene is at hand (the host-side helpers), the patch index is not looked at
 int check_view_spec(const isx_view_spec* s, int n_patches) {
@@ -732,7 +733,7 @@ static_assert(sizeof(isx_patch_field_counts) == kFieldCounters * sizeof(uint64_t
               offsetof(isx_patch_field_counts, pos_outside) == 8 * kFieldPosOutside &&
               offsetof(isx_patch_field_counts, dir_outside) == 8 * kFieldDirOutside &&
               offsetof(isx_patch_field_counts, behind) == 8 * kFieldBehind && offsetof(isx_patch_field_counts, direct) == 8 * kFieldDirect,
-              "isx.h and field_record's counters");
+              "isx.h and PatchFieldMap's counters");
 static_assert(sizeof(isx_patch_field_spec) == 120, "isx.h: isx_patch_field_spec");
 // isx.h: the limits of a patch-field spec; n_patches < 0: no scene is at hand (the host-side helper), the patch index is not looked at
 int check_patch_field_spec(const isx_patch_field_spec* s, int n_patches) {
@@ -758,7 +759,7 @@ size_t patch_field_bins(const isx_patch_field_spec& s) { return (size_t)s.n_x * 
 // isx_scene_order_hist: the device arrays of the call are the histograms [ISX_RESPONSE_FATES][n_orders] and the 21 words of
 // isx_scene_order_counts
 static_assert(sizeof(isx_scene_order_spec) == 16 && sizeof(isx_scene_order_counts) == kRespFates * sizeof(uint64_t),
-              "isx.h: isx_scene_order_spec, and sorder_record's overflow counters");
+              "isx.h: isx_scene_order_spec, and OrderMap's overflow counters");
 // isx.h: the limits of a scene order spec
 int check_scene_order_spec(const isx_scene_order_spec* s) {
   if (s->struct_size != (uint32_t)sizeof(isx_scene_order_spec) || s->reserved0 != 0u || s->reserved1 != 0) return ISX_ERR_BAD_CONFIG;
@@ -768,7 +769,7 @@ int check_scene_order_spec(const isx_scene_order_spec* s) {
 // isx_scene_path_hist: the device arrays of the call are the histograms [ISX_RESPONSE_FATES][n_bins] and the 42 words of
 // isx_scene_path_counts
 static_assert(sizeof(isx_scene_path_spec) == 24 && sizeof(isx_scene_path_counts) == 2 * kRespFates * sizeof(uint64_t),
-              "isx.h: isx_scene_path_spec, and spath_record's overflow counters and checksums");
+              "isx.h: isx_scene_path_spec, and PathMap's overflow counters and checksums");
 // isx.h: the limits of a scene path spec
 int check_scene_path_spec(const isx_scene_path_spec* s) {
   if (s->struct_size != (uint32_t)sizeof(isx_scene_path_spec) || s->reserved0 != 0u || s->reserved1 != 0) return ISX_ERR_BAD_CONFIG;
@@ -994,7 +995,9 @@ enum Route { ROUTE_FUSED, ROUTE_ASSIST, ROUTE_FLUX_PIPE, ROUTE_EXIT_PIPE, ROUTE_
 typedef void (*BinFn)(const DetGrid, const Work);
 // A trace kernel: its address and what it takes behind (Geom, DetGrid, Work).  The constructors read the tail off the kernel's
 // own signature, so a kernel cannot be paired with the wrong arguments; launch_trace() is the one place that passes them.
-enum Tail { TAIL_NONE, TAIL_PATCH, TAIL_BEAM, TAIL_LIST, TAIL_BAFFLE, TAIL_SCENE, TAIL_RESPONSE, TAIL_VIEW, TAIL_FIELD, TAIL_SORDER, TAIL_SPATH };
+enum Tail { TAIL_NONE, TAIL_PATCH, TAIL_BEAM, TAIL_LIST, TAIL_BAFFLE, TAIL_SCENE, TAIL_SCENE_MAP };
+// the sink of a scene map as its kernel takes it (isx_kernels.hpp: the Arg of the map's policy)
+typedef std::variant<std::monostate, RespSink, ViewSink, PatchFieldSink, SOrderSink, SPathSink> MapSink;
 struct TraceKernel {
   const void* fn = nullptr;
   Tail tail = TAIL_NONE;
@@ -1006,11 +1009,8 @@ struct TraceKernel {
   TraceKernel(Fn<FateList> f) : fn((const void*)f), tail(TAIL_LIST) {}
   TraceKernel(Fn<BaffleTab> f) : fn((const void*)f), tail(TAIL_BAFFLE) {}
   TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab> f) : fn((const void*)f), tail(TAIL_SCENE) {}
-  TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab, RespSink> f) : fn((const void*)f), tail(TAIL_RESPONSE) {}
-  TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab, ViewSink> f) : fn((const void*)f), tail(TAIL_VIEW) {}
-  TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab, PatchFieldSink> f) : fn((const void*)f), tail(TAIL_FIELD) {}
-  TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab, SOrderSink> f) : fn((const void*)f), tail(TAIL_SORDER) {}
-  TraceKernel(Fn<PatchTab, BeamSrc, BaffleTab, SPathSink> f) : fn((const void*)f), tail(TAIL_SPATH) {}
+  template <class Sink> using MapFn = Fn<PatchTab, BeamSrc, BaffleTab, Sink>;   // (Sink: an alternative of MapSink -- Plan::set_map)
+  template <class Sink> TraceKernel(MapFn<Sink> f) : fn((const void*)f), tail(TAIL_SCENE_MAP) {}
 };
 struct Plan {
   Route route = ROUTE_FUSED;
@@ -1041,11 +1041,9 @@ struct Plan {
   PatchTab patch_tab{};         // SINK_PATCH; a scene
   BeamSrc beam{};               // isx_fluxmap_beam; a scene
   BaffleTab baffles{};          // isx_fluxmap_baffle; a scene
-  RespSink resp{};              // isx_scene_response (resp.lds_words: the form of the kernel)
-  ViewSink view{};              // isx_scene_view (view.lds_words: the form)
-  PatchFieldSink field{};       // isx_scene_patch_field (field.lds_words: the form)
-  SOrderSink sorder{};          // isx_scene_order_hist (sorder.lds_orders: the orders kept in LDS)
-  SPathSink spath{};            // isx_scene_path_hist (spath.lds_bins: the bins kept in LDS)
+  MapSink map;                  // the sink of a scene map (its lds_* field: the form of the kernel)
+  // a scene map's kernel and its sink, set together: the struct that is filled is the one the kernel's signature names
+  template <class Sink> Sink& set_map(TraceKernel::MapFn<Sink> f) { fn = f; return map.emplace<Sink>(); }
 };
 
 // The one place a trace kernel is launched: (g, d, w) and the tail its signature names, as hipLaunchKernelGGL would pass them.
@@ -1062,11 +1060,7 @@ void launch_trace(const Plan& p, const TraceKernel& k, int grid, hipStream_t str
     case TAIL_BAFFLE: args[na++] = &p.baffles; break;
     default:   // a scene: its three tables, then the sink of a scene map
       args[na++] = &p.patch_tab; args[na++] = &p.beam; args[na++] = &p.baffles;
-      if (k.tail == TAIL_RESPONSE) args[na++] = &p.resp;
-      else if (k.tail == TAIL_VIEW) args[na++] = &p.view;
-      else if (k.tail == TAIL_FIELD) args[na++] = &p.field;
-      else if (k.tail == TAIL_SORDER) args[na++] = &p.sorder;
-      else if (k.tail == TAIL_SPATH) args[na++] = &p.spath;
+      if (k.tail == TAIL_SCENE_MAP) args[na++] = std::visit([](const auto& sink) -> const void* { return &sink; }, p.map);
   }
   (void)hipLaunchKernel(k.fn, dim3(grid), dim3(p.block), const_cast<void**>(args), p.lds, stream);
 }
@@ -1133,10 +1127,11 @@ void trace_shape(Plan& p, Shape sh, bool assist, int per_cu) {
 // p.lds and the 16-byte-rounded 4 w times the resident count stays within lds_limit -- exactly when w <= room: both roundings are
 // to multiples that cap and cap - p.lds rounded down already are.  So one expression serves the maps that lie in LDS whole or not
 // at all (one unit: the map) and the order histograms (a unit per order: as many orders as fit).  All sums in size_t: a field has
-// up to 2^22 words.  Returns the units that went to LDS; p.lds has their bytes.
-size_t plan_scene_map_lds(Plan& p, TraceKernel fn, uint64_t n, size_t head, size_t unit, size_t units) {
+// up to 2^22 words.  `kept`: the units that went to LDS; p.lds has their bytes.  Returns the kernel's sink, zeroed, to be filled.
+template <class Sink>
+Sink& plan_scene_map_lds(Plan& p, TraceKernel::MapFn<Sink> fn, uint64_t n, size_t head, size_t unit, size_t units, size_t& kept) {
   p.route = ROUTE_ASSIST;
-  p.fn = fn;
+  Sink& sink = p.set_map(fn);
   p.launch_max = std::min(kLaunchMax, S.pipe_chunk);
   // (the kernel is built for five waves per SIMD: 640 threads -- nine tracer waves and the assist wave -- are what two
   //  workgroups of a CU may have, unless assist_block was set)
@@ -1146,9 +1141,9 @@ size_t plan_scene_map_lds(Plan& p, TraceKernel fn, uint64_t n, size_t head, size
   const size_t resident = (size_t)blocks_per_cu(p.fn.fn, p.block, p.lds, kResident);
   const size_t cap = (S.lds_limit / resident) & ~(size_t)2047;
   const size_t room = cap > p.lds ? ((cap - p.lds) & ~(size_t)15) / 4 : 0;
-  const size_t kept = std::min(units, room / unit);
+  kept = std::min(units, room / unit);
   p.lds += (kept * unit * 4 + 15) & ~(size_t)15;
-  return kept;
+  return sink;
 }
 
 // The plan of a scene map and the kernel's sink struct, from the call's SceneMap: per map the kernel, what it keeps behind the
@@ -1159,60 +1154,64 @@ Plan plan_scene_map(const Call& k) {
   // (the scene's compact slots: P + 2 wall classes, two sides per baffle, port / other exits / suspended)
   const size_t slots = (size_t)((sc.patches.n_patches + 2) + 2 * sc.baffles.n_baffles + 3);
   Plan p;
+  size_t kept = 0;
   switch (m.sink) {
-    case SINK_RESPONSE: {   // (isx_kernels.hpp: resp_record) the slots times the bins, whole or not at all; "resp_global"
+    case SINK_RESPONSE: {   // (ResponseMap) the slots times the bins, whole or not at all; "resp_global"
       const isx_response_spec& s = m.response();
       const size_t words = slots * response_bins(s);
-      p.resp.lds_words = (uint32_t)(words * plan_scene_map_lds(p, isx_trace_assist_scene_response_kernel, k.n, 0, words,
-                                                               S.resp_global ? 0 : 1));
-      p.resp.out = m.out;
-      for (int a = 0; a < 4; ++a) p.resp.n[a] = (uint32_t)s.n[a];
-      p.resp.B = (uint32_t)response_bins(s);
+      RespSink& r = plan_scene_map_lds(p, isx_trace_assist_scene_response_kernel, k.n, 0, words, S.resp_global ? 0 : 1, kept);
+      r.lds_words = (uint32_t)(words * kept);
+      r.out = m.out;
+      for (int a = 0; a < 4; ++a) r.n[a] = (uint32_t)s.n[a];
+      r.B = (uint32_t)response_bins(s);
       break;
     }
-    case SINK_VIEW: {   // (view_record) behind the four counters the n_u * n_v words of the map, whole or not at all; "view_global"
+    case SINK_VIEW: {   // (ViewMap) behind the four counters the n_u * n_v words of the map, whole or not at all; "view_global"
       const isx_view_spec& v = m.view();
-      p.view.lds_words = (uint32_t)(view_bins(v) * plan_scene_map_lds(p, isx_trace_assist_scene_view_kernel, k.n,
-                                                                      kViewCounters * sizeof(uint32_t), view_bins(v), S.view_global ? 0 : 1));
-      p.view.out = m.out; p.view.counts = m.tail;
-      for (int i = 0; i < 3; ++i) { p.view.axis[i] = v.axis[i]; p.view.e1[i] = v.e1[i]; p.view.e2[i] = v.e2[i]; }
-      p.view.h = v.half_extent; p.view.fnu = (double)v.n_u; p.view.fnv = (double)v.n_v;
-      p.view.patch = v.patch; p.view.n_u = v.n_u;
+      ViewSink& r = plan_scene_map_lds(p, isx_trace_assist_scene_view_kernel, k.n, kViewCounters * sizeof(uint32_t), view_bins(v),
+                                       S.view_global ? 0 : 1, kept);
+      r.lds_words = (uint32_t)(view_bins(v) * kept);
+      r.out = m.out; r.counts = m.tail;
+      for (int i = 0; i < 3; ++i) { r.axis[i] = v.axis[i]; r.e1[i] = v.e1[i]; r.e2[i] = v.e2[i]; }
+      r.h = v.half_extent; r.fnu = (double)v.n_u; r.fnv = (double)v.n_v;
+      r.patch = v.patch; r.n_u = v.n_u;
       break;
     }
-    case SINK_FIELD: {   // (field_record) behind the frame's doubles and the five counters (kFieldHead bytes) the n_x * n_y * n_u * n_v
+    case SINK_FIELD: {   // (PatchFieldMap) behind the frame's doubles and the five counters (kFieldHead bytes) the n_x * n_y * n_u * n_v
                          // words of the field, whole or not at all; "field_global"
       const isx_patch_field_spec& v = m.field();
-      p.field.lds_words = (uint32_t)(patch_field_bins(v) * plan_scene_map_lds(p, isx_trace_assist_scene_field_kernel, k.n,
-                                                                              kFieldHead, patch_field_bins(v), S.field_global ? 0 : 1));
-      p.field.out = m.out; p.field.counts = m.tail;
-      PatchFieldFrame& f = p.field.f;
+      PatchFieldSink& r = plan_scene_map_lds(p, isx_trace_assist_scene_field_kernel, k.n, kFieldHead, patch_field_bins(v),
+                                             S.field_global ? 0 : 1, kept);
+      r.lds_words = (uint32_t)(patch_field_bins(v) * kept);
+      r.out = m.out; r.counts = m.tail;
+      PatchFieldFrame& f = r.f;
       for (int i = 0; i < 3; ++i) { f.axis[i] = v.axis[i]; f.e1[i] = v.e1[i]; f.e2[i] = v.e2[i]; }
       f.h = v.half_extent; f.s = v.pos_scale; f.inv = 1.0 / k.c->r_in;   // (isx.h: inv is formed once, here)
       f.fnx = (double)v.n_x; f.fny = (double)v.n_y; f.fnu = (double)v.n_u; f.fnv = (double)v.n_v;
-      p.field.patch = v.patch; p.field.n_x = v.n_x; p.field.n_u = v.n_u; p.field.n_v = v.n_v;
+      r.patch = v.patch; r.n_x = v.n_x; r.n_u = v.n_u; r.n_v = v.n_v;
       break;
     }
-    case SINK_SORDER: {   // (sorder_record): behind the overflow counters (kSOrderHead words, always) the first L orders of each
+    case SINK_SORDER: {   // (OrderMap): behind the overflow counters (kSOrderHead words, always) the first L orders of each
                  // slot; the orders from L on take one global u64 add each.  L is as large as fits and at most n_orders;
                  // "sorder_lds_orders" >= 0 caps it (0: every order is global).  L is SOrderSink::lds_orders, nothing else.
       const isx_scene_order_spec& s = m.order();
       size_t orders = (size_t)s.n_orders;
       if (S.sorder_lds_orders >= 0) orders = std::min(orders, (size_t)S.sorder_lds_orders);
-      p.sorder.lds_orders = (uint32_t)plan_scene_map_lds(p, isx_trace_assist_scene_order_kernel, k.n,
-                                                         kSOrderHead * sizeof(uint32_t), slots, orders);
-      p.sorder.out = m.out; p.sorder.overflow = m.tail; p.sorder.n_orders = (uint32_t)s.n_orders;
+      SOrderSink& r = plan_scene_map_lds(p, isx_trace_assist_scene_order_kernel, k.n, kSOrderHead * sizeof(uint32_t), slots, orders, kept);
+      r.lds_orders = (uint32_t)kept;
+      r.out = m.out; r.overflow = m.tail; r.n_orders = (uint32_t)s.n_orders;
       break;
     }
-    default: {   // SINK_SPATH (spath_record): SINK_SORDER's hybrid form.  Behind the side arrays of the two rings, the checksums and the
+    default: {   // SINK_SPATH (PathMap): SINK_SORDER's hybrid form.  Behind the side arrays of the two rings, the checksums and the
                  // overflow counters (kSPathHeadBytes, always) the first B bins of each slot; the bins from B on take one global
                  // u64 add each.  B is as large as fits and at most n_bins; "spath_lds_bins" >= 0 caps it (0: every bin is
                  // global).  B is SPathSink::lds_bins, nothing else.
       const isx_scene_path_spec& s = m.path();
       size_t bins = (size_t)s.n_bins;
       if (S.spath_lds_bins >= 0) bins = std::min(bins, (size_t)S.spath_lds_bins);
-      p.spath.lds_bins = (uint32_t)plan_scene_map_lds(p, isx_trace_assist_scene_path_kernel, k.n, kSPathHeadBytes, slots, bins);
-      p.spath.out = m.out; p.spath.counts = m.tail; p.spath.bin_cm = s.bin_cm; p.spath.n_bins = (uint32_t)s.n_bins;
+      SPathSink& r = plan_scene_map_lds(p, isx_trace_assist_scene_path_kernel, k.n, kSPathHeadBytes, slots, bins, kept);
+      r.lds_bins = (uint32_t)kept;
+      r.out = m.out; r.counts = m.tail; r.bin_cm = s.bin_cm; r.n_bins = (uint32_t)s.n_bins;
     }
   }
   return p;

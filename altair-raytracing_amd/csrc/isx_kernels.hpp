@@ -2429,269 +2429,6 @@ struct SceneLds {
   static constexpr size_t beam = kPatchLds, baffle = beam + kBeamSrcBytes, park = baffle + kBaffleLds;
   static constexpr size_t bytes(int tracers) { return park + (size_t)tracers * kBeamParkBytes; }
 };
-// ------------------------------------------------------------------ scene response (isx.h: isx_scene_response)
-// The response sink of a call as the kernel gets it (a kernel argument of its own, read where it is used): the device array
-// [kRespFates][B] (+=), the four axes, B, and the size of the workgroup's u32 block behind the parks -- the compact slots
-// (P + 2 wall classes | 2 per baffle | port, other exits, suspended) times B; 0: the global form, one u64 add per ended ray.
-constexpr int kRespFates = 21, kRespBaffle0 = 10, kRespPort = 18, kRespSuspended = 20;
-struct RespSink {
-  unsigned long long* out;
-  uint32_t n[4];
-  uint32_t B, lds_words;
-};
-// A ray's end: its bin by isx.h's rule on the words of block 0 of Philox stream 3 of the ray -- i_a = (w[a] * n[a]) >> 32, in
-// integers -- and one add to slot `fate` of that bin.  Every census point of the RESP build calls this and nothing else states
-// the rule.  `out` stays a kernel argument's field: a global_atomic, not a flat one.
-__device__ __forceinline__ void resp_record(const RespSink& s, uint32_t* blk, int n_patch, int n_baf, int fate, uint64_t seed,
-                                            uint64_t ray) {
-  uint32_t w[4];
-  draw_block(seed, ray, 0u, 3u, w);
-  const uint32_t i0 = __umulhi(w[0], s.n[0]), i1 = __umulhi(w[1], s.n[1]), i2 = __umulhi(w[2], s.n[2]), i3 = __umulhi(w[3], s.n[3]);
-  const uint32_t b = ((i0 * s.n[1] + i1) * s.n[2] + i2) * s.n[3] + i3;
-  if (s.lds_words != 0u) {
-    const int c = fate < kRespBaffle0 ? fate : fate < kRespPort ? fate - kRespBaffle0 + (n_patch + 2) : fate - kRespPort + (n_patch + 2) + 2 * n_baf;
-    atomicAdd(&blk[(uint32_t)c * s.B + b], 1u);
-  } else {
-    global_add_u64(s.out + ((uint32_t)fate * s.B + b), 1ull);
-  }
-}
-// one flush of the workgroup's block: compact slot -> fate slot
-__device__ __forceinline__ void resp_flush(const RespSink& s, const uint32_t* blk, int n_patch, int n_baf, uint32_t tid, uint32_t nthr) {
-  const uint32_t nw = (uint32_t)(n_patch + 2), nb = nw + 2u * (uint32_t)n_baf;
-  for (uint32_t i = tid; i < s.lds_words; i += nthr) {
-    const uint32_t c = blk[i];
-    if (c) {
-      const uint32_t cs = i / s.B, b = i - cs * s.B;
-      const uint32_t fate = cs < nw ? cs : cs < nb ? cs - nw + (uint32_t)kRespBaffle0 : cs - nb + (uint32_t)kRespPort;
-      global_add_u64(s.out + (fate * s.B + b), (unsigned long long)c);
-    }
-  }
-}
-
-// ------------------------------------------------------------------ scene view (isx.h: isx_scene_view)
-// The view sink of a call as the kernel gets it (a kernel argument of its own, read where it is used -- wave-uniform words in
-// scalar registers, never a register per lane): the device map [n_v][n_u] and the four counters of isx_view_counts (+=), the
-// detector's frame, h, the two axis sizes as doubles (converted by the host: no VALU conversion whose result would stay in
-// vector registers), the selected class, n_u, and the size of the workgroup's u32 map in the LDS -- n_u * n_v, or 0: the global
-// form, one u64 add per binned ray.  The workgroup's block behind the parks is u32[4 counters | map] in both forms.
-constexpr int kViewCounters = 4, kViewBinned = 0, kViewOutside = 1, kViewBehind = 2, kViewDirect = 3;
-struct ViewSink {
-  unsigned long long* out;
-  unsigned long long* counts;
-  double axis[3], e1[3], e2[3];
-  double h, fnu, fnv;
-  int32_t patch, n_u;
-  uint32_t lds_words, pad;
-};
-// A selected ray's end -- absorbed at a wall arrival of the selected class, j its interaction count with that arrival, d the
-// direction of the segment it arrived on (Ray::v, which ray_arrive leaves as it is for an absorbed ray) -- by isx.h's rule,
-// operation for operation: IEEE double, left to right, no fma (-ffp-contract=off), the correctly rounded division and square
-// root.  The in-range test is made on the value floor() would see, as wall_bin's is: NaN and inf compare false.  Both census
-// points of the VIEW build call this and nothing else states the rule.  `out` stays a kernel argument's field: a global_atomic.
-__device__ __forceinline__ void view_record(const ViewSink& s, uint32_t* blk, uint32_t j, const V3& d) {
-  if (j == 1u) { atomicAdd(&blk[kViewDirect], 1u); return; }   // absorbed at its first interaction: straight from the source
-  const double c = (d.x * s.axis[0] + d.y * s.axis[1]) + d.z * s.axis[2];
-  if (!(c > 0.0)) { atomicAdd(&blk[kViewBehind], 1u); return; }
-  const double mag = sqrt((d.x * d.x + d.y * d.y) + d.z * d.z);
-  const double a = (d.x * s.e1[0] + d.y * s.e1[1]) + d.z * s.e1[2];
-  const double b = (d.x * s.e2[0] + d.y * s.e2[1]) + d.z * s.e2[2];
-  const double U = -(a / mag), V = -(b / mag);
-  const double fu = (U + s.h) / (2.0 * s.h) * s.fnu;
-  const double fv = (V + s.h) / (2.0 * s.h) * s.fnv;
-  if (fu >= 0.0 && fu < s.fnu && fv >= 0.0 && fv < s.fnv) {
-    const uint32_t bin = (uint32_t)(int)fv * (uint32_t)s.n_u + (uint32_t)(int)fu;
-    if (s.lds_words != 0u) atomicAdd(&blk[kViewCounters + bin], 1u);   // (binned: the sum of the map, view_flush)
-    else { global_add_u64(s.out + bin, 1ull); atomicAdd(&blk[kViewBinned], 1u); }
-  } else atomicAdd(&blk[kViewOutside], 1u);
-}
-// one flush of the workgroup's map (the LDS form; the global form has none): returns this thread's share of `binned`
-__device__ __forceinline__ uint32_t view_flush(const ViewSink& s, const uint32_t* blk, uint32_t tid, uint32_t nthr) {
-  uint32_t flushed = 0u;
-  for (uint32_t i = tid; i < s.lds_words; i += nthr) {
-    const uint32_t c = blk[kViewCounters + i];
-    if (c) { global_add_u64(s.out + i, (unsigned long long)c); flushed += c; }
-  }
-  return flushed;
-}
-
-// ------------------------------------------------------------------ scene patch field (isx.h: isx_scene_patch_field)
-// The patch-field sink of a call as the kernel gets it.  The sixteen doubles of the rule (PatchFieldFrame: the frame, h, s,
-// inv = 1 / r_in formed by the host, the four axis sizes as doubles) are copied once into the workgroup's LDS and read there, one
-// wave-uniform read where each is used: neither a scalar register nor a lane of a parked VGPR is held for them through the steps.
-// The pointers, the selected class, three axis sizes and the form stay fields of the kernel argument (`out`: a global_atomic).
-// lds_words: n_x * n_y * n_u * n_v, the workgroup's u32 field in the LDS, or 0: the global form, one u64 add per binned ray.  The
-// workgroup's block behind the parks is [PatchFieldFrame | u32[8]: five counters | field] in both forms (kFieldHead bytes, then
-// the field).
-constexpr int kFieldCounters = 5, kFieldCtrWords = 8, kFieldBinned = 0, kFieldPosOutside = 1, kFieldDirOutside = 2, kFieldBehind = 3, kFieldDirect = 4;
-struct PatchFieldFrame {
-  double axis[3], e1[3], e2[3];
-  double h, s, inv, fnx, fny, fnu, fnv;
-};
-struct PatchFieldSink {
-  unsigned long long* out;
-  unsigned long long* counts;
-  PatchFieldFrame f;
-  int32_t patch, n_x, n_u, n_v;
-  uint32_t lds_words, pad;
-};
-constexpr size_t kFieldHead = sizeof(PatchFieldFrame) + kFieldCtrWords * sizeof(uint32_t);
-static_assert(sizeof(PatchFieldFrame) == 128 && kFieldHead == 160, "the workgroup's block: frame | counters | field, 16-byte steps");
-typedef __attribute__((address_space(3))) PatchFieldFrame LdsFieldFrame;
-// A selected ray's end -- absorbed at a wall arrival of the selected class, j its interaction count with that arrival, q the
-// point of that arrival (Ray::p), d the direction of the segment it arrived on (Ray::v) -- by isx.h's rule, operation for
-// operation: IEEE double, left to right, no fma (-ffp-contract=off), the correctly rounded division and square root.  The
-// position part comes first and leaves one word, the position bin, for the direction part, which is view_record's.  The in-range
-// tests are made on the values floor() would see: NaN and inf compare false.  Both census points of the FIELD build call this and
-// nothing else states the rule.
-__device__ __forceinline__ void field_record(const PatchFieldSink& s, const volatile LdsFieldFrame& f, uint32_t* blk, uint32_t j,
-                                             const V3& q, const V3& d) {
-  if (j == 1u) { atomicAdd(&blk[kFieldDirect], 1u); return; }   // absorbed at its first interaction: straight from the source
-  const double cd = (d.x * f.axis[0] + d.y * f.axis[1]) + d.z * f.axis[2];
-  if (!(cd > 0.0)) { atomicAdd(&blk[kFieldBehind], 1u); return; }
-  uint32_t pbin;
-  {
-    const double inv = f.inv, sc = f.s;
-    const double c = ((q.x * f.axis[0] + q.y * f.axis[1]) + q.z * f.axis[2]) * inv;
-    const double w = sqrt(0.5 / (1.0 + c));
-    const double a = (q.x * f.e1[0] + q.y * f.e1[1]) + q.z * f.e1[2];
-    const double b = (q.x * f.e2[0] + q.y * f.e2[1]) + q.z * f.e2[2];
-    const double X = ((a * inv) * w) * sc, Y = ((b * inv) * w) * sc;
-    const double fnx = f.fnx, fny = f.fny;
-    const double fx = (X + 1.0) * 0.5 * fnx;
-    const double fy = (Y + 1.0) * 0.5 * fny;
-    if (!(fx >= 0.0 && fx < fnx && fy >= 0.0 && fy < fny)) { atomicAdd(&blk[kFieldPosOutside], 1u); return; }
-    pbin = (uint32_t)(int)fy * (uint32_t)s.n_x + (uint32_t)(int)fx;
-  }
-  const double mag = sqrt((d.x * d.x + d.y * d.y) + d.z * d.z);
-  const double a = (d.x * f.e1[0] + d.y * f.e1[1]) + d.z * f.e1[2];
-  const double b = (d.x * f.e2[0] + d.y * f.e2[1]) + d.z * f.e2[2];
-  const double U = -(a / mag), V = -(b / mag);
-  const double h = f.h, fnu = f.fnu, fnv = f.fnv;
-  const double fu = (U + h) / (2.0 * h) * fnu;
-  const double fv = (V + h) / (2.0 * h) * fnv;
-  if (fu >= 0.0 && fu < fnu && fv >= 0.0 && fv < fnv) {
-    const uint32_t bin = (pbin * (uint32_t)s.n_v + (uint32_t)(int)fv) * (uint32_t)s.n_u + (uint32_t)(int)fu;
-    if (s.lds_words != 0u) atomicAdd(&blk[kFieldCtrWords + bin], 1u);   // (binned: the sum of the field, field_flush)
-    else { global_add_u64(s.out + bin, 1ull); atomicAdd(&blk[kFieldBinned], 1u); }
-  } else atomicAdd(&blk[kFieldDirOutside], 1u);
-}
-// one flush of the workgroup's field (the LDS form; the global form has none): returns this thread's share of `binned`
-__device__ __forceinline__ uint32_t field_flush(const PatchFieldSink& s, const uint32_t* blk, uint32_t tid, uint32_t nthr) {
-  uint32_t flushed = 0u;
-  for (uint32_t i = tid; i < s.lds_words; i += nthr) {
-    const uint32_t c = blk[kFieldCtrWords + i];
-    if (c) { global_add_u64(s.out + i, (unsigned long long)c); flushed += c; }
-  }
-  return flushed;
-}
-
-// ------------------------------------------------------------------ scene order histograms (isx.h: isx_scene_order_hist)
-// The order sink of a call as the kernel gets it (a kernel argument of its own, read where it is used): the device histograms
-// [kRespFates][n_orders] and the kRespFates overflow counters (+=), n_orders, and L = lds_orders: the orders 0 .. L - 1 of every
-// compact slot (RESP's: P + 2 wall classes | 2 per baffle | port, other exits, suspended) are u32 words of the workgroup's LDS --
-// an order histogram is peaked at low k, a small hot array in global memory is what RESP's global form pays for -- and the orders
-// L .. n_orders - 1, rare and spread over many addresses, take one global u64 add each.  L = 0: every order is global (the
-// diagnostic form).  The workgroup's block behind the parks is u32[kSOrderHead: the overflow counters by fate slot | slots * L:
-// [compact slot][order]] in either case.
-constexpr int kSOrderHead = 24;
-static_assert(kSOrderHead >= kRespFates && kSOrderHead % 4 == 0, "the overflow counters, in 16-byte steps");
-struct SOrderSink {
-  unsigned long long* out;
-  unsigned long long* overflow;
-  uint32_t n_orders, lds_orders;
-};
-// A ray's end: one add for its fate slot and its order k = Ray::j at the end (an integer every kernel carries: nothing is computed
-// in a bounce step for it, no Philox draw).  Both census points of the SORDER build call this and nothing else states the rule.
-// `out` stays a kernel argument's field: a global_atomic, not a flat one.
-__device__ __forceinline__ void sorder_record(const SOrderSink& s, uint32_t* blk, int n_patch, int n_baf, int fate, uint32_t k) {
-  if (k >= s.n_orders) { atomicAdd(&blk[fate], 1u); return; }
-  if (k < s.lds_orders) {
-    const int c = fate < kRespBaffle0 ? fate : fate < kRespPort ? fate - kRespBaffle0 + (n_patch + 2) : fate - kRespPort + (n_patch + 2) + 2 * n_baf;
-    atomicAdd(&blk[(uint32_t)kSOrderHead + (uint32_t)c * s.lds_orders + k], 1u);
-  } else {
-    global_add_u64(s.out + ((uint32_t)fate * s.n_orders + k), 1ull);
-  }
-}
-// one flush of the workgroup's low orders: compact slot -> fate slot (L = 0: nothing to flush)
-__device__ __forceinline__ void sorder_flush(const SOrderSink& s, const uint32_t* blk, int n_patch, int n_baf, uint32_t tid, uint32_t nthr) {
-  const uint32_t nw = (uint32_t)(n_patch + 2), nb = nw + 2u * (uint32_t)n_baf, words = (nb + 3u) * s.lds_orders;
-  for (uint32_t i = tid; i < words; i += nthr) {
-    const uint32_t c = blk[(uint32_t)kSOrderHead + i];
-    if (c) {
-      const uint32_t cs = i / s.lds_orders, k = i - cs * s.lds_orders;
-      const uint32_t fate = cs < nw ? cs : cs < nb ? cs - nw + (uint32_t)kRespBaffle0 : cs - nb + (uint32_t)kRespPort;
-      global_add_u64(s.out + (fate * s.n_orders + k), (unsigned long long)c);
-    }
-  }
-}
-
-// ------------------------------------------------------------------ scene path histograms (isx.h: isx_scene_path_hist)
-// The path sink of a call as the kernel gets it (a kernel argument of its own, read where it is used): the device histograms
-// [kRespFates][n_bins] (+=), the 2 kRespFates words of isx_scene_path_counts (overflow by fate slot, then checksum by fate slot;
-// +=), the bin width in cm, n_bins, and B = lds_bins: the bins 0 .. B - 1 of every compact slot (RESP's) are u32 words of the
-// workgroup's LDS, the bins from B on take one global u64 add each (B = 0: every bin is global, the diagnostic form).
-// This is the one scene sink with per-ray state: a lane carries L, the ray's path length so far, and L follows the ray through
-// every hand-over -- the queue records are full (the resume ring uses both spare words), so L travels in a side array parallel to
-// each ring, at the record's slot.  The workgroup's block behind the parks:
-//   double[kPendCap] | double[kResumeCap]         L of the records of the pending / the resume ring
-//   u64[kSPathHead]                                the checksums by fate slot (64-bit LDS adds)
-//   u32[kSPathHead]                                the overflow counters by fate slot
-//   u32[slots * B]                                 [compact slot][bin]
-// The parked first segment of a fresh beam ray: a ray parked at its first wall point (NaN in the direction's x) has no use for
-// the direction's y -- the interaction forms a new direction from the point alone -- so this build parks the segment's length
-// there: the park keeps its six doubles per ray.
-constexpr int kSPathHead = 24;
-static_assert(kSPathHead >= kRespFates && kSPathHead % 4 == 0, "the checksums and the overflow counters, in 16-byte steps");
-struct SPathSink {
-  unsigned long long* out;
-  unsigned long long* counts;
-  double bin_cm;
-  uint32_t n_bins, lds_bins;
-};
-// isx.h's segment rule, operation for operation (IEEE double, left to right, no fma: -ffp-contract=off; sqrt is the correctly
-// rounded one): the length of the segment a -> b.
-__device__ __forceinline__ double spath_segment(const V3& a, const V3& b) {
-  const double dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
-  return sqrt((dx * dx + dy * dy) + dz * dz);
-}
-// The one place L grows: the ray's point `from` is about to become `to`.  Every arrival of the SPATH build calls this -- the
-// tracers' on the inner sphere, the assist wave's on a baffle and on a boundary, the parking of a fresh ray's first segment.
-__device__ __forceinline__ void spath_advance(double& L, const V3& from, const V3& to) { L = L + spath_segment(from, to); }
-// The leg to the world box is not counted; a ray that is counted below z (slot 18) gets the part of it up to the port plane:
-// p the last interaction point, q the point on the box, portz = cfg->exit_port_z.  A NaN f compares false: nothing is added.
-__device__ __forceinline__ void spath_exit_tail(double& L, const V3& p, const V3& q, double portz) {
-  const double s = spath_segment(p, q);
-  const double f = (portz - p.z) / (q.z - p.z);
-  L = L + ((f > 0.0 && f <= 1.0) ? s * f : 0.0);
-}
-// A ray's end: its checksum word, and one add for its fate slot and its bin -- isx.h's rule: fb = L / bin_cm, overflow unless
-// fb < n_bins (a NaN overflows), else bin (int)fb.  Both census points of the SPATH build call this and nothing else states the
-// rule.  `out` stays a kernel argument's field: a global_atomic, not a flat one.
-__device__ __forceinline__ void spath_record(const SPathSink& s, unsigned long long* cks, uint32_t* blk, int n_patch, int n_baf,
-                                             int fate, double L) {
-  atomicAdd(&cks[fate], (unsigned long long)__double_as_longlong(L));
-  const double fb = L / s.bin_cm;
-  if (!(fb < (double)s.n_bins)) { atomicAdd(&blk[fate], 1u); return; }
-  const uint32_t ib = (uint32_t)(int)fb;
-  if (ib < s.lds_bins) {
-    const int c = fate < kRespBaffle0 ? fate : fate < kRespPort ? fate - kRespBaffle0 + (n_patch + 2) : fate - kRespPort + (n_patch + 2) + 2 * n_baf;
-    atomicAdd(&blk[(uint32_t)kSPathHead + (uint32_t)c * s.lds_bins + ib], 1u);
-  } else {
-    global_add_u64(s.out + ((uint32_t)fate * s.n_bins + ib), 1ull);
-  }
-}
-// one flush of the workgroup's low bins: compact slot -> fate slot (B = 0: nothing to flush)
-__device__ __forceinline__ void spath_flush(const SPathSink& s, const uint32_t* blk, int n_patch, int n_baf, uint32_t tid, uint32_t nthr) {
-  const uint32_t nw = (uint32_t)(n_patch + 2), nb = nw + 2u * (uint32_t)n_baf, words = (nb + 3u) * s.lds_bins;
-  for (uint32_t i = tid; i < words; i += nthr) {
-    const uint32_t c = blk[(uint32_t)kSPathHead + i];
-    if (c) {
-      const uint32_t cs = i / s.lds_bins, k = i - cs * s.lds_bins;
-      const uint32_t fate = cs < nw ? cs : cs < nb ? cs - nw + (uint32_t)kRespBaffle0 : cs - nb + (uint32_t)kRespPort;
-      global_add_u64(s.out + (fate * s.n_bins + k), (unsigned long long)c);
-    }
-  }
-}
 
 // The segment test of isx.h's contract, operation for operation (IEEE double, left to right, no fma: -ffp-contract=off; / is the
 // correctly rounded one): the baffle that the segment p -> q strikes first -- the smallest f, on equal f the lowest index -- as
@@ -3304,9 +3041,6 @@ isx_trace_log_lean_kernel(const Geom g, const DetGrid d, const Work wk) { persis
 // stretch without hand-overs, e.g. a tiny port opening with a large bounce limit or a down-clocked device, is not a failure):
 // a wave that gives up raises stats[7] and the host reports ISX_ERR_HIP instead of hanging the device.
 constexpr uint32_t kPendCap = 512, kResumeCap = 128;
-// SPATH (isx_scene_path_hist): the side arrays of the two rings, and with them everything the build keeps in front of its bins
-constexpr size_t kSPathRingBytes = (size_t)(kPendCap + kResumeCap) * sizeof(double);
-constexpr size_t kSPathHeadBytes = kSPathRingBytes + (size_t)kSPathHead * (sizeof(unsigned long long) + sizeof(uint32_t));
 #ifndef ISX_DONATE_MAX
 #define ISX_DONATE_MAX 32     // a tracer wave with at most this many rays left after the launch's queue ran dry gives them away (0: never;
                               // measured, trace kernel of 5e7 headline rays / of the 1e7-ray disc sweep: 0: 11.35 / 7.13 ms, 16: 11.27 / 6.79,
@@ -3341,6 +3075,364 @@ __device__ __forceinline__ void ray_unpack(const uint4& a, const uint4& b, const
   r.v.y = __longlong_as_double(((long long)c.y << 32) | c.x); r.v.z = __longlong_as_double(((long long)c.w << 32) | c.z);
   r.ido = e.x & ~IDO_TARGET; r.tgt = (e.x & IDO_TARGET) != 0u; r.j = e.y; r.k = 0u;
 }
+
+// ------------------------------------------------------------------ scene maps (isx.h: isx_scene_response, isx_scene_view,
+// isx_scene_patch_field, isx_scene_order_hist, isx_scene_path_hist)
+// A scene map is the scene's trace -- assist_body with patches, beam and baffles -- with one sink in place of the exit lines: no
+// second kernel; the step loop, the rings and the parks are the scene build's.  Every ray is seen once, where it ends, by the
+// wave that takes its census: the tracers for what the inner sphere absorbs or suspends (in the per-trip block of the ended
+// lanes, with the class of the absorbing arrival kept from the bounce step), the assist wave for a baffle's side, a wall class
+// or an exit.  The sink is a policy struct, Traits::Map, and assist_body knows a map by nothing else:
+//   Arg             the sink as the kernel gets it: a kernel argument of its own, read where it is used (wave-uniform words in
+//                   scalar registers, never a register per lane); `out` stays a field of it -- a global_atomic, not a flat one
+//   lines           the build writes exit lines for a binning kernel (NoMap, and NoMap only)
+//   selects         the map bins the rays ONE wall class absorbs (ViewMap, PatchFieldMap): the census asks selected(arg, slot) and
+//                   hands record() the Ray alone -- it reads Ray::v.  The other maps bin every ended ray: record() gets a MapEnd
+//   carries_length  a lane carries L, the path length of its ray, through steps, rings and parks (PathMap; see there); never with
+//                   `selects`: the direction of a ray parked at its first wall point is payload in that build
+//   ends_binned     bin_increments is one per ended ray, added by the waves (ResponseMap); else flush() settles sstat[5]
+//   clear()         the prologue, once: zeroes what the workgroup keeps in its block behind the parks
+//   record()        one ended ray; the two census points call it and nothing else states a map's rule
+//   flush()         the epilogue, once, behind the workgroup's barrier: the block and its counters to global memory
+// `blk` is the workgroup's block behind the parks; its size is the launch's (isx_api.hip: plan_scene_map).  The numeric rules in
+// the record()s are isx.h's, operation for operation: IEEE double, left to right, no fma (-ffp-contract=off), the correctly
+// rounded division and square root; in-range tests are made on the value floor() would see (NaN and inf compare false).
+// To add a map: the Arg struct, a policy with these members, one kernel (Traits: KScene with the Map), one case in plan_scene_map.
+constexpr int kRespFates = 21, kRespBaffle0 = 10, kRespPort = 18, kRespSuspended = 20;
+// An ended ray as a census point has it in hand.  eslot: the slot of the interaction that absorbed it -- a wall class, or
+// kRespBaffle0 + 2 k + side.  fate() is the one statement of isx.h's fate slot.
+struct MapEnd {
+  int st;               // ST_ABSORBED, ST_SUSPENDED, ST_EXITED
+  bool exited, below;   // the census's own flags: st == ST_EXITED, and counted below z
+  int eslot;
+  const Ray& r;         // j: its order; p, v: the last point and the direction of the segment it arrived on; offset()
+  double L;             // carries_length: its path length
+  uint64_t seed, first;
+  int n_patch, n_baf;
+  __device__ __forceinline__ int fate() const {
+    return exited ? (below ? kRespPort : kRespPort + 1) : st == ST_SUSPENDED ? kRespSuspended : eslot;
+  }
+};
+// The workgroup's rows: one per COMPACT slot -- P + 2 wall classes | 2 per baffle | port, other exits, suspended -- where global
+// memory has the kRespFates fate slots.  The rule and its inverse:
+__device__ __forceinline__ int scene_slots(int n_patch, int n_baf) { return (n_patch + 2) + 2 * n_baf + 3; }
+__device__ __forceinline__ int compact_slot(int fate, int n_patch, int n_baf) {
+  return fate < kRespBaffle0 ? fate : fate < kRespPort ? fate - kRespBaffle0 + (n_patch + 2) : fate - kRespPort + (n_patch + 2) + 2 * n_baf;
+}
+__device__ __forceinline__ uint32_t slot_fate(uint32_t cs, uint32_t nw, uint32_t nb) {   // nw = P + 2, nb = nw + 2 n_baf
+  return cs < nw ? cs : cs < nb ? cs - nw + (uint32_t)kRespBaffle0 : cs - nb + (uint32_t)kRespPort;
+}
+__device__ __forceinline__ void map_clear(uint32_t* w, uint32_t words, uint32_t tid, uint32_t nthr) {
+  for (uint32_t b = tid; b < words; b += nthr) w[b] = 0u;
+}
+// one flush of `words` u32 kept as [compact slot][cols] to the rows [fate slot][stride] of `out`
+__device__ __forceinline__ void rows_flush(unsigned long long* out, const uint32_t* blk, uint32_t words, uint32_t cols, uint32_t stride,
+                                           int n_patch, int n_baf, uint32_t tid, uint32_t nthr) {
+  const uint32_t nw = (uint32_t)(n_patch + 2), nb = nw + 2u * (uint32_t)n_baf;
+  for (uint32_t i = tid; i < words; i += nthr) {
+    const uint32_t c = blk[i];
+    if (c) {
+      const uint32_t cs = i / cols, k = i - cs * cols;
+      global_add_u64(out + (slot_fate(cs, nw, nb) * stride + k), (unsigned long long)c);
+    }
+  }
+}
+// The flush of a map with counters (view, field): the map as it lies, its sum added to counter 0 (binned; the global form counted
+// there at the record), then the n_ctr counters; bin_increments = binned.
+__device__ __forceinline__ void counted_flush(unsigned long long* out, unsigned long long* counts, uint32_t* ctr, const uint32_t* map,
+                                              uint32_t words, uint32_t n_ctr, uint32_t tid, uint32_t nthr, unsigned long long* sstat) {
+  uint32_t flushed = 0u;
+  for (uint32_t i = tid; i < words; i += nthr) {
+    const uint32_t c = map[i];
+    if (c) { global_add_u64(out + i, (unsigned long long)c); flushed += c; }
+  }
+  if (flushed) atomicAdd(&ctr[0], flushed);
+  __syncthreads();
+  if (tid < n_ctr) {
+    const uint32_t c = ctr[tid];
+    if (c) global_add_u64(counts + tid, (unsigned long long)c);
+    if (tid == 0u && c) atomicAdd(&sstat[5], (unsigned long long)c);
+  }
+  __syncthreads();
+}
+// The flush of histograms by fate (order, path): blk = u32[head: overflow counters by fate slot | slots x cols], cks = the u64
+// checksums by fate slot or none; `counts` takes the overflow counters and behind them the checksums.  bin_increments = the
+// histograms' sum: every ended ray of the workgroup that did not overflow (the census is complete behind the barrier:
+// exited + absorbed + suspended = ended).
+template <bool CKS>
+__device__ __forceinline__ void fate_hist_flush(unsigned long long* out, unsigned long long* counts, const uint32_t* blk,
+                                                const unsigned long long* cks, uint32_t head, uint32_t cols, uint32_t stride, int n_patch,
+                                                int n_baf, uint32_t tid, uint32_t nthr, unsigned long long* sstat) {
+  rows_flush(out, blk + head, (uint32_t)scene_slots(n_patch, n_baf) * cols, cols, stride, n_patch, n_baf, tid, nthr);
+  if (tid < (uint32_t)kRespFates) {
+    const uint32_t c = blk[tid];
+    if (c) global_add_u64(counts + tid, (unsigned long long)c);
+    if constexpr (CKS) {
+      const unsigned long long k = cks[tid];
+      if (k) global_add_u64(counts + (uint32_t)kRespFates + tid, k);
+    }
+  }
+  if (tid == 64u) {
+    unsigned long long over = 0ull;
+    for (int f = 0; f < kRespFates; ++f) over += (unsigned long long)blk[f];
+    sstat[5] = sstat[1] + sstat[3] + sstat[4] - over;
+  }
+  __syncthreads();
+}
+
+struct NoMap {   // exit lines for a binning kernel, or a sink of the older kind (WALL, ORDER, PATCH, PP)
+  struct Arg {};
+  static constexpr bool lines = true, selects = false, carries_length = false, ends_binned = false;
+};
+
+// isx_scene_response: fates binned over the source's sample space.  Arg: the device array [kRespFates][B] (+=), the four axes, B,
+// and lds_words = slots x B, the workgroup's u32 block [compact slot][B]; 0: the global form, one u64 add per ended ray.
+struct RespSink {
+  unsigned long long* out;
+  uint32_t n[4];
+  uint32_t B, lds_words;
+};
+struct ResponseMap {
+  using Arg = RespSink;
+  static constexpr bool lines = false, selects = false, carries_length = false, ends_binned = true;
+  static __device__ __forceinline__ void clear(const Arg& s, uint32_t* blk, int, int, uint32_t tid, uint32_t nthr) {
+    map_clear(blk, s.lds_words, tid, nthr);
+  }
+  // the bin by isx.h's rule on the words of block 0 of Philox stream 3 of the ray -- i_a = (w[a] * n[a]) >> 32, in integers --
+  // recomputed from the ray's index here: nothing is carried through the steps or the queue records
+  static __device__ __forceinline__ void record(const Arg& s, uint32_t* blk, const MapEnd& e) {
+    const int fate = e.fate();
+    uint32_t w[4];
+    draw_block(e.seed, e.first + (uint64_t)e.r.offset(), 0u, 3u, w);
+    const uint32_t i0 = __umulhi(w[0], s.n[0]), i1 = __umulhi(w[1], s.n[1]), i2 = __umulhi(w[2], s.n[2]), i3 = __umulhi(w[3], s.n[3]);
+    const uint32_t b = ((i0 * s.n[1] + i1) * s.n[2] + i2) * s.n[3] + i3;
+    if (s.lds_words != 0u) atomicAdd(&blk[(uint32_t)compact_slot(fate, e.n_patch, e.n_baf) * s.B + b], 1u);
+    else global_add_u64(s.out + ((uint32_t)fate * s.B + b), 1ull);
+  }
+  static __device__ __forceinline__ void flush(const Arg& s, uint32_t* blk, int n_patch, int n_baf, uint32_t tid, uint32_t nthr,
+                                               unsigned long long*) {
+    rows_flush(s.out, blk, s.lds_words, s.B, s.B, n_patch, n_baf, tid, nthr);   // (the global form: nothing to flush)
+  }
+};
+
+// isx_scene_view: what a wall detector sees -- a ray absorbed at a wall arrival of the selected class, binned by the direction of
+// the segment it arrived on (Ray::v, which ray_arrive leaves as it is for an absorbed ray).  Arg: the device map [n_v][n_u] and
+// the four counters of isx_view_counts (+=), the detector's frame, h, the two axis sizes as doubles (converted by the host: no
+// VALU conversion whose result would stay in vector registers), the selected class, n_u, and lds_words = n_u * n_v, the
+// workgroup's u32 map; 0: the global form, one u64 add per binned ray.  The block is u32[4 counters | map] in both forms.
+constexpr int kViewCounters = 4, kViewBinned = 0, kViewOutside = 1, kViewBehind = 2, kViewDirect = 3;
+struct ViewSink {
+  unsigned long long* out;
+  unsigned long long* counts;
+  double axis[3], e1[3], e2[3];
+  double h, fnu, fnv;
+  int32_t patch, n_u;
+  uint32_t lds_words, pad;
+};
+struct ViewMap {
+  using Arg = ViewSink;
+  static constexpr bool lines = false, selects = true, carries_length = false, ends_binned = false;
+  static __device__ __forceinline__ void clear(const Arg& s, uint32_t* blk, int, int, uint32_t tid, uint32_t nthr) {
+    map_clear(blk, (uint32_t)kViewCounters + s.lds_words, tid, nthr);
+  }
+  static __device__ __forceinline__ bool selected(const Arg& s, int eslot) { return eslot == s.patch; }   // (a baffle's side is a slot above every wall class)
+  static __device__ __forceinline__ void record(const Arg& s, uint32_t* blk, const Ray& r) { bin(s, blk, r.j, r.v); }
+  // a selected ray: j its interaction count with the absorbing arrival, d the direction of the segment it arrived on
+  static __device__ __forceinline__ void bin(const Arg& s, uint32_t* blk, uint32_t j, const V3& d) {
+    if (j == 1u) { atomicAdd(&blk[kViewDirect], 1u); return; }   // absorbed at its first interaction: straight from the source
+    const double c = (d.x * s.axis[0] + d.y * s.axis[1]) + d.z * s.axis[2];
+    if (!(c > 0.0)) { atomicAdd(&blk[kViewBehind], 1u); return; }
+    const double mag = sqrt((d.x * d.x + d.y * d.y) + d.z * d.z);
+    const double a = (d.x * s.e1[0] + d.y * s.e1[1]) + d.z * s.e1[2];
+    const double b = (d.x * s.e2[0] + d.y * s.e2[1]) + d.z * s.e2[2];
+    const double U = -(a / mag), V = -(b / mag);
+    const double fu = (U + s.h) / (2.0 * s.h) * s.fnu;
+    const double fv = (V + s.h) / (2.0 * s.h) * s.fnv;
+    if (fu >= 0.0 && fu < s.fnu && fv >= 0.0 && fv < s.fnv) {
+      const uint32_t bin = (uint32_t)(int)fv * (uint32_t)s.n_u + (uint32_t)(int)fu;
+      if (s.lds_words != 0u) atomicAdd(&blk[kViewCounters + bin], 1u);   // (binned: the sum of the map, counted_flush)
+      else { global_add_u64(s.out + bin, 1ull); atomicAdd(&blk[kViewBinned], 1u); }
+    } else atomicAdd(&blk[kViewOutside], 1u);
+  }
+  static __device__ __forceinline__ void flush(const Arg& s, uint32_t* blk, int, int, uint32_t tid, uint32_t nthr, unsigned long long* sstat) {
+    counted_flush(s.out, s.counts, blk, blk + kViewCounters, s.lds_words, (uint32_t)kViewCounters, tid, nthr, sstat);
+  }
+};
+
+// isx_scene_patch_field: the same rays at the same two points, binned by where on the patch they land (Ray::p) and the direction
+// they arrive from.  The sixteen doubles of the rule (PatchFieldFrame: the frame, h, s, inv = 1 / r_in formed by the host, the four
+// axis sizes as doubles) are copied once into the workgroup's LDS and read there, one wave-uniform read where each is used: neither
+// a scalar register nor a lane of a parked VGPR is held for them through the steps.  The pointers, the selected class, three axis
+// sizes and the form stay fields of the kernel argument.  lds_words = n_x * n_y * n_u * n_v, the workgroup's u32 field, or 0: the
+// global form, one u64 add per binned ray.  The block is [PatchFieldFrame | u32[8]: five counters | field] in both forms
+// (kFieldHead bytes, then the field).
+constexpr int kFieldCounters = 5, kFieldCtrWords = 8, kFieldBinned = 0, kFieldPosOutside = 1, kFieldDirOutside = 2, kFieldBehind = 3, kFieldDirect = 4;
+static_assert(kViewBinned == 0 && kFieldBinned == 0, "counted_flush: binned is counter 0");
+struct PatchFieldFrame {
+  double axis[3], e1[3], e2[3];
+  double h, s, inv, fnx, fny, fnu, fnv;
+};
+struct PatchFieldSink {
+  unsigned long long* out;
+  unsigned long long* counts;
+  PatchFieldFrame f;
+  int32_t patch, n_x, n_u, n_v;
+  uint32_t lds_words, pad;
+};
+constexpr size_t kFieldHead = sizeof(PatchFieldFrame) + kFieldCtrWords * sizeof(uint32_t);
+static_assert(sizeof(PatchFieldFrame) == 128 && kFieldHead == 160, "the workgroup's block: frame | counters | field, 16-byte steps");
+typedef __attribute__((address_space(3))) PatchFieldFrame LdsFieldFrame;
+struct PatchFieldMap {
+  using Arg = PatchFieldSink;
+  static constexpr bool lines = false, selects = true, carries_length = false, ends_binned = false;
+  static __device__ __forceinline__ uint32_t* counters(uint32_t* blk) { return blk + sizeof(PatchFieldFrame) / sizeof(uint32_t); }
+  static __device__ __forceinline__ void clear(const Arg& s, uint32_t* blk, int, int, uint32_t tid, uint32_t nthr) {
+    if (tid == 68u) *reinterpret_cast<PatchFieldFrame*>(blk) = s.f;
+    map_clear(counters(blk), (uint32_t)kFieldCtrWords + s.lds_words, tid, nthr);
+  }
+  // the position part comes first and leaves one word, the position bin, for the direction part, which is ViewMap's
+  static __device__ __forceinline__ bool selected(const Arg& s, int eslot) { return eslot == s.patch; }   // (likewise)
+  static __device__ __forceinline__ void record(const Arg& s, uint32_t* blk, const Ray& r) {
+    bin(s, *(const volatile LdsFieldFrame*)blk, counters(blk), r.j, r.p, r.v);
+  }
+  // a selected ray: j, q the point of the absorbing arrival, d the direction of the segment it arrived on
+  static __device__ __forceinline__ void bin(const Arg& s, const volatile LdsFieldFrame& f, uint32_t* blk, uint32_t j, const V3& q,
+                                             const V3& d) {
+    if (j == 1u) { atomicAdd(&blk[kFieldDirect], 1u); return; }   // absorbed at its first interaction: straight from the source
+    const double cd = (d.x * f.axis[0] + d.y * f.axis[1]) + d.z * f.axis[2];
+    if (!(cd > 0.0)) { atomicAdd(&blk[kFieldBehind], 1u); return; }
+    uint32_t pbin;
+    {
+      const double inv = f.inv, sc = f.s;
+      const double c = ((q.x * f.axis[0] + q.y * f.axis[1]) + q.z * f.axis[2]) * inv;
+      const double w = sqrt(0.5 / (1.0 + c));
+      const double a = (q.x * f.e1[0] + q.y * f.e1[1]) + q.z * f.e1[2];
+      const double b = (q.x * f.e2[0] + q.y * f.e2[1]) + q.z * f.e2[2];
+      const double X = ((a * inv) * w) * sc, Y = ((b * inv) * w) * sc;
+      const double fnx = f.fnx, fny = f.fny;
+      const double fx = (X + 1.0) * 0.5 * fnx;
+      const double fy = (Y + 1.0) * 0.5 * fny;
+      if (!(fx >= 0.0 && fx < fnx && fy >= 0.0 && fy < fny)) { atomicAdd(&blk[kFieldPosOutside], 1u); return; }
+      pbin = (uint32_t)(int)fy * (uint32_t)s.n_x + (uint32_t)(int)fx;
+    }
+    const double mag = sqrt((d.x * d.x + d.y * d.y) + d.z * d.z);
+    const double a = (d.x * f.e1[0] + d.y * f.e1[1]) + d.z * f.e1[2];
+    const double b = (d.x * f.e2[0] + d.y * f.e2[1]) + d.z * f.e2[2];
+    const double U = -(a / mag), V = -(b / mag);
+    const double h = f.h, fnu = f.fnu, fnv = f.fnv;
+    const double fu = (U + h) / (2.0 * h) * fnu;
+    const double fv = (V + h) / (2.0 * h) * fnv;
+    if (fu >= 0.0 && fu < fnu && fv >= 0.0 && fv < fnv) {
+      const uint32_t bin = (pbin * (uint32_t)s.n_v + (uint32_t)(int)fv) * (uint32_t)s.n_u + (uint32_t)(int)fu;
+      if (s.lds_words != 0u) atomicAdd(&blk[kFieldCtrWords + bin], 1u);   // (binned: the sum of the field, counted_flush)
+      else { global_add_u64(s.out + bin, 1ull); atomicAdd(&blk[kFieldBinned], 1u); }
+    } else atomicAdd(&blk[kFieldDirOutside], 1u);
+  }
+  static __device__ __forceinline__ void flush(const Arg& s, uint32_t* blk, int, int, uint32_t tid, uint32_t nthr, unsigned long long* sstat) {
+    counted_flush(s.out, s.counts, counters(blk), counters(blk) + kFieldCtrWords, s.lds_words, (uint32_t)kFieldCounters, tid, nthr, sstat);
+  }
+};
+
+// isx_scene_order_hist: fates by the order k = Ray::j at the end (an integer every kernel carries: nothing is computed in a bounce
+// step for it, no Philox draw).  Arg: the device histograms [kRespFates][n_orders] and the kRespFates overflow counters (+=),
+// n_orders, and L = lds_orders: the orders 0 .. L - 1 of every compact slot are u32 words of the workgroup's LDS -- an order
+// histogram is peaked at low k, a small hot array in global memory is what the response's global form pays for -- and the orders
+// L .. n_orders - 1, rare and spread over many addresses, take one global u64 add each.  L = 0: every order is global (the
+// diagnostic form).  The block is u32[kSOrderHead: the overflow counters by fate slot | slots x L] in either case.
+constexpr int kSOrderHead = 24;
+static_assert(kSOrderHead >= kRespFates && kSOrderHead % 4 == 0, "the overflow counters, in 16-byte steps");
+struct SOrderSink {
+  unsigned long long* out;
+  unsigned long long* overflow;
+  uint32_t n_orders, lds_orders;
+};
+struct OrderMap {
+  using Arg = SOrderSink;
+  static constexpr bool lines = false, selects = false, carries_length = false, ends_binned = false;
+  static __device__ __forceinline__ void clear(const Arg& s, uint32_t* blk, int n_patch, int n_baf, uint32_t tid, uint32_t nthr) {
+    map_clear(blk, (uint32_t)kSOrderHead + (uint32_t)scene_slots(n_patch, n_baf) * s.lds_orders, tid, nthr);
+  }
+  static __device__ __forceinline__ void record(const Arg& s, uint32_t* blk, const MapEnd& e) {
+    const int fate = e.fate();
+    const uint32_t k = e.r.j;
+    if (k >= s.n_orders) { atomicAdd(&blk[fate], 1u); return; }
+    if (k < s.lds_orders) atomicAdd(&blk[(uint32_t)kSOrderHead + (uint32_t)compact_slot(fate, e.n_patch, e.n_baf) * s.lds_orders + k], 1u);
+    else global_add_u64(s.out + ((uint32_t)fate * s.n_orders + k), 1ull);
+  }
+  static __device__ __forceinline__ void flush(const Arg& s, uint32_t* blk, int n_patch, int n_baf, uint32_t tid, uint32_t nthr,
+                                               unsigned long long* sstat) {
+    fate_hist_flush<false>(s.out, s.overflow, blk, nullptr, (uint32_t)kSOrderHead, s.lds_orders, s.n_orders, n_patch, n_baf, tid, nthr, sstat);
+  }
+};
+
+// isx_scene_path_hist: fates by path length, in centimetres.  Arg: the device histograms [kRespFates][n_bins] (+=), the
+// 2 kRespFates words of isx_scene_path_counts (overflow by fate slot, then checksum by fate slot; +=), the bin width in cm, n_bins,
+// and B = lds_bins: OrderMap's hybrid form with bins for orders (B = 0: every bin is global, the diagnostic form).
+// The one map with per-ray state (carries_length): a lane holds L, zero where the ray starts, advanced wherever its point is
+// replaced (spath_advance: the tracers' arrival, the assist wave's ray_arrive and baffle_arrive, the parking of a fresh ray's first
+// segment).  L follows the ray through every hand-over -- the queue records are full (the resume ring uses both spare words), so it
+// travels in a side array parallel to each ring, at the record's slot.  The leg to the world box is not counted; the exit's tail
+// up to the port plane is formed where the exit is taken.  The block:
+//   double[kPendCap] | double[kResumeCap]         L of the records of the pending / the resume ring (written and read with the
+//                                                  records, never cleared)
+//   u64[kSPathHead]                                the checksums by fate slot (64-bit LDS adds)
+//   u32[kSPathHead]                                the overflow counters by fate slot
+//   u32[slots * B]                                 [compact slot][bin]
+// The parked first segment of a fresh beam ray: a ray parked at its first wall point (NaN in the direction's x) has no use for
+// the direction's y -- the interaction forms a new direction from the point alone -- so this build parks the segment's length
+// there: the park keeps its six doubles per ray.  Nothing may read r.v of such a ray, so a map whose record() reads Ray::v
+// (ViewMap, PatchFieldMap) cannot carry a length.
+constexpr int kSPathHead = 24;
+static_assert(kSPathHead >= kRespFates && kSPathHead % 4 == 0, "the checksums and the overflow counters, in 16-byte steps");
+constexpr size_t kSPathRingBytes = (size_t)(kPendCap + kResumeCap) * sizeof(double);
+constexpr size_t kSPathHeadBytes = kSPathRingBytes + (size_t)kSPathHead * (sizeof(unsigned long long) + sizeof(uint32_t));
+struct SPathSink {
+  unsigned long long* out;
+  unsigned long long* counts;
+  double bin_cm;
+  uint32_t n_bins, lds_bins;
+};
+// isx.h's segment rule: the length of the segment a -> b.
+__device__ __forceinline__ double spath_segment(const V3& a, const V3& b) {
+  const double dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
+  return sqrt((dx * dx + dy * dy) + dz * dz);
+}
+// The one place L grows: the ray's point `from` is about to become `to`.
+__device__ __forceinline__ void spath_advance(double& L, const V3& from, const V3& to) { L = L + spath_segment(from, to); }
+// A ray that is counted below z (slot 18) gets the part of the leg to the world box up to the port plane: p the last interaction
+// point, q the point on the box, portz = cfg->exit_port_z.  A NaN f compares false: nothing is added.
+__device__ __forceinline__ void spath_exit_tail(double& L, const V3& p, const V3& q, double portz) {
+  const double s = spath_segment(p, q);
+  const double f = (portz - p.z) / (q.z - p.z);
+  L = L + ((f > 0.0 && f <= 1.0) ? s * f : 0.0);
+}
+struct PathMap {
+  using Arg = SPathSink;
+  static constexpr bool lines = false, selects = false, carries_length = true, ends_binned = false;
+  static __device__ __forceinline__ unsigned long long* checksums(uint32_t* blk) {
+    return reinterpret_cast<unsigned long long*>(reinterpret_cast<double*>(blk) + (kPendCap + kResumeCap));
+  }
+  static __device__ __forceinline__ uint32_t* counters(uint32_t* blk) { return reinterpret_cast<uint32_t*>(checksums(blk) + kSPathHead); }
+  static __device__ __forceinline__ void clear(const Arg& s, uint32_t* blk, int n_patch, int n_baf, uint32_t tid, uint32_t nthr) {
+    map_clear(reinterpret_cast<uint32_t*>(checksums(blk)), (uint32_t)(3 * kSPathHead) + (uint32_t)scene_slots(n_patch, n_baf) * s.lds_bins, tid, nthr);
+  }
+  // the checksum word, and one add for the fate slot and the bin -- fb = L / bin_cm, overflow unless fb < n_bins (a NaN
+  // overflows), else bin (int)fb
+  static __device__ __forceinline__ void record(const Arg& s, uint32_t* blk0, const MapEnd& e) {
+    const int fate = e.fate();
+    uint32_t* blk = counters(blk0);
+    atomicAdd(&checksums(blk0)[fate], (unsigned long long)__double_as_longlong(e.L));
+    const double fb = e.L / s.bin_cm;
+    if (!(fb < (double)s.n_bins)) { atomicAdd(&blk[fate], 1u); return; }
+    const uint32_t ib = (uint32_t)(int)fb;
+    if (ib < s.lds_bins) atomicAdd(&blk[(uint32_t)kSPathHead + (uint32_t)compact_slot(fate, e.n_patch, e.n_baf) * s.lds_bins + ib], 1u);
+    else global_add_u64(s.out + ((uint32_t)fate * s.n_bins + ib), 1ull);
+  }
+  static __device__ __forceinline__ void flush(const Arg& s, uint32_t* blk, int n_patch, int n_baf, uint32_t tid, uint32_t nthr,
+                                               unsigned long long* sstat) {
+    fate_hist_flush<true>(s.out, s.counts, counters(blk), checksums(blk), (uint32_t)kSPathHead, s.lds_bins, s.n_bins, n_patch, n_baf, tid, nthr, sstat);
+  }
+};
 
 // DISC (the shared-ray physical-disc sweep, integratingSphereDetectorSweep.C:134-172 / SINK_DISC): the assist wave writes, for
 // EVERY ray that leaves for the world box, its forward exit segment -- start point, direction, length (8 doubles per slot) --
@@ -3396,48 +3488,52 @@ __device__ __forceinline__ void ray_unpack(const uint4& a, const uint4& b, const
 // boundary's ray_arrive with the class's constants.  The three blocks lie one behind the other behind the rings (SceneLds).  Exit
 // lines are written as in the BEAM and BAFFLE builds; patch_flush adds nothing to bin_increments (the binning kernel's count).
 // The assist wave never waits for the resume ring, as in every BAFFLE build (docs/LOG.md sections 18.4, 19.2).
-// RESP (isx_scene_response; SCENE only): every ray is binned once, where it ends, by the wave that takes its census, as ORDER's
-// are -- resp_record with the fate slot the wave has in hand: the tracers with the class of the arrival that absorbed the ray
-// (kept from the bounce step to the per-trip block of the ended lanes) or "suspended", the assist wave with the baffle's side, the
-// wall class, or the exit with the census's own counted-below-z test.  The bin is recomputed from the ray's index there; nothing
-// is carried through the steps or the queue records.  The workgroup's u32 block, if the launch has one, lies behind the parks.
-// No exit lines, no second kernel; the step loop, the rings and the parks are the SCENE build's, unchanged.
-// VIEW (isx_scene_view; SCENE only, never with RESP): a ray absorbed at a wall arrival of the selected class is binned once, where
-// it ends, by the direction of the segment it arrived on -- view_record at RESP's two census points, with the class kept as RESP
-// keeps it.  The workgroup's u32 block -- four counters, and the map if the launch has one -- lies behind the parks.  No exit
-// lines, no second kernel, no per-ray state.
-// FIELD (isx_scene_patch_field; SCENE only, never with RESP or VIEW): the same rays at the same two points, binned by where on the
-// patch they land and the direction they arrive from -- field_record, which also gets the point of the arrival (Ray::p).  The
-// workgroup's block behind the parks: the frame's doubles, five counters, and the field if the launch has one in the LDS.
-// SORDER (isx_scene_order_hist; SCENE only, never with RESP, VIEW or FIELD): every ray is binned once, where it ends, at RESP's two
-// census points with RESP's fate slot, by its order Ray::j -- sorder_record, which draws nothing.  The workgroup's block behind the
-// parks: the overflow counters and the low orders of every compact slot; the orders above them go to global memory one by one.
-// SPATH (isx_scene_path_hist; SCENE only, never with RESP, VIEW, FIELD or SORDER): the one sink with state carried through the steps.
-// A lane holds L, the path length of its ray: zero where the ray starts, advanced wherever its point is replaced (spath_advance:
-// the tracers' arrival, the assist wave's ray_arrive and baffle_arrive, the parking of a fresh ray's first segment), handed over
-// in a side array parallel to each ring.  The leg to the world box is not counted; the exit's tail up to the port plane is formed
-// where the exit is taken.  Every ray is binned once at RESP's two census points -- spath_record.
+// Map (the scene maps above; scene only): the build's one sink in place of the exit lines, known to this body by its policy alone.
+//
+// A kernel is described by ONE traits struct: KDefault is isx_trace_assist_kernel, and a kernel's traits name what differs.  The
+// paragraphs above are headed by the members in capitals (CH = chord: 1 = the chord identity compiled in; RESC = rescatter: the
+// BRDF source's re-scatter of a primary; PP = perpos).  The body reads K::member directly: with `constexpr int CH = K::chord, SURF =
+// K::surf` as aliases local to assist_body, named inside its generic lambdas, the two PATCH kernels came out with other register
+// names (docs/LOG.md section 30.1).
+struct KDefault {
+  static constexpr int chord = 0, perpos = 0, surf = SURF_LAMBERT;
+  static constexpr bool rescatter = false, disc = false, wall = false, order = false, patch = false, beam = false, list = false, baffle = false;
+  using Map = NoMap;
+};
+template <class K>
+constexpr bool assist_traits_ok() {
+  constexpr bool lean = K::surf == SURF_LAMBERT;
+  constexpr bool plain = lean && K::chord == 0 && !K::rescatter && !K::disc && K::perpos == 0 && !K::wall && !K::order;
+  constexpr bool scene = K::patch && K::beam && K::baffle;   // the three together, and no two of them without the third
+  static_assert(lean || (K::chord == 0 && !K::rescatter), "the chord identity and the BRDF re-scatter pipeline are built for the Lambertian border");
+  static_assert(!(K::wall && K::order), "one LDS block behind the rings");
+  static_assert(!(K::patch || K::beam || K::list || K::baffle) || plain, "patches, beam, ray list, baffles: the explicit Lambertian lean path, no other sink");
+  static_assert(scene || (int)K::patch + (int)K::beam + (int)K::list + (int)K::baffle <= 1, "patches, beam and baffles: one of them, or the scene");
+  static_assert(!(scene && K::list), "ray list: the flux pipeline's own trace");
+  static_assert(K::Map::lines || scene, "a scene map: the scene's trace, nothing else");
+  static_assert(!(K::Map::carries_length && K::Map::selects), "a build that carries the length parks it in Ray::v, which a selecting map reads");
+  return true;
+}
+// What a kernel takes behind (Geom, DetGrid, Work), as its traits say: one table, the scene's three, or those and the map's sink.
 struct FateList { const uint32_t* list; const uint32_t* count; };
-template <int CH, bool RESC, bool DISC = false, int PP = 0, int SURF = SURF_LAMBERT, bool WALL = false, bool ORDER = false, bool PATCH = false,
-          bool BEAM = false, bool LIST = false, bool BAFFLE = false, bool RESP = false, bool VIEW = false, bool FIELD = false,
-          bool SORDER = false, bool SPATH = false>
-__device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk, const PatchTab* tab_arg = nullptr,
-                                            const BeamSrc* beam_arg = nullptr, const FateList* list_arg = nullptr,
-                                            const BaffleTab* baf_arg = nullptr, const RespSink* resp_arg = nullptr,
-                                            const ViewSink* view_arg = nullptr, const PatchFieldSink* field_arg = nullptr,
-                                            const SOrderSink* sorder_arg = nullptr, const SPathSink* spath_arg = nullptr) {
-  constexpr bool LEAN = SURF == SURF_LAMBERT;
-  static_assert(LEAN || (CH == 0 && !RESC), "the chord identity and the BRDF re-scatter pipeline are built for the Lambertian border");
-  static_assert(!PATCH || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER), "wall patches: the explicit Lambertian lean path, no other sink");
-  constexpr bool SCENE = PATCH && BEAM && BAFFLE;   // isx_fluxmap_scene: the three together, and no two of them without the third
-  static_assert(!BEAM || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && (!PATCH || SCENE)), "beam source: the explicit Lambertian lean path, no other sink");
-  static_assert(!LIST || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && !PATCH && !BEAM), "ray list: the explicit Lambertian lean path of the flux pipeline");
-  static_assert(!BAFFLE || (LEAN && CH == 0 && !RESC && !DISC && PP == 0 && !WALL && !ORDER && (!PATCH || SCENE) && (!BEAM || SCENE) && !LIST), "baffles: the explicit Lambertian lean path of the flux pipeline");
-  static_assert(!RESP || SCENE, "scene response: the scene's trace, nothing else");
-  static_assert(!VIEW || (SCENE && !RESP), "scene view: the scene's trace, nothing else");
-  static_assert(!FIELD || (SCENE && !RESP && !VIEW), "scene patch field: the scene's trace, nothing else");
-  static_assert(!SORDER || (SCENE && !RESP && !VIEW && !FIELD), "scene order histograms: the scene's trace, nothing else");
-  static_assert(!SPATH || (SCENE && !RESP && !VIEW && !FIELD && !SORDER), "scene path histograms: the scene's trace, nothing else");
+struct NoTail {};
+struct PatchTail { const PatchTab* tab; };
+struct BeamTail { const BeamSrc* beam; };
+struct ListTail { const FateList* list; };
+struct BaffleTail { const BaffleTab* baf; };
+struct SceneTail { const PatchTab* tab; const BeamSrc* beam; const BaffleTab* baf; };
+template <class M> struct SceneMapTail { const PatchTab* tab; const BeamSrc* beam; const BaffleTab* baf; const typename M::Arg* map; };
+template <class K>
+using AssistTail = std::conditional_t<!K::Map::lines, SceneMapTail<typename K::Map>, std::conditional_t<K::patch && K::beam, SceneTail,
+                   std::conditional_t<K::patch, PatchTail, std::conditional_t<K::beam, BeamTail, std::conditional_t<K::list, ListTail,
+                   std::conditional_t<K::baffle, BaffleTail, NoTail>>>>>>;
+template <class K>
+__device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_arg, const Work& wk, const AssistTail<K>& tail = {}) {
+  static_assert(assist_traits_ok<K>(), "");
+  using Map = typename K::Map;
+  constexpr bool MAP = !Map::lines, LEN = Map::carries_length;
+  constexpr bool LEAN = K::surf == SURF_LAMBERT;
+  constexpr bool SCENE = K::patch && K::beam && K::baffle;   // isx_fluxmap_scene
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned long long* sstat = reinterpret_cast<unsigned long long*>(smem);
   Geom* g_lds = reinterpret_cast<Geom*>(sstat + 8);
@@ -3449,27 +3545,26 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   const int tid = threadIdx.x, lane = tid & 63;
   const int nthr = (int)blockDim.x, wpb = nthr >> 6;
   const int n_tracers = wpb - 1;
-  const WallSpec wspec = wall_spec<WALL>(d_arg);
+  const WallSpec wspec = wall_spec<K::wall>(d_arg);
   const int wall_nmap = d_arg.xm_nx * d_arg.xm_ny;
-  if (WALL) for (int b = tid; b < wall_nmap + 4; b += nthr) hist[b] = 0u;
-  static_assert(!(WALL && ORDER), "one LDS block behind the rings");
-  const OrderSpec ospec = order_spec<ORDER>(d_arg);
-  if (ORDER) for (int b = tid; b < d_arg.nbins; b += nthr) hist[b] = 0u;
+  if (K::wall) for (int b = tid; b < wall_nmap + 4; b += nthr) hist[b] = 0u;
+  const OrderSpec ospec = order_spec<K::order>(d_arg);
+  if (K::order) for (int b = tid; b < d_arg.nbins; b += nthr) hist[b] = 0u;
   // SCENE: the three blocks one behind the other (SceneLds), where each of the three kernels has its one block at `hist`
   constexpr size_t off_beam = SCENE ? SceneLds::beam : 0, off_baf = SCENE ? SceneLds::baffle : 0;
   constexpr size_t off_park = SCENE ? SceneLds::park : kBeamSrcBytes;
   // PATCH: the table | u32[arrivals (n_patch + 2) | absorbed (n_patch + 2)]
   PatchTab* ptab = reinterpret_cast<PatchTab*>(hist);
   uint32_t* pcnt = reinterpret_cast<uint32_t*>(ptab + 1);
-  const int n_patch = PATCH ? d_arg.xm_nx : 0;
-  if constexpr (PATCH) {
-    if (tid == 65) *ptab = *tab_arg;
+  const int n_patch = K::patch ? d_arg.xm_nx : 0;
+  if constexpr (K::patch) {
+    if (tid == 65) *ptab = *tail.tab;
     if (tid < 2 * (n_patch + 2)) pcnt[tid] = 0u;
   }
   // BEAM: the source
   typedef __attribute__((address_space(3))) BeamSrc LdsBeam;
-  if constexpr (BEAM) {
-    if (tid == (SCENE ? 66 : 65)) *reinterpret_cast<BeamSrc*>(reinterpret_cast<unsigned char*>(hist) + off_beam) = *beam_arg;
+  if constexpr (K::beam) {
+    if (tid == (SCENE ? 66 : 65)) *reinterpret_cast<BeamSrc*>(reinterpret_cast<unsigned char*>(hist) + off_beam) = *tail.beam;
   }
   const volatile LdsBeam& beam = *(const volatile LdsBeam*)(reinterpret_cast<unsigned char*>(hist) + off_beam);
   // ... and behind it, per tracer wave, the parked starts of 64 fresh rays: double[6][64] (kBeamParkBytes)
@@ -3481,50 +3576,22 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   typedef __attribute__((address_space(3))) BaffleTab LdsBaffle;
   uint32_t* bcnt = reinterpret_cast<uint32_t*>(reinterpret_cast<BaffleTab*>(reinterpret_cast<unsigned char*>(hist) + off_baf) + 1);
   int n_baf = 0;
-  if constexpr (BAFFLE) {
-    n_baf = baf_arg->n;   // (a kernel argument: wave-uniform, a scalar register)
-    if (tid == (SCENE ? 67 : 65)) *reinterpret_cast<BaffleTab*>(reinterpret_cast<unsigned char*>(hist) + off_baf) = *baf_arg;
+  if constexpr (K::baffle) {
+    n_baf = tail.baf->n;   // (a kernel argument: wave-uniform, a scalar register)
+    if (tid == (SCENE ? 67 : 65)) *reinterpret_cast<BaffleTab*>(reinterpret_cast<unsigned char*>(hist) + off_baf) = *tail.baf;
     if (tid < 4 * kMaxBaffles) bcnt[tid] = 0u;
   }
   const volatile LdsBaffle& baf = *(const volatile LdsBaffle*)(reinterpret_cast<unsigned char*>(hist) + off_baf);
-  // RESP: the workgroup's u32 block behind the parks (RespSink::lds_words of it; none in the global form)
-  uint32_t* rblk = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(hist) + SceneLds::bytes(n_tracers));
-  if constexpr (RESP) {
-    for (uint32_t b = (uint32_t)tid; b < resp_arg->lds_words; b += (uint32_t)nthr) rblk[b] = 0u;
-  }
-  // VIEW: the workgroup's u32 block behind the parks -- four counters | ViewSink::lds_words of the map (none in the global form)
-  if constexpr (VIEW) {
-    for (uint32_t b = (uint32_t)tid; b < (uint32_t)kViewCounters + view_arg->lds_words; b += (uint32_t)nthr) rblk[b] = 0u;
-  }
-  // FIELD: the workgroup's block behind the parks -- the frame's doubles | u32[5 counters (of 8 words) | PatchFieldSink::lds_words
-  // of the field (none in the global form)]
-  uint32_t* fblk = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(rblk) + sizeof(PatchFieldFrame));
-  const volatile LdsFieldFrame& fframe = *(const volatile LdsFieldFrame*)rblk;
-  if constexpr (FIELD) {
-    if (tid == 68) *reinterpret_cast<PatchFieldFrame*>(rblk) = field_arg->f;
-    for (uint32_t b = (uint32_t)tid; b < (uint32_t)kFieldCtrWords + field_arg->lds_words; b += (uint32_t)nthr) fblk[b] = 0u;
-  }
-  // SORDER: the workgroup's block behind the parks -- u32[kSOrderHead overflow counters | compact slots x SOrderSink::lds_orders]
-  if constexpr (SORDER) {
-    const uint32_t words = (uint32_t)kSOrderHead + (uint32_t)((n_patch + 2) + 2 * n_baf + 3) * sorder_arg->lds_orders;
-    for (uint32_t b = (uint32_t)tid; b < words; b += (uint32_t)nthr) rblk[b] = 0u;
-  }
-  // SPATH: the workgroup's block behind the parks -- double[kPendCap] | double[kResumeCap] (L of the rings' records: written and
-  // read with the records, never cleared) | u64[kSPathHead] checksums | u32[kSPathHead overflow counters | compact slots x
-  // SPathSink::lds_bins]
-  double* pend_L = reinterpret_cast<double*>(rblk);
+  // Map: the workgroup's block behind the parks -- the policy says what lies there.  A build that carries the path length
+  // (LEN) keeps the side arrays of the two rings at the block's start: L of the records of the pending / the resume ring.
+  uint32_t* mblk = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(hist) + SceneLds::bytes(n_tracers));
+  double* pend_L = reinterpret_cast<double*>(mblk);
   double* resume_L = pend_L + kPendCap;
-  unsigned long long* pcks = reinterpret_cast<unsigned long long*>(resume_L + kResumeCap);
-  uint32_t* pblk = reinterpret_cast<uint32_t*>(pcks + kSPathHead);
-  if constexpr (SPATH) {
-    const uint32_t words = (uint32_t)(3 * kSPathHead) + (uint32_t)((n_patch + 2) + 2 * n_baf + 3) * spath_arg->lds_bins;
-    uint32_t* z = reinterpret_cast<uint32_t*>(pcks);
-    for (uint32_t b = (uint32_t)tid; b < words; b += (uint32_t)nthr) z[b] = 0u;
-  }
+  if constexpr (MAP) Map::clear(*tail.map, mblk, n_patch, n_baf, (uint32_t)tid, (uint32_t)nthr);
   if (tid < 8) sstat[tid] = 0ull;
   if (tid == 64) {
     *g_lds = g_arg;
-    if constexpr (BEAM) {   // (fresh rays have no common first boundary)
+    if constexpr (K::beam) {   // (fresh rays have no common first boundary)
       g_lds->q0[0] = 0.0; g_lds->q0[1] = 0.0; g_lds->q0[2] = 0.0;
       g_lds->q0_ok = 0;
     } else {
@@ -3534,9 +3601,9 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       d0.x = g_arg.dir0[0]; d0.y = g_arg.dir0[1]; d0.z = g_arg.dir0[2];
       q0 = s0;
       bool ok = next_hit_s1<true>(h0, g_arg, s0, d0, K_NONE, q0);
-      if constexpr (BAFFLE) {   // the launch's shared first segment: a baffle in its way sends every fresh ray to the assist wave
+      if constexpr (K::baffle) {   // the launch's shared first segment: a baffle in its way sends every fresh ray to the assist wave
         double f0;
-        if (ok && baffle_segment(*baf_arg, n_baf, s0, q0, -1, f0) >= 0) ok = false;
+        if (ok && baffle_segment(*tail.baf, n_baf, s0, q0, -1, f0) >= 0) ok = false;
       }
       g_lds->q0[0] = q0.x; g_lds->q0[1] = q0.y; g_lds->q0[2] = q0.z;
       g_lds->q0_ok = ok ? 1 : 0;
@@ -3563,10 +3630,10 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
     bool drained = false;
     typedef __attribute__((address_space(1))) const uint32_t GlbU32;
     uint32_t n_list = 0;                    // LIST: rays of this launch
-    if constexpr (LIST) n_list = (uint32_t)__builtin_amdgcn_readfirstlane((int)((GlbU32*)list_arg->count)[0]);
+    if constexpr (K::list) n_list = (uint32_t)__builtin_amdgcn_readfirstlane((int)((GlbU32*)tail.list->count)[0]);
     Ray r;
     ray_start(g, r, 0);
-    double L = 0.0;                    // SPATH: the path length of the lane's ray so far
+    double L = 0.0;                    // LEN: the path length of the lane's ray so far
     (void)L;
     bool run = false, hand = false;    // hand: the lane's ray waits to be handed to the assist wave
     // (-DISX_DIAG, tools/diag_trace.py: cycles [16] refill, [17] bounce steps, [18] census, [19] hand-over; [23] trips, [24] lanes
@@ -3594,7 +3661,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           if (mine) {
             const uint4* src = resume_q + 4 * ((hd + rank) & (kResumeCap - 1));
             a = src[0]; b = src[1]; c = src[2]; e = src[3];
-            if constexpr (SPATH) lq = resume_L[(hd + rank) & (kResumeCap - 1)];
+            if constexpr (LEN) lq = resume_L[(hd + rank) & (kResumeCap - 1)];
           }
           __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
           uint32_t won = 0;
@@ -3609,7 +3676,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
             ray_unpack(a, b, c, e, r);
             r.on = K_INNER;
             r.cw[0] = 0u; r.cw[1] = 0u; r.cw[2] = e.z; r.cw[3] = e.w;
-            if constexpr (SPATH) L = lq;
+            if constexpr (LEN) L = lq;
             run = true;
           }
           if (lane == 0) __hip_atomic_fetch_sub(&Q->busy, take, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -3620,7 +3687,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       }
       if (dead) {
         if (next == end) {   // this wave's sub-range is used up: the next one off the launch's queue (persistent_body)
-          const uint32_t n32 = LIST ? n_list : (uint32_t)wk.n;
+          const uint32_t n32 = K::list ? n_list : (uint32_t)wk.n;
           const uint32_t share = (n32 - end) / (2u * (uint32_t)n_tracers * gridDim.x);
           const uint32_t want = share >= wk.sub ? wk.sub : (share > 64u ? share : 64u);
           unsigned long long b64 = 0;
@@ -3631,7 +3698,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           else next = kDry;
           park_base = park_end = next;   // (BEAM: nothing of the new sub-range is parked yet)
         }
-        if constexpr (BEAM) {
+        if constexpr (K::beam) {
           // The source is paid per RAY, not per trip: the next 64 rays of the wave's sub-range are sampled by the whole wave at
           // once -- beam_start and the ray's own first segment (rule S1, rin2 from the LDS geometry), one ray per lane -- and parked
           // in the wave's LDS block; a lane that refills copies its ray from there.  A parked ray is its first wall point q with a
@@ -3648,14 +3715,14 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
                 if constexpr (SCENE) {   // a baffle in the way of the ray's own first segment: parked as its start, the assist wave's
                   double f0;
                   if (next_hit_s1<true>(h, g, t.p, t.v, K_NONE, q) && baffle_segment(baf, n_baf, t.p, q, -1, f0) < 0) {
-                    // SPATH: the first segment's length, while its start is in hand, parked in v.y.  INVARIANT of this build: the
+                    // LEN: the first segment's length, while its start is in hand, parked in v.y.  INVARIANT of this build: the
                     // direction of a fresh ray parked at its first wall point is payload, not a direction -- v.x is the NaN mark,
                     // v.y the length, and the lane's r.v keeps both until the ray's first interaction overwrites r.v (the
                     // Lambertian ray_arrive forms the new direction from the point alone; a ray absorbed there keeps them to its
-                    // census, where SPATH reads no direction).  Nothing may read r.v of such a ray: VIEW and FIELD, which read
-                    // r.v at the census, are excluded from SPATH by assist_body's static_assert, and such a ray is never packed
-                    // into a queue record (it arrives in step 0 of the trip that took it).
-                    if constexpr (SPATH) {
+                    // census).  Nothing may read r.v of such a ray: the record() of a map that carries the length reads no
+                    // direction (PathMap), and such a ray is never packed into a queue record (it arrives in step 0 of the trip
+                    // that took it).
+                    if constexpr (LEN) {
                       double l0 = 0.0;
                       spath_advance(l0, t.p, q);
                       t.v.y = l0;
@@ -3676,7 +3743,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
               r.ido = next + rank; r.j = 0; r.on = K_NONE; r.tgt = false; r.k = 0;
               r.p.x = park[0 * 64 + slot]; r.p.y = park[1 * 64 + slot]; r.p.z = park[2 * 64 + slot];
               r.v.x = park[3 * 64 + slot]; r.v.y = park[4 * 64 + slot]; r.v.z = park[5 * 64 + slot];
-              if constexpr (SPATH) L = r.v.x != r.v.x ? r.v.y : 0.0;   // (at its first wall point: the parked length; else at its start)
+              if constexpr (LEN) L = r.v.x != r.v.x ? r.v.y : 0.0;   // (at its first wall point: the parked length; else at its start)
               run = true;
             }
             __builtin_amdgcn_wave_barrier();
@@ -3688,8 +3755,8 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         } else if (next < end) {
           const uint32_t left = end - next;
           const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(dead >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dead, 0u));
-          if constexpr (LIST) {
-            if (!(run || hand) && rank < left) { ray_start(g, r, ((GlbU32*)list_arg->list)[next + rank]); run = true; }
+          if constexpr (K::list) {
+            if (!(run || hand) && rank < left) { ray_start(g, r, ((GlbU32*)tail.list->list)[next + rank]); run = true; }
           } else {
           if (!(run || hand) && rank < left) { ray_start(g, r, next + rank); run = true; }
           }
@@ -3727,19 +3794,19 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       // (the end of a ray as two flags -- lane masks in scalar registers -- instead of a status word per lane; a tracer lane's ray
       //  sits on the inner sphere unless it is fresh, so Ray::on is neither read nor written in the steps)
       bool ended = false, susp = false;
-      int eslot = 0;   // RESP, VIEW, FIELD, SORDER, SPATH: the class of the arrival that absorbed the lane's ray
+      int eslot = 0;   // MAP: the class of the arrival that absorbed the lane's ray
       (void)eslot;
       auto arrive = [&](const V3& q, auto ph, bool record = true) {
-        if (WALL && record) wall_record(wspec, hist, wall_nmap, K_INNER, r.j, q, 1u);
+        if (K::wall && record) wall_record(wspec, hist, wall_nmap, K_INNER, r.j, q, 1u);
         int st;
-        if constexpr (PATCH) {
+        if constexpr (K::patch) {
           Hot hp = h;
           const int cls = patch_arrive<true>(ptab, n_patch, pcnt, K_INNER, q, hp);
-          if constexpr (SPATH) spath_advance(L, r.p, q);   // (a fresh ray sits at q already -- its parked length is in L: + 0.0)
-          st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(hp, g, r, seed, first, K_INNER, q);
+          if constexpr (LEN) spath_advance(L, r.p, q);   // (a fresh ray sits at q already -- its parked length is in L: + 0.0)
+          st = ray_arrive<false, LEAN, K::chord, decltype(ph)::value, false, K::surf>(hp, g, r, seed, first, K_INNER, q);
           if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
-          if constexpr (RESP || VIEW || FIELD || SORDER || SPATH) { if (st == ST_ABSORBED) eslot = cls; }
-        } else st = ray_arrive<false, LEAN, CH, decltype(ph)::value, false, SURF>(h, g, r, seed, first, K_INNER, q);
+          if constexpr (MAP) { if (st == ST_ABSORBED) eslot = cls; }
+        } else st = ray_arrive<false, LEAN, K::chord, decltype(ph)::value, false, K::surf>(h, g, r, seed, first, K_INNER, q);
         if (st != 0) { run = false; ended = true; susp = st == ST_SUSPENDED; }
       };
       // SURF_LOBE: one TRY of the lobe's rejection sampler for every lane that is in an interaction (Ray::k != 0)
@@ -3769,7 +3836,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
             else { hand = true; run = false; }
           } else if (next_hit_s1<false>(h, g, r.p, r.v, K_INNER, q)) arrived = true;
           else { hand = true; run = false; }
-          if (WALL) {   // (the first strikes of the wave's fresh rays: one point, added by one lane)
+          if (K::wall) {   // (the first strikes of the wave's fresh rays: one point, added by one lane)
             const unsigned long long fm = __ballot(arrived && fresh);
             if (fm && lane == __builtin_ctzll(fm)) wall_record(wspec, hist, wall_nmap, K_INNER, 0u, q, (uint32_t)__popcll(fm));
             if (arrived && !fresh) wall_record(wspec, hist, wall_nmap, K_INNER, r.j, q, 1u);
@@ -3788,8 +3855,8 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         lobe_try_pending();
       };
       auto hot_search = [&](V3& q) -> bool {
-        if (CH != 0 && r.tgt) return chord_arrive<true>(h, r, q);
-        if constexpr (BAFFLE) {   // a segment that strikes a baffle is the assist wave's: the ray stays where it is
+        if (K::chord != 0 && r.tgt) return chord_arrive<true>(h, r, q);
+        if constexpr (K::baffle) {   // a segment that strikes a baffle is the assist wave's: the ray stays where it is
           if (!next_hit_s1<false>(h, g, r.p, r.v, K_INNER, q)) return false;
           double f;
           return baffle_segment(baf, n_baf, r.p, q, -1, f) < 0;
@@ -3797,7 +3864,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         return next_hit_s1<false>(h, g, r.p, r.v, K_INNER, q);
       };
       if (next == kDry) { ISX_TD_ADD(14, 1); ISX_TD_ADD(15, __popcll(__ballot(run))); }   // (-DISX_DIAG: trips after the launch's queue ran dry)
-      if constexpr (SURF == SURF_LOBE) {
+      if constexpr (K::surf == SURF_LOBE) {
         ISX_TD_ADD(4, __popcll(__ballot(run)));
         lobe_step(true);
         static_steps<1, kStepsPerTrip>([&](auto rep) {
@@ -3814,7 +3881,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         if (run) {
           const bool fresh = r.j == 0u && !r.scattered();   // (a ray that returns from the assist wave has interactions behind it)
           if (fresh) {
-            if constexpr (BEAM) {   // parked with its first segment done: at its first wall point (NaN in v.x), or to be handed over
+            if constexpr (K::beam) {   // parked with its first segment done: at its first wall point (NaN in v.x), or to be handed over
               if (r.v.x != r.v.x) { q = r.p; arrived = true; }
               else { hand = true; run = false; }
             } else {
@@ -3824,7 +3891,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           } else if (hot_search(q)) arrived = true;
           else { hand = true; run = false; }
         }
-        if (WALL) {   // the first strikes of a wave's fresh rays are one point: counted per wave and added to its bin by one lane
+        if (K::wall) {   // the first strikes of a wave's fresh rays are one point: counted per wave and added to its bin by one lane
           const unsigned long long fm = __ballot(first_strike);
           if (fm && lane == __builtin_ctzll(fm)) wall_record(wspec, hist, wall_nmap, K_INNER, 0u, q, (uint32_t)__popcll(fm));
         }
@@ -3843,7 +3910,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       }
       ISX_TD_MARK(1);
       // ---- rays that ended on the inner sphere (absorbed, suspended): census, or the BRDF re-scatter of a primary
-      if (RESC && ended && h.source_model == 1 && !r.scattered()) {
+      if (K::rescatter && ended && h.source_model == 1 && !r.scattered()) {
         n_wall += r.j;
         r.on = K_INNER;                  // (a primary ends on the inner sphere here: the re-scattered ray starts there and runs on)
         ray_rescatter(g, r, seed, first);
@@ -3854,12 +3921,9 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         if (ended) {
           n_wall += r.j;
           if (n_wall > 0x7fffffffu) { atomicAdd(&sstat[6], (unsigned long long)n_wall); n_wall = 0; }
-          if (ORDER) order_record(ospec, hist, false, false, susp, r.j, 0.0);
-          if constexpr (RESP) resp_record(*resp_arg, rblk, n_patch, n_baf, susp ? kRespSuspended : eslot, seed, first + (uint64_t)r.offset());
-          if constexpr (VIEW) { if (!susp && eslot == view_arg->patch) view_record(*view_arg, rblk, r.j, r.v); }
-          if constexpr (FIELD) { if (!susp && eslot == field_arg->patch) field_record(*field_arg, fframe, fblk, r.j, r.p, r.v); }
-          if constexpr (SORDER) sorder_record(*sorder_arg, rblk, n_patch, n_baf, susp ? kRespSuspended : eslot, r.j);
-          if constexpr (SPATH) spath_record(*spath_arg, pcks, pblk, n_patch, n_baf, susp ? kRespSuspended : eslot, L);
+          if (K::order) order_record(ospec, hist, false, false, susp, r.j, 0.0);
+          if constexpr (Map::selects) { if (!susp && Map::selected(*tail.map, eslot)) Map::record(*tail.map, mblk, r); }
+          else if constexpr (MAP) Map::record(*tail.map, mblk, MapEnd{susp ? ST_SUSPENDED : ST_ABSORBED, false, false, eslot, r, L, seed, first, n_patch, n_baf});
         }
         const unsigned long long me = __ballot(ended);
         if (me) {
@@ -3890,7 +3954,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
             const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
             // (the surface the ray sits on: none for a fresh ray -- Geom::q0_ok = 0 --, else the inner sphere)
             ray_pack(pend_q + 4 * ((base + rank) & (kPendCap - 1)), r, (r.j == 0u && !r.scattered()) ? (uint32_t)K_NONE : (uint32_t)K_INNER, 0u);
-            if constexpr (SPATH) pend_L[(base + rank) & (kPendCap - 1)] = L;
+            if constexpr (LEN) pend_L[(base + rank) & (kPendCap - 1)] = L;
             hand = false;
           }
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -3932,13 +3996,13 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
           if (ok) {
             // (a queue record has no room for a try count: a lane that is in the middle of an interaction finishes its tries first)
-            if constexpr (SURF == SURF_LOBE) { while (__ballot(run && r.k != 0u) != 0ull) lobe_try_pending(); }
+            if constexpr (K::surf == SURF_LOBE) { while (__ballot(run && r.k != 0u) != 0ull) lobe_try_pending(); }
             if (run) {
               const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(live >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)live, 0u));
               // (the record the assist wave writes for a ray that returns: at the top of a trip a lane with an odd interaction
               //  count holds words 2-3 of its block j/2 in cw[2..3] -- bounce_words)
               ray_pack(resume_q + 4 * ((base + rank) & (kResumeCap - 1)), r, r.cw[2], r.cw[3]);
-              if constexpr (SPATH) resume_L[(base + rank) & (kResumeCap - 1)] = L;
+              if constexpr (LEN) resume_L[(base + rank) & (kResumeCap - 1)] = L;
               run = false;
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -3999,15 +4063,15 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       const bool have = (uint32_t)lane < take;
       Ray r;
       ray_start(g, r, 0);
-      double L = 0.0;       // SPATH: the path length of the lane's ray so far
+      double L = 0.0;       // LEN: the path length of the lane's ray so far
       (void)L;
       if (have) {
         const uint4* src = pend_q + 4 * ((hd + (uint32_t)lane) & (kPendCap - 1));
         const uint4 a = src[0], b = src[1], c = src[2], e = src[3];
         ray_unpack(a, b, c, e, r);
         r.on = (int)e.z;
-        if constexpr (SPATH) L = pend_L[(hd + (uint32_t)lane) & (kPendCap - 1)];
-        if constexpr (BAFFLE) r.tgt = false;   // (explicit bounces only: the flag's bit is never set, and need not be carried)
+        if constexpr (LEN) L = pend_L[(hd + (uint32_t)lane) & (kPendCap - 1)];
+        if constexpr (K::baffle) r.tgt = false;   // (explicit bounces only: the flag's bit is never set, and need not be carried)
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");          // (the slots are free once they have been read)
       if (lane == 0) add(&Q->pend_head, take);
@@ -4019,27 +4083,27 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       bool go = have;
       bool given = false;   // BAFFLE: the ray went back to the tracers from inside the step loop
       (void)given;
-      int eslot = 0;        // RESP, VIEW, FIELD, SORDER, SPATH: the slot of the interaction that absorbed the lane's ray (a wall class, or a baffle's side)
+      int eslot = 0;        // MAP: the slot of the interaction that absorbed the lane's ray (a wall class, or a baffle's side)
       (void)eslot;
       for (;;) {
         if (go) {
           V3 q;
           int kind;
-          if constexpr (BAFFLE) {
+          if constexpr (K::baffle) {
             // (a tracer hands over a ray whose segment strikes a baffle with rule S1' intact, and a ray that leaves a baffle is a
             //  fresh ray at an interior point: the whole search of the end-state kernel, rule S1 first)
             kind = next_hit(h, g, r.p, r.v, baffle_on(r.on), q);
           } else {
-          if (CH != 0 && r.tgt) chord_leave(r);
+          if (K::chord != 0 && r.tgt) chord_leave(r);
           else if (r.on == K_INNER) unit_dir(r.v);   // handed over by a tracer whose rule S1' failed: unit direction from here on
           kind = next_hit_generic(g, r.p, r.v, r.on, q);
           }
-          if (WALL && kind != K_BOX) wall_record(wspec, hist, wall_nmap, kind, r.j, q, 1u);
+          if (K::wall && kind != K_BOX) wall_record(wspec, hist, wall_nmap, kind, r.j, q, 1u);
           if constexpr (SCENE) {   // the baffle's interaction, or the class of the wall's arrival and then the wall's interaction
             double bf;
             const int ks = baffle_segment(baf, n_baf, r.p, q, baffle_skip(r.on), bf);
             if (ks >= 0) {
-              if constexpr (SPATH) {
+              if constexpr (LEN) {
                 const V3 x = baffle_point(r.p, q, bf);
                 spath_advance(L, r.p, x);
                 r.p = x;
@@ -4048,26 +4112,26 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
               atomicAdd(&bcnt[ks], 1u);
               st = baffle_arrive(baf, h, r, seed, first, ks >> 1, ks & 1);
               if (st == ST_ABSORBED) atomicAdd(&bcnt[2 * kMaxBaffles + ks], 1u);
-              if constexpr (RESP || VIEW || FIELD || SORDER || SPATH) eslot = kRespBaffle0 + ks;
+              if constexpr (MAP) eslot = kRespBaffle0 + ks;
             } else {
               Hot hp = h;
               int cls = 0;
               if (kind != K_BOX) cls = patch_arrive<false>(ptab, n_patch, pcnt, kind, q, hp);
-              if constexpr (SPATH) {   // (the leg to the world box is not counted: the exit's tail is formed here, with both points in hand)
+              if constexpr (LEN) {   // (the leg to the world box is not counted: the exit's tail is formed here, with both points in hand)
                 if (kind != K_BOX) spath_advance(L, r.p, q);
                 else if (q.z < portz) spath_exit_tail(L, r.p, q, portz);
               }
-              st = ray_arrive<false, LEAN, CH, PH_DIRECT, true, SURF>(hp, g, r, seed, first, kind, q);
+              st = ray_arrive<false, LEAN, K::chord, PH_DIRECT, true, K::surf>(hp, g, r, seed, first, kind, q);
               if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
-              if constexpr (RESP || VIEW || FIELD || SORDER || SPATH) eslot = cls;
+              if constexpr (MAP) eslot = cls;
             }
-          } else if constexpr (PATCH) {
+          } else if constexpr (K::patch) {
             Hot hp = h;
             int cls = 0;
             if (kind != K_BOX) cls = patch_arrive<false>(ptab, n_patch, pcnt, kind, q, hp);
-            st = ray_arrive<false, LEAN, CH, PH_DIRECT, true, SURF>(hp, g, r, seed, first, kind, q);
+            st = ray_arrive<false, LEAN, K::chord, PH_DIRECT, true, K::surf>(hp, g, r, seed, first, kind, q);
             if (st == ST_ABSORBED) atomicAdd(&pcnt[n_patch + 2 + cls], 1u);
-          } else if constexpr (BAFFLE) {
+          } else if constexpr (K::baffle) {
             double bf;
             const int ks = baffle_segment(baf, n_baf, r.p, q, baffle_skip(r.on), bf);
             if (ks >= 0) {   // the segment ends on the baffle: its interaction instead of the boundary's
@@ -4076,18 +4140,18 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
               st = baffle_arrive(baf, h, r, seed, first, ks >> 1, ks & 1);
               if (st == ST_ABSORBED) atomicAdd(&bcnt[2 * kMaxBaffles + ks], 1u);
             } else {
-              st = ray_arrive<false, LEAN, CH, PH_DIRECT, true, SURF>(h, g, r, seed, first, kind, q);
+              st = ray_arrive<false, LEAN, K::chord, PH_DIRECT, true, K::surf>(h, g, r, seed, first, kind, q);
             }
           } else
-          st = ray_arrive<DISC || PP == 2, LEAN, CH, PH_DIRECT, true, SURF>(h, g, r, seed, first, kind, q);   // (DISC: r.prev = start of this segment)
-          if (RESC && st != 0 && h.source_model == 1 && !r.scattered()) {   // nonLambertianFlux.C:253-268
+          st = ray_arrive<K::disc || K::perpos == 2, LEAN, K::chord, PH_DIRECT, true, K::surf>(h, g, r, seed, first, kind, q);   // (DISC: r.prev = start of this segment)
+          if (K::rescatter && st != 0 && h.source_model == 1 && !r.scattered()) {   // nonLambertianFlux.C:253-268
             n_wall += r.j;
             ray_rescatter(g, r, seed, first);
             st = 0;
           }
-          if (st != 0 || (!BAFFLE && r.on == K_INNER)) go = false;
+          if (st != 0 || (!K::baffle && r.on == K_INNER)) go = false;
         }
-        if constexpr (BAFFLE) {
+        if constexpr (K::baffle) {
           // This wave never WAITS for room in the resume ring.  With baffles most rays it is handed come back alive, so that ring
           // fills; the tracer lanes take from it only when they are free, and a lane whose segment strikes a baffle is not free
           // until this wave has taken its ray off the pending ring: with both rings full and every lane holding such a ray a wait
@@ -4120,7 +4184,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
                   cw2 = wv[2]; cw3 = wv[3];
                 }
                 ray_pack(resume_q + 4 * ((pubr + rank) & (kResumeCap - 1)), r, cw2, cw3);
-                if constexpr (SPATH) resume_L[(pubr + rank) & (kResumeCap - 1)] = L;
+                if constexpr (LEN) resume_L[(pubr + rank) & (kResumeCap - 1)] = L;
                 go = false; given = true;
               }
               __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -4147,7 +4211,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         if (go) {
           const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(gm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)gm, 0u));
           ray_pack(pend_q + 4 * ((base + rank) & (kPendCap - 1)), r, (uint32_t)r.on, 0u);
-          if constexpr (SPATH) pend_L[(base + rank) & (kPendCap - 1)] = L;
+          if constexpr (LEN) pend_L[(base + rank) & (kPendCap - 1)] = L;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         if (lane == 0) add(&Q->pend_pub, cnt);
@@ -4159,33 +4223,18 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       const bool below = exited && (r.p.z < portz);                   // isRayPassingThroughExitPort, fluxAtObserver.C:162-166
       if (ended) n_wall += r.j;
       if (n_wall > 0x7fffffffu) { atomicAdd(&sstat[6], (unsigned long long)n_wall); n_wall = 0; }
-      if (ORDER && ended) order_record(ospec, hist, exited, below, st == ST_SUSPENDED, r.j, r.v.z);
-      if constexpr (RESP) {
-        if (ended) resp_record(*resp_arg, rblk, n_patch, n_baf,
-                               exited ? (below ? kRespPort : kRespPort + 1) : st == ST_SUSPENDED ? kRespSuspended : eslot, seed,
-                               first + (uint64_t)r.offset());
-      }
-      if constexpr (VIEW) {   // (a baffle's side is a slot above every wall class: never the selected one)
-        if (ended && st == ST_ABSORBED && eslot == view_arg->patch) view_record(*view_arg, rblk, r.j, r.v);
-      }
-      if constexpr (FIELD) {   // (likewise)
-        if (ended && st == ST_ABSORBED && eslot == field_arg->patch) field_record(*field_arg, fframe, fblk, r.j, r.p, r.v);
-      }
-      if constexpr (SORDER) {
-        if (ended) sorder_record(*sorder_arg, rblk, n_patch, n_baf,
-                                 exited ? (below ? kRespPort : kRespPort + 1) : st == ST_SUSPENDED ? kRespSuspended : eslot, r.j);
-      }
-      if constexpr (SPATH) {
-        if (ended) spath_record(*spath_arg, pcks, pblk, n_patch, n_baf,
-                                exited ? (below ? kRespPort : kRespPort + 1) : st == ST_SUSPENDED ? kRespSuspended : eslot, L);
+      if (K::order && ended) order_record(ospec, hist, exited, below, st == ST_SUSPENDED, r.j, r.v.z);
+      if constexpr (MAP) {
+        if constexpr (Map::selects) { if (ended && st == ST_ABSORBED && Map::selected(*tail.map, eslot)) Map::record(*tail.map, mblk, r); }
+        else if (ended) Map::record(*tail.map, mblk, MapEnd{st, exited, below, eslot, r, L, seed, first, n_patch, n_baf});
       }
       const uint32_t c_ended = (uint32_t)__popcll(__ballot(ended));
       n_ended += c_ended;
       n_exited += (uint32_t)__popcll(__ballot(exited));
       n_susp += (uint32_t)__popcll(__ballot(have && st == ST_SUSPENDED));
       n_counted += (uint32_t)__popcll(__ballot(below));
-      const bool keep = (DISC || PP == 2) ? exited : below;           // what goes to the binning kernel (or is binned here: PP)
-      if (PP != 0) {
+      const bool keep = (K::disc || K::perpos == 2) ? exited : below;           // what goes to the binning kernel (or is binned here: PP)
+      if (K::perpos != 0) {
         // persistent_body's SINK_PERPOS / SINK_DISCPOS, per lane: the ray's own detector group (disc) only
         bool hit0 = false, hit1 = false;
         int b0 = 0, b1 = 0;
@@ -4194,7 +4243,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
           uint64_t grp = (uint64_t)((double)rel / (double)rpg);
           if (grp * rpg > rel) grp--;
           else if ((grp + 1) * rpg <= rel) grp++;
-          if (PP == 1) {
+          if (K::perpos == 1) {
             const double* table = d_arg.table;
             const V3 lp = r.p, lv = r.v;
             if (d_arg.fold == 2) {
@@ -4217,8 +4266,8 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         if (hit1) atomicAdd(&wk.hist[b1], 1ull);
         n_inc += (unsigned long long)__popcll(__ballot(hit0)) + (unsigned long long)__popcll(__ballot(hit1));
       }
-      const unsigned long long m = (PP != 0 || WALL || ORDER || (PATCH && !SCENE)) ? 0ull : __ballot(keep);
-      if (!RESP && !VIEW && !FIELD && !SORDER && !SPATH && m) {   // (RESP, VIEW, FIELD, SORDER, SPATH: no exit lines -- the response / the view / the field / the histograms are the build's one sink, no kernel follows)
+      const unsigned long long m = (K::perpos != 0 || K::wall || K::order || (K::patch && !SCENE)) ? 0ull : __ballot(keep);
+      if (Map::lines && m) {   // (a scene map is the build's one sink: no exit lines, no kernel follows)
         const uint32_t cnt = (uint32_t)__popcll(m);
         if (cnt > reg_left) {   // close the open region, reserve the next one (kRegion)
           if (lane == 0 && reg_id != 0xffffffffu) d_arg.rec_counts[reg_id] = kRegion - reg_left;
@@ -4230,7 +4279,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
         if (keep) {
           const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
           const uint64_t slot = (uint64_t)reg_id * kRegion + (uint64_t)(reg_slot + rank);
-          if (DISC) {   // forward exit segment: start, direction, length (bin_discs' own expression)
+          if (K::disc) {   // forward exit segment: start, direction, length (bin_discs' own expression)
             V3 dl; dl.x = r.p.x - r.prev.x; dl.y = r.p.y - r.prev.y; dl.z = r.p.z - r.prev.z;
             double2* dst = reinterpret_cast<double2*>(d_arg.rec_lines + 8ull * slot);
             dst[0] = make_double2(r.prev.x, r.prev.y); dst[1] = make_double2(r.prev.z, r.v.x); dst[2] = make_double2(r.v.y, r.v.z);
@@ -4248,7 +4297,7 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
       // (BAFFLE: every ray that goes on was given back or requeued inside the step loop -- `back` is false in every lane, this
       //  block is dead in that build, and its wait is the one that build must not have.  The other builds' expression is left
       //  exactly as it was: one more operand changed the code of every older kernel.)
-      const bool back = BAFFLE ? false : (have && st == 0 && !requeued);
+      const bool back = K::baffle ? false : (have && st == 0 && !requeued);
       const unsigned long long bm = __ballot(back);
       if (bm) {
         const uint32_t cnt = (uint32_t)__popcll(bm);
@@ -4301,26 +4350,26 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   // ---- census (persistent_body's epilogue)
   atomicAdd(&sstat[6], (unsigned long long)n_wall);
   if (lane == 0) {
-    if (PP != 0 && n_inc) atomicAdd(&sstat[5], n_inc);
+    if (K::perpos != 0 && n_inc) atomicAdd(&sstat[5], n_inc);
     atomicAdd(&sstat[1], (unsigned long long)n_exited);
     atomicAdd(&sstat[2], (unsigned long long)n_counted);
     atomicAdd(&sstat[3], (unsigned long long)(n_ended - n_exited - n_susp));  // absorbed
     atomicAdd(&sstat[4], (unsigned long long)n_susp);
     atomicAdd(&sstat[0], (unsigned long long)n_taken);
-    if constexpr (RESP) atomicAdd(&sstat[5], (unsigned long long)n_ended);   // bin_increments: one per ended ray
+    if constexpr (Map::ends_binned) atomicAdd(&sstat[5], (unsigned long long)n_ended);   // bin_increments: one per ended ray
   }
   __syncthreads();
   // (BEAM: the thread index rebuilt from the wave's number -- a scalar -- and the lane's rank in the wave: kept from the kernel's
   //  entry for these last lines it is the one register more than the parking of the fresh rays leaves, and went to scratch)
   uint32_t tid_end = (uint32_t)tid;
-  if constexpr (BEAM || BAFFLE) tid_end = beam_wave * 64u + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  if constexpr (K::beam || K::baffle) tid_end = beam_wave * 64u + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   if (tid_end == 0u && Q->failed) atomicAdd(&wk.stats[7], (unsigned long long)Q->failed);
-  if (WALL) {   // one flush of the workgroup's map; binned = its increments
+  if (K::wall) {   // one flush of the workgroup's map; binned = its increments
     const unsigned long long flushed = wall_flush(d_arg, hist, tid, nthr);
     if (flushed) atomicAdd(&sstat[5], flushed);
     __syncthreads();
   }
-  if (ORDER) {   // one flush of the workgroup's block; bin_increments = the histograms' increments
+  if (K::order) {   // one flush of the workgroup's block; bin_increments = the histograms' increments
     const unsigned long long flushed = order_flush(d_arg, hist, tid, nthr);
     if (flushed) atomicAdd(&sstat[5], flushed);
     __syncthreads();
@@ -4328,78 +4377,28 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
   if constexpr (SCENE) {   // one flush of the workgroup's counters (bin_increments is the binning kernel's: the histogram's sum)
     (void)patch_flush(d_arg, pcnt);
   } else
-  if constexpr (PATCH) {   // one flush of the workgroup's counters; bin_increments = the arrivals on the patches
+  if constexpr (K::patch) {   // one flush of the workgroup's counters; bin_increments = the arrivals on the patches
     const unsigned long long flushed = patch_flush(d_arg, pcnt);
     if (flushed) atomicAdd(&sstat[5], flushed);
     __syncthreads();
   }
-  if constexpr (RESP) resp_flush(*resp_arg, rblk, n_patch, n_baf, tid_end, (uint32_t)blockDim.x);   // (the global form: nothing to flush)
-  if constexpr (VIEW) {   // one flush of the workgroup's map, then of its four counters; bin_increments = binned
-    const uint32_t flushed = view_flush(*view_arg, rblk, tid_end, (uint32_t)blockDim.x);
-    if (flushed) atomicAdd(&rblk[kViewBinned], flushed);
-    __syncthreads();
-    if (tid_end < (uint32_t)kViewCounters) {
-      const uint32_t c = rblk[tid_end];
-      if (c) global_add_u64(view_arg->counts + tid_end, (unsigned long long)c);
-      if (tid_end == (uint32_t)kViewBinned && c) atomicAdd(&sstat[5], (unsigned long long)c);
-    }
-    __syncthreads();
-  }
-  if constexpr (FIELD) {   // one flush of the workgroup's field, then of its five counters; bin_increments = binned
-    const uint32_t flushed = field_flush(*field_arg, fblk, tid_end, (uint32_t)blockDim.x);
-    if (flushed) atomicAdd(&fblk[kFieldBinned], flushed);
-    __syncthreads();
-    if (tid_end < (uint32_t)kFieldCounters) {
-      const uint32_t c = fblk[tid_end];
-      if (c) global_add_u64(field_arg->counts + tid_end, (unsigned long long)c);
-      if (tid_end == (uint32_t)kFieldBinned && c) atomicAdd(&sstat[5], (unsigned long long)c);
-    }
-    __syncthreads();
-  }
-  if constexpr (SORDER) {   // one flush of the workgroup's low orders and of its overflow counters; bin_increments = the histograms' sum:
-    sorder_flush(*sorder_arg, rblk, n_patch, n_baf, tid_end, (uint32_t)blockDim.x);   // every ended ray of the workgroup that did not overflow
-    if (tid_end < (uint32_t)kRespFates) {
-      const uint32_t c = rblk[tid_end];
-      if (c) global_add_u64(sorder_arg->overflow + tid_end, (unsigned long long)c);
-    }
-    if (tid_end == 64u) {   // (the census of the workgroup is complete behind the barrier above: exited + absorbed + suspended = ended)
-      unsigned long long over = 0ull;
-      for (int f = 0; f < kRespFates; ++f) over += (unsigned long long)rblk[f];
-      sstat[5] = sstat[1] + sstat[3] + sstat[4] - over;
-    }
-    __syncthreads();
-  }
-  if constexpr (SPATH) {   // one flush of the workgroup's low bins, its overflow counters and its checksums; bin_increments as SORDER's
-    spath_flush(*spath_arg, pblk, n_patch, n_baf, tid_end, (uint32_t)blockDim.x);
-    if (tid_end < (uint32_t)kRespFates) {
-      const uint32_t c = pblk[tid_end];
-      if (c) global_add_u64(spath_arg->counts + tid_end, (unsigned long long)c);
-      const unsigned long long k = pcks[tid_end];
-      if (k) global_add_u64(spath_arg->counts + (uint32_t)kRespFates + tid_end, k);
-    }
-    if (tid_end == 64u) {
-      unsigned long long over = 0ull;
-      for (int f = 0; f < kRespFates; ++f) over += (unsigned long long)pblk[f];
-      sstat[5] = sstat[1] + sstat[3] + sstat[4] - over;
-    }
-    __syncthreads();
-  }
-  if constexpr (BAFFLE) {   // one flush of the workgroup's counters (the thread index rebuilt, as the beam kernel's)
+  if constexpr (MAP) Map::flush(*tail.map, mblk, n_patch, n_baf, tid_end, (uint32_t)blockDim.x, sstat);
+  if constexpr (K::baffle) {   // one flush of the workgroup's counters (the thread index rebuilt, as the beam kernel's)
     uint32_t t3 = tid_end;
     asm volatile("" : "+v"(t3));
     if (t3 < (uint32_t)(4 * kMaxBaffles)) {
       const uint32_t c = bcnt[t3];
-      if (c) global_add_u64(baf_arg->counts + t3, (unsigned long long)c);
+      if (c) global_add_u64(tail.baf->counts + t3, (unsigned long long)c);
     }
   }
   {
     uint32_t t2 = threadIdx.x;
-    if constexpr (BEAM || BAFFLE) t2 = tid_end;
+    if constexpr (K::beam || K::baffle) t2 = tid_end;
     asm volatile("" : "+v"(t2));
     if (t2 < 7u) {
       const unsigned long long c = sstat[t2];
       if (c) atomicAdd(&wk.stats[t2], c);
-      if (WALL && t2 == 5u && c) global_add_u64(d_arg.xm_counts, c);
+      if (K::wall && t2 == 5u && c) global_add_u64(d_arg.xm_counts, c);
     }
   }
 }
@@ -4408,49 +4407,60 @@ __device__ __forceinline__ void assist_body(const Geom& g_arg, const DetGrid& d_
 #define ISX_ASSIST_BLOCK 768
 #endif
 #define ISX_ASSIST_ATTR __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(6, 6)))
+// the kernels' traits: what each has that isx_trace_assist_kernel has not
+struct KChord : KDefault { static constexpr int chord = 1; };
+struct KBrdf : KDefault { static constexpr bool rescatter = true; };
+struct KDisc : KDefault { static constexpr bool disc = true; };
+struct KPerpos : KDefault { static constexpr int perpos = 1; };
+struct KDiscpos : KDefault { static constexpr int perpos = 2; };
+struct KPatch : KDefault { static constexpr bool patch = true; };
+struct KBeam : KDefault { static constexpr bool beam = true; };
+struct KBaffle : KDefault { static constexpr bool baffle = true; };
+struct KList : KDefault { static constexpr bool list = true; };
+struct KScene : KDefault { static constexpr bool patch = true, beam = true, baffle = true; };
+template <class M> struct KSceneMap : KScene { using Map = M; };
+template <class B> struct Wall : B { static constexpr bool wall = true; };     // ... of kernel B with the wall map
+template <class B> struct Order : B { static constexpr bool order = true; };   // ... with the bounce-order histograms
+template <class B> struct Lobe : B { static constexpr int surf = SURF_LOBE; };
+template <class B> struct Rough : B { static constexpr int surf = SURF_ROUGH; };
+
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false>(g, d, wk); }
+isx_trace_assist_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<KDefault>(g, d, wk); }
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_chord_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<1, false>(g, d, wk); }
+isx_trace_assist_chord_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<KChord>(g, d, wk); }
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_brdf_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, true>(g, d, wk); }
+isx_trace_assist_brdf_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<KBrdf>(g, d, wk); }
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_disc_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, true>(g, d, wk); }
+isx_trace_assist_disc_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<KDisc>(g, d, wk); }
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_perpos_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 1>(g, d, wk); }
+isx_trace_assist_perpos_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<KPerpos>(g, d, wk); }
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_discpos_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 2>(g, d, wk); }
+isx_trace_assist_discpos_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<KDiscpos>(g, d, wk); }
 // the wall map (isx_wall_map): the same kernels with the binning at every arrival and the workgroup's u32 map behind the rings
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_wall_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_LAMBERT, true>(g, d, wk); }
+isx_trace_assist_wall_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<Wall<KDefault>>(g, d, wk); }
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_wall_chord_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<1, false, false, 0, SURF_LAMBERT, true>(g, d, wk); }
+isx_trace_assist_wall_chord_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<Wall<KChord>>(g, d, wk); }
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_wall_brdf_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, true, false, 0, SURF_LAMBERT, true>(g, d, wk); }
+isx_trace_assist_wall_brdf_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<Wall<KBrdf>>(g, d, wk); }
 // the bounce-order histograms (isx_order_hist): the same kernels with one LDS add per ended ray and the workgroup's u32 block
 // behind the rings
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_order_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_LAMBERT, false, true>(g, d, wk); }
+isx_trace_assist_order_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<Order<KDefault>>(g, d, wk); }
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_order_chord_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<1, false, false, 0, SURF_LAMBERT, false, true>(g, d, wk); }
+isx_trace_assist_order_chord_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<Order<KChord>>(g, d, wk); }
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_order_brdf_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, true, false, 0, SURF_LAMBERT, false, true>(g, d, wk); }
+isx_trace_assist_order_brdf_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<Order<KBrdf>>(g, d, wk); }
 // the wall patches (isx_wall_patches): the lean explicit kernel with a class and a reflectance per arrival; the patches are a
 // fourth argument
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_patch_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab) {
-  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true>(g, d, wk, &tab);
-}
+isx_trace_assist_patch_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab) { assist_body<KPatch>(g, d, wk, {&tab}); }
 // the beam source (isx_fluxmap_beam): isx_trace_assist_kernel with a sampled start per fresh ray; the source is a fourth argument
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_beam_kernel(const Geom g, const DetGrid d, const Work wk, const BeamSrc beam) {
-  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, false, true>(g, d, wk, nullptr, &beam);
-}
+isx_trace_assist_beam_kernel(const Geom g, const DetGrid d, const Work wk, const BeamSrc beam) { assist_body<KBeam>(g, d, wk, {&beam}); }
 // baffles (isx_fluxmap_baffle): isx_trace_assist_kernel with every segment tested against the discs; the table is a fourth argument
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_baffle_kernel(const Geom g, const DetGrid d, const Work wk, const BaffleTab baf) {
-  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, false, false, false, true>(g, d, wk, nullptr, nullptr, nullptr, &baf);
-}
+isx_trace_assist_baffle_kernel(const Geom g, const DetGrid d, const Work wk, const BaffleTab baf) { assist_body<KBaffle>(g, d, wk, {&baf}); }
 // the scene (isx_fluxmap_scene): beam source, baffles and wall patches in one trace -- the three kernels above in one; the three
 // tables are its fourth to sixth arguments
 // (the three kernels sit at 80 VGPRs each; the three in one kept 12 B of scratch there: five waves per SIMD, and 640-thread
@@ -4458,56 +4468,41 @@ isx_trace_assist_baffle_kernel(const Geom g, const DetGrid d, const Work wk, con
 #ifndef ISX_SCENE_WAVES
 #define ISX_SCENE_WAVES 5
 #endif
-extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_SCENE_WAVES, ISX_SCENE_WAVES)))
+#define ISX_SCENE_ATTR __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_SCENE_WAVES, ISX_SCENE_WAVES)))
+extern "C" __global__ void ISX_SCENE_ATTR
 isx_trace_assist_scene_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab, const BeamSrc beam, const BaffleTab baf) {
-  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true>(g, d, wk, &tab, &beam, nullptr, &baf);
+  assist_body<KScene>(g, d, wk, {&tab, &beam, &baf});
 }
-// the scene response (isx_scene_response): the scene kernel with one add per ended ray -- its fate, binned over the source's sample
-// space (resp_record) -- and no exit lines; the sink is a seventh argument
-extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_SCENE_WAVES, ISX_SCENE_WAVES)))
+// the scene maps: the scene kernel with a map as its one sink and no exit lines (ResponseMap, ViewMap, PatchFieldMap, OrderMap,
+// PathMap); the sink is a seventh argument
+extern "C" __global__ void ISX_SCENE_ATTR
 isx_trace_assist_scene_response_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab, const BeamSrc beam, const BaffleTab baf,
                                        const RespSink resp) {
-  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true, true>(g, d, wk, &tab, &beam, nullptr, &baf, &resp);
+  assist_body<KSceneMap<ResponseMap>>(g, d, wk, {&tab, &beam, &baf, &resp});
 }
-// the scene view (isx_scene_view): the scene kernel with one add per ray absorbed on the selected wall class -- the direction it
-// arrived from, binned in the detector's frame (view_record) -- and no exit lines; the sink is a seventh argument
-extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_SCENE_WAVES, ISX_SCENE_WAVES)))
+extern "C" __global__ void ISX_SCENE_ATTR
 isx_trace_assist_scene_view_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab, const BeamSrc beam, const BaffleTab baf,
                                    const ViewSink view) {
-  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true, false, true>(g, d, wk, &tab, &beam, nullptr, &baf, nullptr,
-                                                                                                   &view);
+  assist_body<KSceneMap<ViewMap>>(g, d, wk, {&tab, &beam, &baf, &view});
 }
-// the scene patch field (isx_scene_patch_field): the scene kernel with one add per ray absorbed on the selected wall class -- where
-// on the patch it lands and the direction it arrived from, binned in the patch's frame (field_record) -- and no exit lines; the
-// sink is a seventh argument
-extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_SCENE_WAVES, ISX_SCENE_WAVES)))
+extern "C" __global__ void ISX_SCENE_ATTR
 isx_trace_assist_scene_field_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab, const BeamSrc beam, const BaffleTab baf,
                                     const PatchFieldSink field) {
-  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true, false, false, true>(g, d, wk, &tab, &beam, nullptr, &baf,
-                                                                                                          nullptr, nullptr, &field);
+  assist_body<KSceneMap<PatchFieldMap>>(g, d, wk, {&tab, &beam, &baf, &field});
 }
-// the scene order histograms (isx_scene_order_hist): the scene kernel with one add per ended ray -- its fate by its interaction
-// count (sorder_record), the low orders in the workgroup's LDS -- and no exit lines; the sink is a seventh argument
-extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_SCENE_WAVES, ISX_SCENE_WAVES)))
+extern "C" __global__ void ISX_SCENE_ATTR
 isx_trace_assist_scene_order_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab, const BeamSrc beam, const BaffleTab baf,
                                     const SOrderSink sorder) {
-  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true, false, false, false, true>(
-      g, d, wk, &tab, &beam, nullptr, &baf, nullptr, nullptr, nullptr, &sorder);
+  assist_body<KSceneMap<OrderMap>>(g, d, wk, {&tab, &beam, &baf, &sorder});
 }
-// the scene path histograms (isx_scene_path_hist): the scene kernel with the path length of every ray carried through its steps
-// and hand-overs (spath_advance) and one add per ended ray -- its fate by its path length (spath_record), the low bins in the
-// workgroup's LDS -- and no exit lines; the sink is a seventh argument
-extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_SCENE_WAVES, ISX_SCENE_WAVES)))
+extern "C" __global__ void ISX_SCENE_ATTR
 isx_trace_assist_scene_path_kernel(const Geom g, const DetGrid d, const Work wk, const PatchTab tab, const BeamSrc beam, const BaffleTab baf,
                                    const SPathSink spath) {
-  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, true, true, false, true, false, false, false, false, true>(
-      g, d, wk, &tab, &beam, nullptr, &baf, nullptr, nullptr, nullptr, nullptr, &spath);
+  assist_body<KSceneMap<PathMap>>(g, d, wk, {&tab, &beam, &baf, &spath});
 }
 // the flux pipeline behind the fate scan: isx_trace_assist_kernel on the rays of a list; the list is a fourth argument
 extern "C" __global__ void ISX_ASSIST_ATTR
-isx_trace_assist_list_kernel(const Geom g, const DetGrid d, const Work wk, const FateList fl) {
-  assist_body<0, false, false, 0, SURF_LAMBERT, false, false, false, false, true>(g, d, wk, nullptr, nullptr, &fl);
-}
+isx_trace_assist_list_kernel(const Geom g, const DetGrid d, const Work wk, const FateList fl) { assist_body<KList>(g, d, wk, {&fl}); }
 // the other border models on the same pipeline (round 5; until then round 1's fused isx_trace_bin_full_kernel served them):
 // the cos^2 lobe of "nonLambertianFlux copy.C":31-70,188-221 and ROBAST's rough-specular border (EnableLambertian(false))
 #ifndef ISX_LOBE_WAVES
@@ -4516,24 +4511,26 @@ isx_trace_assist_list_kernel(const Geom g, const DetGrid d, const Work wk, const
 #ifndef ISX_ROUGH_WAVES
 #define ISX_ROUGH_WAVES 4
 #endif
-extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_LOBE_WAVES, ISX_LOBE_WAVES)))
-isx_trace_assist_lobe_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_LOBE>(g, d, wk); }
-extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_ROUGH_WAVES, ISX_ROUGH_WAVES)))
-isx_trace_assist_rough_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_ROUGH>(g, d, wk); }
+#define ISX_LOBE_ATTR __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_LOBE_WAVES, ISX_LOBE_WAVES)))
+#define ISX_ROUGH_ATTR __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_ROUGH_WAVES, ISX_ROUGH_WAVES)))
+extern "C" __global__ void ISX_LOBE_ATTR
+isx_trace_assist_lobe_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<Lobe<KDefault>>(g, d, wk); }
+extern "C" __global__ void ISX_ROUGH_ATTR
+isx_trace_assist_rough_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<Rough<KDefault>>(g, d, wk); }
 // ... and as per-position sinks: the macros that own these borders sweep one detector position at a time with fresh rays
 // ("nonLambertianFlux copy.C":306-345: 45 x 20 positions x 1e5 rays), i.e. isx_fluxmap_per_position / isx_trace_rays_detector
-extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_LOBE_WAVES, ISX_LOBE_WAVES)))
-isx_trace_assist_perpos_lobe_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 1, SURF_LOBE>(g, d, wk); }
-extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_ROUGH_WAVES, ISX_ROUGH_WAVES)))
-isx_trace_assist_perpos_rough_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 1, SURF_ROUGH>(g, d, wk); }
-extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_LOBE_WAVES, ISX_LOBE_WAVES)))
-isx_trace_assist_wall_lobe_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_LOBE, true>(g, d, wk); }
-extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_ROUGH_WAVES, ISX_ROUGH_WAVES)))
-isx_trace_assist_wall_rough_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_ROUGH, true>(g, d, wk); }
-extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_LOBE_WAVES, ISX_LOBE_WAVES)))
-isx_trace_assist_order_lobe_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_LOBE, false, true>(g, d, wk); }
-extern "C" __global__ void __launch_bounds__(ISX_ASSIST_BLOCK) __attribute__((amdgpu_waves_per_eu(ISX_ROUGH_WAVES, ISX_ROUGH_WAVES)))
-isx_trace_assist_order_rough_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<0, false, false, 0, SURF_ROUGH, false, true>(g, d, wk); }
+extern "C" __global__ void ISX_LOBE_ATTR
+isx_trace_assist_perpos_lobe_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<Lobe<KPerpos>>(g, d, wk); }
+extern "C" __global__ void ISX_ROUGH_ATTR
+isx_trace_assist_perpos_rough_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<Rough<KPerpos>>(g, d, wk); }
+extern "C" __global__ void ISX_LOBE_ATTR
+isx_trace_assist_wall_lobe_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<Wall<Lobe<KDefault>>>(g, d, wk); }
+extern "C" __global__ void ISX_ROUGH_ATTR
+isx_trace_assist_wall_rough_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<Wall<Rough<KDefault>>>(g, d, wk); }
+extern "C" __global__ void ISX_LOBE_ATTR
+isx_trace_assist_order_lobe_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<Order<Lobe<KDefault>>>(g, d, wk); }
+extern "C" __global__ void ISX_ROUGH_ATTR
+isx_trace_assist_order_rough_kernel(const Geom g, const DetGrid d, const Work wk) { assist_body<Order<Rough<KDefault>>>(g, d, wk); }
 
 // ISX_HITLINE_ORIGIN_COMPAT on the pipeline (round 5): what fluxAtObserverFast.C:1181-1201,1285-1288 effectively tested is the line
 // from the origin along lastPoint/|lastPoint| (hit_line_compat).  The trace kernels write last point + final direction as always;
