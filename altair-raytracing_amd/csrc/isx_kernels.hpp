@@ -1026,7 +1026,7 @@ __device__ __forceinline__ void walk_lines_packed(const D& d, uint32_t* __restri
 constexpr int kClasses = 7, kQueueCap = 128;   // a class never holds more than 63 + 64 slots
 constexpr int kSlotWaveWords = kClasses * kQueueCap + 16 + 64;   // LDS words per wave: queues, counters, owner marks
 constexpr int kDeferCap = kDeferCapW;   // candidates a wave can put aside for tiers 2 and 3
-constexpr int kDeferHead = 8;   // words in front of the deferred list's entries: [0] count, [1..2] the unit's side entries (0: none), [4..5] the redo list, [6..7] its capacity
+constexpr int kDeferHead = 8;   // words in front of the deferred list's entries: [0] count, [1..2] the unit's side entries (0: none), [3] the unit's eps bound, [4..5] the redo list, [6..7] its capacity
 constexpr int kColWaveWords = kClasses * kQueueCap + 16 + 64 + kDeferHead + kDeferCap;   // the same + the deferred list (head, entries)
 constexpr int kPiece = 16, kLongest = 24;
 struct SlotQueues {
@@ -1036,7 +1036,9 @@ struct SlotQueues {
   const ColP* colp;   // column-pair table of the workgroup (isx_bin_slots_kernel)
   LdsWord* defer;     // [kDeferHead + kDeferCap] isx_bin_cols_kernel: [0] = entries held, [kDeferHead..] = candidates that wait for tiers 2 and 3
                       // [1..2]: a unit of lines that isx_exit_lines_kernel wrote -- per line of the unit {eps as
-                      // binary32 bits, the ray's offset}; 0: exact lines, today's path.  [4..5] the chunk's redo list ([0] entries,
+                      // binary32 bits, the ray's offset}; 0: exact lines, today's path.  [3]: such a unit's bound, binary32 bits of a
+                      // value at least every eps of the unit (tier 1's band is formed from it, without a read of the side entry);
+                      // 0: exact lines.  [4..5] the chunk's redo list ([0] entries,
                       // [1] overflow, [2..] offset | bin << 32: candidates left to isx_redo_kernel), [6..7] its capacity.  Kept here and
                       // read where they are used: the kernel has no scalar register to hold them across the walk
 };
@@ -1562,17 +1564,18 @@ __device__ __forceinline__ void consume_cols(const D& d, uint32_t* __restrict__ 
     const double Mv = fabs(e0) + (fabs(e1) + fabs(e2)), Mf = fabs(f0) + (fabs(f1) + fabs(f2));
     const double Sg = fma(Md, fma(Md, Mf, Mn * Mv), Mn * Mn);
     band32 = Sg >= 1e-6 ? (float)(1.4e-6 * Sg) * 1.000001f + 1e-30f : __builtin_inff();
-    const uint2* side = defer_side(sq);
-    if (side) {   // (wave-uniform) a unit of lines formed from the rays' words: the ray's own line lies within eps of this one
+    const uint32_t ub = ((volatile LdsWord*)sq.defer)[3];
+    if (ub) {   // (wave-uniform) a unit of lines formed from the rays' words: the ray's own line lies within eps of this one, and eps
+      // is at most the unit's bound (never 0 in such a unit: every eps is >= 1e-30).  A bound above the line's own eps only widens
+      // the band: the same decisions, a few more candidates for tier 2, which reads the line's own side entry.
       // What g can change by over the lines within eps (decide_approx has the terms), from the column's magnitudes: with |dot| <= 1.5,
       // e <= (e / R) Mn (Mn holds R) and D R <= (D^2 + R^2) / 2 <= (Mf + half_w2 + Mn^2) / 2 every term is at most a multiple of
       // (e / R) Tg, Tg = Mf + Mn Mv + Mn^2 + half_w2; the multiples add up to 10.25, and to less than 11 with every magnitude at
       // its largest over those lines while e / R <= 1e-3 (beyond that nothing is decided here).  eps holds the reference's own
       // rounding on the ray's line as well (isx_exit_lines_kernel).
       const float tg = (float)(fma(Mn, Mn + Mv, Mf) + d.half_w2);
-      const float e = __uint_as_float(side_load(side, line).x);
-      const float er = e * rcp_cull((float)R) * 1.0001f;
-      if (e > 0.f) band32 = er <= 1e-3f ? fmaf(1.001f, band32, (13.8f * er) * tg) : __builtin_inff();
+      const float er = __uint_as_float(ub) * rcp_cull((float)R) * 1.0001f;
+      band32 = er <= 1e-3f ? fmaf(1.001f, band32, (13.8f * er) * tg) : __builtin_inff();
     }
   }
   typedef __attribute__((address_space(3))) uint32_t LdsU32;
@@ -5146,13 +5149,14 @@ isx_bin_cols_kernel(const DetGrid d_arg, const Work wk) {
     if (region >= n_regions) break;
     // (bit 31 of a region's count: isx_exit_lines_kernel wrote it -- its lines have a side entry each)
     const uint32_t r_word = (uint32_t)__builtin_amdgcn_readfirstlane((int)d_arg.rec_counts[region]);
-    const uint32_t r_lines = r_word & 0x7fffffffu;
+    // (... and bits 11..30 then hold the largest eps of the region's lines, rounded up: the unit's bound for tier 1)
+    const uint32_t r_lines = (r_word >> 31) ? (r_word & 0x7ffu) : r_word;
     const uint32_t q_first = (unit & ((1u << ushift) - 1u)) * (kRegion >> ushift);
     const uint32_t n_lines = r_lines < q_first + (kRegion >> ushift) ? r_lines : q_first + (kRegion >> ushift);
     const double* lines = d_arg.rec_lines + 6ull * ((uint64_t)region * kRegion + q_first);   // the unit's lines
     {   // the unit's side entries, where the walks and flush_deferred look for them (every walk of the wave's last unit has ended)
       const unsigned long long sp = (r_word >> 31) ? (unsigned long long)(uintptr_t)(reinterpret_cast<const uint2*>(d_arg.log_rec) + ((uint64_t)region * kRegion + q_first)) : 0ull;
-      if (lane == 0) { sq.defer[1] = (uint32_t)sp; sq.defer[2] = (uint32_t)(sp >> 32); }
+      if (lane == 0) { sq.defer[1] = (uint32_t)sp; sq.defer[2] = (uint32_t)(sp >> 32); sq.defer[3] = (r_word >> 31) ? (r_word & 0x7ffff800u) : 0u; }
       __builtin_amdgcn_wave_barrier();
     }
     struct { int n_phi, n_theta; double half_w2, portz, R; const double* table; } dcol;
@@ -5425,7 +5429,8 @@ isx_fate_diag_kernel(const FateConsts f, uint64_t seed, uint64_t first, uint64_t
 //   on the planes z = zcut_in (1 - 1e-6), zcut_out, zcut_out (1 + 1e-6) the line lies inside the rim cone (the middle one: inside
 //   the outer ball) by more than its own deviation there: the solid cone is convex, so no root of the cone lies between the
 //   planes, and a root outside them fails `rr in [rin2, rout2]` by 2e-6; the far root of the outer sphere lies below zcut_out
-//   the generic search on (p', V') ends on the box, and its point lies below portz by more than its deviation
+//   the generic search on (p', V') then ends on the box (no test: the tests above exclude its other branches), and the box point,
+//   formed by the search's own last lines, lies below portz by more than its deviation
 constexpr int kExitBlock = 256;
 constexpr uint32_t kExitBatch = 512;
 constexpr double kExitChord = 0.05, kExitMinDz = 0.02;
@@ -5481,6 +5486,7 @@ isx_exit_lines_kernel(const ExitScan a) {
     q0_ok = next_hit_s1<true>(h, a.g, s0, d0, K_NONE, q0);
   }
   const double rin = a.g.r_in, Hb = a.g.H;
+  const double inv_detR = (1.0 / a.det_R) * (1.0 + 1e-12);   // (eps_ref's divisor, once per wave and rounded up)
   const double zA = a.g.zcut_in * (1.0 - 1e-6), zB = a.g.zcut_out, zC = a.g.zcut_out * (1.0 + 1e-6);
   const double tanc = sqrt(a.g.k2);
   const double rhoA = tanc * fabs(zA), rhoB = sqrt(fmax(a.g.rout2 - zB * zB, 0.0)) * (1.0 - 1e-6), rhoC = tanc * fabs(zC);
@@ -5489,6 +5495,14 @@ isx_exit_lines_kernel(const ExitScan a) {
   uint32_t reg_id = 0xffffffffu, reg_slot = 0, reg_left = 0;
   uint32_t n_wall = 0;      // per lane (an entry adds at most J_CAP + 1, a lane sees at most 2^26 / 64 entries)
   uint32_t n_acc = 0;       // per wave
+  // A region's word: lines in it (bits 0..10), the largest eps of its lines as the upper 20 bits of its binary32 bits, rounded up
+  // (bits 11..30: eps > 0, so the bits order as the values do), bit 31.  The binning kernel's tier 1 works with that one bound.
+  uint32_t reg_eps = 0u;    // per wave: the largest eps bits among the lines of the open region (one wave reduction per batch)
+  auto close_region = [&]() {
+    const uint32_t e = reg_eps > 0x7f800000u ? 0x7f800000u : reg_eps;   // (nothing above +inf: rounding up must not reach bit 31)
+    if (lane == 0 && reg_id != 0xffffffffu) a.rec_counts[reg_id] = (kRegion - reg_left) | (((e + 0x7ffu) >> 11) << 11) | 0x80000000u;
+    reg_eps = 0u;
+  };
   for (uint32_t base = ((uint32_t)blockIdx.x * (uint32_t)(kExitBlock / 64) + (uint32_t)(tid >> 6)) * 64u; base < n_a; base += stride) {
     const uint32_t k = base + (uint32_t)lane;
     const bool have = k < n_a;
@@ -5524,9 +5538,9 @@ isx_exit_lines_kernel(const ExitScan a) {
         if (j != 0u) {
           uint32_t w2[4] = {0u, 0u, 0u, 0u};
           if (j >= 2u || !odd) draw_block(a.seed, ray, (j >> 1) - 1u, 0u, w2);   // (j = 1: block 0 holds both)
-          p = odd ? wall_point(w[0], w[1]) : wall_point(w2[2], w2[3]);
+          p = wall_point(odd ? w[0] : w2[2], odd ? w[1] : w2[3]);   // (the words selected first: one wall point each, not two)
           V3 pp = q0;
-          if (j >= 2u) pp = odd ? wall_point(w2[2], w2[3]) : wall_point(w2[0], w2[1]);
+          if (j >= 2u) pp = wall_point(odd ? w2[2] : w2[0], odd ? w2[3] : w2[1]);
           pp.x = p.x - pp.x; pp.y = p.y - pp.y; pp.z = p.z - pp.z;
           prev2 = dot3(pp, pp);
           ok = prev2 >= (kExitChord * kExitChord) * (rin * rin);
@@ -5542,15 +5556,16 @@ isx_exit_lines_kernel(const ExitScan a) {
         }
         const double ch2 = dot3(V, V);
         ok = ok && ch2 >= (kExitChord * kExitChord) * (rin * rin);
-        const double chord = sqrt(ch2);
         unit_dir(V);
         ok = ok && dot3(p, V) < -1e-3 * rin && V.z <= -kExitMinDz;
         if (ok) {
           // the bounds: the point (drift of |p|^2 over j + 2 steps, divided by the length of the chord that led to it -- known to
           // 1e-6 of the floor, since the chord's own start lies within the scan's bound of 130 words of r_in s_{j-2}), the direction
-          const double eps_p = fma(((double)(j + 2u) * kExitStep + 4e-15) * (rin * rin), 1.001 / sqrt(prev2), 1e-14 * rin);
-          const double eps_V = fma(2.1, eps_p / chord, 2e-14);
-          const double iz = 1.0 / V.z;
+          // Both reciprocal roots are bounds, not results: v_rsq_f64 alone is within 2^-23 of 1/sqrt (operands >= kExitChord^2 r_in^2,
+          // normal), and the factors 1.0011 and 2.1001 hold 1.001 (1 + 1e-6) and 2.1 (1 + 1e-6) with room
+          const double eps_p = fma(((double)(j + 2u) * kExitStep + 4e-15) * (rin * rin), 1.0011 * __builtin_amdgcn_rsq(prev2), 1e-14 * rin);
+          const double eps_V = fma(2.1001, eps_p * __builtin_amdgcn_rsq(ch2), 2e-14);
+          const double iz = -neg_rcp_unit(V.z);   // 1.0 / V.z in its own bits: V.z in [-1, -kExitMinDz]
           // a plane z = zp: the line's point there lies within `rho` of the axis by more than 2.5 (eps_p + t eps_V) / |V.z| + 1e-9 rho
           auto inside = [&](double zp, double rho) {
             const double t = (zp - p.z) * iz;
@@ -5560,13 +5575,22 @@ isx_exit_lines_kernel(const ExitScan a) {
           };
           ok = inside(zA, rhoA) && inside(zB, rhoB) && inside(zC, rhoC);
           if (ok) {
-            const int kind = next_hit_generic(a.g, p, V, K_INNER, P);
+            // The box point in next_hit_generic's own expressions (its last lines; V.z < 0 here).  The search in front of them is
+            // not run: the tests above leave it no other branch
+            const double inf = __builtin_inf();
+            const double tx = V.x > 0.0 ? (Hb - p.x) / V.x : (V.x < 0.0 ? (-Hb - p.x) / V.x : inf);
+            const double ty = V.y > 0.0 ? (Hb - p.y) / V.y : (V.y < 0.0 ? (-Hb - p.y) / V.y : inf);
+            const double tz = (-Hb - p.z) / V.z;
+            double t = tx;
+            if (ty < t) t = ty;
+            if (tz < t) t = tz;
+            P = axpy(t, V, p);
             const double eps_box = 2.5 * fma(4.0 * Hb, eps_V, eps_p) + 1e-9 * Hb;
-            ok = kind == K_BOX && P.z < a.portz - eps_box;
+            ok = P.z < a.portz - eps_box;
             // ... and what tier 1 of the binning kernel needs on top of its own rounding band: the reference's rounding on the ray's
             // line, 1e-13 S_P in units of g with S_P <= 4 (|P - O|^2 + R^2) + half_w2, as a length: tier 1 widens by 13.8 (eps / R) Tg, Tg >= R^2
             const double wz = P.z - a.portz;
-            const double eps_ref = 1e-14 * fma(4.0, fma(P.x, P.x, fma(P.y, P.y, fma(wz, wz, a.det_R * a.det_R))), a.half_w2) / a.det_R;
+            const double eps_ref = 1e-14 * fma(4.0, fma(P.x, P.x, fma(P.y, P.y, fma(wz, wz, a.det_R * a.det_R))), a.half_w2) * inv_detR;
             const double eps_line = (eps_p + a.reach * eps_V + 4e-15 * Hb + eps_ref) * a.eps_scale;
             eps32 = (float)eps_line * 1.0001f + 1e-30f;
           }
@@ -5579,7 +5603,7 @@ isx_exit_lines_kernel(const ExitScan a) {
     if (m) {
       const uint32_t cnt = (uint32_t)__popcll(m);
       if (cnt > reg_left) {   // close the open region, reserve the next one
-        if (lane == 0 && reg_id != 0xffffffffu) a.rec_counts[reg_id] = (kRegion - reg_left) | 0x80000000u;
+        close_region();
         uint32_t id = 0;
         if (lane == 0) id = atomicAdd(a.ctr + Q_REGIONS, 1u);
         reg_id = (uint32_t)__builtin_amdgcn_readfirstlane((int)id);
@@ -5592,6 +5616,16 @@ isx_exit_lines_kernel(const ExitScan a) {
         dst[0] = make_double2(P.x, P.y); dst[1] = make_double2(P.z, V.x); dst[2] = make_double2(V.y, V.z);
         a.side[slot] = make_uint2(__float_as_uint(eps32), off);
         n_wall += j + 1u;
+      }
+      {   // the batch's largest eps into the open region's (a scalar: the kernel keeps its 6 waves per SIMD)
+        uint32_t e = acc ? __float_as_uint(eps32) : 0u;
+#pragma unroll
+        for (int dlt = 32; dlt > 0; dlt >>= 1) {
+          const uint32_t o = (uint32_t)__shfl_xor((int)e, dlt, 64);
+          e = o > e ? o : e;
+        }
+        e = (uint32_t)__builtin_amdgcn_readfirstlane((int)e);
+        reg_eps = e > reg_eps ? e : reg_eps;
       }
       reg_slot += cnt; reg_left -= cnt;
       n_acc += cnt;
@@ -5608,7 +5642,7 @@ isx_exit_lines_kernel(const ExitScan a) {
     }
   }
   if (n_batch) flush_batch();
-  if (lane == 0 && reg_id != 0xffffffffu) a.rec_counts[reg_id] = (kRegion - reg_left) | 0x80000000u;
+  close_region();
   atomicAdd(&s_wall, (unsigned long long)n_wall);
   if (lane == 0) {
     if (n_acc) {   // launched, exited, counted below the port plane
