@@ -161,6 +161,9 @@ constexpr int kBlock = ISX_BLOCK;
 #ifndef ISX_ABL
 #define ISX_ABL 0
 #endif
+#ifndef ISX_COLCULL
+#define ISX_COLCULL 2         // the tilt cull of the column producer (col_cull): 0 off, 1 column test only, 2 column test + row trim
+#endif
 #ifndef ISX_WALK4
 #define ISX_WALK4 1
 #endif
@@ -1205,11 +1208,12 @@ __device__ __forceinline__ void push_slots(const D& d, uint32_t* __restrict__ hi
 struct CapShared {
   double wv;              // line parameter of the foot of O, negated: the caps' centres are the directions of the points at +-sM - wv
   float sM, iL, cosw;     // (smin + smx)/2, 1/|H + sM V|, cos w
+  float slo, shi;         // col_cull: a hit of the cap of side 0 has its point at a parameter in [slo, shi] from the foot of O
   int kind;               // 0 the line has caps, -1 no caps: grazing line, -2 the line cannot hit anything
 };
 __device__ __forceinline__ CapShared prep_shared(const GridConst& k, const V3& P, const V3& V) {
   CapShared o;
-  o.wv = 0.0; o.sM = o.iL = o.cosw = 0.f; o.kind = -1;
+  o.wv = 0.0; o.sM = o.iL = o.cosw = o.slo = o.shi = 0.f; o.kind = -1;
   const double wz = P.z - (double)k.portz;
   const double wv = fma(P.x, V.x, fma(P.y, V.y, wz * V.z));
   const double hx = fma(-wv, V.x, P.x), hy = fma(-wv, V.y, P.y), hz = fma(-wv, V.z, wz);
@@ -1232,6 +1236,13 @@ __device__ __forceinline__ CapShared prep_shared(const GridConst& k, const V3& P
   // grazing line (a cap about h^ and a band: right for any line)
   if (!(cosw > 0.5f && sM * iL > fmaf(sinw, 1.01f, 1e-3f))) return o;
   o.wv = wv; o.sM = sM; o.iL = iL; o.cosw = cosw; o.kind = 0;
+  // the hit point x of a bin lies on the disc: |x - c| <= rho, so |x - O| in [R - rho, R + rho] and its parameter s from the foot
+  // obeys s^2 in [(R - rho)^2 - dO^2, (R + rho)^2 - dO^2]; c.V = s + (c - x).V has the sign of the cap's side, so s > -rho on side 0
+  // (DESIGN.md section 4.4).  1e-6 R^2: the cancellation in binary32; below 1.001 rho the interval starts beyond the foot.
+  const float rm = k.Rf - k.rho, rp = k.Rf + k.rho;
+  const float slo = sqrt_cull(fmaxf(0.f, fmaf(rm, rm, -dO2) - 1e-6f * R2)) * 0.9999f;
+  o.shi = sqrt_cull(fmaf(rp, rp, -dO2) + 1e-6f * R2) * 1.0001f;
+  o.slo = slo > 1.001f * k.rho ? slo : -1.001f * k.rho;
   return o;
 }
 // chord^2 from a cap's centre ON the sphere to its rim: 2 R^2 (1 - cos w)
@@ -1374,10 +1385,17 @@ struct ColPre {     // per line and piercing point: its cap as the column produc
   int kind;                // 0 a cap with columns, -1 no caps: grazing line (bin_culled's box windows), -2 the line cannot hit
                            // anything, -3 this side's cap lies above every detector row
 };
+// The four per-line floats a pass hands to its (line, column) lanes next to the cap.  A grazing line's band (prep_band): u = V x h^
+// and kappa = rho / R with its slack.  A line with caps (prep_cols): the xy parts of the two ends of the side's parameter interval,
+// relative to O and in units of rho_d, (ux, uy) and (uz, kap), for col_cull -- one set of registers for both: the kernel has none
+// to spare, and no pass needs both.
+struct BandPre { float ux, uy, uz, kap; };
 // side 0: the piercing point at the larger line parameter (the only one of a fast-path line), side 1: the other one.
-__device__ __forceinline__ ColPre prep_cols(const GridConst& k, int n_phi, const V3& P, const V3& V, const CapShared& sh, int side) {
+__device__ __forceinline__ ColPre prep_cols(const GridConst& k, int n_phi, const V3& P, const V3& V, const CapShared& sh, int side,
+                                            BandPre& ends) {
   ColPre o;
   o.fx = o.fy = o.a = o.cosw = 0.f; o.jlo = 0; o.ncol = 0; o.kind = sh.kind;
+  ends.ux = ends.uy = ends.uz = ends.kap = 0.f;   // (both ends at O: dmin = 0, nothing culled)
   if (sh.kind != 0) return o;
   float Fx, Fy, mz;
   cap_centre(k, sh, P, V, side, Fx, Fy, mz);
@@ -1385,6 +1403,14 @@ __device__ __forceinline__ ColPre prep_cols(const GridConst& k, int n_phi, const
   o.fx = Fx * sh.iL; o.fy = Fy * sh.iL; o.a = -(mz * sh.iL);
   o.cosw = sh.cosw;
   o.kind = 0;
+#if ISX_COLCULL
+  {   // the ends of the side's parameter interval as points of the line (xy, relative to O), in units of rho_d
+    const double sa = (side == 0 ? (double)sh.slo : -(double)sh.slo) - sh.wv, sb = (side == 0 ? (double)sh.shi : -(double)sh.shi) - sh.wv;
+    const float ir = rcp_cull(k.rho);
+    ends.ux = (float)fma(sa, V.x, P.x) * ir; ends.uy = (float)fma(sa, V.y, P.y) * ir;
+    ends.uz = (float)fma(sb, V.x, P.x) * ir; ends.kap = (float)fma(sb, V.y, P.y) * ir;
+  }
+#endif
   // columns: sin theta_F |sin(phi - phi_F)| <= sin w
   const float sinF = sqrt_cull(fmaf(o.fx, o.fx, o.fy * o.fy));
   const float sinw = sqrt_cull(fmaxf(0.f, fmaf(-o.cosw, o.cosw, 1.0f)));
@@ -1433,6 +1459,28 @@ __device__ __forceinline__ void cap_rows(float fx, float fy, float a, float cosw
   if (hi >= lo) { ilo = lo; cnt = hi - lo + 1; }
 }
 
+// The tilt cull.  The disc of bin (i, j) is spanned by rho^ = (c_phi, s_phi, 0) and u2 = cos theta_i phi^ + sin theta_i z^, phi^ =
+// (-s_phi, c_phi, 0): a point of it lies within rho_d cos theta_i of the meridian plane of column j, and the hit point is a point
+// of the line at a parameter inside the side's interval (prep_shared).  f = phi^ . (x - O) is affine along the line, so its least
+// magnitude over the interval, dmin, is taken at an end, or is 0 where the sign changes: rows with rho_d cos theta_i < dmin cannot
+// be hit.  In units of rho_d: t = dmin (1 - 4e-6) - cs (the rounding of rho_d; cs = 5e-7 times the ends' coordinates: the roundings
+// of the two forms), rows up to theta = acos(t) + 8e-5 (acos_cull underestimates by 6.8e-5 at most) + 1e-3 rows.  ISX_COLCULL 1:
+// only drops the slot whose first row's lower edge lies beyond; 2: trims the slot's high-theta end as well.  (DESIGN.md section
+// 4.4; tests/colcull_np.py)
+__device__ __forceinline__ void col_cull(float xa, float ya, float xb, float yb, float c32, float s32, float inv_dth, int ilo, int& cnt) {
+  const float fa = fmaf(c32, ya, -(s32 * xa)), fb = fmaf(c32, yb, -(s32 * xb));
+  const float cs = 5e-7f * ((fabsf(xa) + fabsf(ya)) + (fabsf(xb) + fabsf(yb)));
+  const float t = fmaf(fminf(fabsf(fa), fabsf(fb)), 1.0f - 4e-6f, -cs);
+  if (!(fa * fb > 0.f && t > 0.f)) return;
+  const float th = acos_cull(fminf(t, 1.0f)) + 8e-5f;
+#if ISX_COLCULL == 1
+  if ((float)ilo > fmaf(th, inv_dth, 1e-3f)) cnt = 0;
+#else
+  const int hi = (int)floorf(fmaf(th, inv_dth, -0.5f + 1e-3f));
+  cnt = max(0, min(cnt, hi - ilo + 1));
+#endif
+}
+
 // ---- GRAZING lines as column slots (round 4; until then such a line was taken one at a time, lane = row: bin_culled's box
 // windows).  A line without caps passes S(O,R) at a distance h from O of about R (or its caps would merge: rho_d comparable to R).
 // Every detector centre c it can hit lies within rho of the line, X(s) = H + s V (H the foot of O, |V| = 1), hence -- e = the part of
@@ -1446,7 +1494,6 @@ __device__ __forceinline__ void cap_rows(float fx, float fy, float a, float cosw
 // N e^(i delta) = (c_phi u_x + s_phi u_y) + i u_z, i.e. theta within asin(rho / (R N)) of delta + m pi: at most two stretches of
 // rows inside the cap's range.  Binary32 with explicit slack (rho: 0.1 % + 2e-3 cm as in box_line; unit vectors and R: 4e-6; angles
 // 2.6e-3 rad + the cull functions' 1e-4; rows 1e-3): never decides a result, a candidate outside the tube is a miss of the exact test.
-struct BandPre { float ux, uy, uz, kap; };   // u = V x h^, kappa = rho / R with its slack
 __device__ __forceinline__ ColPre prep_band(const GridConst& k, int n_phi, const V3& P, const V3& V, BandPre& bp) {
   ColPre o;
   o.fx = o.fy = o.a = o.cosw = 0.f; o.jlo = 0; o.ncol = 0; o.kind = -2;
@@ -1846,6 +1893,7 @@ __device__ __forceinline__ void push_cols(const D& d, uint32_t* __restrict__ his
       const int pos = __hip_atomic_fetch_add(sq.tail + c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       ((volatile LdsWord*)sq.q)[c * kQueueCap + (pos & (kQueueCap - 1))] =
           (uint32_t)line | ((uint32_t)j << 8) | ((uint32_t)i0 << 16) | ((uint32_t)piece << 24);
+      ISX_DIAG_ADD_LANES(5, 1);   // column slots queued (tools/diag_binning.py: col_slots_per_line)
     }
     rem -= piece;
     i0 += piece;
@@ -1890,9 +1938,16 @@ __device__ __forceinline__ void produce_cols_packed(const D& d, uint32_t* __rest
     int ilo = 0, cnt = 0, ilo_b = 0, cnt_b = 0;
     const float c32 = colx[j].c32, s32 = colx[j].s32;
     if (have) cap_rows(fx, fy, a, cw, c32, s32, inv_dth, n_theta, ilo, cnt);
+#if ISX_COLCULL
+    BandPre ob;   // the band of a grazing line, or the interval ends of a line with caps
+    ob.ux = __shfl(bp.ux, owner, 64); ob.uy = __shfl(bp.uy, owner, 64); ob.uz = __shfl(bp.uz, owner, 64); ob.kap = __shfl(bp.kap, owner, 64);
+    if (!band && cnt > 0) col_cull(ob.ux, ob.uy, ob.uz, ob.kap, c32, s32, inv_dth, ilo, cnt);
+#endif
     if (band) {
+#if !ISX_COLCULL
       BandPre ob;
       ob.ux = __shfl(bp.ux, owner, 64); ob.uy = __shfl(bp.uy, owner, 64); ob.uz = __shfl(bp.uz, owner, 64); ob.kap = __shfl(bp.kap, owner, 64);
+#endif
       const int r_lo = ilo, r_hi = ilo + cnt - 1;
       band_rows(ob, c32, s32, inv_dth, r_lo, have ? r_hi : r_lo - 1, ilo, cnt, ilo_b, cnt_b);
     }
@@ -5201,7 +5256,7 @@ isx_bin_cols_kernel(const DetGrid d_arg, const Work wk) {
               if (low2 && caps_may_touch(k, sh)) { sh.kind = -1; low2 = false; }   // the whole line as a grazing line
             }
             graze = sh.kind == -1;
-            pre = prep_cols(k, dcol.n_phi, lp, lv, sh, pass);
+            pre = prep_cols(k, dcol.n_phi, lp, lv, sh, pass, bp);
           } else {
             pre = prep_band(k, dcol.n_phi, lp, lv, bp);
           }

@@ -1,5 +1,5 @@
 """Where the binning work goes (GPU box; needs variants/libisx_diag.so = libisx built with -DISX_DIAG):
-   ISX_LIB_PATH=variants/libisx_diag.so python tools/diag_binning.py"""
+   ISX_LIB_PATH=variants/libisx_diag.so python tools/diag_binning.py [n_rays: the default configuration alone]"""
 import ctypes as C, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -21,6 +21,7 @@ def run(name, c, n):
            "col_iterations_per_line": {"fast": d[4] / max(d[0], 1), "caps": d[5] / max(d[1], 1), "fallback": d[6] / max(d[2], 1)},
            "candidates_per_line": {"fast": d[7] / max(d[0], 1), "caps": d[8] / max(d[1], 1), "fallback": d[9] / max(d[2], 1)},
            "row_passes_per_line": d[11] / lines, "split_passes_per_line": d[10] / lines,
+           "col_slots_per_line": d[5] / lines, "candidates_per_hit": (d[7] + d[8] + d[9]) / max(st.bin_increments, 1),
            "tier2_per_candidate": d[12] / max(d[7] + d[8] + d[9], 1), "tier3_per_candidate": d[13] / max(d[7] + d[8] + d[9], 1),
            "WRONG_DECISIONS": int(d[14]), "candidates_total": int(d[7] + d[8] + d[9]),
            "lane_fill": {"fast": d[7] / max(d[4] * 64, 1), "caps": d[8] / max(d[5] * 64, 1), "fallback": d[9] / max(d[6] * 64, 1)}}
@@ -35,6 +36,9 @@ def run(name, c, n):
         out["slot_kernel_wave_cycles_per_pass"] = float(d[16:22].sum() / max(d[11], 1))
     print(name, json.dumps(out, indent=1))
 c = isx.default_config()
+if len(sys.argv) > 1:   # python tools/diag_binning.py N: the default configuration at N rays only
+    run("headline", c, int(float(sys.argv[1])))
+    sys.exit(0)
 run("headline", c, 20_000_000)
 c.source_model = 1; c.roughness_rad = 0.5; c.reflectance = 1.0; c.max_points = 10000; c.box_half = 200.0
 run("brdf", c, 10_000_000)
